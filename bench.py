@@ -17,10 +17,13 @@ Workloads (`--config`, per GPU; synthetic seeded inputs from fleetrl_amd/synth.p
 N > 1: every rank runs its own shard of that size (weak scaling), no data-path collective; one RCCL all-gather of episode
 returns for logging, outside the timed region and reported as `log_gather_ms`.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (dominant kernel vs the 8 TB/s HBM roof, algorithmic bytes per
-SURVEY.md section 8d), `cpu_baseline` (the CPU oracle -- a port of the reference's algorithm -- timed on this box's host
-cores on a bounded sample of the same workload), `step_many` (K-steps-per-launch open-loop entry) and `host_path` (the
-host-pointer entry points incl. PCIe, what an SB3 loop sees), both reported aside.
+Prints ONE JSON line (rank 0).  A plain run sets up, primes (--prime-steps), warms up, times exactly --steps launches (`ms_per_step`,
+`value`) and prints the headline; `--dump-outputs DIR` writes what the last timed step computed as .npy files.  `--full` adds
+the rest, each measured in runs of its own after the headline's: more timed regions (`reps`), `roofline` (dominant kernel vs
+the 8 TB/s HBM roof, algorithmic bytes per SURVEY.md section 8d, the other launch paths and episode phase), the workload
+invariants, `cpu_baseline` (the CPU oracle -- a port of the reference's algorithm -- timed on the host's cores on a bounded
+sample of the same workload), `step_many` (K-steps-per-launch open-loop entry), `host_path` (the host-pointer entry points incl.
+PCIe, what an SB3 loop sees) and the logging all-gather, all reported aside.
 """
 from __future__ import annotations
 
@@ -191,6 +194,38 @@ class Group:
         self.batch.run_tape_dev(k, self.tape.data_ptr(), self.L, self.obs.data_ptr(), self.reward.data_ptr(), self.done.data_ptr(),
                                 use_graph=use_graph)
 
+    def outputs(self, tag: str) -> dict:
+        """What the tape replay hands its caller after its last step, on the host: observations, rewards, done flags."""
+        return {f"obs{tag}": self.obs.cpu().numpy(), f"reward{tag}": self.reward.cpu().numpy(),
+                f"done{tag}": self.done.cpu().numpy().astype(np.float32)}
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(arrays: dict, out_dir: str, limit: int = DUMP_LIMIT_BYTES) -> list:
+    """Write every array as <out_dir>/<name>.npy.  Arrays are [E, ...] per group (names ending in the same group tag share E); when
+    the whole exceeds `limit`, every group keeps the same fixed, seeded sample of env rows and `env_index<tag>` says which."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        by_tag = {}
+        for name, a in arrays.items():
+            by_tag.setdefault(name[name.find("_"):] if "_" in name else "", []).append(name)
+        share = limit / (total + 8 * sum(arrays[names[0]].shape[0] for names in by_tag.values()))  # (+ the float64 row indices)
+        for tag, names in by_tag.items():
+            rows = arrays[names[0]].shape[0]
+            keep = max(1, int(rows * share))
+            idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+            for name in names:
+                arrays[name] = arrays[name][idx]
+            arrays[f"env_index{tag}"] = idx.astype(np.float64)
+    written = []
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+        written.append(name)
+    return written
+
 
 def self_launch(n: int) -> int:
     """Run this command under `torch.distributed.run` with one rank per GPU; returns the child's exit code."""
@@ -254,14 +289,25 @@ def main():
                     help="the logging all-gather: through torch.distributed (default), or as ONE ncclAllGather issued by the C ABI "
                          "(fleet_gather_episode_stats_rccl; single fleet type, --backend nccl; falls back to torch on any error)")
     ap.add_argument("--device-index", type=int, default=None, help="GPU to use instead of LOCAL_RANK (test hook, see --backend)")
-    ap.add_argument("--prime-ms", type=float, default=300.0, help="untimed clock-ramp replay before the warmup steps")
+    ap.add_argument("--prime-steps", type=int, default=40960,
+                    help="untimed launches before the warmup steps: the clock ramp and the fleets' steady state (about 0.25 s at the "
+                         "default shape)")
     ap.add_argument("--deg", default=None, choices=["none", "linear", "rainflow"],
                     help="override the config's degradation model (diagnostics)")
     ap.add_argument("--split", type=int, default=1,
                     help="diagnostic: run every fleet type's envs as this many handles (own stream each), whose launches overlap")
     ap.add_argument("--reps", type=int, default=None,
-                    help="timed regions of exactly --steps launches each, run back to back; the median region is reported "
-                         "(default: 31 for runs of up to 256 steps, else 7)")
+                    help="with --full: timed regions of exactly --steps launches each in all, run back to back, the headline's region "
+                         "first; their spread and median are reported beside the headline (default: 31 for runs of up to 256 steps, else 7)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: further timed regions (--reps), the kernels' own time and the roofline, the "
+                         "other launch paths and episode phase, the workload invariants, the K-step entry, the host path, the CPU "
+                         "baseline and the logging all-gather.  Without it a run sets up, warms up, times --steps launches and prints "
+                         "the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed launches computed in their last step -- observations (float32), "
+                         "rewards (float64), done flags (as float32), per fleet type -- as DIR/<name>.npy (rank 0; at most 64 MB, a "
+                         "fixed seeded sample of env rows beyond that).  The same arguments give the same inputs on every run")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves, as a CHILD process (nothing in this process
@@ -365,11 +411,13 @@ def main():
         regs = kernel_regions(mode)
         return max(sorted(regs, key=max)[len(regs) // 2]) / args.steps
 
-    # clock ramp: replay the same step (untimed) for a fixed wall time before the W warmup steps, so that a short
-    # --steps/--warmup run measures the same steady state as a long one
-    t_prime = time.perf_counter()
-    while (time.perf_counter() - t_prime) * 1e3 < args.prime_ms:
-        run(4 * L)
+    # clock ramp and steady state: a fixed number of untimed launches before the W warmup steps, so that a short --steps/--warmup
+    # run measures the same steady state as a long one -- the clock's, and the fleet's: a step's duration drifts down over the first
+    # tens of thousands of launches as the fleets' state evolves (7.1 us per step over launches 300 ... 2300 at the headline shape,
+    # 6.3 us over launches 41 000 ... 43 000).  A number of launches, not a wall time, so every run with the same arguments computes
+    # the same outputs.
+    if args.prime_steps > 0:
+        run(args.prime_steps)
         sync()
     # ---- episode phase -------------------------------------------------------------------------------------------------------
     # After a plain reset all envs run their 192-step episodes in lock step -- the reference's vec env does by construction (every env
@@ -400,19 +448,22 @@ def main():
     sync()
     ret = torch.zeros(E, device=dev, dtype=torch.float64)
     ln = torch.zeros(E, device=dev, dtype=torch.int32)
-    gather_episode_stats(ret.to(cdev), ln.to(cdev), equal_shards=True)  # warmup of the logging collective too (RCCL channel setup is not a per-step cost)
+    if args.full:
+        gather_episode_stats(ret.to(cdev), ln.to(cdev), equal_shards=True)  # warmup of the logging collective too (RCCL channel setup is not a per-step cost)
 
     # ---- the timed regions: each is exactly K steps between two barriers ------------------------------------------------------
-    # One region is what the contract describes (barrier + synchronize, K launches, synchronize + barrier).  A single region of
-    # a short run mostly measures the host's wake-up after the synchronize (tens of microseconds against 20 launches of 9 us), so
-    # R regions are run back to back and the MEDIAN one is reported (`reps`, with the fastest and slowest beside it); inside a
-    # region the wait for the device is a spin on hipStreamQuery instead of a blocking synchronize.
+    # One region is what the contract describes (barrier + synchronize, K launches, synchronize + barrier), and its K = --steps
+    # launches are the headline (`ms_per_step`, `value`).  Inside a region the wait for the device is a spin on hipStreamQuery instead
+    # of a blocking synchronize.  A single region of a short run mostly measures the host's wake-up after the synchronize (tens of
+    # microseconds against 20 launches of 9 us): --full runs R - 1 more regions back to back after the headline's and reports the
+    # median, fastest and slowest of all R beside it (`reps`).
     # N > 1: a rank's span ends when ITS device is idle after the K launches; the closing barrier follows, and the line reports the
     # MAX over the ranks of those spans (with the closing RCCL barrier inside the span every rank would report the same figure, the
     # slowest rank's PLUS a collective's latency, and the MAX over ranks would be moot).  `ms_per_step_incl_closing_barrier` keeps the
     # other reading beside it.  N = 1: the synchronize IS the barrier, one figure.
     walls, walls_closed = [], []
-    for _ in range(reps):
+    outputs = None
+    for i in range(reps if args.full else 1):
         barrier()
         t0 = time.perf_counter()
         run(args.steps)
@@ -424,21 +475,26 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
         walls_closed.append(time.perf_counter() - t0)
-    # the kernels' own time (roofline), kept out of the wall-clock regions (kernel_regions above) -- through the headline's launch
-    # path, then through the other paths of the same kernel on the same state (reported beside it, never as `value`)
-    ev_regions = kernel_regions(use_graph)
-    other_paths = {}
-    for name, mode, what in (() if args.lean else (
-            ("open_loop_direct_queue", 2, "OPEN LOOP: the library's own queue, no L2 write-back between the launches of a region; a step's "
-                                          "outputs are visible after the region only (FLEET_LAUNCH_DIRECT: a recorded tape, an open-loop rollout)"),
-            ("closed_loop_hip_graph" if args.steps >= graph_len else "closed_loop_hip_eager", 1 if args.steps >= graph_len else 0,
-             "CLOSED LOOP: HIP's launches, an agent-scope release (L2 write-back) at every kernel boundary -- every step's outputs are "
-             "visible before the next step starts: what fleet_step_dev and every Gym / SB3 loop get"))):
-        if (mode >= 2) != (use_graph >= 2):
-            try:
-                other_paths[name] = {"kernel_ms": kernel_ms(mode), "what": what}
-            except Exception as ex:  # (no queue to be had: see launch_note)
-                other_paths[name] = {"kernel_ms": None, "what": f"unavailable: {ex}"}
+        if i == 0 and args.dump_outputs and rank == 0:  # the headline region's last step, before anything else runs on the state
+            outputs = {}
+            for k, g in enumerate(groups):
+                outputs.update(g.outputs("" if len(groups) == 1 else f"_{k}_{g.use_case}"))
+    if args.full:
+        # the kernels' own time (roofline), kept out of the wall-clock regions (kernel_regions above) -- through the headline's launch
+        # path, then through the other paths of the same kernel on the same state (reported beside it, never as `value`)
+        ev_regions = kernel_regions(use_graph)
+        other_paths = {}
+        for name, mode, what in (() if args.lean else (
+                ("open_loop_direct_queue", 2, "OPEN LOOP: the library's own queue, no L2 write-back between the launches of a region; a step's "
+                                              "outputs are visible after the region only (FLEET_LAUNCH_DIRECT: a recorded tape, an open-loop rollout)"),
+                ("closed_loop_hip_graph" if args.steps >= graph_len else "closed_loop_hip_eager", 1 if args.steps >= graph_len else 0,
+                 "CLOSED LOOP: HIP's launches, an agent-scope release (L2 write-back) at every kernel boundary -- every step's outputs are "
+                 "visible before the next step starts: what fleet_step_dev and every Gym / SB3 loop get"))):
+            if (mode >= 2) != (use_graph >= 2):
+                try:
+                    other_paths[name] = {"kernel_ms": kernel_ms(mode), "what": what}
+                except Exception as ex:  # (no queue to be had: see launch_note)
+                    other_paths[name] = {"kernel_ms": None, "what": f"unavailable: {ex}"}
     # ---- what the run did: the workload's invariants, and the same launches in the OTHER episode phase ---------------------------
     # The invariants are taken in the STAGGERED state (the stationary mixture of episode ages: the same whatever the shape, the step
     # count and the prime time of the run were), over a window of W launches, envs that end an episode inside it left out.
@@ -461,7 +517,9 @@ def main():
         except Exception as ex:  # (an older library run beside the tree by the A/B scripts: no such fields)
             return {"push_fraction": None, "closure_fraction": None, "what": f"unavailable: {ex}"}
 
-    if args.lean:
+    if not args.full:
+        invariants = other_phase_ms = None
+    elif args.lean:
         invariants, other_phase_ms = {"push_fraction": None, "closure_fraction": None, "what": "not taken (--lean)"}, None
     elif args.phase == "locked":
         stagger()
@@ -480,77 +538,124 @@ def main():
     if launched:
         dist.all_reduce(w, op=dist.ReduceOp.MAX)  # every region: the slowest rank's time
     walls, walls_closed = ([float(x) for x in row] for row in w.cpu())
-    order = sorted(range(reps), key=lambda i: walls[i])
-    wall = walls[order[reps // 2]]
-    ev_ms = sorted(ev_regions, key=max)[len(ev_regions) // 2]
-    # every rank's own kernel time per step (N > 1: the line reports rank 0's roofline; the spread over the ranks beside it)
-    k_rank = torch.tensor([max(ev_ms) / args.steps], device=cdev, dtype=torch.float64)
-    k_all = [k_rank.clone() for _ in range(world)] if launched else [k_rank]
-    if launched:
-        dist.all_gather(k_all, k_rank)
-    k_ranks = [float(x.item()) for x in k_all]
-    # ---- logging collective: one all-gather of finished-episode returns / lengths (RCCL over xGMI when N > 1) ------------------
-    t1 = time.perf_counter()
-    off = 0
-    for g in groups:
-        g.batch.get_dev("last_ep_return", ret[off:off + g.E].data_ptr())  # device-side unpack, no host round trip
-        g.batch.get_dev("last_ep_len", ln[off:off + g.E].data_ptr())
-        off += g.E
-    sync()
-    gather_how = "torch.distributed all_gather_into_tensor" if launched else None
-    r_all = n_all = None
-    if args.gather == "capi" and launched and args.backend == "nccl" and len(groups) == 1:
-        # the same gather without PyTorch's collectives: rank 0 makes the RCCL id, the launcher's store hands it round, every rank
-        # creates its communicator and the library issues one ncclAllGather on the handle's stream
-        # Every stage is agreed on by ALL ranks before anybody acts on it (an all_reduce(MIN) of an ok flag): a rank that failed
-        # alone would otherwise sit in the torch gather while the others sit in ncclAllGather.
-        import ctypes as C
+    wall = walls[0]  # the headline: the first region, exactly --steps launches
+    if args.full:
+        ev_ms = sorted(ev_regions, key=max)[len(ev_regions) // 2]
+        # every rank's own kernel time per step (N > 1: the line reports rank 0's roofline; the spread over the ranks beside it)
+        k_rank = torch.tensor([max(ev_ms) / args.steps], device=cdev, dtype=torch.float64)
+        k_all = [k_rank.clone() for _ in range(world)] if launched else [k_rank]
+        if launched:
+            dist.all_gather(k_all, k_rank)
+        k_ranks = [float(x.item()) for x in k_all]
+        # ---- logging collective: one all-gather of finished-episode returns / lengths (RCCL over xGMI when N > 1) --------------
+        t1 = time.perf_counter()
+        off = 0
+        for g in groups:
+            g.batch.get_dev("last_ep_return", ret[off:off + g.E].data_ptr())  # device-side unpack, no host round trip
+            g.batch.get_dev("last_ep_len", ln[off:off + g.E].data_ptr())
+            off += g.E
+        sync()
+        gather_how = "torch.distributed all_gather_into_tensor" if launched else None
+        r_all = n_all = None
+        if args.gather == "capi" and launched and args.backend == "nccl" and len(groups) == 1:
+            # the same gather without PyTorch's collectives: rank 0 makes the RCCL id, the launcher's store hands it round, every rank
+            # creates its communicator and the library issues one ncclAllGather on the handle's stream
+            # Every stage is agreed on by ALL ranks before anybody acts on it (an all_reduce(MIN) of an ok flag): a rank that failed
+            # alone would otherwise sit in the torch gather while the others sit in ncclAllGather.
+            import ctypes as C
 
-        from fleetrl_amd import _capi
+            from fleetrl_amd import _capi
 
-        def all_ok(ok: bool) -> bool:
-            flag = torch.tensor([1 if ok else 0], device=cdev, dtype=torch.int32)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            return bool(flag.item())
+            def all_ok(ok: bool) -> bool:
+                flag = torch.tensor([1 if ok else 0], device=cdev, dtype=torch.int32)
+                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+                return bool(flag.item())
 
-        lib = groups[0].batch.lib
-        comm = C.c_void_p()
-        why = None
-        try:
-            uid = (C.c_char * 128)()
-            ok = True
-            if rank == 0 and lib.fleet_rccl_unique_id(uid) != _capi.OK:
-                ok, why = False, lib.fleet_last_error(None).decode()
-            box = [bytes(uid) if ok else None]
-            dist.broadcast_object_list(box, src=0)
-            ok = box[0] is not None
-            if ok and lib.fleet_rccl_comm_create(local_rank, world, rank, box[0], C.byref(comm)) != _capi.OK:
-                ok, why = False, lib.fleet_last_error(None).decode()
-            if all_ok(ok):  # every rank holds a communicator: the collective can be entered
-                out = torch.zeros((world, 2, E), device=dev, dtype=torch.float64)
-                ok = lib.fleet_gather_episode_stats_rccl(groups[0].batch.h, comm, world, C.c_void_p(out.data_ptr())) == _capi.OK
-                if not ok:
-                    why = lib.fleet_last_error(groups[0].batch.h).decode()
-                sync()
-                if all_ok(ok):
-                    r_all, n_all = out[:, 0, :].reshape(-1), out[:, 1, :].reshape(-1).to(torch.int32)
-                    gather_how = "fleet_gather_episode_stats_rccl: one ncclAllGather issued by the C ABI"
-            if r_all is None:
-                gather_how = f"torch.distributed all_gather_into_tensor (the C-ABI gather failed on some rank: {why or 'another rank'})"
-        finally:
-            if comm:
-                lib.fleet_rccl_comm_destroy(comm)
-    if r_all is None:
-        r_all, n_all = gather_episode_stats(ret.to(cdev), ln.to(cdev), equal_shards=True)
-    barrier()
-    gather_ms = (time.perf_counter() - t1) * 1e3
-    check = os.environ.get("FLEET_BENCH_NO_ERRCHECK") != "1"  # diagnostics only (tools/ab_noerr.sh: ablation builds)
+            lib = groups[0].batch.lib
+            comm = C.c_void_p()
+            why = None
+            try:
+                uid = (C.c_char * 128)()
+                ok = True
+                if rank == 0 and lib.fleet_rccl_unique_id(uid) != _capi.OK:
+                    ok, why = False, lib.fleet_last_error(None).decode()
+                box = [bytes(uid) if ok else None]
+                dist.broadcast_object_list(box, src=0)
+                ok = box[0] is not None
+                if ok and lib.fleet_rccl_comm_create(local_rank, world, rank, box[0], C.byref(comm)) != _capi.OK:
+                    ok, why = False, lib.fleet_last_error(None).decode()
+                if all_ok(ok):  # every rank holds a communicator: the collective can be entered
+                    out = torch.zeros((world, 2, E), device=dev, dtype=torch.float64)
+                    ok = lib.fleet_gather_episode_stats_rccl(groups[0].batch.h, comm, world, C.c_void_p(out.data_ptr())) == _capi.OK
+                    if not ok:
+                        why = lib.fleet_last_error(groups[0].batch.h).decode()
+                    sync()
+                    if all_ok(ok):
+                        r_all, n_all = out[:, 0, :].reshape(-1), out[:, 1, :].reshape(-1).to(torch.int32)
+                        gather_how = "fleet_gather_episode_stats_rccl: one ncclAllGather issued by the C ABI"
+                if r_all is None:
+                    gather_how = f"torch.distributed all_gather_into_tensor (the C-ABI gather failed on some rank: {why or 'another rank'})"
+            finally:
+                if comm:
+                    lib.fleet_rccl_comm_destroy(comm)
+        if r_all is None:
+            r_all, n_all = gather_episode_stats(ret.to(cdev), ln.to(cdev), equal_shards=True)
+        barrier()
+        gather_ms = (time.perf_counter() - t1) * 1e3
+    check = os.environ.get("FLEET_BENCH_NO_ERRCHECK") != "1"  # diagnostics only (tools/archive/ab_noerr.sh: ablation builds)
     for g in groups:
         if check:
             g.batch.check_errors()
 
     out = None
     if rank == 0:
+        g0 = max(groups, key=lambda g: g.E * g.N)
+        fleets = "+".join(g.use_case for g in groups)
+        graph_used = use_graph == 1 and args.steps >= graph_len
+        n_queues = max(g.batch.direct_queues() for g in groups) if use_graph >= 2 else 0
+        if use_graph < 2:
+            launch_desc = launch_note + (f"hipGraph of {graph_len} launches" if graph_used else "eager") + \
+                          ": HIP's launches, an agent-scope release (L2 write-back) at every kernel boundary; CLOSED LOOP: every step's " \
+                          "outputs are visible before the next step starts"
+        else:
+            launch_desc = ("AQL packets written by the library into " + ("an HSA queue" if n_queues < 2 else "two HSA queues") + " of its own "
+                           "(FLEET_LAUNCH_DIRECT): every launch invalidates the per-CU caches, only the last launch of a region writes the "
+                           "dies' L2s back (the env state stays there from step to step; every region records the queue's workgroup -> die "
+                           "placement and every launch checks the die it runs on against it); OPEN LOOP: a step's outputs are visible after "
+                           "the region only (tape replay)" +
+                           ("; the batch as two ranges of workgroups, one in-order chain per queue" if n_queues == 2 else ""))
+        out = {
+            "metric": "env-steps/sec (num_envs x EVs batch, 1 launch per step)",
+            "value": world * E * args.steps / wall,
+            "unit": "env-steps/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": wall * 1e3 / args.steps,
+            # how `ms_per_step` / `value` were taken
+            "timing": f"one region of exactly {args.steps} launches, barrier + synchronize on both sides, the wait inside the region "
+                      "spins on hipStreamQuery"
+                      + ("; a rank's span ends when its own device is idle (MAX over ranks), the closing barrier follows" if launched else ""),
+            **({"ms_per_step_incl_closing_barrier": walls_closed[0] * 1e3 / args.steps} if launched else {}),
+            "errcheck": check,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic", "full": args.full,
+            "config": {"workload": f"{E} envs x {N} EVs per GPU, {fleets} fleet{'s (one third each)' if len(groups) > 1 else ''}, "
+                                   f"{'load+pv' if spec['building'] and spec['pv'] else 'price-only'} obs, {spec['deg']} degradation, "
+                                   f"{'spot_2021-like prices + fixed feed-in tariff, ' if spec['price_year'] == '2021' else ''}"
+                                   f"48 h episodes, random start rows, auto-reset ({spec['what']})"
+                                   + ("; NOTE: 2048 envs per GPU are two wavefronts per SIMD -- the launch is latency-bound (0.17 of the "
+                                      "roof), a multi-GPU run of this config scales while every GPU idles" if args.config == "c4" else ""),
+                       "name": args.config, "envs_per_gpu": E, "evs_per_env": N, "obs_dim": g0.batch.obs_dim,
+                       "groups": [{"use_case": g.use_case, "envs": g.E} for g in groups],
+                       "launch": launch_desc, "launch_mode": launch_mode, "launches_per_step": len(groups) * max(1, n_queues), "prime_steps": args.prime_steps,
+                       "closed_loop": use_graph < 2,  # every step's outputs are visible before the next step starts
+                       "action_tape": f"{L} independent rows x {E * N * 4 / 2**20:.2f} MB of float32 actions resident in HBM, replayed cyclically",
+                       "episode_phase": (f"staggered: episode ages uniform over the {S_ep} steps of an episode, every launch ends "
+                                         f"~1/{S_ep} of the episodes (--phase staggered)" if args.phase == "staggered" else
+                                         f"locked: all envs in the same episode step, one launch in {S_ep} resets every env -- the "
+                                         "reference's vec env by construction (--phase locked)"),
+                       "ev_steps_per_s": world * E * N * args.steps / wall},
+        }
+    if rank == 0 and args.full:
         # dominant kernel: fleet_step_kernel, one launch per step and group.  Average launch duration: HIP events on the
         # kernels' streams around the timed region -- or, for the library's own queue, the dispatch timestamps of the region's
         # first and last packet (start of the first launch to end of the last) -- divided by the launches (the gaps between
@@ -559,7 +664,6 @@ def main():
         k_ms = max(ev_ms) / args.steps
         bytes_launch = sum(g.bytes_step * g.E for g in groups)
         achieved = bytes_launch / (k_ms * 1e-3) / 1e9
-        g0 = max(groups, key=lambda g: g.E * g.N)
         per = [float("nan")] if args.lean else g0.batch.time_steps_dev(min(args.steps, 512), g0.tape.data_ptr(), g0.L, g0.obs.data_ptr(),
                                                                         g0.reward.data_ptr(), g0.done.data_ptr())
         # K-steps-per-launch entry (open-loop rollouts), reported aside
@@ -582,22 +686,8 @@ def main():
         del ktape
         if check:
             g0.batch.check_errors()
-        fleets = "+".join(g.use_case for g in groups)
         traffic, traffic_source = (committed_traffic(args.config, E, N, launch_mode) if not (args.deg or args.use_case)
                                    else (None, "diagnostic override of the workload"))
-        graph_used = use_graph == 1 and args.steps >= graph_len
-        n_queues = max(g.batch.direct_queues() for g in groups) if use_graph >= 2 else 0
-        if use_graph < 2:
-            launch_desc = launch_note + (f"hipGraph of {graph_len} launches" if graph_used else "eager") + \
-                          ": HIP's launches, an agent-scope release (L2 write-back) at every kernel boundary; CLOSED LOOP: every step's " \
-                          "outputs are visible before the next step starts"
-        else:
-            launch_desc = ("AQL packets written by the library into " + ("an HSA queue" if n_queues < 2 else "two HSA queues") + " of its own "
-                           "(FLEET_LAUNCH_DIRECT): every launch invalidates the per-CU caches, only the last launch of a region writes the "
-                           "dies' L2s back (the env state stays there from step to step; every region records the queue's workgroup -> die "
-                           "placement and every launch checks the die it runs on against it); OPEN LOOP: a step's outputs are visible after "
-                           "the region only (tape replay)" +
-                           ("; the batch as two ranges of workgroups, one in-order chain per queue" if n_queues == 2 else ""))
 
         def path_line(kms):
             a = bytes_launch / (kms * 1e-3) / 1e9
@@ -606,38 +696,13 @@ def main():
         paths = {}
         for name, v in other_paths.items():
             paths[name] = dict(path_line(v["kernel_ms"]), what=v["what"]) if v["kernel_ms"] else v
-        out = {
-            "metric": "env-steps/sec (num_envs x EVs batch, 1 launch per step)",
-            "value": world * E * args.steps / wall,
-            "unit": "env-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": wall * 1e3 / args.steps,
-            "reps": reps, "ms_per_step_min": min(walls) * 1e3 / args.steps, "ms_per_step_max": max(walls) * 1e3 / args.steps,
-            # how `ms_per_step` / `value` were taken (not comparable with rounds 1-2, which timed ONE region with a blocking sync)
-            "timing": f"median of {reps} back-to-back regions of exactly {args.steps} launches each, barrier + synchronize on both "
-                      "sides, the wait inside a region spins on hipStreamQuery"
-                      + ("; a rank's span ends when its own device is idle (MAX over ranks), the closing barrier follows" if launched else ""),
-            **({"ms_per_step_incl_closing_barrier": sorted(walls_closed)[reps // 2] * 1e3 / args.steps} if launched else {}),
-            "errcheck": check,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{E} envs x {N} EVs per GPU, {fleets} fleet{'s (one third each)' if len(groups) > 1 else ''}, "
-                                   f"{'load+pv' if spec['building'] and spec['pv'] else 'price-only'} obs, {spec['deg']} degradation, "
-                                   f"{'spot_2021-like prices + fixed feed-in tariff, ' if spec['price_year'] == '2021' else ''}"
-                                   f"48 h episodes, random start rows, auto-reset ({spec['what']})"
-                                   + ("; NOTE: 2048 envs per GPU are two wavefronts per SIMD -- the launch is latency-bound (0.17 of the "
-                                      "roof), a multi-GPU run of this config scales while every GPU idles" if args.config == "c4" else ""),
-                       "name": args.config, "envs_per_gpu": E, "evs_per_env": N, "obs_dim": g0.batch.obs_dim,
-                       "groups": [{"use_case": g.use_case, "envs": g.E} for g in groups],
-                       "launch": launch_desc, "launch_mode": launch_mode, "launches_per_step": len(groups) * max(1, n_queues), "prime_ms": args.prime_ms,
-                       "closed_loop": use_graph < 2,  # every step's outputs are visible before the next step starts
-                       "action_tape": f"{L} independent rows x {E * N * 4 / 2**20:.2f} MB of float32 actions resident in HBM, replayed cyclically",
-                       "episode_phase": (f"staggered: episode ages uniform over the {S_ep} steps of an episode, every launch ends "
-                                         f"~1/{S_ep} of the episodes (--phase staggered)" if args.phase == "staggered" else
-                                         f"locked: all envs in the same episode step, one launch in {S_ep} resets every env -- the "
-                                         "reference's vec env by construction (--phase locked)"),
-                       "workload_invariants": invariants,
-                       "ev_steps_per_s": world * E * N * args.steps / wall},
+        regions_ms = sorted(x * 1e3 / args.steps for x in walls)
+        out["timing"] += (f"; {reps - 1} more such regions back to back after it: the median, fastest and slowest of all {reps} "
+                          "beside it (ms_per_step_median / _min / _max)")
+        out["config"]["workload_invariants"] = invariants
+        out.update({
+            "reps": reps, "ms_per_step_median": regions_ms[reps // 2], "ms_per_step_min": regions_ms[0], "ms_per_step_max": regions_ms[-1],
+            **({"ms_per_step_incl_closing_barrier_median": sorted(walls_closed)[reps // 2] * 1e3 / args.steps} if launched else {}),
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_source": traffic_source,
                          "kernel": kernel_name(N, spec["deg"]), "kernel_ms": k_ms,
@@ -660,7 +725,7 @@ def main():
                           "GBps": (g0.bytes_step - 4 * g0.batch.obs_dim * (K - 1) / K) * g0.E * K * many_reps / (many_ms * 1e-3) / 1e9},
             "log_gather_ms": gather_ms, "collective_backend": (args.backend if launched else None), "log_gather": gather_how,
             "episodes_gathered": int((n_all > 0).sum().item()),
-        }
+        })
         if not args.no_host_path and world == 1:
             out["host_path"] = host_path(g0, groups)
         if not args.no_cpu_baseline and world == 1:  # the CPU leg is a single-GPU-run item (the other ranks would idle)
@@ -670,6 +735,8 @@ def main():
     if launched:
         dist.barrier()
         dist.destroy_process_group()
+    if outputs is not None:
+        out["outputs"] = dump_outputs(outputs, args.dump_outputs)
     if out is not None:
         print(json.dumps(out))
 

@@ -42,11 +42,13 @@ def _prepare_imports():
     warnings.filterwarnings("ignore")
 
 
-def base_config() -> dict:
-    with open(os.path.join(REFERENCE_ROOT, "config.json")) as f:
+def base_config(config_path: str | None = None, data_path: str | None = None) -> dict:
+    """The reference's config.json with the harness's settings; the tests pass the copy stored under tests/golden/inputs and the
+    directory they unpacked the stored input CSVs into."""
+    with open(config_path or os.path.join(REFERENCE_ROOT, "config.json")) as f:
         cfg = json.load(f)
     cfg.update(
-        data_path=os.path.join(REFERENCE_ROOT, "inputs"),
+        data_path=data_path or os.path.join(REFERENCE_ROOT, "inputs"),
         price_name="spot_2020_new.csv",
         tariff_name="spot_2020_new_tariff.csv",
         include_price=True,

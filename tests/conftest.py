@@ -19,3 +19,11 @@ def pytest_collection_modifyitems(config, items):
     for item in items:
         if "reference" in item.keywords and not have_ref:
             item.add_marker(skip_ref)
+
+
+@pytest.fixture(scope="session")
+def reference_inputs(tmp_path_factory):
+    """A `data_path` holding the reference's input CSVs, unpacked once per session from tests/golden/inputs."""
+    from golden_util import unpack_reference_inputs
+
+    return unpack_reference_inputs(str(tmp_path_factory.mktemp("reference_inputs")))

@@ -23,6 +23,32 @@ TRACE_NAMES = sorted(os.path.basename(p)[len("trace_"):-len(".npz")] for p in gl
 
 RT_TRACE_NAMES = sorted(os.path.basename(p)[len("rttrace_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN_DIR, "rttrace_*.npz")))
 
+# The reference's input CSVs the pre-stager tests read, stored xz-compressed (byte-identical once unpacked), and its config.json.
+# The reference ships each single-EV schedule under two names; the copies are made from the one stored file.
+INPUTS_DIR = os.path.join(GOLDEN_DIR, "inputs")
+_INPUT_ALIASES = {"ct_sched_single.csv": "1_ct.csv", "lmd_sched_single.csv": "1_lmd.csv", "ut_sched_single.csv": "1_ut.csv"}
+
+
+def unpack_reference_inputs(dest: str) -> str:
+    """Write the stored input CSVs into `dest` under the reference's file names; returns `dest` (a `data_path`)."""
+    import lzma
+    import shutil
+
+    for f in sorted(os.listdir(INPUTS_DIR)):
+        if f.endswith(".csv.xz"):
+            with lzma.open(os.path.join(INPUTS_DIR, f)) as src, open(os.path.join(dest, f[:-len(".xz")]), "wb") as dst:
+                shutil.copyfileobj(src, dst)
+    for alias, f in _INPUT_ALIASES.items():
+        shutil.copyfile(os.path.join(dest, f), os.path.join(dest, alias))
+    return dest
+
+
+def reference_base_config(data_path: str) -> dict:
+    """oracle.ref_harness.base_config() on the stored config.json, reading its inputs from `data_path`."""
+    from oracle import ref_harness
+
+    return ref_harness.base_config(os.path.join(INPUTS_DIR, "config.json"), data_path)
+
 
 def load_trace(name: str, prefix: str = "trace_") -> SimpleNamespace:
     z = np.load(os.path.join(GOLDEN_DIR, f"{prefix}{name}.npz"), allow_pickle=False)

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ def _json_line(out: str) -> dict:
 
 
 def test_bench_json_contract_single_gpu():
-    res = subprocess.run([sys.executable, "bench.py", "--steps", "300", "--warmup", "20", "--envs-per-gpu", "512", "--prime-ms", "50"],
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "300", "--warmup", "20", "--envs-per-gpu", "512", "--prime-steps", "8192"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     d = _json_line(res.stdout)
@@ -55,8 +56,8 @@ def test_bench_json_contract_single_gpu():
 
 
 def test_bench_through_a_replayed_hipgraph():
-    res = subprocess.run([sys.executable, "bench.py", "--launch", "graph", "--steps", "300", "--warmup", "20", "--envs-per-gpu", "512",
-                          "--prime-ms", "50", "--no-cpu-baseline", "--no-host-path"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    res = subprocess.run([sys.executable, "bench.py", "--full", "--launch", "graph", "--steps", "300", "--warmup", "20", "--envs-per-gpu", "512",
+                          "--prime-steps", "8192", "--no-cpu-baseline", "--no-host-path"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     d = _json_line(res.stdout)
     assert d["config"]["launch"].startswith("hipGraph of 64 launches") and d["config"]["launch_mode"] == "graph" and d["roofline"]["kernel_ms"] > 0
@@ -69,7 +70,7 @@ def test_bench_workload_invariants_agree_across_shapes():
     round 5 had made the large shapes another workload -- batteries saturated, the push dropped out)."""
     inv = {}
     for name, extra in (("c3", ["--config", "c3"]), ("16384x50", ["--config", "c3", "--envs-per-gpu", "16384"]), ("c5", ["--config", "c5"])):
-        res = subprocess.run([sys.executable, "bench.py", *extra, "--steps", "64", "--warmup", "20", "--prime-ms", "50", "--reps", "3",
+        res = subprocess.run([sys.executable, "bench.py", "--full", *extra, "--steps", "64", "--warmup", "20", "--prime-steps", "8192", "--reps", "3",
                               "--no-cpu-baseline", "--no-host-path"], cwd=ROOT, capture_output=True, text=True, timeout=900)
         assert res.returncode == 0, res.stderr[-2000:]
         d = _json_line(res.stdout)
@@ -84,8 +85,8 @@ def test_bench_workload_invariants_agree_across_shapes():
 def test_bench_two_ranks_on_one_gpu_over_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "400", "--warmup", "50", "--envs-per-gpu", "768",
-           "--backend", "gloo", "--device-index", "0", "--prime-ms", "50"]
+           "--master-port", "29533", "bench.py", "--full", "--gpus", "2", "--steps", "400", "--warmup", "50", "--envs-per-gpu", "768",
+           "--backend", "gloo", "--device-index", "0", "--prime-steps", "8192"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)  # the launcher itself never touches the GPU
     assert res.returncode == 0, res.stderr[-3000:]
     d = _json_line(res.stdout)
@@ -100,8 +101,8 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
 def test_bench_plain_python_starts_its_own_ranks():
     """What the driver runs for N > 1 when it has no launcher of its own: `python bench.py --gpus 2`.  bench.py starts
     torch.distributed.run as a child process before anything touches the GPU and relays the single JSON line."""
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "200", "--warmup", "20", "--envs-per-gpu", "512",
-           "--backend", "gloo", "--device-index", "0", "--prime-ms", "50"]
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "200", "--warmup", "20", "--envs-per-gpu", "512",
+           "--backend", "gloo", "--device-index", "0", "--prime-steps", "8192"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -115,8 +116,8 @@ def test_bench_rccl_branch_with_one_rank():
     all_reduce(MAX) of the region times and the all-gather of episode returns execute on RCCL."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29547", "bench.py", "--gpus", "1", "--steps", "200", "--warmup", "20", "--envs-per-gpu", "512",
-           "--backend", "nccl", "--prime-ms", "50", "--no-cpu-baseline", "--no-host-path"]
+           "--master-port", "29547", "bench.py", "--full", "--gpus", "1", "--steps", "200", "--warmup", "20", "--envs-per-gpu", "512",
+           "--backend", "nccl", "--prime-steps", "8192", "--no-cpu-baseline", "--no-host-path"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     d = _json_line(res.stdout)
@@ -133,8 +134,8 @@ def test_bench_eight_ranks_on_one_gpu_over_gloo():
     """The driver's 8-GPU run executes `shard_range`, env-id offsets, the build lock and the gather of eight shards for the first
     time; here the same control flow with eight ranks sharing the one GPU (gloo: RCCL refuses several ranks per device), as
     plain `python bench.py --gpus 8` (self-launch) on BASELINE configs[3]'s fleet type: every rank's finished episodes arrive."""
-    cmd = [sys.executable, "bench.py", "--gpus", "8", "--config", "c4", "--steps", "260", "--warmup", "20", "--envs-per-gpu", "256",
-           "--backend", "gloo", "--device-index", "0", "--prime-ms", "20", "--reps", "3"]
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "8", "--config", "c4", "--steps", "260", "--warmup", "20", "--envs-per-gpu", "256",
+           "--backend", "gloo", "--device-index", "0", "--prime-steps", "4096", "--reps", "3"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=1500, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
@@ -142,3 +143,31 @@ def test_bench_eight_ranks_on_one_gpu_over_gloo():
     assert d["n_gpus"] == 8 and d["collective_backend"] == "gloo" and d["config"]["envs_per_gpu"] == 256
     assert d["episodes_gathered"] == 8 * 256
     assert abs(d["value"] - 8 * 256 * 260 / (d["ms_per_step"] * 260 * 1e-3)) / d["value"] < 1e-9  # whole-job aggregate
+
+
+def test_bench_plain_run_is_lean_and_its_outputs_repeat(tmp_path):
+    """A plain run prints the headline and nothing that needs runs of its own; `--dump-outputs` writes what the timed launches
+    computed in their last step, and two runs with the same arguments write the same arrays."""
+    dumps = []
+    for k in range(2):
+        out_dir = tmp_path / f"run{k}"
+        res = subprocess.run([sys.executable, "bench.py", "--steps", "150", "--warmup", "10", "--envs-per-gpu", "512",
+                              "--prime-steps", "4096", "--dump-outputs", str(out_dir)],
+                             cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        d = _json_line(res.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["full"] is False and d["steps"] == 150 and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] - 512 * 150 / (d["ms_per_step"] * 150 * 1e-3)) / d["value"] < 1e-9
+        for key in ("roofline", "cpu_baseline", "host_path", "step_many", "episodes_gathered", "reps"):
+            assert key not in d, key
+        assert sorted(d["outputs"]) == ["done", "obs", "reward"]
+        arrays = {n: np.load(out_dir / f"{n}.npy") for n in d["outputs"]}
+        assert arrays["obs"].dtype == np.float32 and arrays["obs"].shape == (512, d["config"]["obs_dim"])
+        assert arrays["reward"].dtype == np.float64 and arrays["reward"].shape == (512,)
+        assert arrays["done"].dtype == np.float32 and set(np.unique(arrays["done"])) <= {0.0, 1.0}
+        assert np.isfinite(arrays["obs"]).all() and np.isfinite(arrays["reward"]).all()
+        dumps.append(arrays)
+    for n in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][n], dumps[1][n], err_msg=n)

@@ -73,3 +73,29 @@ def test_every_baseline_config_has_a_bench_mode():
     assert bench.CONFIGS["c3"]["envs"] == 4096 and bench.CONFIGS["c3"]["evs"] == 50
     assert bench.CONFIGS["c5"]["groups"] == ("lmd", "ct", "ut") and bench.CONFIGS["c5"]["envs"] * 8 == 65536
     assert bench.CONFIGS["c4"]["envs"] * 8 == 16384 and bench.CONFIGS["c2"]["deg"] == "linear"
+
+
+def test_dump_outputs_writes_every_array_and_samples_env_rows_over_the_limit(tmp_path):
+    import numpy as np
+
+    rng = np.random.default_rng(3)
+    arrays = {"obs_0_lmd": rng.random((300, 40), dtype=np.float32), "reward_0_lmd": rng.random(300),
+              "obs_1_ct": rng.random((200, 60), dtype=np.float32), "reward_1_ct": rng.random(200)}
+    small = bench.dump_outputs(dict(arrays), str(tmp_path / "all"))
+    assert sorted(small) == sorted(arrays)
+    for n, a in arrays.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "all" / f"{n}.npy"), a)
+    limit = 40_000
+    names = bench.dump_outputs(dict(arrays), str(tmp_path / "cut"), limit=limit)
+    assert sorted(names) == sorted([*arrays, "env_index_0_lmd", "env_index_1_ct"])
+    got = {n: np.load(tmp_path / "cut" / f"{n}.npy") for n in names}
+    assert sum(a.nbytes for a in got.values()) <= limit
+    for tag, rows in (("_0_lmd", 300), ("_1_ct", 200)):
+        idx = got[f"env_index{tag}"]
+        assert idx.dtype == np.float64 and (np.diff(idx) > 0).all() and idx[-1] < rows
+        i = idx.astype(np.int64)
+        np.testing.assert_array_equal(got[f"obs{tag}"], arrays[f"obs{tag}"][i])
+        np.testing.assert_array_equal(got[f"reward{tag}"], arrays[f"reward{tag}"][i])
+    again = bench.dump_outputs(dict(arrays), str(tmp_path / "again"), limit=limit)  # a fixed, seeded sample
+    for n in again:
+        np.testing.assert_array_equal(np.load(tmp_path / "again" / f"{n}.npy"), got[n])

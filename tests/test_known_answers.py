@@ -1,7 +1,6 @@
 """Known-answer anchors recorded from the unmodified reference in SURVEY.md section 4 (K1-K5): whole episodes with a constant
 float64 action from the static start (2020-01-02 19:00, table row 172), summed.  Here the build's own chain -- config ->
-pre-stager (the reference's input CSVs) -> parameters -> CPU oracle -- must reproduce them.  Build container only (needs
-/root/reference/inputs)."""
+pre-stager (the reference's input CSVs, stored under tests/golden/inputs) -> parameters -> CPU oracle -- must reproduce them."""
 import numpy as np
 import pytest
 
@@ -29,13 +28,12 @@ CASES = {
 }
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize("kid", sorted(CASES))
-def test_survey_known_answers(kid):
-    from oracle import ref_harness
+def test_survey_known_answers(kid, reference_inputs):
+    from golden_util import reference_base_config
 
     ov, action, steps, want_reward, want_cash, checks = CASES[kid]
-    cfg = ref_harness.base_config()
+    cfg = reference_base_config(reference_inputs)
     cfg.update(ov)
     rc = resolve_config(cfg)
     tb = build_tables_from_config(cfg)

@@ -1,9 +1,10 @@
 """Host side of the benchmark policies: the night-charging window (`fleetrl_amd.policies.night_schedule`) against the
 reference's own expressions evaluated on the reference's own `env.db` (benchmarking/night_charging.py:50-73 cannot be
-called in isolation -- it sits inside `run_benchmark`, which needs SB3 -- so the test evaluates the same pandas
-expressions on a reference FleetEnv built here; build container only), and the rule restatement of the oracle
-against hand-checked cases."""
-import math
+called in isolation -- it sits inside `run_benchmark`, which needs SB3 -- so oracle/gen_night_schedule.py evaluated the same
+pandas expressions on a reference FleetEnv and stored what they gave in tests/golden/night_schedule_reference.json), and the
+rule restatement of the oracle against hand-checked cases."""
+import json
+import os
 
 import numpy as np
 import pytest
@@ -12,36 +13,26 @@ from fleetrl_amd.policies import night_schedule
 from oracle.fleet_oracle import NightChargingRule
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize("use_case,sched", [("lmd", "lmd_sched_single.csv"), ("ct", "ct_sched_single.csv"), ("ut", "ut_sched_single.csv")])
-def test_night_schedule_matches_reference_expressions(use_case, sched):
-    from oracle import ref_harness
+def test_night_schedule_matches_reference_expressions(use_case, sched, reference_inputs):
     from fleetrl_amd.prestage import build_tables_from_config
+    from golden_util import GOLDEN_DIR, reference_base_config
 
+    with open(os.path.join(GOLDEN_DIR, "night_schedule_reference.json")) as f:
+        want = json.load(f)[use_case]
     ov = dict(use_case=use_case, schedule_name=sched, include_building=False, include_pv=False, deg_emp=True)
-    env = ref_harness.make_ref_env(ov)
-    df = env.db
-    # night_charging.py:52-73, verbatim semantics on the reference's frame
-    df_leaving_home = df[(df["Location"].shift() == "home") & (df["Location"] == "driving")]
-    earliest_dep_time = df_leaving_home["date"].dt.time.min()
-    earliest_dep = earliest_dep_time.hour + earliest_dep_time.minute / 60
-    evse, cap = env.load_calculation.evse_max_power, env.ev_config.init_battery_cap
-    target_soc, eff = env.ev_config.target_soc, env.ev_config.charging_eff
-    max_time_needed = target_soc * cap / eff / evse
-    starting_time = 24 + (earliest_dep - max_time_needed)
-    if starting_time > 24:
-        starting_time = 23.99
-    want_hour = int(math.modf(starting_time)[1])
-    minutes = np.asarray([0, 15, 30, 45])
-    want_minute = int(minutes[np.abs(minutes - int(math.modf(starting_time)[0] * 60)).argmin()])
+    assert want["overrides"] == ov
+    target_soc, cap, eff, evse = want["target_soc"], want["init_battery_cap"], want["charging_eff"], want["evse_power"]
+    max_time_needed = want["max_time_needed"]
+    assert max_time_needed == target_soc * cap / eff / evse
 
-    cfg = ref_harness.base_config()
+    cfg = reference_base_config(reference_inputs)
     cfg.update(ov)
     tb = build_tables_from_config(cfg)
     got = night_schedule(tb, target_soc=target_soc, init_battery_cap=cap, charging_eff=eff, evse_power=evse)
-    assert got == (want_hour, want_minute, int(max_time_needed))
-    lh = df_leaving_home["date"].dt.hour.values
-    lm = df_leaving_home["date"].dt.minute.values
+    assert got == (want["hour"], want["minute"], int(max_time_needed))
+    lh = np.asarray(want["leave_hour"])
+    lm = np.asarray(want["leave_minute"])
     ph, pm, pt = NightChargingRule.parameters(lh, lm, target_soc, cap, eff, evse)
     assert (ph, pm, int(pt)) == got
 

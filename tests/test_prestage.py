@@ -1,6 +1,6 @@
 """Pre-stager (fleetrl_amd/prestage.py) against the reference's own `db` columns stored in the golden traces.
 
-Needs the reference's input CSVs, so it only runs in the build container (marker `reference`)."""
+Reads the reference's input CSVs from the copies stored under tests/golden/inputs (fixture `reference_inputs`)."""
 import os
 
 import numpy as np
@@ -10,20 +10,16 @@ from golden_util import TRACE_NAMES, load_trace
 from fleetrl_amd.params import table_extrema
 from fleetrl_amd.prestage import build_tables_from_config, load_schedule_csv, stack_single_ev_schedules
 
-INPUTS = "/root/reference/inputs"
-
-
-@pytest.mark.reference
 @pytest.mark.parametrize("name", TRACE_NAMES)
-def test_prestage_bit_identical_to_reference_db(name):
+def test_prestage_bit_identical_to_reference_db(name, reference_inputs):
     g = load_trace(name)
     cfg = dict(g.cfg)
-    cfg["data_path"] = INPUTS
+    cfg["data_path"] = reference_inputs
     sched = None
     if g.N > 1:
         uc = "lmd" if cfg["use_case"] == "custom" else cfg["use_case"]
-        sched = stack_single_ev_schedules(load_schedule_csv(os.path.join(INPUTS, f"1_{uc}.csv")),
-                                          load_schedule_csv(os.path.join(INPUTS, f"1_{uc}_eval.csv")), g.N)
+        sched = stack_single_ev_schedules(load_schedule_csv(os.path.join(reference_inputs, f"1_{uc}.csv")),
+                                          load_schedule_csv(os.path.join(reference_inputs, f"1_{uc}_eval.csv")), g.N)
     tb = build_tables_from_config(cfg, schedule=sched)
     w0 = int(g.sc_window_row0)
     w1 = w0 + g.tables.T
@@ -60,15 +56,14 @@ def test_kahan_group_sum_matches_sequential_compensated_sum():
         assert got[gidx] == s
 
 
-@pytest.mark.reference
-def test_prestage_real_time_keeps_the_irregular_rows():
+def test_prestage_real_time_keeps_the_irregular_rows(reference_inputs):
     """real_time: no resampling (data_processing.py:54-62, 73-82); the reference's own irregular example inputs/test_lmd.csv
     against the `db` columns stored in the real_time trace made from it (window starting at row 0)."""
     from golden_util import load_rt_trace
 
     g = load_rt_trace("lmd1_both_irregular")
     cfg = dict(g.cfg)
-    cfg["data_path"] = INPUTS
+    cfg["data_path"] = reference_inputs
     tb = build_tables_from_config(cfg)
     n = g.tables.T
     assert tb.T == 35041  # one row more than a year of quarter hours: 00:07

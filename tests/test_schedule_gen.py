@@ -98,17 +98,16 @@ def test_csv_round_trip_in_the_reference_schema(tmp_path):
     np.testing.assert_allclose(back.consumption, direct.consumption, rtol=1e-14)  # pandas' default float parser is within an ulp or two (the reference reads its CSVs the same way)
 
 
-@pytest.mark.reference
-def test_gen_schedule_config_route(tmp_path):
+def test_gen_schedule_config_route(tmp_path, reference_inputs):
     """`gen_schedule=True` (fleet_environment.py:180-182, 969-992): the file is generated into data_path under gen_name and
-    becomes the schedule of the env; prices / load come from the reference's input files (container only)."""
+    becomes the schedule of the env; prices / load come from the reference's input files (stored under tests/golden/inputs)."""
     from fleetrl_amd.prestage import build_tables_from_config
-    from oracle.ref_harness import base_config
+    from golden_util import reference_base_config
 
-    src = "/root/reference/inputs"
+    src = reference_inputs
     for fn in os.listdir(src):
         os.symlink(os.path.join(src, fn), tmp_path / fn)
-    cfg = base_config()
+    cfg = reference_base_config(src)
     cfg.update(data_path=str(tmp_path), use_case="ut", gen_schedule=True, gen_name="gen_ut", gen_n_evs=4, gen_start_date="2020-01-01 00:00",
                gen_end_date="2020-12-31 23:45", building_name="load_ut.csv", include_building=True, include_pv=True, seed=4)
     assert generate_from_config(dict(cfg)) == "gen_ut.csv"

@@ -2,7 +2,7 @@
 # (phase-locked) 192-step episode: rocprofv3 --kernel-trace of `bench.py --lean`, the long back-to-back runs folded modulo the episode length
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/prof/fold; rm -rf $OUT; mkdir -p $OUT $R/gpurun_out/r06; cd $R
-rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -- python3 bench.py --no-cpu-baseline --no-host-path --lean --steps 1920 --warmup 192 "$@" > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -- python3 bench.py --full --no-cpu-baseline --no-host-path --lean --steps 1920 --warmup 192 "$@" > $OUT/bench.log 2>&1
 python3 - $OUT <<'PY' | tee $R/gpurun_out/r06/launch_by_episode_step.log
 import glob, sys
 import numpy as np, pandas as pd

@@ -7,7 +7,7 @@ TAG=$1; CNT=$2; shift; shift
 OUT=$R/gpurun_out/prof/$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd $R
-timeout 240 rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d $OUT/pmc -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-host-path "$@" > $OUT/bench.log 2>&1
+timeout 240 rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d $OUT/pmc -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-host-path "$@" > $OUT/bench.log 2>&1
 python3 - "$OUT" <<'PY'
 import glob, os, sys
 import pandas as pd

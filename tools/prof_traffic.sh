@@ -8,9 +8,9 @@ TAG=$1; shift
 OUT=$R/gpurun_out/prof/$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd $R
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --lean "$@" > $OUT/bench_fetch.log 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --lean "$@" > $OUT/bench_write.log 2>&1
-rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/l2 -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --lean "$@" > $OUT/bench_l2.log 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --lean "$@" > $OUT/bench_fetch.log 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --lean "$@" > $OUT/bench_write.log 2>&1
+rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/l2 -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --lean "$@" > $OUT/bench_l2.log 2>&1
 python3 - "$OUT" "$@" <<'PY'
 import glob, json, os, sys
 import pandas as pd

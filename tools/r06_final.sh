@@ -8,10 +8,10 @@ timeout 300 python3 -m pytest tests/test_hip_parity.py -m gpu -q -s -p no:cachep
 bash tools/r06_profiles.sh > gpurun_out/r06/profiles.log 2>&1
 cp gpurun_out/r06p/r06_traffic_*.json profiles/
 OUT=gpurun_out/r06p
-timeout 300 python3 bench.py > $OUT/r06_bench_default.json 2> $OUT/bench2.err
-timeout 300 python3 bench.py --steps 20 --warmup 5 > $OUT/r06_bench_default_20steps.json 2>> $OUT/bench2.err
-timeout 300 python3 bench.py --config c5 --no-cpu-baseline > $OUT/r06_bench_c5.json 2>> $OUT/bench2.err
-timeout 300 python3 bench.py --envs-per-gpu 16384 --no-cpu-baseline --no-host-path > $OUT/r06_bench_16384x50.json 2>> $OUT/bench2.err
+timeout 300 python3 bench.py --full > $OUT/r06_bench_default.json 2> $OUT/bench2.err
+timeout 300 python3 bench.py --full --steps 20 --warmup 5 > $OUT/r06_bench_default_20steps.json 2>> $OUT/bench2.err
+timeout 300 python3 bench.py --full --config c5 --no-cpu-baseline > $OUT/r06_bench_c5.json 2>> $OUT/bench2.err
+timeout 300 python3 bench.py --full --envs-per-gpu 16384 --no-cpu-baseline --no-host-path > $OUT/r06_bench_16384x50.json 2>> $OUT/bench2.err
 for f in default default_20steps c5 16384x50; do python3 -c "
 import json; d=json.loads(open('$OUT/r06_bench_$f.json').read().strip().splitlines()[-1]); r=d['roofline']; print('$f', 'ms/step %.4f'%d['ms_per_step'], 'kernel_ms %.4f frac %.3f'%(r['kernel_ms'],r['frac']), 'traffic', r['traffic'], 'many %.3e'%d['step_many']['env_steps_per_s'])"; done
 cat gpurun_out/r06/gpu_tests.txt; head -3 gpurun_out/r06/obs_words_identical.txt

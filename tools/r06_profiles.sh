@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r06p
 rm -rf $OUT; mkdir -p $OUT
 cd $R
-B="timeout 300 python3 bench.py"
+B="timeout 300 python3 bench.py --full"
 $B > $OUT/r06_bench_default.json 2> $OUT/bench.err
 $B --steps 20 --warmup 5 > $OUT/r06_bench_default_20steps.json 2>> $OUT/bench.err
 for c in c2 c4 c5; do $B --config $c --no-cpu-baseline > $OUT/r06_bench_$c.json 2>> $OUT/bench.err; done
@@ -21,7 +21,7 @@ $B --launch graph --no-cpu-baseline --no-host-path > $OUT/r06_bench_default_grap
 $B --launch graph --steps 20 --warmup 5 --no-cpu-baseline --no-host-path > $OUT/r06_bench_default_20steps_graph.json 2>> $OUT/bench.err
 $B --phase staggered --no-cpu-baseline --no-host-path > $OUT/r06_bench_default_staggered.json 2>> $OUT/bench.err
 $B --launch direct1 --envs-per-gpu 16384 --no-cpu-baseline --no-host-path > $OUT/r06_bench_16384x50_onequeue.json 2>> $OUT/bench.err
-kt() { timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$1 -- python3 bench.py --no-cpu-baseline --no-host-path --lean "${@:2}" > $OUT/kt_$1.log 2>&1; cp $OUT/kt_$1/*/*kernel_stats.csv $OUT/r06_step_kernel_stats_$1.csv; rm -rf $OUT/kt_$1; }
+kt() { timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$1 -- python3 bench.py --full --no-cpu-baseline --no-host-path --lean "${@:2}" > $OUT/kt_$1.log 2>&1; cp $OUT/kt_$1/*/*kernel_stats.csv $OUT/r06_step_kernel_stats_$1.csv; rm -rf $OUT/kt_$1; }
 kt c3
 kt c3_graph --launch graph
 kt c2 --config c2
