@@ -117,7 +117,8 @@ class FleetBatch:
         elif bits & _capi.DEVERR_SOH_MISMATCH:
             exc = RuntimeError("Degradation calculation is not correct")
         else:
-            exc = IndexError(f"the episode runs past the last table row: {where}")
+            exc = IndexError(f"the episode runs past the last table row (or, stepped past done without auto-reset, its rainflow "
+                             f"stack outgrew the workspace of one episode): {where}")
         exc.status, exc.error_bits, exc.env, exc.detail = _capi.ERR_STATE, bits, e, f"{where}: {msg}"
         raise exc
 

@@ -129,7 +129,8 @@ struct EnvRec {
                            // fleet_environment.py:665), -1 if there is none: SOC samples logged AFTER it are never counted -- the
                            // reference's reset() clears the log (:338-339) before anybody reads them -- so the streaming count
                            // stops there (a quarter of all EV-steps with 48 h episodes).  INT32_MAX: count everything
-                           // (fleet_set_rainflow_count_all, diagnostics).  Set by reset; head bit 29 caches `t < rf_until`.
+                           // (fleet_set_rainflow_count_all, diagnostics; and without auto-reset, where the env may be stepped
+                           // past its finish row and the reference's later 14:45 rows read those samples).  Set by reset; head bit 29 caches `t < rf_until`.
   uint32_t err;            // FLEET_DEVERR_* bits
   int32_t start_done;      // [30:0] row the running episode started on (episode.start_time), [31] episode.done
   double ep_return;        // episode.cumulative_reward

@@ -480,7 +480,10 @@ __device__ __forceinline__ void rf_finish(const FleetDev& d, const EvIx& i, cons
   if (!q.push) return;
   double* row = rf_row_of(d, i);
   double* stk = row + RF_HDR_WORDS;
-  if (tail >= d.stack_cap) {  // cannot happen (pushes <= samples < stack_cap); refuse instead of overrunning
+  // Within an episode this cannot happen (pushes <= samples < stack_cap).  Past the finish row (no auto-reset) the samples keep
+  // coming while the workspace stays sized for one episode: what must fit then is the stack depth, which only a long run of
+  // ever smaller swings makes grow.  Refuse instead of overrunning -- the step that would overflow raises the error bit.
+  if (tail >= d.stack_cap) {
     err |= FLEET_DEVERR_TABLE_END;
     return;
   }
@@ -739,7 +742,9 @@ __device__ __forceinline__ void reset_ev(const FleetDev& d, int e, int c, int st
 }
 // Start row, finish row and sample count of the env's next episode (time pickers, :351-355) -- every lane of the env computes
 // them for itself (registers, no exchange).
-// `rf_until`: the last row of the new episode on which the degradation model runs (EnvRec::rf_until).
+// `rf_until`: the last row of the new episode on which the degradation model runs (EnvRec::rf_until).  Without auto-reset the
+// env may be stepped past its finish row (gymnasium.Env path: the reference keeps logging and evaluating, :655-671), so the
+// count never stops there.
 __device__ __forceinline__ int reset_times(const FleetDev& d, int e, EnvHead& r, int& rf_until) {
   const FleetCold* cd = d.cold;
   const int start = choose_start(cd, d.E, e, r.episodes);
@@ -749,7 +754,7 @@ __device__ __forceinline__ int reset_times(const FleetDev& d, int e, EnvHead& r,
   // the degradation model is evaluated on the rows (start, t_end] that carry FLEET_TFLAG_DEG; what is logged after the last of
   // them is cleared by the next reset() unread
   const int last = cd->tab_last_deg[r.t_end > d.T - 1 ? d.T - 1 : r.t_end];
-  rf_until = cd->rf_count_all ? INT32_MAX : (last > start ? last : -1);
+  rf_until = (cd->rf_count_all || !d.auto_reset) ? INT32_MAX : (last > start ? last : -1);
   return start;
 }
 // The env's part: its record (episode counters zeroed :402-404, the head with the row flags the episode's first step needs).
@@ -1143,7 +1148,10 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
     int t1 = t + 1;  // :508
     if (t1 > d.T - 1) { t1 = d.T - 1; err |= FLEET_DEVERR_TABLE_END; }
     const int t2 = t1 + 1 > d.T - 1 ? d.T - 1 : t1 + 1;  // the row the NEXT step advances to
-    const bool is_done = (t + 1 == r.t_end);  // :627-628
+    const bool is_done = (t + 1 == r.t_end);  // :627-628 -- the step that finishes the episode
+    // episode.done as step() returns it (:702): sticky until the next reset.  Only without auto-reset can a step start at or past
+    // the finish row (t_end = -1, an irregular-grid episode that never ends, compares as the largest row).
+    const bool done_now = is_done || (!d.auto_reset && (uint32_t)(t + 1) > (uint32_t)r.t_end);
     const bool resets = is_done && d.auto_reset;
     const bool rf_live = MULTI ? (t < rf_until) : head_live;  // the sample of row t + 1 is counted
     // where this step's observation goes: with vec-env auto-reset the terminal observation is reported aside
@@ -1173,9 +1181,10 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
     if (!MULTI && G >= 64 && ((DEG == FLEET_DEG_RAINFLOW && deg_row) || is_done)) __builtin_amdgcn_s_setprio(3);
     const size_t abase = ((size_t)(rt ? 0 : k) * d.E + e) * N;
 
-    // data log: the step's row (not written for the step that ends the episode, :679) -- its observation goes to the log's own
-    // buffer, so K-step launches log every step although they only return the last observation
-    const bool logs = log_on && env_ok && !is_done;
+    // data log: the step's row (not written for the step that ends the episode nor for any step past it, :679: `episode.done` is
+    // sticky) -- its observation goes to the log's own buffer, so K-step launches log every step although they only return the
+    // last observation
+    const bool logs = log_on && env_ok && !done_now;
     const size_t lrow = logs ? (size_t)(lp % d.log_cap) * d.E + e : 0;
     float* const log_obs_row = logs ? d.log_obs + lrow * d.obs_dim : nullptr;
 
@@ -1414,7 +1423,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
         d.env[e].cashflow = cash;  // cashflow = -charging_cost + discharging_revenue (ev_charger.py:225)
         if (!MULTI) {
           reward[e] = rew;
-          done[e] = is_done ? 1 : 0;
+          done[e] = done_now ? 1 : 0;
         }
       }
     }
@@ -1476,10 +1485,11 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
         penalty_record = 0.0;
       }
     }
+    last_done = done_now;
     if (rt) {
       // EventManager.check_event (event_manager.py:16-31): the advanced row's clock minute == 15 is an event of its own;
-      // the end of the episode is one (:629); running off the table ends the loop (the reference would raise there)
-      last_done = is_done;
+      // the end of the episode is one (:629) -- a step past it is not; running off the table ends the loop (the reference
+      // would raise there)
       const int hm1 = d.cold->tab_hm[t1];
       const bool minute15 = ((hm1 & 255) == 15) && !(hm1 & 0x8000);  // minute == 15 and second == 0
       if (group_any<G>(ev_lane) || is_done || minute15 || (t + 1 > d.T - 1)) break;
@@ -1507,7 +1517,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
     if (log_on) d.log_pos[e] = lp;
     if (MULTI) {
       reward[e] = rt ? last_rew : reward_sum;
-      if (done && (rt || steps == 1)) done[e] = (rt ? last_done : (n_done != 0)) ? 1 : 0;  // one agent step: its done flag
+      if (done && (rt || steps == 1)) done[e] = last_done ? 1 : 0;  // one agent step: its done flag
       if (done_count) done_count[e] = n_done;
       if (kPol && act_mode == FLEET_ACT_POLICY_NIGHT) d.cold->night_start[e] = night_st;
     }

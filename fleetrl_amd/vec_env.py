@@ -361,7 +361,11 @@ class FleetEnv(_GymEnv):
         return obs[0], self.info
 
     def step(self, actions):
-        """:436-702 -> (obs float32[obs_dim], reward float, done bool, truncated False, info {})."""
+        """:436-702 -> (obs float32[obs_dim], reward float, done bool, truncated False, info {}).
+
+        No auto-reset: after the finish row the env may be stepped on, as the reference allows.  `done` then stays True (and
+        `is_done()` with it) until reset(); the degradation log keeps growing and each 14:45 row evaluates it, so SoH moves
+        and carries into the next episode; get_log() gets no rows past done."""
         a = np.asarray(actions)
         a = a.reshape(1, -1) if a.dtype == np.float64 else a.astype(np.float32).reshape(1, -1)
         obs, rew, done, _ = self.core.batch.step(a)

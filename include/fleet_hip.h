@@ -98,7 +98,12 @@ typedef struct FleetParams {
   int32_t start_lo;         /* inclusive */
   int32_t start_hi;         /* inclusive */
   int32_t auto_reset;       /* 1: VecEnv semantics (done envs are reset inside the step, terminal obs reported)
-                               0: gymnasium.Env semantics (obs of a done env is its terminal obs)           */
+                               0: gymnasium.Env semantics (obs of a done env is its terminal obs).  An env may be
+                               stepped past its finish row until reset: done stays 1 (episode.done is sticky,
+                               fleet_environment.py:627-628, :702), the SOC log keeps growing and its 14:45 rows
+                               evaluate the degradation model, the data log writes nothing (:679).  The rainflow
+                               stack workspace holds episode_steps + 3 entries: a run past done whose stack outgrows
+                               it sets FLEET_DEVERR_TABLE_END in that step instead of returning a wrong result */
   int32_t env_id_offset;    /* global index of env 0 of this handle (multi-GPU sharding keeps RNG streams env-stable) */
   int32_t log_data;         /* 1: device-side data log -- every row the reference's DataLogger would get
                                (utils/data_logger/data_logger.py:21-68; call sites fleet_environment.py:420-432, 659-690) is
@@ -211,7 +216,7 @@ typedef struct FleetEnvBatch* fleet_handle;
 #define FLEET_F_RF_STACK 22      /* i32 [E,N] reversal points on the EV's rainflow stack (bench.py derives the share of EV-steps that
                                     push a reversal point / close a cycle from the two: the workload's invariants)               */
 #define FLEET_F_RF_UNTIL 23      /* i32 [E]   the last table row of the running episode on which the degradation model is evaluated
-                                    (-1: none; INT32_MAX after fleet_set_rainflow_count_all): SOC samples logged after it are not
+                                    (-1: none; INT32_MAX after fleet_set_rainflow_count_all or with auto_reset = 0): SOC samples logged after it are not
                                     counted, see fleet_set_rainflow_count_all                                                   */
 
 /* ---- lifetime ------------------------------------------------------------------------------------- */
@@ -256,12 +261,14 @@ int fleet_rollout_policy_dev(fleet_handle h, int policy, int K, float* obs, doub
  * distributed rule instead.  Each env keeps its own "charging since" state, which -- like the reference's loop
  * variable -- survives episode resets; this call clears it.  Not callable while a captured graph is replaying. */
 int fleet_set_night_policy(fleet_handle h, int charging_hour, int charging_minute, int max_hours);
-/* The rainflow count stops at the episode's last degradation row.  The reference appends one SOC sample per EV and step to
- * LogDataDeg (fleet_environment.py:655) and runs rainflow.extract_cycles on that log only on the 14:45 rows (:665,
+/* With auto_reset = 1 the rainflow count stops at the episode's last degradation row.  The reference appends one SOC sample per
+ * EV and step to LogDataDeg (fleet_environment.py:655) and runs rainflow.extract_cycles on that log only on the 14:45 rows (:665,
  * rainflow_sei_degradation.py:132); reset() clears the log (:338-339).  What is logged between an episode's last 14:45 row and
- * its end is therefore never read by anybody -- with 48 h episodes a quarter of all samples -- and the kernels, which count
- * while they log, stop counting there (FLEET_F_RF_UNTIL; state of health, fd_cyc, rainflow_length, observations, rewards:
- * exactly as with the full count, tests/test_rf_tail_gpu.py).  `on` != 0 keeps the count running to the end of every episode
+ * its end is therefore never read by anybody when the env is reset at its finish -- with 48 h episodes a quarter of all samples
+ * -- and the kernels, which count while they log, stop counting there (FLEET_F_RF_UNTIL; state of health, fd_cyc,
+ * rainflow_length, observations, rewards: exactly as with the full count, tests/test_rf_tail_gpu.py).  With auto_reset = 0 an
+ * env may be stepped past its finish row, and the reference's later 14:45 rows read those samples: the count never stops then
+ * (FLEET_F_RF_UNTIL = INT32_MAX, tests/test_past_done_gpu.py).  `on` != 0 keeps the count running to the end of every episode
  * from each env's next reset on (FLEET_F_RF_CYCLES / FLEET_F_RF_STACK then describe the whole series: diagnostics, the
  * adversarial count tests).  Default: off.  Not callable while a captured graph is replaying. */
 int fleet_set_rainflow_count_all(fleet_handle h, int on);

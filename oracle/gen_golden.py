@@ -2,6 +2,7 @@
 """Generate the committed golden fixtures under tests/golden/ by running the UNMODIFIED reference.
 
 Run in the build container only (needs /root/reference):   python oracle/gen_golden.py [name ...]
+(real_time traces: `python oracle/gen_golden.py rt [name ...]`; past-done traces: `python oracle/gen_golden.py pd [name ...]`)
 
 For every configuration below it builds `E` independent reference `FleetEnv` objects, drives each through
 `episodes` consecutive episodes with seeded float32-valued actions (fed to the reference as float64 copies,
@@ -449,11 +450,179 @@ def run_config_rt(name: str):
     print(f"rt {name}: wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB), window rows [{w0},{w1})", flush=True)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# past-done traces (tests/golden/pdtrace_<name>.npz, pdrttrace_<name>.npz): the gymnasium.Env path, no auto-reset.  Each env
+# runs reset(); one full episode; `past` more step() calls after done (the reference allows them: `episode.done` stays True,
+# LogDataDeg.soc_log keeps growing and the 14:45 rows run the degradation model on the whole log); reset(); one more full
+# episode (the carry-over of what the past-done evaluations changed, quirk Q6).  Three segments per env; arrays indexed by
+# the env's running step count, `seg_steps[E, 3]` steps per segment; the degradation state is recorded at the end of each.
+# ---------------------------------------------------------------------------------------------------------------
+PD_CONFIGS = {
+    # name -> (overrides, n_evs, E, past-done steps, real_time)
+    # env 0 starts at 14:30, so that its episode finishes on a 14:30 row and the first step past done is a degradation row
+    "ct5_both_rainflow": (dict(use_case="ct", building_name="load_ct.csv", include_building=True, include_pv=True,
+                               calculate_degradation=True, deg_emp=False, episode_length=24), 5, 2, 202, False),
+    # linear model on the extended log, and the DataLogger, which writes nothing after done (fleet_environment.py:679)
+    "lmd3_price_linear_log": (dict(use_case="lmd", include_building=False, include_pv=False, calculate_degradation=True,
+                                   deg_emp=True, episode_length=24, log_data=True), 3, 2, 202, False),
+    # event-skipping steps past done: the loop leaves on events only (done is not one again, :627-629)
+    "ct3_both_rainflow": (dict(use_case="ct", building_name="load_ct.csv", include_building=True, include_pv=True,
+                               calculate_degradation=True, deg_emp=False, episode_length=24, real_time=True), 3, 2, 60, True),
+}
+
+
+def run_config_pd(name: str):
+    import json
+
+    from oracle.ref_harness import base_config
+
+    ov, n_evs, E, past, rt = PD_CONFIGS[name]
+    ov = dict(ov)
+    dp, sched = stacked_inputs_dir(ov["use_case"], n_evs)
+    ov.update(data_path=dp, schedule_name=sched)
+    ov.setdefault("target_soc", 0.85)
+    rng = np.random.default_rng(sum(map(ord, "pd_" + name)))
+    ep_rows = ov["episode_length"] * 4
+    cap = 2 * ep_rows + past
+    rec, scalars, db0 = None, {}, None
+    starts = np.zeros((2, E), dtype=np.int32)
+    t0 = time.time()
+    for e in range(E):
+        env = make_ref_env(ov)
+        N = int(env.num_cars)
+        T = len(env.db) // N
+        if rec is None:
+            D = env.observation_space.shape[0]
+            rec = dict(
+                actions=np.zeros((E, cap, N), np.float32), obs=np.zeros((E, cap, D), np.float32),
+                reset_obs=np.zeros((E, 2, D), np.float32), seg_steps=np.zeros((E, 3), np.int32),
+                reward=np.zeros((E, cap)), done=np.zeros((E, cap), np.uint8), cashflow=np.zeros((E, cap)),
+                soc=np.zeros((E, cap, N)), hours_left=np.zeros((E, cap, N)), soh=np.zeros((E, cap, N)),
+                soc_deg=np.zeros((E, cap, N)), target_soc=np.zeros((E, cap, N)), time_idx=np.zeros((E, cap), np.int32),
+                rf_len=np.zeros((E, 3, N), np.int32), fd_cyc=np.zeros((E, 3, N)), fd_cal=np.zeros((E, 3, N)),
+                sei_l=np.zeros((E, 3, N)), soc_log_len=np.zeros((E, 3), np.int32),
+            )
+            db0 = env.db
+            lc = env.load_calculation
+            scalars = dict(grid_connection=lc.grid_connection, evse_power=lc.evse_max_power, batt_cap_nominal=lc.batt_cap,
+                           init_battery_cap=env.ev_config.init_battery_cap, price_multiplier=env.score_config.price_multiplier,
+                           obs_dim=D, num_cars=N, table_rows_full=T)
+        dates0 = env.db["date"].values[:T]
+        acts = make_actions_rt(rng, cap, N) if rt else make_actions(rng, cap, N, "wide")
+        rec["actions"][e] = acts
+        if e == 0:
+            span0 = int(rng.integers(0, T - 1 - 60 * 96 - 20 * 96))
+        starts[:, e] = rng.integers(span0, span0 + 20 * 96, size=2)
+        if e == 0:
+            starts[0, 0] = (starts[0, 0] // 96) * 96 + 58  # 14:30
+        k = 0
+
+        def one_step():
+            nonlocal k
+            obs, r, d, _tr, _info = env.step(acts[k].astype(np.float64))
+            rec["obs"][e, k] = obs
+            rec["reward"][e, k] = r
+            rec["done"][e, k] = d
+            rec["cashflow"][e, k] = env.episode.current_charging_expense
+            rec["soc"][e, k] = np.asarray(env.episode.soc, dtype=np.float64)
+            rec["hours_left"][e, k] = np.asarray(env.episode.hours_left, dtype=np.float64)
+            rec["soh"][e, k] = np.asarray(env.episode.soh, dtype=np.float64)
+            rec["soc_deg"][e, k] = np.asarray(env.episode.soc_deg, dtype=np.float64)
+            rec["target_soc"][e, k] = np.asarray(env.target_soc, dtype=np.float64)
+            rec["time_idx"][e, k] = int(np.searchsorted(dates0, np.datetime64(env.episode.time)))
+            k += 1
+            return d
+
+        def checkpoint(seg, n):
+            rec["seg_steps"][e, seg] = n
+            rec["soc_log_len"][e, seg] = len(env.deg_data_logger.soc_log)
+            if ov["calculate_degradation"] and not ov["deg_emp"]:
+                sd = env.sei_deg
+                rec["rf_len"][e, seg] = sd.rainflow_length
+                rec["fd_cyc"][e, seg] = sd.fd_cyc
+                rec["fd_cal"][e, seg] = sd.fd_cal
+                rec["sei_l"][e, seg] = sd.l
+
+        for ep in range(2):
+            set_static_start(env, int(starts[ep, e]))
+            obs, _ = env.reset()
+            rec["reset_obs"][e, ep] = obs
+            n = 0
+            while True:
+                n += 1
+                if one_step():
+                    break
+            assert rt or n == ep_rows, "episode must end exactly after episode_length hours"
+            checkpoint(2 * ep, n)
+            if ep == 0:
+                for _ in range(past):
+                    assert one_step(), "done is sticky in the reference"
+                checkpoint(1, past)
+        if ov.get("log_data"):
+            lg = env.data_logger.log.reset_index(drop=True)
+            rows = len(lg)
+            if "log_reward" not in rec:
+                rec.update(log_rows=np.zeros(E, np.int32), log_reward=np.zeros((E, cap)), log_cashflow=np.zeros((E, cap)),
+                           log_penalty=np.zeros((E, cap)), log_grid=np.zeros((E, cap)), log_socv=np.zeros((E, cap)),
+                           log_episode=np.zeros((E, cap), np.int32), log_time=np.zeros((E, cap), np.int64),
+                           log_deg=np.zeros((E, cap, N)), log_charge=np.zeros((E, cap, N)), log_soh=np.zeros((E, cap, N)),
+                           log_obs=np.zeros((E, cap, rec["obs"].shape[2]), np.float32), log_action=np.zeros((E, cap, N)))
+            assert rows <= cap
+            rec["log_rows"][e] = rows
+            rec["log_reward"][e, :rows] = lg["Reward"].astype(float).values
+            rec["log_cashflow"][e, :rows] = lg["Cashflow"].astype(float).values
+            rec["log_penalty"][e, :rows] = lg["Penalties"].astype(float).values
+            rec["log_grid"][e, :rows] = lg["Grid overloading"].astype(float).values
+            rec["log_socv"][e, :rows] = lg["SOC violation"].astype(float).values
+            rec["log_episode"][e, :rows] = lg["Episode"].astype(int).values
+            rec["log_time"][e, :rows] = lg["Time"].values.astype("datetime64[s]").astype(np.int64)
+            for q in range(rows):
+                rec["log_deg"][e, q] = np.broadcast_to(np.asarray(lg["Degradation"].iloc[q], dtype=np.float64), (N,))
+                rec["log_charge"][e, q] = np.asarray(lg["Charging energy"].iloc[q], dtype=np.float64)
+                rec["log_soh"][e, q] = np.asarray(lg["SOH"].iloc[q], dtype=np.float64)
+                rec["log_obs"][e, q] = np.asarray(lg["Observation"].iloc[q], dtype=np.float32)
+                rec["log_action"][e, q] = np.asarray(lg["Action"].iloc[q], dtype=np.float64)
+        print(f"  pd {name}: env {e + 1}/{E}: {rec['seg_steps'][e].tolist()} steps ({time.time() - t0:.0f}s)", flush=True)
+    N, T = scalars["num_cars"], scalars["table_rows_full"]
+    L2 = (ov.get("price_lookahead", 8) + 2) * 4 + 1
+    w0 = (int(starts.min()) // 96) * 96
+    used = int(rec["seg_steps"].sum(axis=1).max())
+    w1 = min(T, int(max(rec["time_idx"][:, :used].max(), starts.max() + ep_rows)) + L2 + 1)
+    col = lambda c: db0[c].values.reshape(N, T).T[w0:w1]  # noqa: E731
+    one = lambda c: db0[c].values[:T][w0:w1] if c in db0 else np.zeros(w1 - w0)  # noqa: E731
+    tables = dict(dates=db0["date"].values[:T][w0:w1].astype("datetime64[s]").astype(np.int64), there=col("There").astype(np.uint8),
+                  time_left=col("time_left").astype(np.float64), soc_on_return=col("SOC_on_return").astype(np.float64),
+                  delu=one("DELU"), tariff=one("tariff"), prc=one("price_reward_curve"), trc=one("tariff_reward_curve"),
+                  load=one("load"), pv=one("pv"))
+    ext = dict(max_time_left=float(np.nanmax(db0["time_left"].values)), max_delu=float(np.nanmax(db0["DELU"].values)),
+               min_delu=float(np.nanmin(db0["DELU"].values)), max_tariff=float(np.nanmax(db0["tariff"].values)),
+               min_tariff=float(np.nanmin(db0["tariff"].values)),
+               max_load=float(np.nanmax(db0["load"].values)) if "load" in db0 else 0.0,
+               max_pv=float(np.nanmax(db0["pv"].values)) if "pv" in db0 else 0.0)
+    scalars.update({f"ext_{k}": v for k, v in ext.items()})
+    scalars["window_row0"] = w0
+    full_cfg = base_config()
+    full_cfg.update(ov)
+    full_cfg["data_path"] = "<not shipped>"
+    out = {f"tab_{k}": v for k, v in tables.items()}
+    out.update({f"sc_{k}": np.asarray(v) for k, v in scalars.items()})
+    out["cfg_json"] = np.asarray(json.dumps(full_cfg))
+    out.update({k: (v[:, :used] if (v.ndim > 1 and v.shape[1] == cap and not k.startswith("log_")) else v) for k, v in rec.items()})
+    out["starts"] = starts - w0
+    out["time_idx"] = out["time_idx"] - w0
+    path = os.path.join(GOLDEN, f"{'pdrttrace' if rt else 'pdtrace'}_{name}.npz")
+    np.savez_compressed(path, **out)
+    print(f"pd {name}: wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB), window rows [{w0},{w1})", flush=True)
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
     if args and args[0] == "rt":
         for n in args[1:] or list(RT_CONFIGS):
             run_config_rt(n)
+    elif args and args[0] == "pd":
+        for n in args[1:] or list(PD_CONFIGS):
+            run_config_pd(n)
     else:
         for n in args or list(CONFIGS):
             run_config(n)

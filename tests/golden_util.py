@@ -213,3 +213,63 @@ def replay_rt(g, engine, *, float_rtol=1e-9, obs_exact=True):
     assert not np.any(engine.get("error_bits")), "device/oracle error bits set"
     assert np.all(g.n_steps < g.ep_rows + 1), "the trace must actually skip rows"
     return worst
+
+
+# past-done traces (oracle/gen_golden.py `run_config_pd`): no auto-reset; per env reset(), one episode, `seg_steps[e, 1]` steps
+# past done, reset(), one more episode.  Their own prefixes: replay() above assumes auto-reset.
+PD_TRACE_NAMES = sorted(os.path.basename(p)[len("pdtrace_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN_DIR, "pdtrace_*.npz")))
+PD_RT_TRACE_NAMES = sorted(os.path.basename(p)[len("pdrttrace_"):-len(".npz")]
+                           for p in glob.glob(os.path.join(GOLDEN_DIR, "pdrttrace_*.npz")))
+
+
+def load_pd_trace(name: str, rt: bool = False) -> SimpleNamespace:
+    g = load_trace(name, prefix="pdrttrace_" if rt else "pdtrace_")
+    g.ep_rows = g.rc.episode_length * (60 // g.rc.minutes)
+    return g
+
+
+def replay_pd(g, engine, e, *, float_rtol=1e-9, obs_exact=True, done_getter=None):
+    """Replay golden env `e` of a past-done trace on a one-env engine without auto-reset (its start schedule is set here).
+    At every step: done (and `done_getter()`, the engine's own episode.done, when given), time row and hours_left bit-exact,
+    obs exact or within 1e-5, reward / cashflow / SOC / SoH within `float_rtol`; the rainflow state (rainflow_length exact,
+    fd_cyc / fd_cal / l) at the end of each of the three segments.  Returns the largest relative errors seen."""
+    assert engine.E == 1
+    engine.set_start_schedule(g.starts[:, [e]])
+    worst = dict(reward=0.0, soc=0.0, soh=0.0)
+    cmp = (lambda a, b, m: np.testing.assert_array_equal(a, b, err_msg=m)) if obs_exact else \
+          (lambda a, b, m: np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6, err_msg=m))
+    seg_end = np.cumsum(g.seg_steps[e])
+    k = 0
+    for seg in range(3):
+        if seg != 1:
+            obs = engine.reset()
+            cmp(obs[0], g.reset_obs[e, seg // 2], f"reset obs, episode {seg // 2}")
+            np.testing.assert_array_equal(engine.get("start_idx"), g.starts[seg // 2, [e]])
+        while k < seg_end[seg]:
+            obs, rew, done, _ = engine.step(g.actions[e, k][None])
+            what = f"env {e}, segment {seg}, step {k}"
+            assert bool(done[0]) == bool(g.done[e, k]), f"done flag, {what}"
+            if done_getter is not None:
+                assert bool(done_getter()) == bool(g.done[e, k]), f"episode.done / is_done(), {what}"
+            cmp(obs[0], g.obs[e, k], f"obs, {what}")
+            np.testing.assert_allclose(rew[0], g.reward[e, k], rtol=float_rtol, atol=1e-12, err_msg=f"reward, {what}")
+            np.testing.assert_allclose(engine.get("cashflow")[0], g.cashflow[e, k], rtol=float_rtol, atol=1e-13, err_msg=what)
+            np.testing.assert_array_equal(engine.get("time_idx")[0], g.time_idx[e, k], err_msg=f"time row, {what}")
+            np.testing.assert_array_equal(engine.get("hours_left")[0].astype(np.float64), g.hours_left[e, k], err_msg=what)
+            np.testing.assert_allclose(engine.get("soc")[0], g.soc[e, k], rtol=float_rtol, atol=1e-15, err_msg=f"soc, {what}")
+            np.testing.assert_allclose(engine.get("soh")[0], g.soh[e, k], rtol=float_rtol, atol=0, err_msg=f"soh, {what}")
+            np.testing.assert_allclose(engine.get("soc_deg")[0], g.soc_deg[e, k], rtol=float_rtol, atol=1e-15, err_msg=what)
+            np.testing.assert_array_equal(engine.get("target_soc")[0], g.target_soc[e, k], err_msg=what)
+            worst["reward"] = max(worst["reward"], rel_err(rew[0], g.reward[e, k]))
+            worst["soc"] = max(worst["soc"], rel_err(engine.get("soc")[0], g.soc[e, k]))
+            worst["soh"] = max(worst["soh"], rel_err(engine.get("soh")[0], g.soh[e, k]))
+            k += 1
+        assert g.done[e, k - 1], f"segment {seg} of env {e} must end done"
+        if g.rc.deg_mode == 2:
+            what = f"rainflow state after segment {seg}, env {e}"
+            np.testing.assert_array_equal(engine.get("rf_len")[0], g.rf_len[e, seg], err_msg=what)
+            np.testing.assert_allclose(engine.get("fd_cyc")[0], g.fd_cyc[e, seg], rtol=1e-9, atol=1e-18, err_msg=what)
+            np.testing.assert_allclose(engine.get("fd_cal")[0], g.fd_cal[e, seg], rtol=1e-9, atol=1e-18, err_msg=what)
+            np.testing.assert_allclose(engine.get("sei_l")[0], g.sei_l[e, seg], rtol=1e-9, atol=1e-18, err_msg=what)
+    assert not np.any(engine.get("error_bits")), "device/oracle error bits set"
+    return worst
