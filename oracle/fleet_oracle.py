@@ -46,6 +46,8 @@ def load():
         lib.oracle_get.argtypes = [vp, C.c_int, vp]
         lib.oracle_get_dist_factor.argtypes = [vp, vp]
         lib.oracle_rainflow.argtypes = [vp, C.c_int, vp]
+        lib.oracle_rainflow_many.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+        lib.oracle_rainflow_many.restype = None
         lib.oracle_soc_violation_penalty.argtypes = [C.c_double]
         lib.oracle_soc_violation_penalty.restype = C.c_double
         lib.oracle_overloading_penalty.argtypes = [C.c_double, C.c_double]
@@ -62,6 +64,19 @@ def rainflow(series) -> np.ndarray:
     out = np.zeros((max(len(s), 1), 4))
     n = load().oracle_rainflow(s.ctypes.data, len(s), out.ctypes.data)
     return out[:n]
+
+
+def rainflow_many(series, lengths) -> tuple[np.ndarray, np.ndarray]:
+    """rainflow() of M series at once: `series` [M, S] (row m holds its first lengths[m] samples).  Returns the cycles
+    [M, S, 4] (rows beyond a series' count are zero) and the counts [M]."""
+    s = np.ascontiguousarray(series, dtype=np.float64)
+    n = np.ascontiguousarray(lengths, dtype=np.int32)
+    M, S = s.shape
+    assert n.shape == (M,) and (n <= S).all()
+    out = np.zeros((M, S, 4))
+    nc = np.zeros(M, dtype=np.int32)
+    load().oracle_rainflow_many(s.ctypes.data, n.ctypes.data, M, S, out.ctypes.data, nc.ctypes.data)
+    return out, nc
 
 
 class OracleBatch:

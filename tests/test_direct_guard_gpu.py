@@ -195,26 +195,39 @@ def test_direct_run_at_the_headline_shape_against_the_oracle():
         np.testing.assert_allclose(o[0].cpu().numpy(), oc, rtol=1e-5, atol=1e-6, err_msg=f"obs after {done_steps} launches")
         np.testing.assert_allclose(o[1].cpu().numpy(), rc, rtol=1e-9, atol=1e-12, err_msg=f"reward after {done_steps} launches")
     np.testing.assert_allclose(b.get("soc"), cpu.get("soc"), rtol=1e-9, atol=1e-15)
-    np.testing.assert_allclose(b.get("soh"), cpu.get("soh"), rtol=1e-9)
-    # The cycle bookkeeping: the reference's reversal extraction compares SOC samples EXACTLY, so an EV whose SOC saturates (this tape
+    # The cycle bookkeeping.  The reference's reversal extraction compares SOC samples EXACTLY, so an EV whose SOC saturates (this tape
     # drives batteries into their limits, like bench.py's) can count one cycle more or less in one engine than in the other once the
-    # two SoH values differ in their last bits ("What that implies over very long horizons"): at most a handful
-    # of the 204 800 EVs, and never anything but the cycle bookkeeping of those EVs.
-    fd_h, fd_c, len_h, len_c = b.get("fd_cyc"), cpu.get("fd_cyc"), b.get("rf_len"), cpu.get("rf_len")
-    off = ~np.isclose(fd_h, fd_c, rtol=1e-8, atol=1e-18) | (len_h != len_c)
-    if off.any():
-        import warnings
+    # two SoH values differ in their last bits.  Every such EV is re-run on its own and attributed to an exact
+    # tie of one series (degradation_model.attribute: each engine's count is the model's on its own samples, the samples agree to
+    # 1e-12 up to there); it is then held to SoH 1e-5, every other EV to 1e-9 and to the oracle's bookkeeping.
+    from degradation_model import attribute_by_rerun, book_mismatch
 
-        e, c = np.argwhere(off)[0]
-        warnings.warn(f"{int(off.sum())} of {off.size} EVs differ in their cycle bookkeeping; first: env {e} EV {c}: fd_cyc {fd_h[e, c]!r} / "
-                      f"{fd_c[e, c]!r}, rainflow_length {len_h[e, c]} / {len_c[e, c]}, soh {b.get('soh')[e, c]!r} / {cpu.get('soh')[e, c]!r}, "
-                      f"sei_l {b.get('sei_l')[e, c]!r} / {cpu.get('sei_l')[e, c]!r}")
-    assert off.sum() <= 4, f"{int(off.sum())} EVs differ in their cycle bookkeeping"
+    book = ("rf_len", "fd_cyc", "fd_cal", "sei_l")
+    off = book_mismatch({f: b.get(f) for f in book}, {f: cpu.get(f) for f in book})
+    np.testing.assert_allclose(b.get("soh")[~off], cpu.get("soh")[~off], rtol=1e-9)
+    np.testing.assert_allclose(b.get("soh")[off], cpu.get("soh")[off], rtol=1e-5)
+    assert off.sum() <= E * N * steps / 2e7, f"{int(off.sum())} EVs differ in their cycle bookkeeping"  # tests/test_degradation_recount_gpu.py
+    for e in np.flatnonzero(off.any(axis=1)):
+        pe = make_params(resolve_config(bench_config(1, N, "ct")), tb, 1, auto_reset=False, seed=0, env_id_offset=int(e))
+        recs = attribute_by_rerun(lambda: FleetBatch(pe, tb, tf), lambda: OracleBatch(pe, tb, tf), tb,
+                                  lambda k: acts[_tape_row(k, (1, 63, 200, 136)) % L, [e]], steps, lambda k, d: d, int(e),
+                                  np.flatnonzero(off[e]), init_soh=p.init_soh, temp=p.temperature, dt=p.dt,
+                                  final_gpu={f: b.get(f)[e] for f in ("rf_len", "fd_cyc", "sei_l", "soh")}, what="direct run")
+        print(f"env {e}: bookkeeping differs from the oracle's through an exact tie: {recs}")
     for f in ("time_idx", "episodes", "hours_left"):
         np.testing.assert_array_equal(b.get(f), cpu.get(f), err_msg=f)
     assert b.get("episodes").min() >= 2
     b.check_errors()
     b.close(); cpu.close()
+
+
+def _tape_row(k, chunks):
+    """The tape row step k of a sequence of runs of `chunks` steps reads (every run replays the tape from row 0)."""
+    for n in chunks:
+        if k < n:
+            return k
+        k -= n
+    raise IndexError(k)
 
 
 def test_rainflow_cycle_and_stack_getters_count_what_a_plain_rainflow_counts():

@@ -93,32 +93,38 @@ def _pair(n_evs, num_envs, deg, episode_length=24, seed=0):
     return tb, FleetBatch(p, tb, tf), OracleBatch(p, tb, tf, threads=4)
 
 
-def _assert_state_equal(hip, cpu, deg, what, live=slice(None)):
-    """`live`: the envs whose SOC-dependent state is compared (flags, rows and hours_left are compared for every env)."""
+def _assert_state_equal(hip, cpu, deg, what, agree=None):
+    """`agree`: [E, N] the EVs whose cycle bookkeeping agrees with the oracle's (default all).  The others -- attributed to an exact
+    tie of the reversal extraction, see test_batch_past_done_matches_oracle_step_by_step -- are held to SOC / SoH 1e-4 and their
+    bookkeeping to the recount of the kernels' own samples."""
     np.testing.assert_array_equal(hip.get("time_idx"), cpu.get("time_idx"), err_msg=what)
     np.testing.assert_array_equal(hip.get("hours_left"), cpu.get("hours_left"), err_msg=what)
     np.testing.assert_array_equal(hip.get("done"), cpu.get("done"), err_msg=f"episode.done, {what}")
-    np.testing.assert_allclose(hip.get("soc")[live], cpu.get("soc")[live], rtol=1e-9, atol=1e-12, err_msg=what)
-    np.testing.assert_allclose(hip.get("soh")[live], cpu.get("soh")[live], rtol=1e-9, atol=0, err_msg=f"soh, {what}")
+    ok = np.ones(hip.get("soc").shape, bool) if agree is None else agree
+    np.testing.assert_allclose(hip.get("soc")[ok], cpu.get("soc")[ok], rtol=1e-9, atol=1e-12, err_msg=what)
+    np.testing.assert_allclose(hip.get("soh")[ok], cpu.get("soh")[ok], rtol=1e-9, atol=0, err_msg=f"soh, {what}")
+    # (one cycle counted otherwise moves SoH by that cycle's degradation -- measured 3.2e-5 at N = 65 -- and the capacity with it,
+    # so the SOC charged afterwards: 1.2e-5)
+    np.testing.assert_allclose(hip.get("soc")[~ok], cpu.get("soc")[~ok], rtol=1e-4, atol=1e-9, err_msg=what)
+    np.testing.assert_allclose(hip.get("soh")[~ok], cpu.get("soh")[~ok], rtol=1e-4, atol=0, err_msg=f"soh, {what}")
     if deg == "rainflow":
-        np.testing.assert_array_equal(hip.get("rf_len")[live], cpu.get("rf_len")[live], err_msg=f"rainflow_length, {what}")
-        np.testing.assert_allclose(hip.get("fd_cyc")[live], cpu.get("fd_cyc")[live], rtol=1e-8, atol=1e-18, err_msg=f"fd_cyc, {what}")
-        np.testing.assert_allclose(hip.get("sei_l")[live], cpu.get("sei_l")[live], rtol=1e-9, atol=1e-18, err_msg=f"l, {what}")
-
-
-def _cycle_bookkeeping_differs(hip, cpu):
-    """[E] envs with an EV whose rainflow count differs.  The reference's reversal extraction compares SOC samples EXACTLY, and
-    the two engines' SOC may differ in its last bit: an EV whose series holds a near-tie can then count one
-    cycle more or less -- the same allowance as tests/test_direct_guard_gpu.py; the long series past done make it likelier."""
-    off = (hip.get("rf_len") != cpu.get("rf_len")) | ~np.isclose(hip.get("fd_cyc"), cpu.get("fd_cyc"), rtol=1e-8, atol=1e-18)
-    return off.any(axis=1)
+        np.testing.assert_array_equal(hip.get("rf_len")[ok], cpu.get("rf_len")[ok], err_msg=f"rainflow_length, {what}")
+        np.testing.assert_allclose(hip.get("fd_cyc")[ok], cpu.get("fd_cyc")[ok], rtol=1e-8, atol=1e-18, err_msg=f"fd_cyc, {what}")
+        np.testing.assert_allclose(hip.get("sei_l")[ok], cpu.get("sei_l")[ok], rtol=1e-9, atol=1e-18, err_msg=f"l, {what}")
 
 
 @pytest.mark.parametrize("n_evs,deg", [(1, "rainflow"), (5, "rainflow"), (50, "rainflow"), (64, "rainflow"), (65, "rainflow"),
                                        (130, "rainflow"), (200, "rainflow"), (5, "linear"), (65, "linear")])
 def test_batch_past_done_matches_oracle_step_by_step(n_evs, deg):
     """Envs on staggered start rows, so that some are past done while others are mid-episode; then half of them reset while the
-    others run on past done.  done and the degradation state compared at every step (every 14:45 row among them)."""
+    others run on past done.  done and the degradation state compared at every step (every 14:45 row among them), and every
+    EV's bookkeeping against the recount of the kernels' own samples (tests/degradation_model.py).  An EV whose bookkeeping
+    differs from the oracle's must be an exact tie of the reversal extraction on one side (degradation_model.attribute, on a
+    re-run of its env alone); it stays compared (obs 1e-5, SoH 1e-4)."""
+    from degradation_model import Recount, RecountCheck, attribute_by_rerun, book_mismatch
+    from fleetrl_amd.batch import FleetBatch
+    from oracle.fleet_oracle import OracleBatch
+
     E = 5
     tb, hip, cpu = _pair(n_evs, E, deg)
     ep = 96
@@ -128,45 +134,67 @@ def test_batch_past_done_matches_oracle_step_by_step(n_evs, deg):
     hip.set_start_schedule(starts)
     cpu.set_start_schedule(starts)
     np.testing.assert_array_equal(hip.reset(), cpu.reset())
+    p = hip.params
+    chk = RecountCheck(Recount(E, n_evs, deg, init_soh=p.init_soh, temp=p.temperature, dt=p.dt, evse_power=p.evse_power), tb)
+    chk.reset(hip.get)
     # explicit resets: two envs restart 20 steps in, one 50 steps in (so the finishes are staggered: some envs are past done
     # while others are mid-episode); at 3 episodes' length half of the envs start their next episode, the others go on
     resets = {20: [0, 1, 0, 1, 0], 50: [0, 0, 0, 0, 1], 3 * ep: [1, 0, 1, 0, 1]}
     n_deg_past = np.zeros(E, dtype=np.int64)
-    live = np.ones(E, dtype=bool)  # envs whose cycle bookkeeping still agrees (see _cycle_bookkeeping_differs)
-    for s in range(3 * ep + 60):
+    off = np.zeros((E, n_evs), bool)  # EVs whose cycle bookkeeping differs from the oracle's
+    tape = []
+    steps = 3 * ep + 60
+    for s in range(steps):
         if s in resets:
             mask = np.array(resets[s], np.uint8)
             np.testing.assert_array_equal(hip.reset(mask)[mask == 1], cpu.reset(mask)[mask == 1])
+            chk.reset(hip.get, mask.astype(bool))
         a = rng.uniform(-1, 1, size=(E, n_evs))
         a[rng.random(a.shape) < 0.2] = 0.0
         a = a.astype(np.float32)
+        tape.append(a)
         oh, rh, dh, _ = hip.step(a)
         oc, rc, dc, _ = cpu.step(a)
         what = f"step {s}"
+        chk.step(hip.get, what)
         np.testing.assert_array_equal(dh, dc, err_msg=f"done, {what}")
-        if deg == "rainflow" and (live & _cycle_bookkeeping_differs(hip, cpu)).any():
-            import warnings
-
-            e = int(np.flatnonzero(live & _cycle_bookkeeping_differs(hip, cpu))[0])
-            warnings.warn(f"env {e}: an EV's rainflow count differs from the oracle's at {what} (last-bit SOC near-tie); "
-                          "its SOC-dependent state is no longer compared")
-            live[e] = False
-        np.testing.assert_allclose(oh[live], oc[live], rtol=1e-5, atol=1e-6, err_msg=f"obs, {what}")
-        np.testing.assert_allclose(rh[live], rc[live], rtol=1e-9, atol=1e-9, err_msg=f"reward, {what}")
-        _assert_state_equal(hip, cpu, deg, what, live)
+        if deg == "rainflow":
+            book = ("rf_len", "fd_cyc", "fd_cal", "sei_l")
+            off |= book_mismatch({f: hip.get(f) for f in book}, {f: cpu.get(f) for f in book})
+        env_ok = ~off.any(axis=1)
+        np.testing.assert_allclose(oh, oc, rtol=1e-5, atol=1e-6, err_msg=f"obs, {what}")
+        np.testing.assert_allclose(rh[env_ok], rc[env_ok], rtol=1e-9, atol=1e-9, err_msg=f"reward, {what}")
+        np.testing.assert_allclose(rh[~env_ok], rc[~env_ok], rtol=1e-5, atol=1e-6, err_msg=f"reward, {what}")
+        _assert_state_equal(hip, cpu, deg, what, ~off)
         t = cpu.get("time_idx")
         n_deg_past += dc.astype(bool) & (tb.hour[t] == 14) & (tb.minute[t] == 45)
         if s == 100:
             assert dc.any() and not dc.all()  # some envs past done, others mid-episode
     hip.check_errors()
     assert not cpu.get("error_bits").any()
-    assert live.sum() >= E - 1, f"{E - int(live.sum())} envs differ in their cycle bookkeeping"
     assert np.all(n_deg_past >= 1) and n_deg_past.max() >= 2, n_deg_past  # model evaluations past done
     np.testing.assert_array_equal(hip.get("episodes"), cpu.get("episodes"))
     if deg == "rainflow":  # the count did not stop at the episode's last 14:45 row
         assert np.all(hip.get("rf_until") == np.iinfo(np.int32).max)
+    print(chk.report(f"past done {E}x{n_evs} {deg}"))
+    for e in np.flatnonzero(off.any(axis=1)):
+        from fleetrl_amd.params import time_features
+
+        tf = time_features(tb)
+        p1 = _pair(n_evs, 1, deg)[1].params
+        recs = attribute_by_rerun(lambda: _sched(FleetBatch(p1, tb, tf), starts[:, [e]]),
+                                  lambda: _sched(OracleBatch(p1, tb, tf), starts[:, [e]]), tb,
+                                  lambda k: tape[k][[e]], steps, lambda k, d: k + 1 in resets and resets[k + 1][e] == 1, int(e),
+                                  np.flatnonzero(off[e]), init_soh=p.init_soh, temp=p.temperature, dt=p.dt,
+                                  final_gpu={f: hip.get(f)[e] for f in ("rf_len", "fd_cyc", "sei_l", "soh")}, what=f"past done {n_evs}")
+        print(f"env {e}: bookkeeping differs from the oracle's through an exact tie: {recs}")
     hip.close()
     cpu.close()
+
+
+def _sched(x, starts):
+    x.set_start_schedule(starts)
+    return x
 
 
 def test_past_done_tape_is_bit_identical_in_every_launch_mode():
