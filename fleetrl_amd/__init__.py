@@ -1,6 +1,7 @@
 """fleetrl_amd -- MI355X-native batched FleetRL `FleetEnv.step()` hot path.
 
     from fleetrl_amd import FleetEnv, FleetVecEnv, FleetVectorEnv, FleetMixedVecEnv
+    from fleetrl_amd import FleetVecNormalize, DeviceNormalizer, sync_normalization
 """
 __version__ = "0.1.0"
 
@@ -14,6 +15,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import mixed
 
         return mixed.FleetMixedVecEnv
+    if name in ("FleetVecNormalize", "DeviceNormalizer", "sync_normalization"):
+        from . import vec_normalize
+
+        return getattr(vec_normalize, name)
     if name in ("FleetBatch", "FleetHipError"):
         from . import batch
 

@@ -87,6 +87,13 @@ _TABLE_FIELDS = (
 )
 
 
+class FleetNormParams(C.Structure):
+    """include/fleet_hip.h FleetNormParams (the running normaliser, fleet_norm_*)."""
+    _fields_ = [("struct_bytes", C.c_int32), ("num_envs", C.c_int32), ("obs_dim", C.c_int32), ("training", C.c_int32),
+                ("norm_obs", C.c_int32), ("norm_reward", C.c_int32), ("clip_obs", C.c_double), ("clip_reward", C.c_double),
+                ("gamma", C.c_double), ("epsilon", C.c_double)]
+
+
 class FleetTablesC(C.Structure):
     _fields_ = list(_TABLE_FIELDS)
 
@@ -236,6 +243,24 @@ def load_library():
     if hasattr(lib, "fleet_selftest_division"):  # (absent from the round-4 library the A/B scripts run beside the tree's)
         lib.fleet_selftest_division.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.fleet_selftest_division.restype = C.c_int
+    # the running normaliser (fleet_norm.hip)
+    dp = C.POINTER(C.c_double)
+    lib.fleet_norm_create.argtypes = [C.c_int, C.POINTER(FleetNormParams), C.POINTER(vp)]
+    lib.fleet_norm_destroy.argtypes = [vp]
+    lib.fleet_norm_last_error.argtypes = [vp]
+    lib.fleet_norm_last_error.restype = C.c_char_p
+    lib.fleet_norm_set_stream.argtypes = [vp, vp]
+    lib.fleet_norm_configure.argtypes = [vp, C.POINTER(FleetNormParams)]
+    lib.fleet_norm_reset_dev.argtypes = [vp, f32p, f32p]
+    lib.fleet_norm_step_dev.argtypes = [vp, f32p, f64p, u8p, f32p, f32p, f64p, f32p]
+    lib.fleet_norm_get_state.argtypes = [vp, vp, vp, dp, dp, dp, dp, vp]
+    lib.fleet_norm_set_state.argtypes = [vp, vp, vp, dp, dp, dp, dp, vp]
+    lib.fleet_norm_original_host.argtypes = [vp, vp, vp]
+    lib.fleet_reset_host_norm.argtypes = [vp, vp, f32p]
+    lib.fleet_step_host_norm.argtypes = [vp, vp, vp, C.c_int, f32p, f64p, u8p, f32p]
+    for name in NORM_SYMBOLS:
+        if name != "fleet_norm_last_error":
+            getattr(lib, name).restype = C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
                  "fleet_log_capacity", "fleet_log_read",
                  "fleet_log_clear", "fleet_synchronize", "fleet_set_start_schedule",
@@ -250,6 +275,12 @@ def load_library():
     return lib
 
 
+NORM_SYMBOLS = (
+    "fleet_norm_create", "fleet_norm_destroy", "fleet_norm_last_error", "fleet_norm_set_stream", "fleet_norm_configure",
+    "fleet_norm_reset_dev", "fleet_norm_step_dev", "fleet_norm_get_state", "fleet_norm_set_state", "fleet_norm_original_host",
+    "fleet_reset_host_norm", "fleet_step_host_norm",
+)
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -261,4 +292,4 @@ EXPORTED_SYMBOLS = (
     "fleet_time_regions_begin", "fleet_time_regions_read", "fleet_rccl_unique_id", "fleet_rccl_comm_create",
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
-)
+) + NORM_SYMBOLS

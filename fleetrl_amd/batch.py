@@ -216,8 +216,15 @@ class FleetBatch:
         self._check(self.lib.fleet_set_start_schedule(self.h, s.ctypes.data, s.shape[0]))
 
     # ---- host (NumPy) path ---------------------------------------------------------------------------------
-    def reset(self, mask=None, out: np.ndarray | None = None) -> np.ndarray:
+    def reset(self, mask=None, out: np.ndarray | None = None, norm=None) -> np.ndarray:
+        """`norm`: a fleetrl_amd.vec_normalize.DeviceNormalizer of the same shape -- the observations come back normalised
+        (fleet_reset_host_norm; no mask then)."""
         obs = out if out is not None else np.zeros((self.E, self.obs_dim), dtype=np.float32)
+        if norm is not None:
+            if mask is not None:
+                raise ValueError("reset with a normaliser resets every env (no mask)")
+            self._check(self.lib.fleet_reset_host_norm(self.h, norm.h, obs.ctypes.data))
+            return obs
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
         self._check(self.lib.fleet_reset_host(self.h, None if m is None else m.ctypes.data, obs.ctypes.data))
         return obs
@@ -237,7 +244,7 @@ class FleetBatch:
 
     OBS_RING = 4  # pinned observation buffers step() cycles through
 
-    def step(self, actions, copy: bool = True):
+    def step(self, actions, copy: bool = True, norm=None):
         """-> (obs f32[E,obs_dim], reward f64[E], done u8[E], terminal_obs f32[E,obs_dim]); `terminal_obs` is a buffer
         reused between calls whose rows are valid only where `done` is set.
         `copy=True` (default) returns a fresh array, like the reference's env does every step (the transfer is pipelined with the
@@ -245,7 +252,9 @@ class FleetBatch:
         that buffer itself (no 4 * E * obs_dim byte copy on the host): it is overwritten OBS_RING calls later -- enough for an SB3 loop, which
         holds the previous observation while it steps and copies what it keeps; not for code that collects observations in a
         list.  Either way the memory stays valid for as long as the returned array is referenced -- with `copy=False` that is
-        page-locked memory (E * obs_dim * 4 bytes per retained array), which stays pinned until the array is dropped."""
+        page-locked memory (E * obs_dim * 4 bytes per retained array), which stays pinned until the array is dropped.
+        `norm`: a fleetrl_amd.vec_normalize.DeviceNormalizer of the same shape -- obs, reward and the terminal rows come back
+        normalised (fleet_step_host_norm); last_step_episodes() still reports the raw returns."""
         a, dt = self._act(actions, (self.E, self.N))
         if _PinnedBuffer._dead:
             _PinnedBuffer.drain()
@@ -265,8 +274,12 @@ class FleetBatch:
         term = self._term
         rew = np.empty(self.E)
         done = np.empty(self.E, dtype=np.uint8)
-        self._check(self.lib.fleet_step_host(self.h, a.ctypes.data, dt, obs.ctypes.data, rew.ctypes.data,
-                                              done.ctypes.data, term.ctypes.data), device_errors=True)
+        if norm is not None:
+            self._check(self.lib.fleet_step_host_norm(self.h, norm.h, a.ctypes.data, dt, obs.ctypes.data, rew.ctypes.data,
+                                                      done.ctypes.data, term.ctypes.data), device_errors=True)
+        else:
+            self._check(self.lib.fleet_step_host(self.h, a.ctypes.data, dt, obs.ctypes.data, rew.ctypes.data,
+                                                  done.ctypes.data, term.ctypes.data), device_errors=True)
         return obs, rew, done, term
 
     def last_step_episodes(self):

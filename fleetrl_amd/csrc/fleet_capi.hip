@@ -24,6 +24,7 @@
 
 #include "fleet_device.h"
 #include "fleet_direct.h"
+#include "fleet_norm.h"
 
 namespace {
 
@@ -897,12 +898,24 @@ int fleet_reset_host(fleet_handle h, const uint8_t* mask, float* obs) {
   return FLEET_OK;
 }
 
-int fleet_step_host(fleet_handle h, const void* actions, int act_dtype, float* obs, double* reward, uint8_t* done,
-                    float* terminal_obs) {
+}  // extern "C"
+
+// fleet_step_host and fleet_step_host_norm: the step, then (with a normaliser) its three launches on the handle's stream, then
+// the transfers -- the normalised observations from the normaliser's buffer, rewards normalised in place in the small block,
+// terminal rows of done envs normalised in place before they are compacted
+static int step_host_impl(fleet_handle h, fleet_norm_handle nrm, const void* actions, int act_dtype, float* obs, double* reward,
+                          uint8_t* done, float* terminal_obs) {
   FLEET_ENTER(h);
   if (!h || !actions || !obs || !reward || !done || (act_dtype != FLEET_ACT_F32 && act_dtype != FLEET_ACT_F64)) {
     if (h) h->error = "fleet_step_host: null buffer or bad action dtype";
     return FLEET_ERR_INVALID;
+  }
+  if (nrm) {
+    std::string why;
+    if (fleet_norm_check_fit(nrm, h->d.E, h->d.obs_dim, h->device, &why) != FLEET_OK) {
+      h->error = "fleet_step_host_norm: " + why;
+      return FLEET_ERR_INVALID;
+    }
   }
   HIP_TRY(h, hipSetDevice(h->device));
   const int E = h->d.E;
@@ -926,6 +939,12 @@ int fleet_step_host(fleet_handle h, const void* actions, int act_dtype, float* o
   HIP_TRY(h, hipMemcpyAsync(h->st_actions, asrc, abytes, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, fleet_launch_step(h->d, h->st_actions, act_dtype, 1, h->st_obs, h->st_reward, h->st_done,
                                terminal_obs ? h->st_term : nullptr, nullptr, h->stream));
+  const float* obs_src = h->st_obs;
+  if (nrm) {
+    obs_src = fleet_norm_out_buffer(nrm);
+    HIP_TRY(h, fleet_norm_enqueue_step(nrm, h->st_obs, h->st_reward, h->st_done, terminal_obs ? h->st_term : nullptr,
+                                       fleet_norm_out_buffer(nrm), h->st_reward, terminal_obs ? h->st_term : nullptr, h->stream));
+  }
   if (terminal_obs)
     HIP_TRY(h, fleet_launch_term_compact(h->d, h->st_done, h->st_term, reinterpret_cast<int32_t*>(h->st_small + h->small_off_idx),
                                          reinterpret_cast<int32_t*>(h->st_small + h->small_off_count),
@@ -940,7 +959,7 @@ int fleet_step_host(fleet_handle h, const void* actions, int act_dtype, float* o
   const bool obs_pinned = pinned(obs);
   (void)hipGetLastError();
   if (obs_pinned || OD < (size_t)1 << 18) {
-    HIP_TRY(h, hipMemcpyAsync(obs, h->st_obs, OD, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(obs, obs_src, OD, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
   } else {
     if (!h->pin_obs) {
@@ -954,7 +973,7 @@ int fleet_step_host(fleet_handle h, const void* actions, int act_dtype, float* o
     const size_t first = (OD / (2 * (size_t)P)) & ~(size_t)4095;
     for (int c = 1; c < P; ++c) cut[c] = (first + (OD - first) * (size_t)(c - 1) / (size_t)(P - 1)) & ~(size_t)4095;
     cut[P] = OD;
-    const char* src = reinterpret_cast<const char*>(h->st_obs);
+    const char* src = reinterpret_cast<const char*>(obs_src);
     for (int c = 0; c < P; ++c) {
       if (cut[c + 1] > cut[c])
         HIP_TRY(h, hipMemcpyAsync(h->pin_obs + cut[c], src + cut[c], cut[c + 1] - cut[c], hipMemcpyDeviceToHost, h->stream));
@@ -1000,6 +1019,39 @@ int fleet_step_host(fleet_handle h, const void* actions, int act_dtype, float* o
     (void)fleet_check_errors(h);  // names the env in fleet_last_error
     return FLEET_ERR_STATE;
   }
+  return FLEET_OK;
+}
+
+extern "C" {
+
+int fleet_step_host(fleet_handle h, const void* actions, int act_dtype, float* obs, double* reward, uint8_t* done,
+                    float* terminal_obs) {
+  return step_host_impl(h, nullptr, actions, act_dtype, obs, reward, done, terminal_obs);
+}
+
+int fleet_step_host_norm(fleet_handle h, fleet_norm_handle n, const void* actions, int act_dtype, float* obs, double* reward,
+                         uint8_t* done, float* terminal_obs) {
+  if (!n) {
+    if (h) h->error = "fleet_step_host_norm: null normaliser";
+    return FLEET_ERR_INVALID;
+  }
+  return step_host_impl(h, n, actions, act_dtype, obs, reward, done, terminal_obs);
+}
+
+int fleet_reset_host_norm(fleet_handle h, fleet_norm_handle n, float* obs) {
+  FLEET_ENTER(h);
+  if (!h || !obs) return FLEET_ERR_INVALID;
+  std::string why;
+  if (fleet_norm_check_fit(n, h->d.E, h->d.obs_dim, h->device, &why) != FLEET_OK) {
+    h->error = "fleet_reset_host_norm: " + why;
+    return FLEET_ERR_INVALID;
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t OD = (size_t)h->d.E * h->d.obs_dim * sizeof(float);
+  HIP_TRY(h, fleet_launch_reset(h->d, nullptr, h->st_obs, h->stream));
+  HIP_TRY(h, fleet_norm_enqueue_reset(n, h->st_obs, fleet_norm_out_buffer(n), h->stream));
+  HIP_TRY(h, hipMemcpyAsync(obs, fleet_norm_out_buffer(n), OD, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   return FLEET_OK;
 }
 

@@ -198,16 +198,24 @@ class FleetVecEnv(_SB3VecEnv):
             self.reset_infos = [{} for _ in range(self.num_envs)]
 
     def reset(self):
+        return self._reset()
+
+    def _reset(self, norm=None):
         self.core.clear_start_overrides()
         self._any_override = False
-        return self.core.batch.reset()
+        return self.core.batch.reset(norm=norm)
 
     def step_async(self, actions):
         self._actions = actions
 
     def step_wait(self):
+        obs, rew, dones, infos = self._step_wait()
+        return obs, rew.astype(np.float32), dones, infos
+
+    def _step_wait(self, norm=None):
+        """step_wait with the float64 rewards; `norm` (a DeviceNormalizer): normalised outputs (FleetVecNormalize)."""
         acts = np.asarray(self._actions).reshape(self.num_envs, -1)
-        obs, rew, done, term = self.core.batch.step(acts, copy=self.copy_obs)
+        obs, rew, done, term = self.core.batch.step(acts, copy=self.copy_obs, norm=norm)
         dones = done.astype(bool)
         # the reference's info is always {} (:235): the envs that did not finish share ONE empty dict per step (4096 dict
         # allocations per step cost more than the step); an env that finished gets a dict of its own
@@ -220,7 +228,7 @@ class FleetVecEnv(_SB3VecEnv):
                             "episode": {"r": float(ret[k]), "l": int(ln[k])}}
             if self._any_override:
                 self.core.clear_start_overrides(dones)
-        return obs, rew.astype(np.float32), dones, infos
+        return obs, rew, dones, infos
 
     def step(self, actions):
         self.step_async(actions)

@@ -425,6 +425,60 @@ int fleet_selftest_division(int device, uint64_t n_pairs, uint64_t seed, uint64_
  * feeds is a 1e-5-sized correction to the state of health). */
 int fleet_selftest_stress(int device, uint64_t n_samples, uint64_t seed, double* max_rel_err);
 
+/* ---- running observation / reward normaliser (fleet_norm.hip) ------------------------------------------------------------
+ * stable-baselines3 2.3.2 `VecNormalize` on the device (DESIGN.md "VecNormalize on the device").  State: obs_rms {mean[D],
+ * var[D], count}, ret_rms {mean, var, count} (start 0 / 1 / 1e-4) and the discounted returns[E] (start 0), all float64.
+ *   reset:  returns = 0; if training && norm_obs: obs_rms.update(obs); obs' = normalise(obs)
+ *   step:   if training && norm_obs: obs_rms.update(obs)          (the post-auto-reset rows; terminal rows never)
+ *           obs' = clip((obs - mean) / sqrt(var + epsilon), +-clip_obs)   in float64, rounded once to float32
+ *           if training: returns = returns * gamma + r; ret_rms.update(returns)      (also with norm_reward = 0)
+ *           r'   = clip(r / sqrt(ret_rms.var + epsilon), +-clip_reward)
+ *           terminal' = normalise(terminal) for the rows of done envs (same, updated statistics); returns[done] = 0
+ *   update(X, n rows): d = mean(X) - mean; tot = count + n; mean += d * n / tot;
+ *           var = (var * count + var(X) * n + d * d * count * n / tot) / tot; count = tot
+ * r is the raw float64 reward rounded to float32 (what VecNormalize sees on top of FleetVecEnv, whose rewards are float32); the
+ * batch moments are accumulated in float64 (SB3 accumulates the observations' in float32).  No floating-point atomics: results
+ * are bit-reproducible from run to run.  A normaliser has its own E and D; calls on one normaliser are serialised by the caller. */
+typedef struct FleetNormParams {
+  int32_t struct_bytes;  /* sizeof(FleetNormParams) */
+  int32_t num_envs;      /* E >= 1 */
+  int32_t obs_dim;       /* D >= 1 */
+  int32_t training, norm_obs, norm_reward;
+  double clip_obs, clip_reward;  /* > 0 */
+  double gamma;                  /* 0 <= gamma <= 1 */
+  double epsilon;                /* > 0 */
+} FleetNormParams;
+typedef struct FleetNorm* fleet_norm_handle;
+
+int fleet_norm_create(int device, const FleetNormParams* p, fleet_norm_handle* out);  /* allocates everything the steps need */
+int fleet_norm_destroy(fleet_norm_handle n);
+const char* fleet_norm_last_error(fleet_norm_handle n);  /* n may be NULL: error of the last failed fleet_norm_create */
+/* launch on an external hipStream_t (borrowed; NULL = the null stream) from now on instead of the normaliser's own stream */
+int fleet_norm_set_stream(fleet_norm_handle n, void* hip_stream);
+/* new training / norm_obs / norm_reward flags and constants; num_envs and obs_dim must stay what they were */
+int fleet_norm_configure(fleet_norm_handle n, const FleetNormParams* p);
+/* device pointers, asynchronous on the normaliser's stream.  obs may equal raw_obs (in place; fleet_norm_original_host then has
+ * no raw observations), reward may equal raw_reward, terminal may equal raw_terminal.  raw_terminal / terminal: [E,D] or NULL;
+ * only the rows of done envs are read and written. */
+int fleet_norm_reset_dev(fleet_norm_handle n, const float* raw_obs, float* obs);
+int fleet_norm_step_dev(fleet_norm_handle n, const float* raw_obs, const double* raw_reward, const uint8_t* done,
+                        const float* raw_terminal, float* obs, double* reward, float* terminal);
+/* host buffers, synchronous; any pointer may be NULL (not read / not written).  set_state recomputes what the steps derive from
+ * the statistics. */
+int fleet_norm_get_state(fleet_norm_handle n, double* obs_mean, double* obs_var, double* obs_count, double* ret_mean,
+                         double* ret_var, double* ret_count, double* returns);
+int fleet_norm_set_state(fleet_norm_handle n, const double* obs_mean, const double* obs_var, const double* obs_count,
+                         const double* ret_mean, const double* ret_var, const double* ret_count, const double* returns);
+/* the raw observations [E,D] and rewards [E] of the last reset / step (SB3's get_original_obs / get_original_reward), to HOST
+ * buffers (either may be NULL).  FLEET_ERR_STATE for the observations after an in-place call (they are gone) or before any call. */
+int fleet_norm_original_host(fleet_norm_handle n, float* obs, double* reward);
+/* The host path with the normaliser between the env's kernels and the transfers, on h's stream: fleet_reset_host (no mask) /
+ * fleet_step_host with normalised obs, reward and terminal rows.  fleet_last_step_episodes keeps reporting the raw episode
+ * returns.  FLEET_ERR_INVALID when the normaliser's E, D or device differ from the env's. */
+int fleet_reset_host_norm(fleet_handle h, fleet_norm_handle n, float* obs);
+int fleet_step_host_norm(fleet_handle h, fleet_norm_handle n, const void* actions, int act_dtype, float* obs, double* reward,
+                         uint8_t* done, float* terminal_obs);
+
 #ifdef __cplusplus
 }
 #endif
