@@ -20,6 +20,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "fleet_device.h"
@@ -80,6 +81,36 @@ class CopyPool {
   std::atomic<int> pending_{0};
 };
 
+// What a prepared replay of an action tape depends on (a captured graph, the argument blocks of a direct run): reused while equal.
+struct TapeKey {
+  const void* tape = nullptr;
+  int len = 0, dtype = 0;
+  float* obs = nullptr;
+  float* term = nullptr;
+  double* reward = nullptr;
+  uint8_t* done = nullptr;
+  int mode = 0;
+  uint64_t gen = 0;
+  bool operator==(const TapeKey& o) const {
+    return std::tie(tape, len, dtype, obs, term, reward, done, mode, gen) ==
+           std::tie(o.tape, o.len, o.dtype, o.obs, o.term, o.reward, o.done, o.mode, o.gen);
+  }
+};
+
+// A tape: `tape_len` rows of [E, N] actions in the action dtype, replayed cyclically
+size_t tape_row_bytes(const FleetDev& d, int act_dtype) { return (size_t)d.E * d.N * (act_dtype == FLEET_ACT_F64 ? 8 : 4); }
+const void* tape_row(const FleetDev& d, const void* tape, int tape_len, int act_dtype, int i) {
+  return static_cast<const char*>(tape) + (size_t)(i % tape_len) * tape_row_bytes(d, act_dtype);
+}
+
+// A batch of more wavefronts than are resident at once (256 CUs x 4 SIMDs x 5 of this kernel = 5120) runs on the library's own queues
+// as two ranges of workgroups, one per queue (FLEET_LAUNCH_DIRECT); one wavefront per env or less only (the wider groups were not
+// measured to gain)
+#ifndef FLEET_DIRECT_SPLIT_WAVES
+#define FLEET_DIRECT_SPLIT_WAVES 6144
+#endif
+constexpr size_t kDirectSplitWaves = FLEET_DIRECT_SPLIT_WAVES;
+
 struct Batch {
   FleetParams p{};
   FleetDev d{};
@@ -120,22 +151,12 @@ struct Batch {
   std::vector<hipEvent_t> region_events;  // fleet_time_regions_begin / _read
   // cached tape graph
   hipGraphExec_t graph_exec = nullptr;
-  const void* graph_tape = nullptr;
-  int graph_len = 0, graph_dtype = 0;
-  float* graph_obs = nullptr;
-  double* graph_reward = nullptr;
-  uint8_t* graph_done = nullptr;
+  TapeKey graph_key;
   // direct AQL submission of tape runs (fleet_direct.hip; FLEET_LAUNCH_DIRECT): the handle's own HSA queue, what its prepared
   // argument blocks describe, the spans of the timed runs waited for so far
   FleetDirect* direct = nullptr;
-  const void* dq_tape = nullptr;
-  int dq_len = 0, dq_dtype = 0, dq_mode = 0;
-  float* dq_obs = nullptr;
-  float* dq_term = nullptr;
-  double* dq_reward = nullptr;
-  uint8_t* dq_done = nullptr;
-  uint64_t dq_gen = 0;   // the handle's generation the prepared argument blocks were made in
-  int dq_timed = 0;      // 0 / 1 (first and last packet of a run) / 2 (every packet): fleet_direct_submit
+  TapeKey dq_key;
+  bool dq_timed = false;  // runs carry dispatch timestamps on their first and last packets: fleet_direct_submit
   std::vector<double> dq_spans_us;
   // Every call that changes what a launch's argument block embeds (the handle's streams, its start schedule, its policy parameters:
   // anything a later version may move into FleetDev) bumps the generation: argument blocks prepared before it are never reused.
@@ -1312,9 +1333,8 @@ static int direct_ready(fleet_handle h, const void* tape, int tape_len, int act_
                "(the call itself waits for the stream's earlier work; fleet_wait_step / fleet_synchronize order what follows)";
     return FLEET_ERR_INVALID;
   }
-  const bool stale = !h->direct || h->dq_gen != h->gen || h->dq_tape != tape || h->dq_len != tape_len || h->dq_dtype != act_dtype ||
-                     h->dq_obs != obs || h->dq_term != terminal_obs || h->dq_reward != reward || h->dq_done != done || h->dq_mode != mode;
-  if (stale) {
+  const TapeKey key{tape, tape_len, act_dtype, obs, terminal_obs, reward, done, mode, h->gen};
+  if (!h->direct || !(h->dq_key == key)) {
     // (the launches in flight read the argument blocks that are about to be replaced)
     int rc = h->direct ? fleet_direct_wait(h->direct, &h->dq_spans_us, &h->error) : FLEET_OK;
     if (rc != FLEET_OK) return rc;
@@ -1328,19 +1348,11 @@ static int direct_ready(fleet_handle h, const void* tape, int tape_len, int act_
       h->error = "direct submission serves single-step launches only (no real_time, no data log)";
       return FLEET_ERR_INVALID;
     }
-    // a batch of more wavefronts than are resident at once (256 CUs x 4 SIMDs x 5 of this kernel = 5120) runs as two ranges of
-    // workgroups on two queues; one wavefront per env or less only (the wider groups were not measured to gain)
-#ifndef FLEET_DIRECT_SPLIT_WAVES
-#define FLEET_DIRECT_SPLIT_WAVES 6144
-#endif
-    const bool split = mode == FLEET_LAUNCH_DIRECT && h->d.N <= 64 && (size_t)L.grid * (L.block / 64) >= FLEET_DIRECT_SPLIT_WAVES;
-    h->dq_tape = nullptr;  // whatever happens below, the old key describes nothing any more
-    h->dq_len = 0;
-    const size_t row = (size_t)h->d.E * h->d.N * (act_dtype == FLEET_ACT_F64 ? 8 : 4);
-    rc = fleet_direct_prepare(h->direct, L, tape, tape_len, row, split, &h->error);
+    const bool split = mode == FLEET_LAUNCH_DIRECT && h->d.N <= 64 && (size_t)L.grid * (L.block / 64) >= kDirectSplitWaves;
+    h->dq_key = TapeKey{};  // whatever happens below, the old key describes nothing any more
+    rc = fleet_direct_prepare(h->direct, L, tape, tape_len, tape_row_bytes(h->d, act_dtype), split, &h->error);
     if (rc != FLEET_OK) return rc;
-    h->dq_mode = mode; h->dq_gen = h->gen;
-    h->dq_tape = tape; h->dq_len = tape_len; h->dq_dtype = act_dtype; h->dq_obs = obs; h->dq_term = terminal_obs; h->dq_reward = reward; h->dq_done = done;
+    h->dq_key = key;
   }
   // what the stream was given before (a reset, a copy of actions ...) has completed before the first packet is written
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1355,8 +1367,6 @@ int fleet_run_tape_dev(fleet_handle h, int steps, const void* tape, int tape_len
     return FLEET_ERR_INVALID;
   }
   HIP_TRY(h, hipSetDevice(h->device));
-  const size_t row = (size_t)h->d.E * h->d.N * (act_dtype == FLEET_ACT_F64 ? 8 : 4);
-  const char* base = static_cast<const char*>(tape);
   if (use_graph == FLEET_LAUNCH_DIRECT || use_graph == FLEET_LAUNCH_DIRECT_ONE_QUEUE) {
     // the library's own AQL packets: the launches of the run keep their state in the dies' L2s (fleet_direct.hip), the last one
     // writes it back.  Asynchronous like the other forms; not on the HIP stream -- the next call on the handle waits for the run.
@@ -1371,9 +1381,9 @@ int fleet_run_tape_dev(fleet_handle h, int steps, const void* tape, int tape_len
   // turn the replay into many short graphs: every hipGraphLaunch costs the host ~10 us)
   const int glen = tape_len * ((64 + tape_len - 1) / tape_len);
   if (use_graph && steps >= glen) {
-    const bool stale = !h->graph_exec || h->graph_tape != tape || h->graph_len != tape_len || h->graph_dtype != act_dtype ||
-                       h->graph_obs != obs || h->graph_reward != reward || h->graph_done != done;
-    if (stale) {
+    // (no generation: the graph reads everything else through device memory, and a change of stream drops it)
+    const TapeKey key{tape, tape_len, act_dtype, obs, nullptr, reward, done, FLEET_LAUNCH_GRAPH, 0};
+    if (!h->graph_exec || !(h->graph_key == key)) {
       drop_graph(h);
       hipGraph_t graph = nullptr;
       // capture is not allowed on the legacy null stream (what torch's default stream is): record on the handle's own
@@ -1381,7 +1391,8 @@ int fleet_run_tape_dev(fleet_handle h, int steps, const void* tape, int tape_len
       hipStream_t cap = h->stream ? h->stream : h->own_stream;
       HIP_TRY(h, hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
       for (int k = 0; k < glen; ++k) {
-        hipError_t e = fleet_launch_step(h->d, base + (size_t)(k % tape_len) * row, act_dtype, 1, obs, reward, done, nullptr, nullptr, cap);
+        hipError_t e = fleet_launch_step(h->d, tape_row(h->d, tape, tape_len, act_dtype, k), act_dtype, 1, obs, reward, done, nullptr,
+                                         nullptr, cap);
         if (e != hipSuccess) {
           (void)hipStreamEndCapture(cap, &graph);
           if (graph) (void)hipGraphDestroy(graph);
@@ -1398,13 +1409,12 @@ int fleet_run_tape_dev(fleet_handle h, int steps, const void* tape, int tape_len
         return FLEET_ERR_HIP;
       }
       (void)hipGraphUpload(h->graph_exec, h->stream);  // best effort: the first replay does not pay for the upload
-      h->graph_tape = tape; h->graph_len = tape_len; h->graph_dtype = act_dtype;
-      h->graph_obs = obs; h->graph_reward = reward; h->graph_done = done;
+      h->graph_key = key;
     }
     for (; i + glen <= steps; i += glen) HIP_TRY(h, hipGraphLaunch(h->graph_exec, h->stream));
   }
   for (; i < steps; ++i)
-    HIP_TRY(h, fleet_launch_step(h->d, base + (size_t)(i % tape_len) * row, act_dtype, 1, obs, reward, done, nullptr, nullptr,
+    HIP_TRY(h, fleet_launch_step(h->d, tape_row(h->d, tape, tape_len, act_dtype, i), act_dtype, 1, obs, reward, done, nullptr, nullptr,
                                  h->stream));
   return FLEET_OK;
 }
@@ -1454,10 +1464,10 @@ int fleet_time_regions_begin(fleet_handle h, int regions, int steps, const void*
   HIP_TRY(h, hipSetDevice(h->device));
   if (use_graph == FLEET_LAUNCH_DIRECT || use_graph == FLEET_LAUNCH_DIRECT_ONE_QUEUE) {  // the runs' own dispatch timestamps: start of the first launch -> end of the last
     h->dq_spans_us.clear();
-    h->dq_timed = 1;
+    h->dq_timed = true;
     int rc = FLEET_OK;
     for (int r = 0; r < regions && rc == FLEET_OK; ++r) rc = fleet_run_tape_dev(h, steps, tape, tape_len, act_dtype, obs, reward, done, use_graph);
-    h->dq_timed = 0;
+    h->dq_timed = false;
     return rc;
   }
   for (auto& e : h->region_events)
@@ -1507,8 +1517,6 @@ int fleet_time_steps_dev(fleet_handle h, int steps, const void* tape, int tape_l
     return FLEET_ERR_INVALID;
   }
   HIP_TRY(h, hipSetDevice(h->device));
-  const size_t row = (size_t)h->d.E * h->d.N * (act_dtype == FLEET_ACT_F64 ? 8 : 4);
-  const char* base = static_cast<const char*>(tape);
   std::vector<hipEvent_t> ev(2 * (size_t)steps, nullptr);
   int rc = FLEET_OK;
   for (auto& e : ev)
@@ -1516,7 +1524,7 @@ int fleet_time_steps_dev(fleet_handle h, int steps, const void* tape, int tape_l
   if (rc == FLEET_OK) {
     for (int i = 0; i < steps && rc == FLEET_OK; ++i) {
       if (hipEventRecord(ev[2 * i], h->stream) != hipSuccess) rc = FLEET_ERR_HIP;
-      if (fleet_launch_step(h->d, base + (size_t)(i % tape_len) * row, act_dtype, 1, obs, reward, done, nullptr, nullptr,
+      if (fleet_launch_step(h->d, tape_row(h->d, tape, tape_len, act_dtype, i), act_dtype, 1, obs, reward, done, nullptr, nullptr,
                             h->stream) != hipSuccess)
         rc = FLEET_ERR_HIP;
       if (hipEventRecord(ev[2 * i + 1], h->stream) != hipSuccess) rc = FLEET_ERR_HIP;

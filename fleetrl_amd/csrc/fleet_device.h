@@ -260,8 +260,8 @@ hipError_t fleet_launch_step(const FleetDev& d, const void* actions, int act_dty
                              uint8_t* done, float* terminal_obs, int32_t* done_count, hipStream_t s);
 // A single-step launch written down instead of issued (direct AQL submission, fleet_direct.hip): the host-side kernel symbol (its
 // name resolves the kernel in the code object), the launch geometry and the kernel-argument block; `actions_offset` = where the two
-// copies of the action pointer sit in it (a tape replay patches them per step).  host_fn == nullptr / hipErrorNotSupported: not a
-// single-step configuration (real_time, data log).
+// copies of the action pointer sit in it (a tape replay patches them per step).  The same instance and arguments fleet_launch_step
+// would issue.  hipErrorNotSupported: not a single-step configuration (real_time, data log).
 struct FleetStepLaunch {
   const void* host_fn;
   unsigned grid, block, args_bytes;

@@ -9,7 +9,8 @@ struct FleetDirect;  // HSA queues of the handle's own on the HIP device's agent
 
 // Opens the queue, loads `<library>.gfx950.hsaco` from beside the library, checks that it is the library's twin (source hash) and
 // PROBES the placement the mode relies on (workgroup w of every launch on the same die).  FLEET_OK / FLEET_ERR_*; *err says why not.
-// FLEET_ERR_UNSUPPORTED: the platform does not place workgroups the way the mode needs (callers fall back to HIP's launches).
+// FLEET_ERR_UNSUPPORTED: the platform does not place workgroups the way the mode needs; the C ABI returns it, and its caller chooses
+// FLEET_LAUNCH_GRAPH or FLEET_LAUNCH_EAGER instead (as bench.py does).
 int fleet_direct_open(int hip_device, FleetDirect** out, std::string* err);
 void fleet_direct_close(FleetDirect* q);
 // What the probe found: map[k] = the die of workgroups w with (w & 7) == k on queue 0 (-1: no probe yet); *num_xcc = dies of the agent;
@@ -28,9 +29,8 @@ int fleet_direct_parts(FleetDirect* q);  // 1 or 2: how the prepared launch is l
 // `steps` launches (tape rows 0, 1, ... cyclically) behind the run's placement-record launch, asynchronous.  Fences: every packet acquires
 // at agent scope (the vector / scalar L1s are invalidated; the first at system scope) and releases NOTHING -- except the last, which
 // releases at system scope.
-// `timed`: completion signals with dispatch timestamps -- 1: on the first and the last packet of the run (fleet_direct_wait reports the
-// span); 2: on every packet (fleet_direct_wait reports each launch's own start -> end).
-int fleet_direct_submit(FleetDirect* q, int steps, int timed, std::string* err);
+// `timed`: completion signals with dispatch timestamps on the first and the last packet of the run (fleet_direct_wait reports the span).
+int fleet_direct_submit(FleetDirect* q, int steps, bool timed, std::string* err);
 bool fleet_direct_busy(FleetDirect* q);   // something submitted has not completed
 // waits for everything submitted; spans_us (nullable): per timed run since the last wait, in order (see fleet_direct_submit)
 int fleet_direct_wait(FleetDirect* q, std::vector<double>* spans_us, std::string* err);

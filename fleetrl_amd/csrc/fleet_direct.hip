@@ -16,8 +16,9 @@
 // workgroups (round-robin over the dies, dispatch after dispatch from the same die of the queue: tools/ubench/xcc_map.cpp) -- it is not a
 // documented contract (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement & inter-workgroup visibility").  So:
 //   * fleet_direct_open PROBES it on the queue it has just created -- a chain of launches, with and without a multiple of 8
-//     workgroups, each workgroup writing down HW_REG_XCC_ID -- and refuses the mode (FLEET_ERR_UNSUPPORTED; callers fall back to HIP's
-//     launches) unless the map workgroup -> die is periodic in 8 and identical from launch to launch;
+//     workgroups, each workgroup writing down HW_REG_XCC_ID -- and refuses the mode (FLEET_ERR_UNSUPPORTED, returned through the C ABI:
+//     the caller chooses the hipGraph or eager launches) unless the map workgroup -> die is periodic in 8 and identical from launch to
+//     launch;
 //   * the die a queue starts dealing from is NOT a constant of the queue: it moves by one whenever a queue is created or destroyed in
 //     the process (found by this library's own tests: the second queue of a split run moved the first one's; then measured,
 //     tools/ubench/xcc_map.cpp).  So the FIRST launch of every run -- a chain of launches that ends with the release; its first
@@ -144,9 +145,9 @@ struct FleetDirect {
   std::vector<unsigned char> kargs_host;  // what was uploaded (the fault hook patches a block of it)
   unsigned packed_n_offset = 0, guard_offset = 0, rec_offset = 0;
   static constexpr size_t kBlockBytes = sizeof(FleetStepLaunch::args);
-  // signals: a pool; the ones handed out since the last wait; per timed run what its spans are read from
+  // signals: a pool; the ones handed out since the last wait; per timed run what its span is read from
   std::vector<hsa_signal_t> pool, pending;
-  struct Mark { hsa_signal_t first[2], last[2]; int parts; std::vector<hsa_signal_t> each; };
+  struct Mark { hsa_signal_t first[2], last[2]; int parts; };
   std::vector<Mark> marks;
   hsa_signal_t last[2] = {};
   bool in_flight = false;
@@ -578,7 +579,7 @@ int fleet_direct_fault(FleetDirect* q, int kind, int tape_row, std::string* err)
   return FLEET_OK;
 }
 
-int fleet_direct_submit(FleetDirect* q, int steps, int timed, std::string* err) {
+int fleet_direct_submit(FleetDirect* q, int steps, bool timed, std::string* err) {
   if (!q || !q->queue[0] || q->tape_len < 1 || steps < 1) return FLEET_ERR_INVALID;
   if (q->pending.size() > 4096) {  // a caller that submits run after run without ever waiting (more than any timed series): a wait recycles the signals
     const int rc = fleet_direct_wait(q, nullptr, err);
@@ -593,23 +594,12 @@ int fleet_direct_submit(FleetDirect* q, int steps, int timed, std::string* err) 
   };
   for (int part = 0; part < q->parts; ++part) {
     m.last[part] = need_signal();
-    m.first[part] = (timed == 1) ? need_signal() : hsa_signal_t{};
-    if (!m.last[part].handle || (timed == 1 && !m.first[part].handle)) {
+    // (one packet cannot carry two signals: a run of one launch is timed by that packet's own start and end)
+    m.first[part] = !timed ? hsa_signal_t{} : steps == 1 ? m.last[part] : need_signal();
+    if (!m.last[part].handle || (timed && !m.first[part].handle)) {
       if (err) *err = "fleet_direct_submit: hsa_signal_create failed";
       return FLEET_ERR_HIP;
     }
-  }
-  if (timed == 2) {  // every packet carries a signal of its own (the last one of each part: m.last)
-    m.each.resize((size_t)steps * q->parts);
-    for (int i = 0; i < steps; ++i)
-      for (int part = 0; part < q->parts; ++part) {
-        hsa_signal_t s = (i == steps - 1) ? m.last[part] : need_signal();
-        if (!s.handle) {
-          if (err) *err = "fleet_direct_submit: hsa_signal_create failed";
-          return FLEET_ERR_HIP;
-        }
-        m.each[(size_t)i * q->parts + part] = s;
-      }
   }
   // the run's first launch goes out with the block that has it write the placement record into the others (header comment)
   const size_t first_blocks = (size_t)q->parts * q->tape_len * FleetDirect::kBlockBytes;
@@ -621,10 +611,7 @@ int fleet_direct_submit(FleetDirect* q, int steps, int timed, std::string* err) 
   }
   for (int i = 0; i < steps; ++i)
     for (int part = 0; part < q->parts; ++part) {  // step by step, queue by queue: both chains get going at once
-      hsa_signal_t sig{};
-      if (timed == 2) sig = m.each[(size_t)i * q->parts + part];
-      else if (i == steps - 1) sig = m.last[part];
-      else if (timed == 1 && i == 0) sig = m.first[part];
+      const hsa_signal_t sig = (i == steps - 1) ? m.last[part] : (timed && i == 0) ? m.first[part] : hsa_signal_t{};
       // the first packet after a release acquires at system scope (whatever the host or another queue wrote meanwhile), the others
       // at agent scope; a packet releases only when it is the last of a run that asks for it
       const int acq = (i == 0) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_AGENT;
@@ -634,12 +621,8 @@ int fleet_direct_submit(FleetDirect* q, int steps, int timed, std::string* err) 
                           : q->kargs_dev + ((size_t)part * q->tape_len + (size_t)(i % q->tape_len)) * FleetDirect::kBlockBytes,
                    acq, rel, sig);
     }
-  if (timed) {
-    if (timed == 1 && steps == 1)  // (one packet cannot carry two signals: its own start and end are the span then)
-      for (int part = 0; part < q->parts; ++part) m.first[part] = m.last[part];
-    q->marks.push_back(std::move(m));
-  }
-  for (int part = 0; part < 2; ++part) q->last[part] = part < q->parts ? (timed ? q->marks.back().last[part] : m.last[part]) : hsa_signal_t{};
+  if (timed) q->marks.push_back(m);
+  for (int part = 0; part < 2; ++part) q->last[part] = part < q->parts ? m.last[part] : hsa_signal_t{};
   q->in_flight = true;
   if (q->fault_rotate) {  // (the hook corrupts ONE run: the next one records as ever)
     q->fault_rotate = 0;
@@ -681,22 +664,7 @@ int fleet_direct_wait(FleetDirect* q, std::vector<double>* spans_us, std::string
     q->in_flight = false;
   }
   auto us = [&](uint64_t t0, uint64_t t1, bool ok) { return ok && q->tick_hz && t1 > t0 ? (double)(t1 - t0) * 1e6 / (double)q->tick_hz : -1.0; };
-  for (const FleetDirect::Mark& m : q->marks) {
-    if (!m.each.empty()) {  // every launch's own duration; with two queues a step lasts from its earlier start to its later end
-      for (size_t i = 0; i < m.each.size() / m.parts; ++i) {
-        uint64_t t0 = UINT64_MAX, t1 = 0;
-        bool ok = true;
-        for (int part = 0; part < m.parts; ++part) {
-          hsa_amd_profiling_dispatch_time_t a{};
-          ok = ok && hsa_amd_profiling_get_dispatch_time(q->agent, m.each[i * m.parts + part], &a) == HSA_STATUS_SUCCESS;
-          t0 = a.start < t0 ? a.start : t0;
-          t1 = a.end > t1 ? a.end : t1;
-        }
-        if (spans_us) spans_us->push_back(us(t0, t1, ok));
-      }
-      continue;
-    }
-    // a timed run: from the earlier start of its first launches to the later end of its last
+  for (const FleetDirect::Mark& m : q->marks) {  // a timed run: from the earlier start of its first launches to the later end of its last
     uint64_t t0 = UINT64_MAX, t1 = 0;
     bool ok = true;
     for (int part = 0; part < m.parts; ++part) {

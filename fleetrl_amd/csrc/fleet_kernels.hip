@@ -121,7 +121,7 @@ __device__ __forceinline__ double dpp_add(double v) {
 template <int G>
 __device__ __forceinline__ bool group_any(bool v) {
   const unsigned long long m = __ballot(v);
-  if (G >= 64) return m != 0ull;  // (groups of several wavefronts never run the event-skipping loop: launch_step_gd)
+  if (G >= 64) return m != 0ull;  // (groups of several wavefronts never run the event-skipping loop: plan_step_gd)
   const int base = (int)(threadIdx.x % 64) & ~(G - 1);
   return ((m >> base) & ((1ull << (G % 64)) - 1ull)) != 0ull;
 }
@@ -966,8 +966,9 @@ struct StepKernargPrefix {
   FleetDev d_arg;
 };
 static_assert(offsetof(StepKernargPrefix, d_arg) == 48 && alignof(FleetDev) == 8, "twelve preloaded dwords, then the argument block");
-// ... and the whole argument list: what a launch that does not go through hipLaunchKernel (fleet_describe_step: AQL packets written by
-// the library itself, fleet_direct.hip) puts into the kernel-argument segment.  Checked against the code object's metadata at load.
+// ... and the whole argument list as the kernel-argument segment holds it: what every step launch is given (step_args), field by field
+// on a HIP stream, as one block in the AQL packets the library writes itself (fleet_describe_step, fleet_direct.hip).  Checked against
+// the code object's metadata at load.
 struct StepKernargs {
   const Hot* p_hot;
   const SegRec* p_run;
@@ -990,7 +991,9 @@ struct StepKernargs {
 };
 static_assert(offsetof(StepKernargs, d_arg) == offsetof(StepKernargPrefix, d_arg) && sizeof(StepKernargs) <= sizeof(FleetStepLaunch::args),
               "the argument block of a described launch");
-thread_local FleetStepLaunch* t_describe = nullptr;  // set by fleet_describe_step around fleet_launch_step
+static_assert(offsetof(StepKernargs, rec_rows) == offsetof(StepKernargs, rec_blocks) + 8 &&
+                  offsetof(StepKernargs, rec_rotate) == offsetof(StepKernargs, rec_rows) + 4,
+              "fleet_direct_prepare fills rec_blocks, rec_rows and rec_rotate as one 16-byte piece");
 
 // What a K-step instance carries besides the action tape (MULTI only; round 5): the built-in policies and the event-skipping loop of
 // real_time each cost the tape rollout scalar registers it spills and branches it never takes -- compiled per use, the tape-only
@@ -1733,108 +1736,68 @@ int group_size(int N) {
   return G;
 }
 
-// A K-step launch without the data log: the instance that carries what the launch uses -- the tape only, the built-in policies, or the
-// event-skipping loop (groups of 32 lanes and more; smaller groups keep ONE instance with everything behind run-time tests).
-template <int G, int DEG, bool WIDE>
-void launch_many(const FleetDev& d, dim3 grid, dim3 block, const void* actions, int act_mode, int K, float* obs, double* reward,
-                 uint8_t* done, float* terminal_obs, int32_t* done_count, hipStream_t s) {
-#define FLEET_PRE_ARGS d.hot, d.run, d.soh, actions, d.E, d.N, d.env,  /* the leading arguments (12 dwords, preloaded) */
-#define FLEET_MANY(MODE)                                                                                                          \
-  hipLaunchKernelGGL((fleet_step_kernel<G, DEG, true, WIDE, false, false, MODE>), grid, block, 0, s, FLEET_PRE_ARGS d, actions, act_mode, K, \
-                     obs, reward, done, terminal_obs, done_count, 0ull, nullptr, 0, 0)
-  if (G < 32) FLEET_MANY(kModeAll);
-  else if (d.real_time) FLEET_MANY((G < 32 ? kModeAll : kModeRt));
-  else if (act_mode >= FLEET_ACT_POLICY_UNCONTROLLED) FLEET_MANY((G < 32 ? kModeAll : kModePolicy));
-  else FLEET_MANY((G < 32 ? kModeAll : kModeTape));
-#undef FLEET_MANY
-}
+// The launch a step configuration takes: the instance of fleet_step_kernel, its grid of kBlock-thread workgroups, and whether it is
+// the single-step instance (the only kind fleet_describe_step writes down).  Every instance has the same signature.
+using StepKernelFn = decltype(&fleet_step_kernel<1, FLEET_DEG_NONE, false, false>);
+struct StepPlan {
+  StepKernelFn fn;
+  unsigned grid;
+  bool single;
+};
 
-// A single-step launch goes to the HIP stream -- or, when fleet_describe_step asks, is written down instead: kernel, grid and the
-// argument block, for the AQL packets the library writes itself (fleet_direct.hip).
-inline void describe_launch(FleetStepLaunch* L, const void* host_fn, dim3 grid, dim3 block, const FleetDev& d, const void* actions,
-                            int act_mode, float* obs, double* reward, uint8_t* done, float* terminal_obs, int32_t* done_count) {
-  StepKernargs a{};
-  a.p_hot = d.hot; a.p_run = d.run; a.p_soh = d.soh; a.p_actions = actions; a.p_E = d.E; a.p_N = d.N; a.p_env = d.env;
-  a.d_arg = d; a.actions = actions; a.act_mode = act_mode; a.K = 1;
-  a.obs = obs; a.reward = reward; a.done = done; a.terminal_obs = terminal_obs; a.done_count = done_count;
-  L->host_fn = host_fn; L->grid = grid.x; L->block = block.x; L->args_bytes = (unsigned)sizeof a;
-  L->actions_offset[0] = (unsigned)offsetof(StepKernargs, p_actions); L->actions_offset[1] = (unsigned)offsetof(StepKernargs, actions);
-  L->packed_n_offset = (unsigned)offsetof(StepKernargs, p_N);
-  L->guard_offset = (unsigned)offsetof(StepKernargs, guard_bytes);
-  L->rec_offset = (unsigned)offsetof(StepKernargs, rec_blocks);  // (then rec_rows and rec_rotate)
-  static_assert(offsetof(StepKernargs, rec_rows) == offsetof(StepKernargs, rec_blocks) + 8 && offsetof(StepKernargs, rec_rotate) == offsetof(StepKernargs, rec_rows) + 4,
-                "fleet_direct_prepare fills the three as one 16-byte piece");
-  memcpy(L->args, &a, sizeof a);
-}
-#define FLEET_LAUNCH_SINGLE(KERNEL, GRID)                                                                                              \
-  do {                                                                                                                                 \
-    if (t_describe) describe_launch(t_describe, (const void*)(KERNEL), GRID, block, d, actions, f64, obs, reward, done, terminal_obs, done_count); \
-    else hipLaunchKernelGGL(KERNEL, GRID, block, 0, s, FLEET_PRE_ARGS d, actions, f64, 1, obs, reward, done, terminal_obs, done_count, 0ull, nullptr, 0, 0); \
-  } while (0)
-
-template <int G, int DEG>
-hipError_t launch_step_gd(const FleetDev& d, const void* actions, int act_dtype, int K, float* obs, double* reward,
-                          uint8_t* done, float* terminal_obs, int32_t* done_count, hipStream_t s) {
+// Instance selection.  G (EVs per env rounded up to a power of two, at most 64) and DEG come from the switches of plan_step; an env
+// of 65 ... kMaxGroup EVs re-enters with a group of two or four wavefronts (G = 128 / 256), one of more EVs than lanes (or that needs
+// the real_time or data-log code) with WIDE: every lane walks several EVs.  The `if constexpr` tests keep kernels that a (G, WIDE)
+// never launches from being instantiated at all.
+template <int G, int DEG, bool WIDE = false>
+StepPlan plan_step_gd(const FleetDev& d, int act_mode, int K, bool has_done_count) {
+  if constexpr (G == 64 && !WIDE) {
+    if (d.N > kMaxGroup || (d.N > 64 && (d.real_time || d.log_pos))) return plan_step_gd<64, DEG, true>(d, act_mode, K, has_done_count);
+    if (d.N > 128) return plan_step_gd<256, DEG>(d, act_mode, K, has_done_count);
+    if (d.N > 64) return plan_step_gd<128, DEG>(d, act_mode, K, has_done_count);
+  }
   const int epb = kBlock / G;
-  const dim3 grid((d.E + epb - 1) / epb), block(kBlock);
-  const int f64 = act_dtype;  // FLEET_ACT_F32 / FLEET_ACT_F64 / FLEET_ACT_POLICY_* (policies: MULTI kernel only)
-  // the single-step kernel carries neither the policies, nor the event-skipping loop, nor the data-log code
-  const bool single = (K == 1 && !done_count && act_dtype < FLEET_ACT_POLICY_UNCONTROLLED && !d.real_time && !d.log_pos);
-  if (t_describe && !single) return hipErrorNotSupported;  // only single-step launches are described
-  // K steps per launch from a tape or a built-in policy keep one EV per lane too (not the event-skipping loop, not the data log)
-  const bool many_grouped = (!single && !d.real_time && !d.log_pos);
-  if (G == 64 && (single || many_grouped) && d.N > 64 && d.N <= kMaxGroup) {  // one EV per lane, two or four wavefronts per env
-    constexpr int GG2 = (G == 64) ? 128 : G, GG4 = (G == 64) ? 256 : G;  // (only instantiated behind G == 64)
-    if (many_grouped) {
-      if (d.N <= 128) launch_many<GG2, DEG, false>(d, dim3((d.E + 1) / 2), block, actions, f64, K, obs, reward, done, terminal_obs, done_count, s);
-      else launch_many<GG4, DEG, false>(d, dim3(d.E), block, actions, f64, K, obs, reward, done, terminal_obs, done_count, s);
-      return hipGetLastError();
-    }
-    if (d.N <= 128) {
-      const dim3 g2((d.E + 1) / 2);
-      if (f64 == FLEET_ACT_F64)
-        FLEET_LAUNCH_SINGLE((fleet_step_kernel<GG2, DEG, false, false, false, true>), g2);
-      else
-        FLEET_LAUNCH_SINGLE((fleet_step_kernel<GG2, DEG, false, false>), g2);
-    } else {
-      const dim3 g4(d.E);
-      if (f64 == FLEET_ACT_F64)
-        FLEET_LAUNCH_SINGLE((fleet_step_kernel<GG4, DEG, false, false, false, true>), g4);
-      else
-        FLEET_LAUNCH_SINGLE((fleet_step_kernel<GG4, DEG, false, false>), g4);
-    }
-    return hipGetLastError();
+  const unsigned grid = (unsigned)((d.E + epb - 1) / epb);
+  // the single-step kernel carries neither the policies, nor the event-skipping loop, nor the data-log code; with WIDE it reads
+  // either action dtype at run time
+  if (K == 1 && !has_done_count && act_mode < FLEET_ACT_POLICY_UNCONTROLLED && !d.real_time && !d.log_pos) {
+    if constexpr (!WIDE)
+      if (act_mode == FLEET_ACT_F64) return {&fleet_step_kernel<G, DEG, false, false, false, true>, grid, true};
+    return {&fleet_step_kernel<G, DEG, false, WIDE>, grid, true};
   }
-  if (G == 64 && d.N > G) {  // more EVs than lanes: every lane walks several EVs
-    if (single)
-      FLEET_LAUNCH_SINGLE((fleet_step_kernel<G, DEG, false, (G == 64)>), grid);
-    else if (d.log_pos)
-      hipLaunchKernelGGL((fleet_step_kernel<G, DEG, true, (G == 64), true>), grid, block, 0, s, FLEET_PRE_ARGS d, actions, f64, K, obs, reward,
-                         done, terminal_obs, done_count, 0ull, nullptr, 0, 0);
-    else
-      launch_many<G, DEG, (G == 64)>(d, grid, block, actions, f64, K, obs, reward, done, terminal_obs, done_count, s);
-  } else {
-    if (single && f64 == FLEET_ACT_F64)
-      FLEET_LAUNCH_SINGLE((fleet_step_kernel<G, DEG, false, false, false, true>), grid);
-    else if (single)
-      FLEET_LAUNCH_SINGLE((fleet_step_kernel<G, DEG, false, false>), grid);
-    else if (d.log_pos)
-      hipLaunchKernelGGL((fleet_step_kernel<G, DEG, true, false, true>), grid, block, 0, s, FLEET_PRE_ARGS d, actions, f64, K, obs, reward, done,
-                         terminal_obs, done_count, 0ull, nullptr, 0, 0);
-    else
-      launch_many<G, DEG, false>(d, grid, block, actions, f64, K, obs, reward, done, terminal_obs, done_count, s);
+  // K steps per launch: the data log (groups of one wavefront or less); from 32 lanes on the instance that carries what the launch
+  // uses -- the event-skipping loop, the built-in policies, or the tape only; smaller groups keep ONE instance with everything behind
+  // run-time tests
+  if constexpr (G <= 64)
+    if (d.log_pos) return {&fleet_step_kernel<G, DEG, true, WIDE, true>, grid, false};
+  if constexpr (G >= 32) {
+    if (d.real_time) return {&fleet_step_kernel<G, DEG, true, WIDE, false, false, kModeRt>, grid, false};
+    if (act_mode >= FLEET_ACT_POLICY_UNCONTROLLED) return {&fleet_step_kernel<G, DEG, true, WIDE, false, false, kModePolicy>, grid, false};
+    return {&fleet_step_kernel<G, DEG, true, WIDE, false, false, kModeTape>, grid, false};
   }
-  return hipGetLastError();
+  // (no `else` above: this instance stays instantiated for every group, and kModeRt for G = 128 / 256, though no launch takes them --
+  // the set of instances this selection has always compiled)
+  return {&fleet_step_kernel<G, DEG, true, WIDE, false, false, kModeAll>, grid, false};
 }
 
 template <int G>
-hipError_t launch_step_g(const FleetDev& d, const void* actions, int act_dtype, int K, float* obs, double* reward,
-                         uint8_t* done, float* terminal_obs, int32_t* done_count, hipStream_t s) {
+StepPlan plan_step_g(const FleetDev& d, int act_mode, int K, bool has_done_count) {
   switch (d.deg_mode) {
-    case FLEET_DEG_NONE: return launch_step_gd<G, FLEET_DEG_NONE>(d, actions, act_dtype, K, obs, reward, done, terminal_obs, done_count, s);
-    case FLEET_DEG_LINEAR: return launch_step_gd<G, FLEET_DEG_LINEAR>(d, actions, act_dtype, K, obs, reward, done, terminal_obs, done_count, s);
-    default: return launch_step_gd<G, FLEET_DEG_RAINFLOW>(d, actions, act_dtype, K, obs, reward, done, terminal_obs, done_count, s);
+    case FLEET_DEG_NONE: return plan_step_gd<G, FLEET_DEG_NONE>(d, act_mode, K, has_done_count);
+    case FLEET_DEG_LINEAR: return plan_step_gd<G, FLEET_DEG_LINEAR>(d, act_mode, K, has_done_count);
+    default: return plan_step_gd<G, FLEET_DEG_RAINFLOW>(d, act_mode, K, has_done_count);
   }
+}
+
+// The argument block of a step launch, as issued on a HIP stream; a run on the library's own queue fills in the placement record's
+// fields itself (fleet_direct_prepare).
+StepKernargs step_args(const FleetDev& d, const void* actions, int act_mode, int K, float* obs, double* reward, uint8_t* done,
+                       float* terminal_obs, int32_t* done_count) {
+  StepKernargs a{};
+  a.p_hot = d.hot; a.p_run = d.run; a.p_soh = d.soh; a.p_actions = actions; a.p_E = d.E; a.p_N = d.N; a.p_env = d.env;
+  a.d_arg = d; a.actions = actions; a.act_mode = act_mode; a.K = K;
+  a.obs = obs; a.reward = reward; a.done = done; a.terminal_obs = terminal_obs; a.done_count = done_count;
+  return a;
 }
 
 template <int G>
@@ -1880,21 +1843,34 @@ hipError_t fleet_launch_reset(const FleetDev& d, const uint8_t* mask, float* obs
 #undef CALL
 }
 
-hipError_t fleet_launch_step(const FleetDev& d, const void* actions, int act_dtype, int K, float* obs, double* reward,
-                             uint8_t* done, float* terminal_obs, int32_t* done_count, hipStream_t s) {
-#define CALL(Gv) launch_step_g<Gv>(d, actions, act_dtype, K, obs, reward, done, terminal_obs, done_count, s)
+static StepPlan plan_step(const FleetDev& d, int act_mode, int K, bool has_done_count) {
+#define CALL(Gv) plan_step_g<Gv>(d, act_mode, K, has_done_count)
   FLEET_DISPATCH_G(d.N, CALL)
 #undef CALL
 }
 
+hipError_t fleet_launch_step(const FleetDev& d, const void* actions, int act_dtype, int K, float* obs, double* reward,
+                             uint8_t* done, float* terminal_obs, int32_t* done_count, hipStream_t s) {
+  const StepPlan p = plan_step(d, act_dtype, K, done_count != nullptr);
+  const StepKernargs a = step_args(d, actions, act_dtype, K, obs, reward, done, terminal_obs, done_count);
+  hipLaunchKernelGGL(p.fn, dim3(p.grid), dim3(kBlock), 0, s, a.p_hot, a.p_run, a.p_soh, a.p_actions, a.p_E, a.p_N, a.p_env, a.d_arg,
+                     a.actions, a.act_mode, a.K, a.obs, a.reward, a.done, a.terminal_obs, a.done_count, a.guard_bytes, a.rec_blocks,
+                     a.rec_rows, a.rec_rotate);
+  return hipGetLastError();
+}
+
 hipError_t fleet_describe_step(const FleetDev& d, const void* actions, int act_dtype, float* obs, double* reward, uint8_t* done,
                                float* terminal_obs, FleetStepLaunch* out) {
-  out->host_fn = nullptr;
-  t_describe = out;
-  const hipError_t e = fleet_launch_step(d, actions, act_dtype, 1, obs, reward, done, terminal_obs, nullptr, nullptr);
-  t_describe = nullptr;
-  if (e != hipSuccess) return e;
-  return out->host_fn ? hipSuccess : hipErrorNotSupported;
+  const StepPlan p = plan_step(d, act_dtype, 1, false);
+  if (!p.single) return hipErrorNotSupported;
+  const StepKernargs a = step_args(d, actions, act_dtype, 1, obs, reward, done, terminal_obs, nullptr);
+  out->host_fn = (const void*)p.fn; out->grid = p.grid; out->block = kBlock; out->args_bytes = (unsigned)sizeof a;
+  out->actions_offset[0] = (unsigned)offsetof(StepKernargs, p_actions); out->actions_offset[1] = (unsigned)offsetof(StepKernargs, actions);
+  out->packed_n_offset = (unsigned)offsetof(StepKernargs, p_N);
+  out->guard_offset = (unsigned)offsetof(StepKernargs, guard_bytes);
+  out->rec_offset = (unsigned)offsetof(StepKernargs, rec_blocks);  // (then rec_rows and rec_rotate)
+  memcpy(out->args, &a, sizeof a);
+  return hipSuccess;
 }
 
 hipError_t fleet_launch_term_compact(const FleetDev& d, const uint8_t* done, const float* term, int32_t* idx, int32_t* count,
