@@ -20,6 +20,8 @@ ACT_F32, ACT_F64 = 0, 1
 # fleet_run_tape_dev / fleet_time_regions_begin: how the launches reach the GPU (include/fleet_hip.h FLEET_LAUNCH_*)
 LAUNCH_EAGER, LAUNCH_GRAPH, LAUNCH_DIRECT, LAUNCH_DIRECT_ONE_QUEUE = 0, 1, 2, 3
 POLICY_UNCONTROLLED, POLICY_DISTRIBUTED, POLICY_NIGHT = 2, 3, 4
+# fleet_lp_plan_dev status bits per (env, EV) (include/fleet_hip.h FLEET_LP_*)
+LP_UNREACHABLE, LP_NEG_RETURN, LP_ABOVE_TARGET, LP_GRID_NEGATIVE = 1, 2, 4, 8
 
 DEVERR_OBS_FORMAT, DEVERR_NEG_LIFE, DEVERR_SOH_MISMATCH, DEVERR_DOD_RANGE, DEVERR_TABLE_END, DEVERR_INTERNAL, DEVERR_PLACEMENT = 1, 2, 4, 8, 16, 32, 64
 
@@ -202,6 +204,7 @@ def load_library():
     lib.fleet_step_many_dev.argtypes = [vp, C.c_int, vp, C.c_int, f32p, f64p, vp]
     lib.fleet_rollout_policy_dev.argtypes = [vp, C.c_int, C.c_int, f32p, f64p, vp]
     lib.fleet_set_night_policy.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    lib.fleet_lp_plan_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     if hasattr(lib, "fleet_set_rainflow_count_all"):  # (absent from the older libraries the A/B scripts run beside the tree's)
         lib.fleet_set_rainflow_count_all.argtypes = [vp, C.c_int]
         lib.fleet_set_rainflow_count_all.restype = C.c_int
@@ -292,4 +295,5 @@ EXPORTED_SYMBOLS = (
     "fleet_time_regions_begin", "fleet_time_regions_read", "fleet_rccl_unique_id", "fleet_rccl_comm_create",
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
+    "fleet_lp_plan_dev",
 ) + NORM_SYMBOLS

@@ -308,6 +308,14 @@ class FleetBatch:
         """K steps in one launch with a built-in policy (_capi.POLICY_UNCONTROLLED / POLICY_DISTRIBUTED / POLICY_NIGHT)."""
         self._check(self.lib.fleet_rollout_policy_dev(self.h, int(policy), int(K), obs_ptr, reward_sum_ptr, done_count_ptr))
 
+    def lp_plan_dev(self, H: int, actions_ptr: int, soc_plan_ptr: int | None, bound_ptr: int, plan_cost_ptr: int, status_ptr: int,
+                    act_dtype: int = _capi.ACT_F64):
+        """The linear-optimisation benchmark's plan of the next H rows from every env's live state (include/fleet_hip.h
+        fleet_lp_plan_dev): actions [H,E,N], soc_plan [H+1,E,N] (or None), bound / plan_cost f64 [E], status i32 [E,N].  Raises
+        when an env has fewer than H rows left in its episode.  See fleetrl_amd.lp_benchmark for the NumPy-level driver."""
+        self._check(self.lib.fleet_lp_plan_dev(self.h, int(H), actions_ptr, int(act_dtype), soc_plan_ptr, bound_ptr, plan_cost_ptr,
+                                               status_ptr))
+
     def set_night_policy(self, charging_hour: int, charging_minute: int, max_hours: int):
         """Parameters of _capi.POLICY_NIGHT (see fleetrl_amd.policies.night_schedule); clears the per-env window state."""
         self._check(self.lib.fleet_set_night_policy(self.h, int(charging_hour), int(charging_minute), int(max_hours)))

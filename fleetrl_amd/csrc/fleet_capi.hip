@@ -25,6 +25,7 @@
 
 #include "fleet_device.h"
 #include "fleet_direct.h"
+#include "fleet_lp.h"
 #include "fleet_norm.h"
 
 namespace {
@@ -161,6 +162,9 @@ struct Batch {
   // Every call that changes what a launch's argument block embeds (the handle's streams, its start schedule, its policy parameters:
   // anything a later version may move into FleetDev) bumps the generation: argument blocks prepared before it are never reused.
   uint64_t gen = 1;
+  // fleet_lp_plan_dev: the planner's device scratch, kept for the next call (grows, never shrinks)
+  void* lp_scratch = nullptr;
+  size_t lp_scratch_bytes = 0;
 };
 
 // A run submitted to the handle's own queue is not on its HIP stream: every entry point that touches the handle waits for it first.
@@ -721,6 +725,7 @@ int fleet_destroy(fleet_handle h) {
   for (auto& e : h->obs_piece_ev)
     if (e) (void)hipEventDestroy(e);
   if (h->dev_sched) (void)hipFree(h->dev_sched);
+  if (h->lp_scratch) (void)hipFree(h->lp_scratch);
   for (auto& e : h->region_events)
     if (e) (void)hipEventDestroy(e);
   if (h->ev_start) (void)hipEventDestroy(h->ev_start);
@@ -844,6 +849,58 @@ int fleet_step_many_dev(fleet_handle h, int K, const void* actions, int act_dtyp
   // K == 1 without done_count is the single-step kernel (it writes the per-step reward = the sum of one, and the done flag
   // to the staging buffer); with done_count the launcher takes the multi-step kernel, which counts episode ends
   HIP_TRY(h, fleet_launch_step(h->d, actions, act_dtype, K, obs, reward_sum, h->st_done, nullptr, done_count, h->stream));
+  return FLEET_OK;
+}
+
+int fleet_lp_plan_dev(fleet_handle h, int H, void* actions, int act_dtype, double* soc_plan, double* bound, double* plan_cost,
+                      int32_t* status) {
+  FLEET_ENTER(h);
+  if (!h || H < 1 || !actions || !bound || !plan_cost || !status || (act_dtype != FLEET_ACT_F32 && act_dtype != FLEET_ACT_F64)) {
+    if (h) h->error = "fleet_lp_plan_dev: bad argument";
+    return FLEET_ERR_INVALID;
+  }
+  if (h->d.real_time) {
+    h->error = "fleet_lp_plan_dev is not available with real_time = 1 (the model has a fixed step)";
+    return FLEET_ERR_INVALID;
+  }
+  const size_t lanes = (size_t)h->d.E * h->d.N;
+  if ((size_t)H > (size_t)INT32_MAX / 16 || fleet_lp_scratch_bytes(1, H) > ((size_t)1 << 40) / lanes) {
+    h->error = "fleet_lp_plan_dev: horizon too long for this batch";
+    return FLEET_ERR_INVALID;
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  // the plan is replayed on the episode it was made for: every env must have H rows left in its running episode
+  std::vector<EnvRec> env(h->d.E);
+  HIP_TRY(h, hipMemcpyAsync(env.data(), h->d.env, env.size() * sizeof(EnvRec), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  for (int e = 0; e < h->d.E; ++e) {
+    const int t = env[e].h.t, t_end = env[e].h.t_end;
+    const bool done = ((uint32_t)env[e].start_done >> 31) != 0u;
+    if (done || t < 0 || (int64_t)t + H > (int64_t)t_end || (int64_t)t + H > (int64_t)h->d.T) {
+      h->error = "fleet_lp_plan_dev: env " + std::to_string(e) + " at row " + std::to_string(t) + " has " +
+                 std::to_string(done ? 0 : std::max(0, std::min(t_end, h->d.T) - t)) + " rows left in its episode, fewer than H = " +
+                 std::to_string(H);
+      return FLEET_ERR_INVALID;
+    }
+  }
+  const size_t need = fleet_lp_scratch_bytes(lanes, H);
+  if (need > h->lp_scratch_bytes) {
+    if (h->lp_scratch) HIP_TRY(h, hipFree(h->lp_scratch));
+    h->lp_scratch = nullptr;
+    h->lp_scratch_bytes = 0;
+    HIP_TRY(h, hipMalloc(&h->lp_scratch, need));
+    h->lp_scratch_bytes = need;
+  }
+  FleetLpArgs a{};
+  a.H = H;
+  a.act_dtype = act_dtype;
+  a.actions = actions;
+  a.soc_plan = soc_plan;
+  a.bound = bound;
+  a.plan_cost = plan_cost;
+  a.status = status;
+  a.scratch = static_cast<double*>(h->lp_scratch);
+  HIP_TRY(h, fleet_launch_lp_plan(h->d, a, h->stream));
   return FLEET_OK;
 }
 

@@ -273,6 +273,24 @@ int fleet_set_night_policy(fleet_handle h, int charging_hour, int charging_minut
  * adversarial count tests).  Default: off.  Not callable while a captured graph is replaying. */
 int fleet_set_rainflow_count_all(fleet_handle h, int on);
 
+/* ---- linear-optimisation benchmark (benchmarking/linear_optimization.py:55-247) ------------------------
+ * The reference's perfect-foresight plan, one exact solve per (env, EV): H rows from every env's current row (its live state:
+ * time row, SOC of the EVs that are plugged in).  actions [H,E,N] (FLEET_ACT_F32 / FLEET_ACT_F64) is the tape to replay with
+ * fleet_step_dev / fleet_step_many_dev from this very state; soc_plan [H+1,E,N] (or NULL) the planned SOC of every row (0 while
+ * an EV is away); bound [E] the optimum of the LP relaxation (a lower bound on the reference's MILP), plan_cost [E] the MILP
+ * objective of the tape (gap = plan_cost - bound >= 0), both in EUR and summed over the env's EVs; status [E,N] the FLEET_LP_*
+ * bits.  Every env must have at least H rows left in its running episode (else FLEET_ERR_INVALID and nothing is launched), so
+ * that the replay never auto-resets in the middle of the plan.  Reads the env state synchronously (one small copy), then runs
+ * asynchronously on the handle's stream; device pointers.  Not available with real_time = 1.  Two calls on the same state give
+ * bit-identical outputs. */
+#define FLEET_LP_UNREACHABLE 1   /* a parking session cannot reach target_soc by its departure row: its target was lowered to the
+                                    highest reachable SOC (full power on every row)                                          */
+#define FLEET_LP_NEG_RETURN 2    /* a SOC_on_return (or a starting SOC) below 0 was clamped to 0                            */
+#define FLEET_LP_ABOVE_TARGET 4  /* a starting SOC or SOC_on_return above target_soc was clamped to target_soc               */
+#define FLEET_LP_GRID_NEGATIVE 8 /* a row of the horizon has load - pv > grid_connection: its grid limit was taken as 0       */
+int fleet_lp_plan_dev(fleet_handle h, int H, void* actions, int act_dtype, double* soc_plan, double* bound, double* plan_cost,
+                      int32_t* status);
+
 /* ---- reset / step, host pointers, synchronous ------------------------------------------------------------ */
 int fleet_reset_host(fleet_handle h, const uint8_t* mask, float* obs);
 /* terminal_obs (or NULL): rows of envs that finished in this step are written; all other rows are left untouched.
