@@ -240,6 +240,11 @@ def load_library():
         lib.fleet_debug_direct_fault.argtypes = [vp, C.c_int, C.c_int]
         for name in ("fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault"):
             getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "fleet_step_instance"):  # (absent from older libraries the A/B scripts run beside the tree's)
+        lib.fleet_step_instance.argtypes = [C.c_int] * 8 + [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]
+        lib.fleet_step_instance.restype = C.c_int
+        lib.fleet_max_evs_per_lane_group.argtypes = []
+        lib.fleet_max_evs_per_lane_group.restype = C.c_int
     if hasattr(lib, "fleet_selftest_stress"):
         lib.fleet_selftest_stress.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]
         lib.fleet_selftest_stress.restype = C.c_int
@@ -295,5 +300,18 @@ EXPORTED_SYMBOLS = (
     "fleet_time_regions_begin", "fleet_time_regions_read", "fleet_rccl_unique_id", "fleet_rccl_comm_create",
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
-    "fleet_lp_plan_dev",
+    "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
 ) + NORM_SYMBOLS
+
+
+def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,
+                  has_done_count: bool = False) -> tuple[str, int]:
+    """(name, grid) of the step-kernel instance a launch of this kind takes (include/fleet_hip.h fleet_step_instance; needs the
+    library, but no GPU)."""
+    name = C.create_string_buffer(64)
+    grid = C.c_uint32()
+    rc = load_library().fleet_step_instance(int(num_envs), int(num_cars), int(deg_mode), int(bool(real_time)), int(bool(log_data)),
+                                            int(act_mode), int(K), int(bool(has_done_count)), name, len(name), C.byref(grid))
+    if rc != OK:
+        raise FleetHipError(rc, "fleet_step_instance: argument out of range")
+    return name.value.decode(), int(grid.value)

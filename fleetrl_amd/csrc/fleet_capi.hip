@@ -1505,6 +1505,24 @@ int fleet_direct_split_plan(uint32_t grid_workgroups, int split, uint32_t part_g
   return parts;
 }
 
+int fleet_step_instance(int num_envs, int num_cars, int deg_mode, int real_time, int log_data, int act_mode, int K,
+                        int has_done_count, char* name, size_t name_bytes, uint32_t* grid) {
+  if (num_envs < 1 || num_cars < 1 || num_cars > 65535 || deg_mode < FLEET_DEG_NONE || deg_mode > FLEET_DEG_RAINFLOW ||
+      act_mode < FLEET_ACT_F32 || act_mode > FLEET_ACT_POLICY_NIGHT || K < 1 || !name || name_bytes < 1 || !grid)
+    return FLEET_ERR_INVALID;
+  static int32_t log_on;  // the selection only asks whether the log exists
+  FleetDev d{};
+  d.E = num_envs;
+  d.N = num_cars;
+  d.deg_mode = deg_mode;
+  d.real_time = real_time != 0;
+  d.log_pos = log_data ? &log_on : nullptr;
+  unsigned g = 0;
+  const int n = fleet_describe_step_instance(d, act_mode, K, has_done_count != 0, name, name_bytes, &g);
+  *grid = g;
+  return (n < 0 || (size_t)n >= name_bytes) ? FLEET_ERR_INVALID : FLEET_OK;
+}
+
 int fleet_debug_direct_fault(fleet_handle h, int kind, int tape_row) {
   if (!h || !h->direct) {
     if (h) h->error = "fleet_debug_direct_fault: no prepared run (run one through the library's own queue first)";

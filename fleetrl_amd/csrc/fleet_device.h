@@ -255,7 +255,8 @@ struct FleetDev {
 
 // launchers implemented in fleet_kernels.hip
 hipError_t fleet_launch_reset(const FleetDev& d, const uint8_t* mask, float* obs, hipStream_t s);
-int fleet_max_evs_per_lane_group();  // up to this many EVs per env the single-step kernel gives every EV a lane (fleet_kernels.hip kMaxGroup)
+// (fleet_max_evs_per_lane_group, include/fleet_hip.h: up to this many EVs per env the single-step kernel gives every EV a lane,
+// fleet_kernels.hip kMaxGroup)
 hipError_t fleet_launch_step(const FleetDev& d, const void* actions, int act_dtype, int K, float* obs, double* reward,
                              uint8_t* done, float* terminal_obs, int32_t* done_count, hipStream_t s);
 // A single-step launch written down instead of issued (direct AQL submission, fleet_direct.hip): the host-side kernel symbol (its
@@ -271,6 +272,16 @@ struct FleetStepLaunch {
   unsigned rec_offset;       // where {blocks pointer, rows, rotate} of a run's FIRST launch sit (the launch that writes the record)
   alignas(8) unsigned char args[640];  // (also the distance between two argument blocks of a run: fleet_direct.hip, the step kernel's record)
 };
+// The template arguments of an instance of fleet_step_kernel
+struct FleetStepInstance {
+  int G, deg;
+  bool multi, wide, log, a64;
+  int mode;
+};
+// The instance a launch takes, by name (as fleet_step_instance reports it), and its grid.  Reads d.E, d.N, d.deg_mode, d.real_time
+// and whether d.log_pos is set -- what the selection reads -- so a FleetDev with only those filled in will do.  Returns snprintf's count.
+int fleet_describe_step_instance(const FleetDev& d, int act_mode, int K, bool has_done_count, char* name, size_t name_bytes,
+                                 unsigned* grid);
 hipError_t fleet_describe_step(const FleetDev& d, const void* actions, int act_dtype, float* obs, double* reward, uint8_t* done,
                                float* terminal_obs, FleetStepLaunch* out);
 // compact the terminal observations of the envs with done[e] != 0 (env order): idx[k], *count, compact[k, obs_dim]

@@ -39,6 +39,7 @@
 // (rainflow_length, quirk Q6), at O(stack depth) instead of O(history).
 #include "fleet_device.h"
 #include <cstddef>
+#include <cstdio>
 #include <cstring>
 
 #ifdef FLEET_STAMPS
@@ -1743,7 +1744,15 @@ struct StepPlan {
   StepKernelFn fn;
   unsigned grid;
   bool single;
+  const FleetStepInstance* id;  // the template arguments of `fn` (fleet_step_instance: which kernel a configuration takes)
 };
+// The one place that takes an instance's address: the description is formed from the same template arguments as the pointer, so
+// the two cannot disagree.
+template <int G, int DEG, bool MULTI, bool WIDE, bool LOG = false, bool A64 = false, int MODE = kModeAll>
+StepPlan step_instance(unsigned grid, bool single) {
+  static constexpr FleetStepInstance id{G, DEG, MULTI, WIDE, LOG, A64, MODE};
+  return {&fleet_step_kernel<G, DEG, MULTI, WIDE, LOG, A64, MODE>, grid, single, &id};
+}
 
 // Instance selection.  G (EVs per env rounded up to a power of two, at most 64) and DEG come from the switches of plan_step; an env
 // of 65 ... kMaxGroup EVs re-enters with a group of two or four wavefronts (G = 128 / 256), one of more EVs than lanes (or that needs
@@ -1762,22 +1771,22 @@ StepPlan plan_step_gd(const FleetDev& d, int act_mode, int K, bool has_done_coun
   // either action dtype at run time
   if (K == 1 && !has_done_count && act_mode < FLEET_ACT_POLICY_UNCONTROLLED && !d.real_time && !d.log_pos) {
     if constexpr (!WIDE)
-      if (act_mode == FLEET_ACT_F64) return {&fleet_step_kernel<G, DEG, false, false, false, true>, grid, true};
-    return {&fleet_step_kernel<G, DEG, false, WIDE>, grid, true};
+      if (act_mode == FLEET_ACT_F64) return step_instance<G, DEG, false, false, false, true>(grid, true);
+    return step_instance<G, DEG, false, WIDE>(grid, true);
   }
   // K steps per launch: the data log (groups of one wavefront or less); from 32 lanes on the instance that carries what the launch
   // uses -- the event-skipping loop, the built-in policies, or the tape only; smaller groups keep ONE instance with everything behind
   // run-time tests
   if constexpr (G <= 64)
-    if (d.log_pos) return {&fleet_step_kernel<G, DEG, true, WIDE, true>, grid, false};
+    if (d.log_pos) return step_instance<G, DEG, true, WIDE, true>(grid, false);
   if constexpr (G >= 32) {
-    if (d.real_time) return {&fleet_step_kernel<G, DEG, true, WIDE, false, false, kModeRt>, grid, false};
-    if (act_mode >= FLEET_ACT_POLICY_UNCONTROLLED) return {&fleet_step_kernel<G, DEG, true, WIDE, false, false, kModePolicy>, grid, false};
-    return {&fleet_step_kernel<G, DEG, true, WIDE, false, false, kModeTape>, grid, false};
+    if (d.real_time) return step_instance<G, DEG, true, WIDE, false, false, kModeRt>(grid, false);
+    if (act_mode >= FLEET_ACT_POLICY_UNCONTROLLED) return step_instance<G, DEG, true, WIDE, false, false, kModePolicy>(grid, false);
+    return step_instance<G, DEG, true, WIDE, false, false, kModeTape>(grid, false);
   }
   // (no `else` above: this instance stays instantiated for every group, and kModeRt for G = 128 / 256, though no launch takes them --
   // the set of instances this selection has always compiled)
-  return {&fleet_step_kernel<G, DEG, true, WIDE, false, false, kModeAll>, grid, false};
+  return step_instance<G, DEG, true, WIDE, false, false, kModeAll>(grid, false);
 }
 
 template <int G>
@@ -1857,6 +1866,23 @@ hipError_t fleet_launch_step(const FleetDev& d, const void* actions, int act_dty
                      a.actions, a.act_mode, a.K, a.obs, a.reward, a.done, a.terminal_obs, a.done_count, a.guard_bytes, a.rec_blocks,
                      a.rec_rows, a.rec_rotate);
   return hipGetLastError();
+}
+
+// "G64.rainflow.multi.policy": lanes per env (with `w` where every lane walks several EVs), degradation model, single step or K
+// steps per launch, then what the instance carries -- the data log, or the part of the K-step code it was cut to (`all`: everything
+// behind run-time tests); a single-step instance the action dtype it reads (`any`: either, chosen at run time).  Combinations of
+// template arguments no launch takes today get every tag that applies, so that two instances never share a name.
+int fleet_describe_step_instance(const FleetDev& d, int act_mode, int K, bool has_done_count, char* name, size_t name_bytes,
+                                 unsigned* grid) {
+  const StepPlan p = plan_step(d, act_mode, K, has_done_count);
+  const FleetStepInstance& i = *p.id;
+  static const char* const deg[] = {"none", "linear", "rainflow"};
+  static const char* const mode[] = {".all", ".tape", ".policy", ".rt"};
+  const char* dtype = i.a64 ? ".f64" : i.multi ? "" : i.wide ? ".any" : ".f32";
+  const char* part = (i.multi && !i.log) || i.mode != kModeAll ? mode[i.mode] : "";
+  *grid = p.grid;
+  return snprintf(name, name_bytes, "G%d%s.%s.%s%s%s%s", i.G, i.wide ? "w" : "", deg[i.deg], i.multi ? "multi" : "single",
+                  i.log ? ".log" : "", part, dtype);
 }
 
 hipError_t fleet_describe_step(const FleetDev& d, const void* actions, int act_dtype, float* obs, double* reward, uint8_t* done,

@@ -408,6 +408,20 @@ int fleet_direct_placement(fleet_handle h, int32_t map8[8], int32_t* num_xcc, in
 /* How a grid of `grid_workgroups` is laid over the handle's queues (a pure function, no device needed): returns 1 (part_grid[0] = the
  * whole grid) or 2 (two ranges of workgroups: part_grid[0] a multiple of 8 that fits the kernel's 16-bit first-workgroup field). */
 int fleet_direct_split_plan(uint32_t grid_workgroups, int split, uint32_t part_grid[2]);
+/* Which instance of the step kernel a launch of this kind takes, and its grid of workgroups for `num_envs` envs (a pure function, no
+ * device and no handle needed; it runs the library's own launch planner).  A launch is described by the handle's configuration
+ * (num_cars, deg_mode, real_time, log_data) and by the call: act_mode = FLEET_ACT_F32 / FLEET_ACT_F64 (an action buffer) or a
+ * FLEET_ACT_POLICY_*, K = steps per launch, has_done_count = whether fleet_step_many_dev / fleet_rollout_policy_dev got a
+ * done_count buffer (fleet_step_dev, fleet_step_host and the tape replays: K = 1, has_done_count = 0).  name: e.g.
+ * "G64.rainflow.single.f32" (the benchmark's kernel), "G32.linear.multi.policy", "G64w.none.multi.log": lanes per env (`w`: every
+ * lane walks several EVs), degradation model, single step or K steps per launch, what the instance carries.  Every distinct name is
+ * separately compiled code; tests/test_step_instances_cpu.py keeps a test case for each.  FLEET_ERR_INVALID: an argument out of
+ * range or a name buffer that is too short (48 bytes are enough). */
+int fleet_step_instance(int num_envs, int num_cars, int deg_mode, int real_time, int log_data, int act_mode, int K,
+                        int has_done_count, char* name, size_t name_bytes, uint32_t* grid);
+/* Up to this many EVs per env every EV has a lane of its own (groups of up to four wavefronts per env); beyond it the lanes of one
+ * wavefront walk several EVs each. */
+int fleet_max_evs_per_lane_group(void);
 /* TEST HOOK for the placement guard (the handle must have run through its own queue before) --
  * kind 1: the handle's NEXT run gets a placement record shifted by one workgroup: what its launches would see if the queue's first
  *         die had moved in the middle of the run;

@@ -79,6 +79,15 @@ def rainflow_many(series, lengths) -> tuple[np.ndarray, np.ndarray]:
     return out, nc
 
 
+# oracle-only fields of `get` (fleet_oracle.c ORACLE_F_*): what the env's last pass through the step body handed to the reference's
+# DataLogger beside reward and cashflow -- the device library has these in its data log only
+ORACLE_FIELDS = {
+    "overload": (1000, np.float64, False),
+    "soc_missing": (1001, np.float64, False),
+    "charge_energy": (1002, np.float64, True),
+}
+
+
 class OracleBatch:
     """Batch of reference-exact CPU envs sharing one table set (mirrors the product's FleetBatch)."""
 
@@ -133,7 +142,7 @@ class OracleBatch:
         return obs, rew, done, term
 
     def get(self, name: str) -> np.ndarray:
-        fid, dtype, per_car = _capi.FIELDS[name]
+        fid, dtype, per_car = ORACLE_FIELDS[name] if name in ORACLE_FIELDS else _capi.FIELDS[name]
         out = np.zeros((self.E, self.N) if per_car else (self.E,), dtype=dtype)
         if self.lib.oracle_get(self.h, fid, out.ctypes.data):
             raise KeyError(name)

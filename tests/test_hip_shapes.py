@@ -430,8 +430,8 @@ def test_seeded_random_configurations(case):
 @pytest.mark.parametrize("n_evs,num_envs", [(50, 70), (130, 21), (100, 9), (8, 45)])
 def test_k_steps_per_launch_match_the_oracle_step_by_step(n_evs, num_envs):
     """`fleet_step_many_dev` at the geometries of the BASELINE shapes -- one env per wavefront with one EV per lane (N = 50: the
-    kernel that carries the head of each EV's rainflow row in registers over the K steps), several EVs per lane (N = 130) and
-    several envs per wavefront (N = 8) -- against the oracle stepped one row at a time with the same action tape: launches of
+    kernel that carries the head of each EV's rainflow row in registers over the K steps), four wavefronts per env (N = 130, still
+    one EV per lane; two wavefronts at N = 100) and several envs per wavefront (N = 8) -- against the oracle stepped one row at a time with the same action tape: launches of
     61 steps over 24 h episodes with auto-reset, i.e. episode ends, in-launch resets and daily degradation rows fall INSIDE
     launches, and single steps follow the last launch on the same handle."""
     import torch
