@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NODEVICE, ERR_UNSUPPORTED = 0, 1, 2, 3, 4, 5
 DEG_NONE, DEG_LINEAR, DEG_RAINFLOW = 0, 1, 2
@@ -98,6 +98,40 @@ class FleetNormParams(C.Structure):
 
 class FleetTablesC(C.Structure):
     _fields_ = list(_TABLE_FIELDS)
+
+
+# ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
+STATE_MAGIC = 0x4554415453544C46
+STATE_ALIGN = 256
+STATE_SECTIONS = 16
+# section id -> (name, dtype, shape as a function of the header's numbers)
+STATE_SECTION_NAMES = ("hot", "run", "soh", "soc_deg", "sei", "env", "night_start", "last_len", "rf_rows", "log_pos", "log_row",
+                       "log_env", "log_ev", "log_obs", "sched")
+SEC_SCHED = 14
+
+
+class FleetStateSection(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class FleetStateLayout(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("alignment", C.c_int32), ("header_bytes", C.c_uint64), ("total_bytes", C.c_uint64),
+                ("num_envs", C.c_int32), ("num_cars", C.c_int32), ("obs_dim", C.c_int32), ("stack_cap", C.c_int32),
+                ("rf_row_stride", C.c_int32), ("log_cap", C.c_int32), ("sec", FleetStateSection * STATE_SECTIONS)]
+
+
+class FleetStateFingerprint(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_cars", "table_rows", "episode_steps", "deg_mode", "real_time", "price_lookahead",
+                                          "bl_pv_lookahead", "include_building", "include_pv", "aux", "normalize", "stack_cap",
+                                          "rf_row_stride", "log_cap", "picker_mode", "reserved")] + \
+               [("seed", C.c_uint64), ("dt", C.c_double), ("table_hash", C.c_uint64)]
+
+
+class FleetStateHeader(C.Structure):
+    _fields_ = [("magic", C.c_uint64), ("abi_version", C.c_int32), ("header_bytes", C.c_int32), ("fp", FleetStateFingerprint)] + \
+               [(n, C.c_int32) for n in ("num_envs", "env_id_offset", "obs_dim", "night_hour", "night_minute", "night_limit_s",
+                                          "rf_count_all", "sched_n")] + \
+               [("total_bytes", C.c_uint64), ("sec", FleetStateSection * STATE_SECTIONS)]
 
 
 def pack_tables(tables, time_feat: np.ndarray | None):
@@ -251,6 +285,16 @@ def load_library():
     if hasattr(lib, "fleet_selftest_division"):  # (absent from the round-4 library the A/B scripts run beside the tree's)
         lib.fleet_selftest_division.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.fleet_selftest_division.restype = C.c_int
+    # env state (fleet_state.hip)
+    lib.fleet_state_layout.argtypes = [C.POINTER(FleetParams), C.POINTER(FleetStateLayout)]
+    lib.fleet_state_table_hash.argtypes = [C.POINTER(FleetParams), C.POINTER(FleetTablesC), C.POINTER(C.c_uint64)]
+    lib.fleet_state_check.argtypes = [C.POINTER(FleetParams), C.c_uint64, vp, C.c_uint64]
+    lib.fleet_state_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+    for name in ("fleet_state_save_dev", "fleet_state_load_dev", "fleet_state_save_host", "fleet_state_load_host"):
+        getattr(lib, name).argtypes = [vp, vp, C.c_uint64]
+    lib.fleet_fork_envs.argtypes = [vp, vp, vp, vp, C.c_int]
+    for name in STATE_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
     # the running normaliser (fleet_norm.hip)
     dp = C.POINTER(C.c_double)
     lib.fleet_norm_create.argtypes = [C.c_int, C.POINTER(FleetNormParams), C.POINTER(vp)]
@@ -289,6 +333,11 @@ NORM_SYMBOLS = (
     "fleet_reset_host_norm", "fleet_step_host_norm",
 )
 
+STATE_SYMBOLS = (
+    "fleet_state_layout", "fleet_state_table_hash", "fleet_state_check", "fleet_state_bytes", "fleet_state_save_dev",
+    "fleet_state_load_dev", "fleet_state_save_host", "fleet_state_load_host", "fleet_fork_envs",
+)
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -301,7 +350,7 @@ EXPORTED_SYMBOLS = (
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
-) + NORM_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,
@@ -315,3 +364,98 @@ def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, 
     if rc != OK:
         raise FleetHipError(rc, "fleet_step_instance: argument out of range")
     return name.value.decode(), int(grid.value)
+
+
+def state_layout(params: FleetParams) -> FleetStateLayout:
+    """fleet_state_layout: sizes and offsets of every section of a state blob for these parameters (needs the library, no GPU)."""
+    out = FleetStateLayout()
+    lib = load_library()
+    if lib.fleet_state_layout(C.byref(params), C.byref(out)) != OK:
+        raise FleetHipError(ERR_INVALID, lib.fleet_last_error(None).decode())
+    return out
+
+
+def state_table_hash(params: FleetParams, tables, time_feat=None) -> int:
+    """fleet_state_table_hash: the hash of the table contents a handle created from them carries in its fingerprint (no GPU)."""
+    tc, keep = pack_tables(tables, time_feat)
+    out = C.c_uint64()
+    lib = load_library()
+    rc = lib.fleet_state_table_hash(C.byref(params), C.byref(tc), C.byref(out))
+    del keep
+    if rc != OK:
+        raise FleetHipError(rc, lib.fleet_last_error(None).decode())
+    return int(out.value)
+
+
+def state_check(params: FleetParams, table_hash: int, blob: np.ndarray) -> None:
+    """fleet_state_check: raises FleetHipError (ERR_INVALID, naming the field) unless the host blob fits these parameters and tables."""
+    b = np.ascontiguousarray(blob, dtype=np.uint8)
+    lib = load_library()
+    rc = lib.fleet_state_check(C.byref(params), int(table_hash), b.ctypes.data, b.size)
+    if rc != OK:
+        raise FleetHipError(rc, lib.fleet_last_error(None).decode())
+
+
+# dtypes of the structured sections (fleetrl_amd/csrc/fleet_device.h: Hot, SegRec, SeiRec, EnvRec)
+HOT_DTYPE = np.dtype([("x", "<f8"), ("hl", "<f4"), ("bits", "<u4")])
+RUN_DTYPE = np.dtype([("sor", "<f8"), ("tlx", "<u4"), ("se", "<u4")])
+SEI_DTYPE = np.dtype([("fd_cyc", "<f8"), ("fd_cal", "<f8"), ("sei_l", "<f8"), ("sei_soh", "<f8")])
+ENV_DTYPE = np.dtype([("t", "<i4"), ("t_end", "<i4"), ("nsamp", "<i4"), ("episodes", "<i4"), ("ep_len", "<i4"), ("rf_until", "<i4"),
+                      ("err", "<u4"), ("start_done", "<i4"), ("ep_return", "<f8"), ("last_ep_return", "<f8"), ("cashflow", "<f8"),
+                      ("penalty_record", "<f8")])
+
+
+def state_header(blob: np.ndarray) -> FleetStateHeader:
+    b = np.ascontiguousarray(blob[:C.sizeof(FleetStateHeader)], dtype=np.uint8)
+    if b.size < C.sizeof(FleetStateHeader):
+        raise FleetHipError(ERR_INVALID, "the blob is shorter than a header")
+    h = FleetStateHeader.from_buffer_copy(b.tobytes())
+    if h.magic != STATE_MAGIC:
+        raise FleetHipError(ERR_INVALID, "magic: not a fleet state blob")
+    return h
+
+
+def state_views(blob: np.ndarray) -> dict:
+    """Named NumPy views of a host blob's sections, shaped by the blob's own header: {"header": u8 view of the header bytes,
+    "hot": [E,N] records, "run", "soh", "soc_deg", "sei", "env": [E] records, "night_start", "last_len", "rf_rows": [E,N,stride]
+    f64, "log_*", "sched": [n,E] i32}; absent sections are left out.  Views: writing to them edits the blob."""
+    if blob.dtype != np.uint8 or blob.ndim != 1 or not blob.flags.c_contiguous:
+        raise ValueError("a state blob is a contiguous 1-d uint8 array")
+    h = state_header(blob)
+    if h.total_bytes > blob.size:
+        raise FleetHipError(ERR_INVALID, "the blob is shorter than its header says")
+    E, N, D, cap, stride = h.num_envs, h.fp.num_cars, h.obs_dim, h.fp.log_cap, h.fp.rf_row_stride
+    shapes = {"hot": (HOT_DTYPE, (E, N)), "run": (RUN_DTYPE, (E, N)), "soh": (np.float64, (E, N)), "soc_deg": (np.float64, (E, N)),
+              "sei": (SEI_DTYPE, (E, N)), "env": (ENV_DTYPE, (E,)), "night_start": (np.int32, (E,)), "last_len": (np.int32, (E,)),
+              "rf_rows": (np.float64, (E, N, stride)), "log_pos": (np.int32, (E,)), "log_row": (np.int32, (cap, E)),
+              "log_env": (np.float64, (cap, E, 4)), "log_ev": (np.float64, (cap, E, 4, N)), "log_obs": (np.float32, (cap, E, D)),
+              "sched": (np.int32, (h.sched_n, E))}
+    out = {"header": blob[:C.sizeof(FleetStateHeader)]}
+    for s, name in enumerate(STATE_SECTION_NAMES):
+        off, n = int(h.sec[s].offset), int(h.sec[s].bytes)
+        if not n:
+            continue
+        dtype, shape = shapes[name]
+        if off % STATE_ALIGN or off + n > blob.size or n != int(np.prod(shape)) * np.dtype(dtype).itemsize:
+            raise FleetHipError(ERR_INVALID, f"section {name!r} of the blob does not match its header")
+        out[name] = blob[off:off + n].view(dtype).reshape(shape)
+    return out
+
+
+def state_from_views(d: dict) -> np.ndarray:
+    """The blob a `state_views` dict describes, rebuilt from the arrays (which may be copies, e.g. read back from an .npz)."""
+    hb = np.ascontiguousarray(d["header"], dtype=np.uint8).reshape(-1)
+    h = state_header(hb)
+    blob = np.zeros(int(h.total_bytes), dtype=np.uint8)
+    blob[:hb.size] = hb
+    views = state_views(blob)
+    for name, v in views.items():
+        if name == "header":
+            continue
+        if name not in d:
+            raise FleetHipError(ERR_INVALID, f"the state lacks section {name!r}")
+        a = np.asarray(d[name])
+        if a.dtype != v.dtype or a.shape != v.shape:
+            raise FleetHipError(ERR_INVALID, f"section {name!r}: expected {v.dtype} {v.shape}, got {a.dtype} {a.shape}")
+        v[...] = a
+    return blob

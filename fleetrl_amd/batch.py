@@ -383,6 +383,68 @@ class FleetBatch:
         self._check(self.lib.fleet_timer_read(self.h, C.byref(ms)))
         return float(ms.value)
 
+    # ---- env state: save, load, fork (include/fleet_hip.h "env state") -------------------------------------------------------
+    def state_bytes(self) -> int:
+        """Bytes a blob of this handle needs now (the start schedule, if one is set, included)."""
+        n = C.c_uint64()
+        self._check(self.lib.fleet_state_bytes(self.h, C.byref(n)))
+        return int(n.value)
+
+    @staticmethod
+    def _is_tensor(x) -> bool:
+        return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
+
+    def save_state(self, out=None):
+        """The handle's whole state as one blob.  `out`: a torch uint8 tensor on the handle's device (fleet_state_save_dev: the
+        call first reads the handle's error word back, which drains the stream, then enqueues the copies on it and returns), a 1-d
+        NumPy uint8 array (synchronous: fleet_state_save_host), or None (a fresh NumPy array).
+        Returns `out`.  Raises FleetHipError(ERR_STATE) when an env has device error bits raised."""
+        need = self.state_bytes()
+        if out is None:
+            out = np.empty(need, dtype=np.uint8)
+        if self._is_tensor(out):
+            if not out.is_cuda or out.device.index != self.device or str(out.dtype) != "torch.uint8" or not out.is_contiguous():
+                raise ValueError("save_state: a contiguous torch.uint8 tensor on the handle's device, or a NumPy uint8 array")
+            self._check(self.lib.fleet_state_save_dev(self.h, out.data_ptr(), int(out.numel())))
+            return out
+        if out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous:
+            raise ValueError("save_state: a contiguous 1-d NumPy uint8 array")
+        self._check(self.lib.fleet_state_save_host(self.h, out.ctypes.data, int(out.size)))
+        return out
+
+    def load_state(self, blob):
+        """Replace the handle's state by a blob of save_state (torch uint8 device tensor or NumPy uint8 array) of a handle with the
+        same fingerprint and number of envs: the handle then continues bit-identically to the one that was saved.  The header is
+        checked before anything is touched (FleetHipError ERR_INVALID names the field)."""
+        if self._is_tensor(blob):
+            if not blob.is_cuda or blob.device.index != self.device or str(blob.dtype) != "torch.uint8" or not blob.is_contiguous():
+                raise ValueError("load_state: a contiguous torch.uint8 tensor on the handle's device, or a NumPy uint8 array")
+            self._check(self.lib.fleet_state_load_dev(self.h, blob.data_ptr(), int(blob.numel())))
+            return
+        b = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        self._check(self.lib.fleet_state_load_host(self.h, b.ctypes.data, int(b.size)))
+
+    def state_dict(self) -> dict:
+        """Named NumPy views of a fresh host blob (`_capi.state_views`): for inspection and `np.savez`."""
+        return _capi.state_views(self.save_state())
+
+    def load_state_dict(self, d: dict):
+        self.load_state(_capi.state_from_views(d))
+
+    def fork_envs(self, src_idx, dst_idx, source: "FleetBatch | None" = None):
+        """Copy env src_idx[i] of `source` (default: this batch) to env dst_idx[i] of this batch on the device (fleet_fork_envs).
+        A scalar `src_idx` is broadcast to every destination.  The destination continues the source's running episode
+        bit-identically and draws its own start row at its next reset."""
+        src = self if source is None else source
+        d = np.ascontiguousarray(np.atleast_1d(dst_idx), dtype=np.int32)
+        s = np.atleast_1d(np.asarray(src_idx, dtype=np.int32))
+        if s.size == 1 and d.size != 1:
+            s = np.full(d.size, s[0], dtype=np.int32)
+        s = np.ascontiguousarray(s)
+        if s.shape != d.shape or d.ndim != 1:
+            raise ValueError("fork_envs: src_idx and dst_idx must be 1-d and of equal length (or src_idx a scalar)")
+        self._check(self.lib.fleet_fork_envs(self.h, src.h, d.ctypes.data, s.ctypes.data, int(d.size)))
+
     # ---- state access ----------------------------------------------------------------------------------------
     def get(self, name: str) -> np.ndarray:
         fid, dtype, per_car = _capi.FIELDS[name]

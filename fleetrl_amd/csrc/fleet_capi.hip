@@ -27,6 +27,7 @@
 #include "fleet_direct.h"
 #include "fleet_lp.h"
 #include "fleet_norm.h"
+#include "fleet_state.h"
 
 namespace {
 
@@ -165,6 +166,11 @@ struct Batch {
   // fleet_lp_plan_dev: the planner's device scratch, kept for the next call (grows, never shrinks)
   void* lp_scratch = nullptr;
   size_t lp_scratch_bytes = 0;
+  // env state (fleet_state.hip): the hash of the table contents the handle was created from (half of its fingerprint), pinned
+  // staging for a blob header, what a fork keeps between calls (index pairs on the device and their pinned staging, an event)
+  uint64_t table_hash = 0;
+  FleetStateHeader* pin_state_hdr = nullptr;
+  FleetForkScratch fork;
 };
 
 // A run submitted to the handle's own queue is not on its HIP stream: every entry point that touches the handle waits for it first.
@@ -441,6 +447,7 @@ int create_impl(const FleetParams* p, const FleetTables* t, int device, Batch* b
   }
   b->p = *p;
   b->device = device;
+  b->table_hash = fleet_state_hash_tables(*p, *t);
   HIP_TRY(b, hipSetDevice(device));
   HIP_TRY(b, hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking));
   b->stream = b->own_stream;
@@ -682,6 +689,8 @@ void drop_graph(Batch* b) {
 
 }  // namespace
 
+void fleet_set_create_error(const std::string& why) { g_create_error = why; }
+
 struct FleetEnvBatch : Batch {};
 
 extern "C" {
@@ -726,6 +735,8 @@ int fleet_destroy(fleet_handle h) {
     if (e) (void)hipEventDestroy(e);
   if (h->dev_sched) (void)hipFree(h->dev_sched);
   if (h->lp_scratch) (void)hipFree(h->lp_scratch);
+  fleet_state_fork_release(&h->fork);
+  if (h->pin_state_hdr) (void)hipHostFree(h->pin_state_hdr);
   for (auto& e : h->region_events)
     if (e) (void)hipEventDestroy(e);
   if (h->ev_start) (void)hipEventDestroy(h->ev_start);
@@ -1345,6 +1356,88 @@ int fleet_check_errors(fleet_handle h) {
       return FLEET_ERR_STATE;
     }
   return FLEET_OK;
+}
+
+// ---- env state: save, load, fork (fleet_state.hip does the work; here: what belongs to the handle) -------------------------------
+static FleetStateRefs state_refs(fleet_handle h) {
+  return FleetStateRefs{&h->p, &h->d, &h->cold_host, h->cold_dev, &h->dev_sched, h->table_hash, h->stream, h->pin_state_hdr, &h->error};
+}
+
+// The handle's error word, read back (drains the stream): a handle with device error bits raised is neither saved nor forked.
+static int state_clean(fleet_handle h, const char* who) {
+  uint32_t any = 0;
+  HIP_TRY(h, hipMemcpyAsync(&any, h->d.err_any, sizeof any, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  if (any) {
+    char names[400], buf[640];
+    snprintf(buf, sizeof buf, "%s: the handle has device error bits raised (0x%x:%s) and its state is not saved or forked", who, any,
+             deverr_names(any, names, sizeof names));
+    h->error = buf;
+    return FLEET_ERR_STATE;
+  }
+  return FLEET_OK;
+}
+
+static int state_save(fleet_handle h, void* blob, uint64_t bytes, bool host) {
+  FLEET_ENTER(h);
+  if (!h) return FLEET_ERR_INVALID;
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (!h->pin_state_hdr) HIP_TRY(h, hipHostMalloc((void**)&h->pin_state_hdr, sizeof(FleetStateHeader), hipHostMallocDefault));
+  const int rc = state_clean(h, host ? "fleet_state_save_host" : "fleet_state_save_dev");
+  if (rc != FLEET_OK) return rc;
+  return fleet_state_save(state_refs(h), blob, bytes, host);
+}
+
+static int state_load(fleet_handle h, const void* blob, uint64_t bytes, bool host) {
+  FLEET_ENTER(h);
+  if (!h) return FLEET_ERR_INVALID;
+  HIP_TRY(h, hipSetDevice(h->device));
+  const int rc = fleet_state_load(state_refs(h), blob, bytes, host);
+  if (rc != FLEET_OK) return rc;
+  // the start schedule and the policy parameters may have changed: nothing prepared before is reused (Batch::gen); what the host
+  // path remembers of its last step belongs to the state that has just been replaced
+  h->gen += 1;
+  h->host_step_has_episodes = false;
+  h->last_step_err = 0;
+  return FLEET_OK;
+}
+
+int fleet_state_bytes(fleet_handle h, uint64_t* bytes) {
+  if (!h || !bytes) return FLEET_ERR_INVALID;
+  *bytes = fleet_state_blob_bytes(state_refs(h));
+  return FLEET_OK;
+}
+int fleet_state_save_dev(fleet_handle h, void* blob_dev, uint64_t bytes) { return state_save(h, blob_dev, bytes, false); }
+int fleet_state_save_host(fleet_handle h, void* blob_host, uint64_t bytes) { return state_save(h, blob_host, bytes, true); }
+int fleet_state_load_dev(fleet_handle h, const void* blob_dev, uint64_t bytes) { return state_load(h, blob_dev, bytes, false); }
+int fleet_state_load_host(fleet_handle h, const void* blob_host, uint64_t bytes) { return state_load(h, blob_host, bytes, true); }
+
+int fleet_fork_envs(fleet_handle dst, fleet_handle src, const int32_t* dst_idx_host, const int32_t* src_idx_host, int n) {
+  FLEET_ENTER(dst);
+  if (!dst || !src) return FLEET_ERR_INVALID;
+  if (src != dst) {
+    const int rc = direct_drain(src);
+    if (rc != FLEET_OK) {
+      dst->error = "fleet_fork_envs: the source handle: " + src->error;
+      return rc;
+    }
+  }
+  if (dst->device != src->device) {
+    dst->error = "fleet_fork_envs: the two handles are on different devices";
+    return FLEET_ERR_INVALID;
+  }
+  if (dst->d.log_pos || src->d.log_pos) {
+    dst->error = "fleet_fork_envs: a handle with the data log on is not forked (log_data = 1)";
+    return FLEET_ERR_UNSUPPORTED;
+  }
+  HIP_TRY(dst, hipSetDevice(dst->device));
+  int rc = state_clean(dst, "fleet_fork_envs");
+  if (rc != FLEET_OK) return rc;
+  if (src != dst && (rc = state_clean(src, "fleet_fork_envs")) != FLEET_OK) {
+    dst->error = src->error;
+    return rc;
+  }
+  return fleet_state_fork(state_refs(dst), state_refs(src), src == dst, dst_idx_host, src_idx_host, n, &dst->fork);
 }
 
 int fleet_timer_start(fleet_handle h) {

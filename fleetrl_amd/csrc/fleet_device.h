@@ -199,6 +199,13 @@ struct FleetCold {
 };
 #define FLEET_NIGHT_IDLE INT32_MIN
 
+// THE STATE of a handle (fleet_state.hip: save, load, fork) is everything a step reads that a step or a reset has written:
+//   per env    hot[N], run[N], soh[N], soc_deg[N], sei[N]; the EnvRec; the EVs' rainflow rows (RfHdr + stack) when deg_mode is
+//              rainflow; cold.night_start[e], cold.last_len[e]; the data-log ring slots and log_pos[e] when the log is on;
+//   per handle the start schedule (cold.sched, cold.sched_n), the night-policy parameters (cold.night_hour / _minute / _limit_s),
+//              cold.rf_count_all.
+// Not state: the tables, the other FleetCold scalars, staging buffers, the LP scratch, prepared graphs and argument blocks, streams.
+// Record sizes of the sections, in FLEET_SEC_* order: Hot 16, SegRec 16, f64, f64, SeiRec 32, EnvRec 64, i32, i32, rf_row_stride * 8.
 struct FleetDev {
   // ---- sizes / flags --------------------------------------------------------------------------------
   int E, N, T;

@@ -122,6 +122,25 @@ class FleetMixedVecEnv(_SB3VecEnv):
     def seed(self, seed=None):
         return [None] * self.num_envs  # the reference ignores reset(seed=...) (quirk Q12)
 
+    # -- env state: one state per fleet group (FleetCore.save_state / load_state) ---------------------------------------------
+    def save_state(self, path) -> None:
+        """One `.npz`: group g's state (FleetCore.state_arrays) under the prefix `g<g>_`."""
+        import io
+
+        out = io.BytesIO()
+        np.savez(out, n_groups=np.int64(len(self.cores)),
+                 **{f"g{g}_{k}": v for g, core in enumerate(self.cores) for k, v in core.state_arrays().items()})
+        with open(path, "wb") as fh:
+            fh.write(out.getvalue())
+
+    def load_state(self, path) -> None:
+        with np.load(path, allow_pickle=False) as z:
+            if int(z["n_groups"]) != len(self.cores):
+                raise _capi.FleetHipError(_capi.ERR_INVALID, "the file holds the state of another number of fleet groups")
+            for g, core in enumerate(self.cores):
+                pre = f"g{g}_"
+                core.load_state_arrays({k[len(pre):]: z[k] for k in z.files if k.startswith(pre)})
+
     def close(self):
         for core in self.cores:
             core.close()

@@ -59,6 +59,9 @@ class FleetCore:
         """`tables`: ready-made FleetTables (else built from the CSVs the config names); `start_rows`: injected episode
         start rows [n_episodes, num_envs]; `extrema` / `start_range`: overrides for tables that are a cut window of a
         longer table (see fleetrl_amd.params.make_params)."""
+        # (kept for __deepcopy__: a copy is a new handle built from the same arguments, then a device-to-device load of the state)
+        self._ctor = dict(env_config=env_config, num_envs=num_envs, schedule=schedule, device=device, auto_reset=auto_reset,
+                          seed=seed, env_id_offset=env_id_offset, extrema=extrema, start_range=start_range)
         self.rc: ResolvedConfig = resolve_config(env_config)
         self.env_config = self.rc.raw
         if tables is None:
@@ -75,6 +78,7 @@ class FleetCore:
         self.single_observation_space = Box(low=low, high=high, dtype=np.float32)          # fleet_environment.py:316-319
         self.single_action_space = Box(low=-1, high=1, shape=(self.num_cars,), dtype=np.float32)  # :322-325
         self._start_time_override = [None] * self.num_envs
+        self._any_override = False  # any entry of _start_time_override set: the vec envs clear the entries of finished envs only then
         if start_rows is not None:
             self.batch.set_start_schedule(start_rows)
         # DataLogger (utils/data_logger/data_logger.py): the rows live in a device-side ring written by the kernels
@@ -162,6 +166,7 @@ class FleetCore:
         reset() picks its own start again.  Replicated: affects get_start_time() until the next reset."""
         for i in (range(self.num_envs) if indices is None else indices):
             self._start_time_override[i] = start_time
+        self._any_override = any(o is not None for o in self._start_time_override)
 
     def get_dist_factor(self):
         return list(self.batch.dist_factor())
@@ -170,6 +175,81 @@ class FleetCore:
         for i in range(self.num_envs):
             if mask is None or mask[i]:
                 self._start_time_override[i] = None
+        self._any_override = mask is not None and any(o is not None for o in self._start_time_override)
+
+    # -- env state: checkpoint, resume, fork, copy (include/fleet_hip.h "env state") ---------------------------------------
+    def state_arrays(self) -> dict:
+        """What save_state writes: the sections of the device state by name (`state_<section>`, FleetBatch.state_dict) and the
+        start-time overrides this layer holds (`set_start_time`), as strings -- nothing that needs pickling."""
+        ov = self._start_time_override
+        out = {"py_override_set": np.array([o is not None for o in ov], dtype=bool),
+               "py_override_is_str": np.array([isinstance(o, str) for o in ov], dtype=bool),  # (anything else: a timestamp)
+               "py_override": np.array(["" if o is None else str(o) for o in ov], dtype=np.str_)}
+        out.update({"state_" + k: v for k, v in self.batch.state_dict().items()})
+        return out
+
+    def load_state_arrays(self, z) -> None:
+        d = {k[len("state_"):]: z[k] for k in z if k.startswith("state_")}
+        isset, text, is_str = np.asarray(z["py_override_set"]), np.asarray(z["py_override"]), np.asarray(z["py_override_is_str"])
+        if isset.shape != (self.num_envs,):
+            raise _capi.FleetHipError(_capi.ERR_INVALID, "num_envs: the file holds the state of another number of envs")
+        self.batch.load_state_dict(d)  # (the library checks the state's fingerprint before it touches anything)
+
+        def stamp(t):
+            try:
+                import pandas as pd
+
+                return pd.Timestamp(t)
+            except Exception:
+                return t
+
+        self._start_time_override = [(str(t) if q else stamp(str(t))) if s else None for s, t, q in zip(isset, text, is_str)]
+        self._any_override = bool(isset.any())
+
+    def save_state(self, path) -> None:
+        """The whole env state as an `.npz` (`path` is written as given), in the style of vec_normalize.save_state; together with
+        `FleetVecNormalize.save` this checkpoints the environment side of a training run."""
+        import io
+
+        buf = io.BytesIO()
+        np.savez(buf, **self.state_arrays())
+        with open(path, "wb") as fh:
+            fh.write(buf.getvalue())
+
+    def load_state(self, path) -> None:
+        """Resume from save_state's file (read with `allow_pickle=False`): the env must be built from the same config, tables and
+        number of envs.  It then continues bit-identically to the env that was saved."""
+        with np.load(path, allow_pickle=False) as z:
+            self.load_state_arrays({k: z[k] for k in z.files})
+
+    def fork_envs(self, src_idx, dst_idx, source=None) -> None:
+        """Copy env src_idx[i] of `source` (a FleetCore or anything with a `.core`; default: this one) to env dst_idx[i] here, on the
+        device (FleetBatch.fork_envs): e.g. one state in every env of a batch, to compare policies on the same episode."""
+        src = self if source is None else getattr(source, "core", source)
+        self.batch.fork_envs(src_idx, dst_idx, source=src.batch)
+        s = np.atleast_1d(src_idx)
+        d = np.atleast_1d(dst_idx)
+        for k, i in enumerate(d):
+            self._start_time_override[int(i)] = src._start_time_override[int(s[k % len(s)])]
+        self._any_override = any(o is not None for o in self._start_time_override)
+
+    def __deepcopy__(self, memo):
+        """`copy.deepcopy(env)` as with the reference's plain-Python env: an independent env that continues from the same row.  A new
+        handle from the constructor's arguments (the tables are shared, they are read-only), then the state device to device."""
+        new = FleetCore(tables=self.tables, **self._ctor)
+        memo[id(self)] = new
+        try:
+            import torch
+
+            blob = torch.empty(self.batch.state_bytes(), dtype=torch.uint8, device=torch.device("cuda", self.batch.device))
+            self.batch.save_state(blob)
+            self.batch.synchronize()  # the copy's stream is another one
+            new.batch.load_state(blob)
+        except ImportError:  # no PyTorch in the process: the same blob through host memory
+            new.batch.load_state(self.batch.save_state())
+        new._start_time_override = list(self._start_time_override)
+        new._any_override = self._any_override
+        return new
 
     def close(self):
         self.batch.close()
@@ -186,7 +266,6 @@ class FleetVecEnv(_SB3VecEnv):
         self.copy_obs = bool(kw.pop("copy_obs", True))
         self.core = FleetCore(env_config, num_envs, auto_reset=True, **kw)
         self._actions = None
-        self._any_override = False
         if _SB3VecEnv is not object:  # sets num_envs / spaces / reset_infos / _seeds / _options and asks get_attr("render_mode")
             _SB3VecEnv.__init__(self, self.core.num_envs, self.core.single_observation_space, self.core.single_action_space)
         else:
@@ -202,7 +281,6 @@ class FleetVecEnv(_SB3VecEnv):
 
     def _reset(self, norm=None):
         self.core.clear_start_overrides()
-        self._any_override = False
         return self.core.batch.reset(norm=norm)
 
     def step_async(self, actions):
@@ -226,7 +304,7 @@ class FleetVecEnv(_SB3VecEnv):
             for k, i in enumerate(idx):
                 infos[i] = {"terminal_observation": term[i].copy(), "TimeLimit.truncated": False,
                             "episode": {"r": float(ret[k]), "l": int(ln[k])}}
-            if self._any_override:
+            if self.core._any_override:  # (also overrides that came in through load_state / fork_envs)
                 self.core.clear_start_overrides(dones)
         return obs, rew, dones, infos
 
@@ -245,7 +323,6 @@ class FleetVecEnv(_SB3VecEnv):
         """`VecEnv.env_method("is_done")[0]` etc. -- the reference's documented way to reach its getters (:741-799)."""
         idx = self._indices(indices)
         if method_name == "set_start_time":
-            self._any_override = True
             self.core.set_start_time(*method_args, indices=idx, **method_kwargs)
             return [None] * len(idx)
         fn = getattr(self.core, method_name, None)
@@ -404,3 +481,39 @@ class FleetEnv(_GymEnv):
 
     def get_dist_factor(self):
         return self.core.get_dist_factor()[0]
+
+
+# ---- env state on the three env classes: every attribute copied, the engine (`core`) through FleetCore.__deepcopy__ ----------------
+# (plain functions attached to the classes, not a base class: without gymnasium / SB3 the classes derive from `object` alone)
+_HANDLE_BOUND = ("_torch_stream",)  # caches of what the ORIGINAL handle was told (step_torch: the stream it adopted)
+
+
+def _deepcopy_by_core(self, memo):
+    import copy
+
+    new = self.__class__.__new__(self.__class__)
+    memo[id(self)] = new
+    for k, v in self.__dict__.items():
+        if k not in _HANDLE_BOUND:  # the copy's handle is new and launches on its own stream until step_torch hands it torch's
+            new.__dict__[k] = copy.deepcopy(v, memo)
+    return new
+
+
+def _save_state(self, path):
+    """The env state as an `.npz` (FleetCore.save_state)."""
+    self.core.save_state(path)
+
+
+def _load_state(self, path):
+    """Resume from save_state's file (FleetCore.load_state): same config, tables and number of envs."""
+    self.core.load_state(path)
+
+
+def _fork_envs(self, src_idx, dst_idx, source=None):
+    """Copy env src_idx[i] of `source` (default: this env) to env dst_idx[i] here, on the device (FleetCore.fork_envs)."""
+    self.core.fork_envs(src_idx, dst_idx, source=source)
+
+
+for _cls in (FleetVecEnv, FleetVectorEnv, FleetEnv):
+    _cls.__deepcopy__, _cls.save_state, _cls.load_state, _cls.fork_envs = _deepcopy_by_core, _save_state, _load_state, _fork_envs
+del _cls

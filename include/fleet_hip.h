@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define FLEET_ABI_VERSION 10
+#define FLEET_ABI_VERSION 11
 
 /* status codes */
 #define FLEET_OK 0
@@ -363,6 +363,115 @@ int fleet_log_clear(fleet_handle h);     /* forget all rows (asynchronous on the
 int fleet_check_errors(fleet_handle h);
 /* the OR of all envs' error bits as of the last fleet_step_host (no device work) */
 int fleet_last_step_error_bits(fleet_handle h, uint32_t* bits);
+
+/* ---- env state: save, restore, fork (fleet_state.hip; DESIGN.md "Env state in the caller's hands") -------------------------
+ * "The state" of a handle is everything a step reads that a step or a reset has written (the list: fleet_device.h, beside FleetDev):
+ * per env the hot / schedule / SoH / soc_deg / SEI records, the env record, the EVs' rainflow rows (rainflow degradation), the
+ * night policy's window state, the length of the last episode and the data-log ring (log_data = 1); per handle the start schedule,
+ * the night-policy parameters and the fleet_set_rainflow_count_all switch.  Tables, scalars, streams and prepared launches are not.
+ *
+ * A state is a BLOB: a FleetStateHeader at offset 0, then one plain copy of every array ("section") at a 256-byte-aligned offset,
+ * in the order of the FLEET_SEC_* ids; the bytes between two sections are zero.  The header carries a FINGERPRINT -- the FleetParams
+ * fields that fix the layout and the meaning of the state, and a 64-bit hash of the table contents (fleet_state_table_hash, computed
+ * once by fleet_create) -- and a blob is only loaded into, and envs are only forked between, handles whose fingerprints are equal.
+ * num_envs is not part of it (a fork may cross handles of different E; a load needs the same E); auto_reset and env_id_offset are
+ * not either: the start-row sampler is keyed by the GLOBAL env id, so a state loaded under another env_id_offset continues its
+ * running episodes unchanged and draws other start rows from the next reset on.
+ * A handle with device error bits raised (fleet_check_errors) is neither saved nor forked: FLEET_ERR_STATE. */
+#define FLEET_STATE_MAGIC 0x4554415453544c46ull   /* "FLTSTATE" read as a little-endian 64-bit word */
+#define FLEET_STATE_ALIGN 256
+#define FLEET_SEC_HOT 0          /* [E,N]  16 B  hot record                                                   */
+#define FLEET_SEC_RUN 1          /* [E,N]  16 B  schedule record of the next row                              */
+#define FLEET_SEC_SOH 2          /* [E,N]  f64                                                                */
+#define FLEET_SEC_SOC_DEG 3      /* [E,N]  f64                                                                */
+#define FLEET_SEC_SEI 4          /* [E,N]  4 x f64  fd_cyc, fd_cal, l, soh                                    */
+#define FLEET_SEC_ENV 5          /* [E]    64 B  env record                                                   */
+#define FLEET_SEC_NIGHT_START 6  /* [E]    i32   night policy: row the charging window opened on              */
+#define FLEET_SEC_LAST_LEN 7     /* [E]    i32   length of the last finished episode                          */
+#define FLEET_SEC_RF_ROWS 8      /* [E*N, rf_row_stride] f64  rainflow rows (header + stack); FLEET_DEG_RAINFLOW only */
+#define FLEET_SEC_LOG_POS 9      /* [E] i32                      the data-log ring; log_data = 1 only         */
+#define FLEET_SEC_LOG_ROW 10     /* [log_cap,E] i32                                                           */
+#define FLEET_SEC_LOG_ENV 11     /* [log_cap,E,4] f64                                                         */
+#define FLEET_SEC_LOG_EV 12      /* [log_cap,E,4,N] f64                                                       */
+#define FLEET_SEC_LOG_OBS 13     /* [log_cap,E,obs_dim] f32                                                   */
+#define FLEET_SEC_SCHED 14       /* [sched_n,E] i32  the start schedule; absent from fleet_state_layout (its size belongs to the
+                                    handle, not to FleetParams): a blob with a schedule is longer than the layout's total      */
+#define FLEET_STATE_SECTIONS 16
+typedef struct FleetStateSection {
+  uint64_t offset;  /* from the start of the blob, a multiple of FLEET_STATE_ALIGN */
+  uint64_t bytes;   /* 0: the section is absent */
+} FleetStateSection;
+typedef struct FleetStateLayout {
+  int32_t struct_bytes;   /* sizeof(FleetStateLayout) */
+  int32_t alignment;      /* FLEET_STATE_ALIGN */
+  uint64_t header_bytes;  /* sizeof(FleetStateHeader) rounded up to the alignment: where section 0 starts */
+  uint64_t total_bytes;   /* of a blob without a start schedule */
+  int32_t num_envs, num_cars, obs_dim;
+  int32_t stack_cap;      /* entries of an EV's rainflow stack workspace (0 without rainflow degradation) */
+  int32_t rf_row_stride;  /* f64 words per rainflow row: 6 header words + the stack, rounded up to 16 */
+  int32_t log_cap;        /* rows per env of the data-log ring (0: off) */
+  FleetStateSection sec[FLEET_STATE_SECTIONS];
+} FleetStateLayout;
+typedef struct FleetStateFingerprint {
+  int32_t num_cars, table_rows, episode_steps, deg_mode, real_time;
+  int32_t price_lookahead, bl_pv_lookahead, include_building, include_pv, aux, normalize;  /* the observer: obs_dim, log rows */
+  int32_t stack_cap, rf_row_stride, log_cap;
+  int32_t picker_mode, reserved;
+  uint64_t seed;
+  double dt;
+  uint64_t table_hash;
+} FleetStateFingerprint;
+typedef struct FleetStateHeader {
+  uint64_t magic;         /* FLEET_STATE_MAGIC */
+  int32_t abi_version;    /* FLEET_ABI_VERSION of the library that wrote the blob */
+  int32_t header_bytes;   /* sizeof(FleetStateHeader) */
+  FleetStateFingerprint fp;
+  int32_t num_envs;       /* E: must match on load */
+  int32_t env_id_offset;  /* recorded; may differ on load */
+  int32_t obs_dim;
+  int32_t night_hour, night_minute, night_limit_s;  /* fleet_set_night_policy (night_hour < 0: not configured) */
+  int32_t rf_count_all;   /* fleet_set_rainflow_count_all */
+  int32_t sched_n;        /* episodes of the start schedule (0: none) */
+  uint64_t total_bytes;   /* of this blob, the schedule included */
+  FleetStateSection sec[FLEET_STATE_SECTIONS];
+} FleetStateHeader;
+
+/* No device needed.  Sizes, offsets and alignment of every section for these parameters (regular time grid: on an irregular one
+ * the rainflow workspace follows the tables' finish rows, and the header of a saved blob is the authority). */
+int fleet_state_layout(const FleetParams* p, FleetStateLayout* out);
+/* No device needed.  The 64-bit hash of the table contents that fleet_create computes, 8 bytes at a time: `there` and every
+ * per-row array of FleetTables in full, of time_left and soc_on_return every 16th row and the last one (hashing all of them cost
+ * 11 % of fleet_create at T = 35 040, N = 50; the subset's cost: DESIGN.md, "Env state in the caller's hands").  Tables that differ only in time_left / soc_on_return values of the
+ * rows in between hash alike. */
+int fleet_state_table_hash(const FleetParams* p, const FleetTables* t, uint64_t* hash);
+/* No device needed.  Does the blob whose first `bytes` bytes start at blob_header_host fit a handle created from `p` and tables
+ * of hash `table_hash`?  FLEET_ERR_INVALID (fleet_last_error(NULL) names the field) for a wrong magic, ABI version, num_envs, a
+ * fingerprint field that differs, or a blob shorter than its header says. */
+int fleet_state_check(const FleetParams* p, uint64_t table_hash, const void* blob_header_host, uint64_t bytes);
+/* Bytes a blob of this handle needs now (fleet_state_layout's total plus the start schedule, if one is set). */
+int fleet_state_bytes(fleet_handle h, uint64_t* bytes);
+/* Save: one copy per section on the handle's stream, after a direct run has drained.  Every save first reads the handle's error
+ * word back (one 4-byte copy and a synchronise: what the stream holds is finished when the call returns from that); _dev then
+ * only enqueues -- the blob is device memory, 16-byte aligned, and valid once the stream has got there -- and _host waits for the
+ * copies.  `bytes` = the size of the buffer, at least fleet_state_bytes.  Two saves of one state are byte-identical. */
+int fleet_state_save_dev(fleet_handle h, void* blob_dev, uint64_t bytes);
+int fleet_state_save_host(fleet_handle h, void* blob_host, uint64_t bytes);
+/* Load: the header is validated before the device state is touched (_dev reads it back first: one small synchronous copy); then
+ * the sections are copied in, the start schedule, night-policy parameters and the count-all switch are restored, the host path's
+ * finished-episode list and last error word are cleared.  The handle then continues bit-identically to the one that was saved. */
+int fleet_state_load_dev(fleet_handle h, const void* blob_dev, uint64_t bytes);
+int fleet_state_load_host(fleet_handle h, const void* blob_host, uint64_t bytes);
+/* Fork: env src_idx[i] of `src` is copied to env dst_idx[i] of `dst` (HOST index arrays, n pairs) by one kernel on dst's stream,
+ * ordered behind src's stream (and src's stream behind it).  dst may be src.  Like a save it first reads both handles' error
+ * words back, which drains their streams; the index upload and the kernel are then enqueued and not waited for.  Checked on the host before anything is launched
+ * (FLEET_ERR_INVALID): same device, equal fingerprints (E may differ), indices in range, no duplicate in dst_idx (src_idx may
+ * repeat: broadcast), disjoint index sets when dst == src.  FLEET_ERR_UNSUPPORTED when either handle has the data log on;
+ * FLEET_ERR_STATE when either has device error bits raised.  Of a rainflow row only the live part moves (the header and the
+ * source's stack entries); the destination's words beyond it keep their old, unread contents.
+ * The copy includes the episode counter: the destination continues the source's running episode bit-identically (same actions,
+ * same outputs) and at its next reset draws the start row of (its OWN global env id, the copied episode count), or its own column
+ * of its handle's start schedule.  The night policy's parameters and the start schedule stay the destination handle's own. */
+int fleet_fork_envs(fleet_handle dst, fleet_handle src, const int32_t* dst_idx_host, const int32_t* src_idx_host, int n);
 
 /* ---- measurement helpers (bench.py): HIP events on the handle's stream ------------------------------- */
 int fleet_timer_start(fleet_handle h);
