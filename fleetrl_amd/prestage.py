@@ -139,7 +139,9 @@ def stack_single_ev_schedules(base: Schedule, alt: Schedule | None, n_evs: int, 
 def _resample_regular(s: Schedule, minutes: int) -> Schedule:
     """Equivalent of `groupby("ID").resample(freq).agg(first/sum/mean)` (data_processing.py:61-64) for
     schedules whose rows fall into regular `minutes` buckets.  Rows already on the grid (all shipped
-    files) pass through untouched; finer rows are aggregated (sum consumption, mean power, first station)."""
+    files) pass through untouched; finer rows are aggregated (sum consumption, mean power, first station).  pandas sums a
+    bucket with a compensation term (see `_kahan_group_sum`): from four rows per bucket on (60-minute steps from the
+    shipped 15-minute files) a plain running sum differs in the last bit, and `SOC_on_return` inherits it."""
     step = np.timedelta64(minutes * 60, "s")
     out = {k: [] for k in ("date", "ev_id", "consumption", "power_rating", "station_none", "station_code")}
     for c in range(s.num_cars):
@@ -159,13 +161,22 @@ def _resample_regular(s: Schedule, minutes: int) -> Schedule:
             continue
         counts = np.bincount(b, minlength=nb)
         if np.any(counts == 0):
-            raise ValueError("schedule has empty time buckets after resampling; fill the gaps first")
+            raise ValueError(f"schedule has empty time buckets after resampling to {minutes} min (its rows are further apart); the "
+                             "reference fails on such a schedule too (DataLoader.compute_from_schedule: \"Merge keys contain "
+                             "null values on left side\"): unsupported, use rows at least as fine as the model's step")
+        if np.any(counts != counts[0]):
+            raise ValueError(f"schedule rows do not fill the {minutes}-min buckets evenly (e.g. 15-minute rows resampled to 20 "
+                             "minutes); the reference runs such a configuration on a table whose dates are the buckets' first "
+                             "rows (00:00, 00:30, 00:45, ...) while its clock advances by the model's step: not a meaningful "
+                             "mode, unsupported -- use a step that is a multiple of the schedule's row spacing")
         first = np.concatenate(([0], np.cumsum(counts)[:-1]))
         start = origin + ((d[0] - origin) // step) * step
         out["date"].append(start + np.arange(nb) * step)
         out["ev_id"].append(np.full(nb, c, dtype=np.int64))
-        out["consumption"].append(np.bincount(b, weights=s.consumption[m], minlength=nb))
-        out["power_rating"].append(np.bincount(b, weights=s.power_rating[m], minlength=nb) / counts)
+        head = np.zeros(d.size, dtype=bool)
+        head[first] = True
+        out["consumption"].append(_kahan_group_sum(b, s.consumption[m], nb, head))
+        out["power_rating"].append(_kahan_group_sum(b, s.power_rating[m], nb, head) / counts)
         out["station_none"].append(s.station_none[m][first])
         out["station_code"].append(s.station_code[m][first])
     return Schedule(**{k: np.concatenate(v) for k, v in out.items()})

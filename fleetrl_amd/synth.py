@@ -66,9 +66,13 @@ def synth_tables(use_case: str, n_evs: int, *, seed: int = 1234, target_soc: flo
                  include_building: bool = True, include_pv: bool = True, minutes: int = 15, price_year: str = "2020",
                  feed_in: str = "spot") -> FleetTables:
     """`price_year`: "2020" | "2021" (see PRICE_YEARS); `feed_in`: "spot" (the tariff follows the spot price, like the
-    reference's spot_*_tariff files) or "fixed" (a constant feed-in tariff, like inputs/fixed_feed_in.csv)."""
+    reference's spot_*_tariff files) or "fixed" (a constant feed-in tariff, like inputs/fixed_feed_in.csv).
+    `minutes`: the model's step; the schedule is always drawn on 15-minute rows (the generator's only grid, like the shipped
+    files) and `build_tables` resamples it to coarser steps the way the reference does (data_processing.py:54-64)."""
+    if minutes % 15:
+        raise ValueError("synthetic tables are resampled from 15-minute schedules: minutes must be a multiple of 15")
     init_cap = {"lmd": 60.0, "ut": 50.0, "ct": 16.7}[use_case]
-    sched = synth_schedule(use_case, n_evs, seed=seed, minutes=minutes)
+    sched = synth_schedule(use_case, n_evs, seed=seed)
     dates, spot, load, pv = synth_hourly(use_case, n_evs, seed=seed, price_year=price_year)
     tariff = spot if feed_in == "spot" else np.full_like(spot, FIXED_FEED_IN)
     return build_tables(

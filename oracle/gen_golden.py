@@ -30,6 +30,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from oracle.param_sets import LOOK0, LOOK12X14, MIN30, MIN60, OFFDEF, OFFDEF_NORM  # noqa: E402
 from oracle.ref_harness import make_ref_env, set_static_start, stacked_inputs_dir  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -108,7 +109,37 @@ CONFIGS = {
                                              max_batt_cap_in_all_use_cases=60, ignore_price_reward=True,
                                              ignore_overloading_penalty=True, ignore_invalid_penalty=True,
                                              ignore_overcharging_penalty=True), 3, 2, 2, "full"),
+    # ---- scalar parameters off their defaults (oracle/param_sets.py) ----
+    # every scalar off default at once, no two twins equal; on-board charger below the EVSE; discharging really happens
+    "ct3_both_rainflow_offdef": (dict(use_case="ct", building_name="load_ct.csv", include_building=True, include_pv=True,
+                                      calculate_degradation=True, deg_emp=False, episode_length=24, **OFFDEF), 3, 2, 2, "wide"),
+    # the same idea with linear degradation and normalised observations: every derived normaliser constant off default
+    "ut3_both_norm_linear_offdef": (dict(use_case="ut", building_name="load_ut.csv", include_building=True, include_pv=True,
+                                         normalize_in_env=True, calculate_degradation=True, deg_emp=True, episode_length=24,
+                                         **OFFDEF_NORM), 3, 2, 2, "wide"),
+    # look-ahead edges: none at all (price-only and load + pv observers), and a 66-float env-level tail
+    "lmd2_price_linear_look0": (dict(use_case="lmd", include_building=False, include_pv=False, calculate_degradation=True,
+                                     deg_emp=True, episode_length=24, **LOOK0), 2, 2, 2, "wide"),
+    "ct2_both_rainflow_look0": (dict(use_case="ct", building_name="load_ct.csv", include_building=True, include_pv=True,
+                                     calculate_degradation=True, deg_emp=False, episode_length=24, **LOOK0), 2, 2, 2, "charge"),
+    "ut3_both_rainflow_look12x14": (dict(use_case="ut", building_name="load_ut.csv", include_building=True, include_pv=True,
+                                         calculate_degradation=True, deg_emp=False, episode_length=24, **LOOK12X14),
+                                    3, 2, 2, "wide"),
+    # 30- and 60-minute steps: no row is 14:45, so the reference never calls its degradation model
+    "ct3_both_rainflow_min30": (dict(use_case="ct", building_name="load_ct.csv", include_building=True, include_pv=True,
+                                     calculate_degradation=True, deg_emp=False, episode_length=48, **MIN30), 3, 2, 2, "wide"),
+    "lmd3_both_linear_min60": (dict(use_case="lmd", building_name="load_lmd.csv", include_building=True, include_pv=True,
+                                    calculate_degradation=True, deg_emp=True, episode_length=48, **MIN60), 3, 2, 2, "wide"),
 }
+
+
+def time_grid(ov: dict):
+    """(steps per hour, rows per day, stored look-ahead rows, row of 14:30 within a day or None) of a configuration."""
+    sph = ov.get("time_steps_per_hour", 4)
+    minutes = ov.get("minutes", 15)
+    assert sph * minutes == 60, "freq, minutes and time_steps_per_hour are set together"
+    look = (max(ov.get("price_lookahead", 8), ov.get("bl_pv_lookahead", 4)) + 2) * sph + 1
+    return sph, 24 * sph, look, (14 * sph + 30 // minutes if 30 % minutes == 0 else None)
 
 
 def make_actions(rng: np.random.Generator, steps: int, n: int, mode: str) -> np.ndarray:
@@ -134,7 +165,8 @@ def run_config(name: str):
         ov.update(data_path=dp, schedule_name=sched)
     ov.setdefault("target_soc", 0.85)
     rng = np.random.default_rng(sum(map(ord, name.replace("_log", ""))))
-    ep_steps = ov["episode_length"] * 4
+    sph, day, L2, row1430 = time_grid(ov)
+    ep_steps = ov["episode_length"] * sph
     total = ep_steps * episodes
     rec = None
     starts = np.zeros((episodes, E), dtype=np.int32)
@@ -182,10 +214,10 @@ def run_config(name: str):
         # start rows: anywhere in the training range, plus a forced 14:30 start (degradation on the very first step)
         # (kept inside one 45-day span per configuration so that the stored table window stays small)
         if e == 0:
-            span0 = int(rng.integers(0, T - 1 - 60 * 96 - 45 * 96))
-        cand = rng.integers(span0, span0 + 45 * 96, size=episodes)
-        if e == 0 and episodes > 1:
-            cand[1] = (cand[1] // 96) * 96 + 58
+            span0 = int(rng.integers(0, T - 1 - 60 * day - 45 * day))
+        cand = rng.integers(span0, span0 + 45 * day, size=episodes)
+        if e == 0 and episodes > 1 and row1430 is not None:
+            cand[1] = (cand[1] // day) * day + row1430
         starts[:, e] = cand
         k = 0
         for ep in range(episodes):
@@ -245,8 +277,7 @@ def run_config(name: str):
     # ---- tables: the reference's db columns for the rows the episodes touch --------------------------------
     N = scalars["num_cars"]
     T = scalars["table_rows_full"]
-    L2 = (ov.get("price_lookahead", 8) + 2) * 4 + 1
-    w0 = (int(starts.min()) // 96) * 96
+    w0 = (int(starts.min()) // day) * day
     w1 = min(T, int(starts.max()) + ep_steps + L2 + 1)
     col = lambda c: db0[c].values.reshape(N, T).T[w0:w1]  # noqa: E731
     dates = db0["date"].values[:T][w0:w1].astype("datetime64[s]")
@@ -309,6 +340,9 @@ RT_CONFIGS = {
                                    calculate_degradation=True, deg_emp=False, episode_length=24, real_time=True, log_data=True), 3, 2, 2),
     "lmd1_both_irregular": (dict(use_case="lmd", schedule_name="test_lmd.csv", building_name="load_lmd.csv", include_building=True,
                                  include_pv=True, calculate_degradation=True, deg_emp=True, episode_length=24, real_time=True), 0, 2, 2),
+    # every scalar off its default (oracle/param_sets.py): the event thresholds interact with target_soc and the penalties
+    "ct3_both_rainflow_offdef": (dict(use_case="ct", building_name="load_ct.csv", include_building=True, include_pv=True,
+                                      calculate_degradation=True, deg_emp=False, episode_length=24, real_time=True, **OFFDEF), 3, 2, 2),
 }
 
 
@@ -334,7 +368,8 @@ def run_config_rt(name: str):
         ov.update(data_path=dp, schedule_name=sched)
     ov.setdefault("target_soc", 0.85)
     rng = np.random.default_rng(sum(map(ord, "rt_" + name)))
-    ep_rows = ov["episode_length"] * 4
+    sph, day, L2, _ = time_grid(ov)
+    ep_rows = ov["episode_length"] * sph
     cap = ep_rows * episodes  # an agent step spans >= 1 row
     rec, scalars, db0 = None, {}, None
     starts = np.zeros((episodes, E), dtype=np.int32)
@@ -362,8 +397,8 @@ def run_config_rt(name: str):
         acts = make_actions_rt(rng, cap, N)
         rec["actions"][e] = acts
         if e == 0:
-            span0 = 0 if name.endswith("irregular") else int(rng.integers(0, T - 1 - 60 * 96 - 20 * 96))
-        starts[:, e] = rng.integers(span0, span0 + 20 * 96, size=episodes)
+            span0 = 0 if name.endswith("irregular") else int(rng.integers(0, T - 1 - 60 * day - 20 * day))
+        starts[:, e] = rng.integers(span0, span0 + 20 * day, size=episodes)
         if name.endswith("irregular") and e == 0:
             starts[0, 0] = 0
         k = 0
@@ -419,8 +454,7 @@ def run_config_rt(name: str):
         print(f"  rt {name}: env {e + 1}/{E}: {rec['n_steps'][e].tolist()} agent steps for {ep_rows} rows per episode "
               f"({time.time() - t0:.0f}s)", flush=True)
     N, T = scalars["num_cars"], scalars["table_rows_full"]
-    L2 = (ov.get("price_lookahead", 8) + 2) * 4 + 1
-    w0 = (int(starts.min()) // 96) * 96
+    w0 = (int(starts.min()) // day) * day
     w1 = min(T, int(starts.max()) + ep_rows + L2 + 1)
     col = lambda c: db0[c].values.reshape(N, T).T[w0:w1]  # noqa: E731
     one = lambda c: db0[c].values[:T][w0:w1] if c in db0 else np.zeros(w1 - w0)  # noqa: E731

@@ -83,6 +83,39 @@ def test_unsupported_flag_combinations_are_rejected():
             validate_supported(resolve_config(cfg))
 
 
+def test_a_step_finer_than_the_schedule_rows_is_rejected_like_the_reference():
+    """minutes = 5 (or 10) on 15-minute schedules: `validate_supported` cannot know the schedule's rows (5 divides 60, and a
+    5-minute schedule would be fine); the pre-stager, which does, refuses with the reference's own failure -- resampling leaves
+    empty buckets, DataLoader.compute_from_schedule dies on them ("Merge keys contain null values on left side").  Coarser steps
+    the reference runs (30, 60: trace_*_min30 / *_min60) pass."""
+    from fleetrl_amd.synth import synth_hourly, synth_schedule
+    from fleetrl_amd.prestage import build_tables
+
+    sched = synth_schedule("lmd", 2, days=14)
+    dates, spot, load, pv = synth_hourly("lmd", 2)
+    kw = dict(target_soc=0.85, target_soc_lunch=0.65, init_battery_cap=60.0, is_caretaker=False, spot=(dates, spot),
+              tariff=(dates, spot), load=None, pv=None, fixed_markup=10, variable_multiplier=1.5, feed_in_deduction=0.25)
+    for minutes in (5, 10):
+        cfg = _cfg()
+        cfg.update(minutes=minutes, time_steps_per_hour=60 // minutes, freq=f"{minutes}T")
+        validate_supported(resolve_config(cfg))
+        with pytest.raises(ValueError, match="Merge keys contain null values"):
+            build_tables(sched, minutes=minutes, **kw)
+    # minutes = 20 runs in the reference, on a table whose date column is 00:00, 00:30, 00:45, 01:00, ... (the first row of each
+    # bucket; seen in a trace generated from it) under a clock that advances by 20 minutes: refused where the rows are known
+    cfg = _cfg()
+    cfg.update(minutes=20, time_steps_per_hour=3, freq="20T")
+    validate_supported(resolve_config(cfg))
+    with pytest.raises(ValueError, match="do not fill the 20-min buckets evenly"):
+        build_tables(sched, minutes=20, **kw)
+    for minutes in (30, 60):
+        assert build_tables(sched, minutes=minutes, **kw).minutes_per_step == minutes
+    with pytest.raises(ValueError, match="divide 60"):
+        cfg = _cfg()
+        cfg.update(minutes=7)
+        validate_supported(resolve_config(cfg))
+
+
 def test_picker_ranges():
     g = load_trace("lmd1_price_linear")
     # a full-year table starting 2020-01-01 00:00: build a tiny stand-in with the same date axis

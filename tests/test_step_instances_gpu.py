@@ -111,24 +111,27 @@ class ExpectedLog:
 class Pair:
     """The HIP batch and the oracle of one case, built from the same FleetParams, and the comparisons of one use each."""
 
-    def __init__(self, case, log_rows=0):
+    def __init__(self, case, log_rows=0, cfg=None, tables=None):
+        """`cfg` / `tables` (a (FleetTables, time features) pair): another config dict and other tables than the case's own
+        (tests/test_param_space_gpu.py); the episode is then `episode_length` hours at the config's own step."""
         import torch
 
         from fleetrl_amd.batch import FleetBatch
         from oracle.fleet_oracle import OracleBatch
 
         self.case, self.torch, self.dev = case, torch, torch.device("cuda", 0)
-        self.tb, tf = _tables(case.uc, case.n_evs)
-        self.rc = resolve_config(si.config_of(case))
+        self.tb, tf = _tables(case.uc, case.n_evs) if tables is None else tables
+        self.rc = resolve_config(si.config_of(case) if cfg is None else cfg)
         p = make_params(self.rc, self.tb, case.num_envs, seed=case.seed + 1)
         if case.log_data:
             p.log_capacity = log_rows
-        assert (p.auto_reset, p.log_data, p.real_time, p.episode_steps) == (1, int(case.log_data), int(case.real_time), 96)
+        ep_steps = 96 if cfg is None else self.rc.episode_length * 60 // self.rc.minutes
+        assert (p.auto_reset, p.log_data, p.real_time, p.episode_steps) == (1, int(case.log_data), int(case.real_time), ep_steps)
         self.p, self.E, self.N = p, case.num_envs, case.n_evs
         self.hip, self.cpu = FleetBatch(p, self.tb, tf), OracleBatch(p, self.tb, tf, threads=4)
         self.rng = np.random.default_rng(1000 + case.seed)
         self.s = 0  # steps taken so far: the phase of the action mix
-        self.log = ExpectedLog(self.cpu, log_rows, self.hip.obs_dim, 96) if case.log_data else None
+        self.log = ExpectedLog(self.cpu, log_rows, self.hip.obs_dim, ep_steps) if case.log_data else None
         # the handle's own configuration must lead every launch of the case to the instance the case was written for
         for ln in case.launches():
             got = _capi.step_instance(self.hip.E, self.hip.N, p.deg_mode, p.real_time, p.log_data, ln.act_mode, ln.K, ln.has_done_count)[0]
@@ -295,13 +298,14 @@ class Pair:
 RT_STEPS = 210  # every step advances an env by at least one row: more than two 96-row episodes
 
 
-def _run(case):
+def _run(case, make_pair=Pair):
+    """`make_pair(case, log_rows=...)`: the pair of the case (tests/test_param_space_gpu.py builds it under a parameter set)."""
     if case.log_data and case.real_time:
-        pair = Pair(case, log_rows=4 * RT_STEPS + 32)  # a row with clock minute 15 is an event: at most 4 rows per step, plus resets
+        pair = make_pair(case, log_rows=4 * RT_STEPS + 32)  # a row with clock minute 15 is an event: at most 4 rows per step, plus resets
     elif case.log_data:
-        pair = Pair(case, log_rows=400)
+        pair = make_pair(case, log_rows=400)
     else:
-        pair = Pair(case)
+        pair = make_pair(case)
     try:
         if case.real_time:
             assert case.uses == ("rt",)
