@@ -100,6 +100,30 @@ class FleetTablesC(C.Structure):
     _fields_ = list(_TABLE_FIELDS)
 
 
+# ---- rollout buffer (include/fleet_hip.h "rollout buffer on the device", fleet_rollout_*) -----------------------------------------
+ROLLOUT_ALIGN = 256
+ROLLOUT_ARRAY_NAMES = ("obs", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns")
+
+
+class FleetRolloutParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("num_envs", C.c_int32), ("n_steps", C.c_int32), ("obs_dim", C.c_int32),
+                ("act_dim", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double), ("gae_lambda", C.c_double)]
+
+
+class FleetRolloutLayout(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("alignment", C.c_int32), ("total_bytes", C.c_uint64),
+                ("offset", C.c_uint64 * len(ROLLOUT_ARRAY_NAMES)), ("bytes", C.c_uint64 * len(ROLLOUT_ARRAY_NAMES)),
+                ("row_bytes", C.c_uint64 * len(ROLLOUT_ARRAY_NAMES)), ("error_offset", C.c_uint64)]
+
+
+class FleetRolloutArrays(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ROLLOUT_ARRAY_NAMES]
+
+
+class FleetRolloutSlot(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "actions", "reward", "episode_start", "value", "log_prob")]
+
+
 # ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
 STATE_MAGIC = 0x4554415453544C46
 STATE_ALIGN = 256
@@ -313,6 +337,22 @@ def load_library():
     for name in NORM_SYMBOLS:
         if name != "fleet_norm_last_error":
             getattr(lib, name).restype = C.c_int
+    # the rollout buffer (fleet_rollout.hip)
+    lib.fleet_rollout_layout.argtypes = [C.POINTER(FleetRolloutParams), C.POINTER(FleetRolloutLayout)]
+    lib.fleet_rollout_create.argtypes = [C.c_int, C.POINTER(FleetRolloutParams), C.POINTER(vp)]
+    lib.fleet_rollout_destroy.argtypes = [vp]
+    lib.fleet_rollout_last_error.argtypes = [vp]
+    lib.fleet_rollout_last_error.restype = C.c_char_p
+    lib.fleet_rollout_set_stream.argtypes = [vp, vp]
+    lib.fleet_rollout_arrays.argtypes = [vp, C.POINTER(FleetRolloutArrays)]
+    lib.fleet_rollout_slot.argtypes = [vp, C.c_int, C.POINTER(FleetRolloutSlot)]
+    lib.fleet_rollout_add_dev.argtypes = [vp, C.c_int, f32p, f32p, vp, C.c_int, u8p, f32p, f32p, f32p, u8p]
+    lib.fleet_rollout_finish_dev.argtypes = [vp, f32p, u8p]
+    lib.fleet_rollout_gather_dev.argtypes = [vp, vp, C.c_int, f32p, f32p, f32p, f32p, f32p, f32p]
+    lib.fleet_rollout_check_errors.argtypes = [vp]
+    for name in ROLLOUT_SYMBOLS:
+        if name != "fleet_rollout_last_error":
+            getattr(lib, name).restype = C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
                  "fleet_log_capacity", "fleet_log_read",
                  "fleet_log_clear", "fleet_synchronize", "fleet_set_start_schedule",
@@ -338,6 +378,12 @@ STATE_SYMBOLS = (
     "fleet_state_load_dev", "fleet_state_save_host", "fleet_state_load_host", "fleet_fork_envs",
 )
 
+ROLLOUT_SYMBOLS = (
+    "fleet_rollout_layout", "fleet_rollout_create", "fleet_rollout_destroy", "fleet_rollout_last_error", "fleet_rollout_set_stream",
+    "fleet_rollout_arrays", "fleet_rollout_slot", "fleet_rollout_add_dev", "fleet_rollout_finish_dev", "fleet_rollout_gather_dev",
+    "fleet_rollout_check_errors",
+)
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -350,7 +396,7 @@ EXPORTED_SYMBOLS = (
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
-) + NORM_SYMBOLS + STATE_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,
@@ -364,6 +410,19 @@ def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, 
     if rc != OK:
         raise FleetHipError(rc, "fleet_step_instance: argument out of range")
     return name.value.decode(), int(grid.value)
+
+
+def rollout_layout(num_envs: int, n_steps: int, obs_dim: int, act_dim: int, gamma: float = 0.99,
+                   gae_lambda: float = 0.95) -> FleetRolloutLayout:
+    """fleet_rollout_layout: bytes and offsets of the rollout buffer's arrays (needs the library, no GPU)."""
+    p = FleetRolloutParams(C.sizeof(FleetRolloutParams), int(num_envs), int(n_steps), int(obs_dim), int(act_dim), 0, float(gamma),
+                           float(gae_lambda))
+    out = FleetRolloutLayout()
+    lib = load_library()
+    rc = lib.fleet_rollout_layout(C.byref(p), C.byref(out))
+    if rc != OK:
+        raise FleetHipError(rc, lib.fleet_rollout_last_error(None).decode())
+    return out
 
 
 def state_layout(params: FleetParams) -> FleetStateLayout:

@@ -620,6 +620,107 @@ int fleet_reset_host_norm(fleet_handle h, fleet_norm_handle n, float* obs);
 int fleet_step_host_norm(fleet_handle h, fleet_norm_handle n, const void* actions, int act_dtype, float* obs, double* reward,
                          uint8_t* done, float* terminal_obs);
 
+/* ---- rollout buffer on the device (fleet_rollout.hip; DESIGN.md "Rollouts on the device") -----------------------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * stable-baselines3 2.3.2 `RolloutBuffer` in device memory: K time rows of E envs, SB3's layout (time-major), float32 throughout,
+ *   obs f32[K,E,D]  actions f32[K,E,A]  rewards f32[K,E]  episode_starts u8[K,E]  values f32[K,E]  log_probs f32[K,E]
+ *   advantages f32[K,E]  returns f32[K,E]
+ * in ONE device allocation, each array at a 256-byte-aligned offset (fleet_rollout_layout), followed by one 32-bit error word.
+ * Every *_dev call takes device pointers, only enqueues (no host synchronisation) and runs on the buffer's stream: its own, or
+ * the one fleet_rollout_set_stream borrowed.  Calls on one buffer are serialised by the caller.  No atomics, no random numbers.
+ *   add     row t <- (obs, actions, f32(reward), episode_start, value, log_prob); a source that IS the row's own address
+ *           (fleet_rollout_slot) is not copied: an env / normaliser step wrote it there
+ *   finish  SB3's compute_returns_and_advantage, operation for operation in float32: g = f32(gamma), gl = f32(gamma * gae_lambda)
+ *           (the product in float64), last = 0; for t = K-1 .. 0:
+ *             nnt = 1 - (t == K-1 ? dones : episode_starts[t+1]);  nv = (t == K-1 ? last_values : values[t+1])
+ *             delta = (rewards[t] + (g * nv) * nnt) - values[t];   last = delta + (gl * nnt) * last
+ *             advantages[t] = last;  returns[t] = last + values[t]
+ *   gather  SB3's get() for one minibatch: flat indices i = e * K + t (the order of SB3's swap_and_flatten) -> rows of six arrays */
+typedef struct FleetRolloutParams {
+  int32_t struct_bytes;  /* sizeof(FleetRolloutParams) */
+  int32_t num_envs;      /* E >= 1 */
+  int32_t n_steps;       /* K >= 1; E * K < 2^31 */
+  int32_t obs_dim;       /* D >= 1 */
+  int32_t act_dim;       /* A >= 1 */
+  int32_t reserved;      /* 0 */
+  double gamma;          /* 0 <= gamma <= 1 */
+  double gae_lambda;     /* 0 <= gae_lambda <= 1 */
+} FleetRolloutParams;
+#define FLEET_ROLLOUT_ALIGN 256
+#define FLEET_ROLLOUT_OBS 0
+#define FLEET_ROLLOUT_ACTIONS 1
+#define FLEET_ROLLOUT_REWARDS 2
+#define FLEET_ROLLOUT_EPISODE_STARTS 3
+#define FLEET_ROLLOUT_VALUES 4
+#define FLEET_ROLLOUT_LOG_PROBS 5
+#define FLEET_ROLLOUT_ADVANTAGES 6
+#define FLEET_ROLLOUT_RETURNS 7
+#define FLEET_ROLLOUT_ARRAYS 8
+typedef struct FleetRolloutLayout {
+  int32_t struct_bytes;  /* sizeof(FleetRolloutLayout) */
+  int32_t alignment;     /* FLEET_ROLLOUT_ALIGN */
+  uint64_t total_bytes;  /* of the allocation, the error word included */
+  uint64_t offset[FLEET_ROLLOUT_ARRAYS];      /* of array FLEET_ROLLOUT_*, a multiple of the alignment */
+  uint64_t bytes[FLEET_ROLLOUT_ARRAYS];       /* K * E * (D | A | 1) * (4 | 1) */
+  uint64_t row_bytes[FLEET_ROLLOUT_ARRAYS];   /* of one time row: bytes / K */
+  uint64_t error_offset; /* of the 32-bit error word */
+} FleetRolloutLayout;
+typedef struct FleetRolloutArrays {  /* base addresses (row 0) of the eight arrays, device memory */
+  float* obs;
+  float* actions;
+  float* rewards;
+  uint8_t* episode_starts;
+  float* values;
+  float* log_probs;
+  float* advantages;
+  float* returns;
+} FleetRolloutArrays;
+typedef struct FleetRolloutSlot {  /* addresses of ONE time row: what fleet_rollout_add_dev skips when it is handed them */
+  float* obs;              /* [E,D] */
+  float* actions;          /* [E,A] */
+  float* reward;           /* [E]   */
+  uint8_t* episode_start;  /* [E]   */
+  float* value;            /* [E]   */
+  float* log_prob;         /* [E]   */
+} FleetRolloutSlot;
+typedef struct FleetRollout* fleet_rollout_handle;
+
+/* No device needed.  FLEET_ERR_INVALID (fleet_rollout_last_error(NULL) says why) for parameters fleet_rollout_create refuses. */
+int fleet_rollout_layout(const FleetRolloutParams* p, FleetRolloutLayout* out);
+/* The parameters are validated BEFORE the device is touched: FLEET_ERR_INVALID for E, K, D or A < 1, E * K >= 2^31, gamma or
+ * gae_lambda outside [0, 1] (NaN included), a wrong struct_bytes, a null pointer.  Then: one allocation, zero-filled. */
+int fleet_rollout_create(int device, const FleetRolloutParams* p, fleet_rollout_handle* out);
+int fleet_rollout_destroy(fleet_rollout_handle r);
+const char* fleet_rollout_last_error(fleet_rollout_handle r);  /* r may be NULL: error of the last failed create / layout */
+/* launch on an external hipStream_t (borrowed; NULL = the null stream) from now on instead of the buffer's own stream; waits for
+ * what the previous stream still holds of this buffer's work */
+int fleet_rollout_set_stream(fleet_rollout_handle r, void* hip_stream);
+int fleet_rollout_arrays(fleet_rollout_handle r, FleetRolloutArrays* out);
+/* the addresses of time row t (0 <= t < K).  Pass them as obs_out / done_out of the env or normaliser step that produces the row
+ * and again to fleet_rollout_add_dev, which then leaves those arrays alone. */
+int fleet_rollout_slot(fleet_rollout_handle r, int t, FleetRolloutSlot* out);
+/* One launch: time row t <- the sources (device memory, none NULL).  reward: f64[E] (reward_dtype = FLEET_ACT_F64; what the
+ * normaliser and the env emit) or f32[E] (FLEET_ACT_F32), rounded ONCE to float32 as SB3's assignment into its float32 array does.
+ * A source equal to the row's own address is skipped.  terminal_value f32[E] (or NULL: off, the reference's behaviour) with
+ * done u8[E] (the step's dones, required with it): SB3's time-limit bootstrap, rewards[t,e] = f32(reward[e]) + f32(gamma) *
+ * terminal_value[e] where done[e] != 0, in float32.  FLEET_ERR_INVALID: t outside [0, K), a null source. */
+int fleet_rollout_add_dev(fleet_rollout_handle r, int t, const float* obs, const float* actions, const void* reward,
+                          int reward_dtype, const uint8_t* episode_start, const float* value, const float* log_prob,
+                          const float* terminal_value, const uint8_t* done);
+/* One launch, one lane per env: advantages and returns of all K rows from the stored rewards, values and episode_starts and from
+ * last_values f32[E], dones u8[E] (the value of, and the dones before, the observation after the last row).  Bit-identical to the
+ * float32 recurrence above evaluated in NumPy. */
+int fleet_rollout_finish_dev(fleet_rollout_handle r, const float* last_values, const uint8_t* dones);
+/* One launch: out_x[b] = x[t, e] for indices[b] = e * K + t, b < batch; indices i32[batch] in device memory, the permutation is the
+ * caller's.  Any output may be NULL (not wanted).  Rows of obs (and of actions) move as 16-byte words when D (A) is a multiple of
+ * 4 and the output is 16-byte aligned, as single floats otherwise.  An index outside [0, K * E) writes nothing for its row and sets
+ * the buffer's error word (fleet_rollout_check_errors). */
+int fleet_rollout_gather_dev(fleet_rollout_handle r, const int32_t* indices, int batch, float* out_obs, float* out_actions,
+                             float* out_values, float* out_log_probs, float* out_advantages, float* out_returns);
+/* Waits for the stream, reads the error word back: FLEET_OK, or FLEET_ERR_STATE (a gather met an index out of range since the last
+ * check) -- the word is cleared, so the next check is clean. */
+int fleet_rollout_check_errors(fleet_rollout_handle r);
+
 #ifdef __cplusplus
 }
 #endif
