@@ -3,7 +3,7 @@
     from fleetrl_amd import FleetEnv, FleetVecEnv, FleetVectorEnv, FleetMixedVecEnv
     from fleetrl_amd import FleetVecNormalize, DeviceNormalizer, sync_normalization
     from fleetrl_amd import plan_linear_optimization, run_linear_optimization
-    from fleetrl_amd import DeviceRolloutBuffer
+    from fleetrl_amd import DeviceRolloutBuffer, DeviceReplayBuffer
 """
 __version__ = "0.1.0"
 
@@ -25,6 +25,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import rollout
 
         return getattr(rollout, name)
+    if name in ("DeviceReplayBuffer", "ReplayBatch"):
+        from . import replay
+
+        return getattr(replay, name)
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

@@ -124,6 +124,27 @@ class FleetRolloutSlot(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("obs", "actions", "reward", "episode_start", "value", "log_prob")]
 
 
+# ---- replay buffer (include/fleet_hip.h "replay buffer on the device", fleet_replay_*) ------------------------------------------
+REPLAY_ALIGN = 256
+REPLAY_ARRAY_NAMES = ("observations", "next_observations", "actions", "rewards", "dones", "timeouts")
+
+
+class FleetReplayParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("num_envs", C.c_int32), ("buffer_size", C.c_int32), ("obs_dim", C.c_int32),
+                ("act_dim", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class FleetReplayLayout(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("alignment", C.c_int32), ("rows", C.c_int32), ("reserved", C.c_int32),
+                ("total_bytes", C.c_uint64), ("offset", C.c_uint64 * len(REPLAY_ARRAY_NAMES)),
+                ("bytes", C.c_uint64 * len(REPLAY_ARRAY_NAMES)), ("row_bytes", C.c_uint64 * len(REPLAY_ARRAY_NAMES)),
+                ("error_offset", C.c_uint64)]
+
+
+class FleetReplayArrays(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in REPLAY_ARRAY_NAMES]
+
+
 # ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
 STATE_MAGIC = 0x4554415453544C46
 STATE_ALIGN = 256
@@ -353,6 +374,23 @@ def load_library():
     for name in ROLLOUT_SYMBOLS:
         if name != "fleet_rollout_last_error":
             getattr(lib, name).restype = C.c_int
+    # the replay buffer (fleet_replay.hip)
+    lib.fleet_replay_layout.argtypes = [C.POINTER(FleetReplayParams), C.POINTER(FleetReplayLayout)]
+    lib.fleet_replay_create.argtypes = [C.c_int, C.POINTER(FleetReplayParams), C.POINTER(vp)]
+    lib.fleet_replay_destroy.argtypes = [vp]
+    lib.fleet_replay_last_error.argtypes = [vp]
+    lib.fleet_replay_last_error.restype = C.c_char_p
+    lib.fleet_replay_set_stream.argtypes = [vp, vp]
+    lib.fleet_replay_arrays.argtypes = [vp, C.POINTER(FleetReplayArrays)]
+    lib.fleet_replay_add_dev.argtypes = [vp, f32p, f32p, f32p, vp, C.c_int, u8p, f32p, u8p]
+    lib.fleet_replay_gather_dev.argtypes = [vp, vp, vp, C.c_int, vp, f32p, f32p, f32p, f32p, f32p]
+    lib.fleet_replay_sample_dev.argtypes = [vp, C.c_int, vp, f32p, f32p, f32p, f32p, f32p, vp, vp]
+    lib.fleet_replay_check_errors.argtypes = [vp]
+    lib.fleet_replay_size.argtypes = [vp, i32p, i32p, i32p, C.POINTER(C.c_uint64)]
+    lib.fleet_replay_set_position.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint64]
+    for name in REPLAY_SYMBOLS:
+        if name != "fleet_replay_last_error":
+            getattr(lib, name).restype = C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
                  "fleet_log_capacity", "fleet_log_read",
                  "fleet_log_clear", "fleet_synchronize", "fleet_set_start_schedule",
@@ -384,6 +422,12 @@ ROLLOUT_SYMBOLS = (
     "fleet_rollout_check_errors",
 )
 
+REPLAY_SYMBOLS = (
+    "fleet_replay_layout", "fleet_replay_create", "fleet_replay_destroy", "fleet_replay_last_error", "fleet_replay_set_stream",
+    "fleet_replay_arrays", "fleet_replay_add_dev", "fleet_replay_gather_dev", "fleet_replay_sample_dev", "fleet_replay_check_errors",
+    "fleet_replay_size", "fleet_replay_set_position",
+)
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -396,7 +440,7 @@ EXPORTED_SYMBOLS = (
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,
@@ -422,6 +466,17 @@ def rollout_layout(num_envs: int, n_steps: int, obs_dim: int, act_dim: int, gamm
     rc = lib.fleet_rollout_layout(C.byref(p), C.byref(out))
     if rc != OK:
         raise FleetHipError(rc, lib.fleet_rollout_last_error(None).decode())
+    return out
+
+
+def replay_layout(buffer_size: int, num_envs: int, obs_dim: int, act_dim: int) -> FleetReplayLayout:
+    """fleet_replay_layout: rows, bytes and offsets of the replay buffer's arrays (needs the library, no GPU)."""
+    p = FleetReplayParams(C.sizeof(FleetReplayParams), int(num_envs), int(buffer_size), int(obs_dim), int(act_dim), 0, 0)
+    out = FleetReplayLayout()
+    lib = load_library()
+    rc = lib.fleet_replay_layout(C.byref(p), C.byref(out))
+    if rc != OK:
+        raise FleetHipError(rc, lib.fleet_replay_last_error(None).decode())
     return out
 
 

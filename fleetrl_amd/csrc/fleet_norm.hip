@@ -29,8 +29,6 @@ constexpr int kWaves = 4;    // waves per workgroup (256 threads)
 constexpr int kThreads = 64 * kWaves;
 constexpr int kApplyMaxBlocks = 2048;
 
-__device__ inline double clip(double v, double c) { return v < -c ? -c : (v > c ? c : v); }
-
 __global__ __launch_bounds__(kThreads) void norm_moments(const float* __restrict__ obs, int E, int D, int tiles,
                                                          const double* __restrict__ raw_reward, const double* __restrict__ returns,
                                                          double gamma, double* __restrict__ part_obs, double* __restrict__ part_ret) {
@@ -180,8 +178,6 @@ struct ApplyArgs {
   int norm_obs, norm_reward, update_returns, reset;
 };
 
-__device__ inline float norm1(float x, double m, double s, double c) { return (float)clip(((double)x - m) / s, c); }
-
 template <bool kVec>
 __global__ __launch_bounds__(kThreads) void norm_apply(ApplyArgs a) {
   const size_t gid = (size_t)blockIdx.x * kThreads + threadIdx.x;
@@ -197,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void norm_apply(ApplyArgs a) {
     const double nr = a.update_returns ? a.returns[e] * a.gamma + r : a.returns[e];
     a.returns[e] = d ? 0.0 : nr;
     a.raw_copy[e] = raw;
-    a.reward[e] = a.norm_reward ? clip(r / a.ret_stat[2], a.clip_reward) : r;
+    a.reward[e] = a.norm_reward ? fleet_norm_reward1(r, a.ret_stat[2], a.clip_reward) : r;
   }
   const bool write_obs = a.norm_obs || a.out != a.raw;
   const bool write_term = a.raw_term && (a.norm_obs || a.term != a.raw_term);
@@ -216,14 +212,14 @@ __global__ __launch_bounds__(kThreads) void norm_apply(ApplyArgs a) {
       }
       if (write_obs) {
         float4 x = *reinterpret_cast<const float4*>(a.raw + flat);
-        if (a.norm_obs) x = make_float4(norm1(x.x, m[0], s[0], c), norm1(x.y, m[1], s[1], c), norm1(x.z, m[2], s[2], c),
-                                        norm1(x.w, m[3], s[3], c));
+        if (a.norm_obs) x = make_float4(fleet_norm_obs1(x.x, m[0], s[0], c), fleet_norm_obs1(x.y, m[1], s[1], c), fleet_norm_obs1(x.z, m[2], s[2], c),
+                                        fleet_norm_obs1(x.w, m[3], s[3], c));
         *reinterpret_cast<float4*>(a.out + flat) = x;
       }
       if (write_term && a.done[row]) {
         float4 x = *reinterpret_cast<const float4*>(a.raw_term + flat);
-        if (a.norm_obs) x = make_float4(norm1(x.x, m[0], s[0], c), norm1(x.y, m[1], s[1], c), norm1(x.z, m[2], s[2], c),
-                                        norm1(x.w, m[3], s[3], c));
+        if (a.norm_obs) x = make_float4(fleet_norm_obs1(x.x, m[0], s[0], c), fleet_norm_obs1(x.y, m[1], s[1], c), fleet_norm_obs1(x.z, m[2], s[2], c),
+                                        fleet_norm_obs1(x.w, m[3], s[3], c));
         *reinterpret_cast<float4*>(a.term + flat) = x;
       }
     }
@@ -235,11 +231,11 @@ __global__ __launch_bounds__(kThreads) void norm_apply(ApplyArgs a) {
       const double m = a.mean[col], s = a.sd[col];
       if (write_obs) {
         const float x = a.raw[i];
-        a.out[i] = a.norm_obs ? norm1(x, m, s, c) : x;
+        a.out[i] = a.norm_obs ? fleet_norm_obs1(x, m, s, c) : x;
       }
       if (write_term && a.done[row]) {
         const float x = a.raw_term[i];
-        a.term[i] = a.norm_obs ? norm1(x, m, s, c) : x;
+        a.term[i] = a.norm_obs ? fleet_norm_obs1(x, m, s, c) : x;
       }
     }
   }
@@ -277,6 +273,9 @@ struct FleetNorm {
   float* out_obs = nullptr;
   const float* last_raw_obs = nullptr;  // nullptr: none (no call yet, or the last one was in place)
   bool have_reward = false;
+  // readers of the statistics on other streams (fleet_norm_begin_read / _end_read), created on first use
+  hipEvent_t writer_event = nullptr, reader_event = nullptr;
+  bool reader_pending = false;
 };
 
 #define NORM_TRY(n, expr)                                                   \
@@ -337,6 +336,12 @@ ApplyArgs base_args(FleetNorm* n) {
   return a;
 }
 
+// a kernel on another stream still reads the statistics: stream `s` (or the host) waits for it
+hipError_t wait_reader(FleetNorm* n, hipStream_t s, bool host = false) {
+  n->reader_pending = false;
+  return host ? hipEventSynchronize(n->reader_event) : hipStreamWaitEvent(s, n->reader_event, 0);
+}
+
 hipError_t derive(FleetNorm* n, hipStream_t s) {
   hipLaunchKernelGGL(norm_derive, dim3((n->D + kThreads - 1) / kThreads), dim3(kThreads), 0, s, n->D, n->p.epsilon, n->obs_var,
                      n->obs_sd, n->ret_stat);
@@ -361,12 +366,45 @@ int fleet_norm_check_fit(fleet_norm_handle n, int E, int D, int device, std::str
 
 float* fleet_norm_out_buffer(fleet_norm_handle n) { return n->out_obs; }
 
+hipError_t fleet_norm_begin_read(fleet_norm_handle n, hipStream_t s, FleetNormView* out) {
+  if (n->last_stream != s) {
+    hipError_t e = n->writer_event ? hipSuccess : hipEventCreateWithFlags(&n->writer_event, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(n->writer_event, n->last_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s, n->writer_event, 0);
+    if (e != hipSuccess) return e;
+  }
+  out->obs_mean = n->obs_mean;
+  out->obs_sd = n->obs_sd;
+  out->ret_stat = n->ret_stat;
+  out->clip_obs = n->p.clip_obs;
+  out->clip_reward = n->p.clip_reward;
+  out->norm_obs = n->p.norm_obs != 0;
+  out->norm_reward = n->p.norm_reward != 0;
+  out->E = n->E;
+  out->D = n->D;
+  out->device = n->device;
+  return hipSuccess;
+}
+
+hipError_t fleet_norm_end_read(fleet_norm_handle n, hipStream_t s) {
+  if (n->last_stream == s) return hipSuccess;  // (stream order already puts the next update behind the reader)
+  hipError_t e = n->reader_event ? hipSuccess : hipEventCreateWithFlags(&n->reader_event, hipEventDisableTiming);
+  if (e == hipSuccess && n->reader_pending) e = hipStreamWaitEvent(s, n->reader_event, 0);  // an earlier reader elsewhere: chain
+  if (e == hipSuccess) e = hipEventRecord(n->reader_event, s);
+  if (e == hipSuccess) n->reader_pending = true;
+  return e;
+}
+
 hipError_t fleet_norm_enqueue_reset(fleet_norm_handle n, const float* raw_obs, float* obs, hipStream_t s) {
   if (n->last_stream != s) {  // work of the last call on another stream (the env's, the normaliser's own) uses the same state
     const hipError_t e = hipStreamSynchronize(n->last_stream);
     if (e != hipSuccess) return e;
   }
   n->last_stream = s;
+  if (n->reader_pending) {
+    const hipError_t e = wait_reader(n, s);
+    if (e != hipSuccess) return e;
+  }
   const bool upd = n->p.training && n->p.norm_obs;
   if (upd) {
     const hipError_t e = launch_update(n, raw_obs, true, nullptr, false, s);
@@ -387,6 +425,10 @@ hipError_t fleet_norm_enqueue_step(fleet_norm_handle n, const float* raw_obs, co
     if (e != hipSuccess) return e;
   }
   n->last_stream = s;
+  if (n->reader_pending) {
+    const hipError_t e = wait_reader(n, s);
+    if (e != hipSuccess) return e;
+  }
   if (n->p.training) {
     const hipError_t e = launch_update(n, raw_obs, n->p.norm_obs != 0, raw_reward, true, s);
     if (e != hipSuccess) return e;
@@ -472,8 +514,11 @@ int fleet_norm_destroy(fleet_norm_handle n) {
   (void)hipSetDevice(n->device);
   if (n->last_stream) (void)hipStreamSynchronize(n->last_stream);
   if (n->own_stream) (void)hipStreamSynchronize(n->own_stream);
+  if (n->reader_pending) (void)hipEventSynchronize(n->reader_event);
   if (n->block) (void)hipFree(n->block);
   if (n->own_stream) (void)hipStreamDestroy(n->own_stream);
+  if (n->writer_event) (void)hipEventDestroy(n->writer_event);
+  if (n->reader_event) (void)hipEventDestroy(n->reader_event);
   delete n;
   return FLEET_OK;
 }
@@ -501,6 +546,7 @@ int fleet_norm_configure(fleet_norm_handle n, const FleetNormParams* p) {
   }
   NORM_TRY(n, hipSetDevice(n->device));
   NORM_TRY(n, hipStreamSynchronize(n->last_stream));
+  if (n->reader_pending) NORM_TRY(n, wait_reader(n, nullptr, true));
   n->p = *p;
   NORM_TRY(n, derive(n, n->stream));
   n->last_stream = n->stream;
@@ -568,6 +614,7 @@ int fleet_norm_set_state(fleet_norm_handle n, const double* obs_mean, const doub
   }
   NORM_TRY(n, hipSetDevice(n->device));
   NORM_TRY(n, hipStreamSynchronize(n->last_stream));
+  if (n->reader_pending) NORM_TRY(n, wait_reader(n, nullptr, true));
   if (obs_mean) NORM_TRY(n, hipMemcpy(n->obs_mean, obs_mean, D * 8, hipMemcpyHostToDevice));
   if (obs_var) NORM_TRY(n, hipMemcpy(n->obs_var, obs_var, D * 8, hipMemcpyHostToDevice));
   if (returns) NORM_TRY(n, hipMemcpy(n->returns, returns, E * 8, hipMemcpyHostToDevice));

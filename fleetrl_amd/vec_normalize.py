@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import io
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -31,6 +32,10 @@ try:
     from stable_baselines3.common.vec_env import VecEnvWrapper as _SB3VecEnvWrapper
 except ImportError:  # pragma: no cover - depends on the installation
     _SB3VecEnvWrapper = object
+
+
+# FleetVecNormalize.original_torch()
+OriginalTensors = namedtuple("OriginalTensors", ["obs", "reward", "terminal"])
 
 
 @dataclass
@@ -371,6 +376,16 @@ class FleetVecNormalize(_SB3VecEnvWrapper):
         self.venv.core.clear_start_overrides()
         batch.reset_dev(self._torch[0].data_ptr())
         return self.norm.reset_torch(self._torch[0], out=obs_out)
+
+    def original_torch(self) -> OriginalTensors:
+        """The device twin of get_original_obs / get_original_reward: the wrapper's own raw tensors of the last `step_torch` /
+        `reset_torch` -- obs f32 [E,D], reward f64 [E], terminal f32 [E,D] -- as an off-policy buffer stores them
+        (`DeviceReplayBuffer.add`).  They are views, overwritten by the next step: consume them (or copy them) before it.  After a
+        reset only `obs` is meaningful.  `terminal` is valid only when the step was asked for the terminal rows (`terminal_out`
+        given), and then only in the rows of envs that finished: the other rows are stale."""
+        if self._torch is None:
+            raise FleetHipError(_capi.ERR_STATE, "original_torch: no step_torch / reset_torch yet")
+        return OriginalTensors(*self._torch)
 
     # ---- SB3 VecNormalize helpers (host NumPy, arbitrary arrays) -----------------------------------------------------
     def get_original_obs(self) -> np.ndarray:

@@ -721,6 +721,101 @@ int fleet_rollout_gather_dev(fleet_rollout_handle r, const int32_t* indices, int
  * check) -- the word is cleared, so the next check is clean. */
 int fleet_rollout_check_errors(fleet_rollout_handle r);
 
+/* ---- replay buffer on the device (fleet_replay.hip; DESIGN.md "Replay on the device") ------------------------------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * stable-baselines3 2.3.2 `ReplayBuffer` (optimize_memory_usage = False) in device memory: a ring of R = max(buffer_size / E, 1)
+ * rows of E envs,
+ *   observations f32[R,E,D]  next_observations f32[R,E,D]  actions f32[R,E,A]  rewards f32[R,E]  dones u8[R,E]  timeouts u8[R,E]
+ * in ONE device allocation, each array at a 256-byte-aligned offset (fleet_replay_layout), followed by one 32-bit error word.
+ * The observations and rewards are stored RAW and normalised when a minibatch is sampled, with the normaliser's statistics of that
+ * moment (SB3's _get_samples -> _normalize_obs / _normalize_reward).  Every *_dev call takes device pointers, only enqueues (no
+ * host synchronisation) and runs on the buffer's stream: its own, or the one fleet_replay_set_stream borrowed.  Calls on one buffer
+ * are serialised by the caller.  No atomics.  The host keeps the write position, the `full` flag and the count of drawn minibatches.
+ *   add     row pos <- (obs, done ? terminal : next_obs, action, f32(reward), done != 0, timeout); pos = (pos + 1) % R
+ *   gather  rows (rows[b], envs[b]) of the five sampled arrays, normalised; dones' = f32(done) * (1 - f32(timeout))
+ *   sample  the same at indices drawn on the device: sample b of call c takes one Philox4x32-10 block, key (seed lo, seed hi),
+ *           counter (b, 0, c lo, c hi) -> x0..x3;  row = mulhi64(x0 | x1 << 32, upper), env = mulhi64(x2 | x3 << 32, E),
+ *           upper = full ? R : pos  (a 64-bit multiply-high: bias <= n / 2^64, never equal to n, no rejection loop)
+ *   normalisation (a fleet_norm_handle given): obs' = (float)clip(((double)x - mean[col]) / sd[col], +-clip_obs) when its norm_obs
+ *           is set, r' = (float)clip((double)r / ret_sd, +-clip_reward) when its norm_reward is set: the normaliser's own
+ *           arithmetic, read from its device block when the launch RUNS, behind the normaliser's last enqueued launch */
+typedef struct FleetReplayParams {
+  int32_t struct_bytes;  /* sizeof(FleetReplayParams) */
+  int32_t num_envs;      /* E >= 1 */
+  int32_t buffer_size;   /* transitions, >= 1; R = max(buffer_size / E, 1), R * E < 2^31 */
+  int32_t obs_dim;       /* D >= 1 */
+  int32_t act_dim;       /* A >= 1 */
+  int32_t reserved;      /* 0 */
+  uint64_t seed;         /* Philox key of the index draw */
+} FleetReplayParams;
+#define FLEET_REPLAY_ALIGN 256
+#define FLEET_REPLAY_OBS 0
+#define FLEET_REPLAY_NEXT_OBS 1
+#define FLEET_REPLAY_ACTIONS 2
+#define FLEET_REPLAY_REWARDS 3
+#define FLEET_REPLAY_DONES 4
+#define FLEET_REPLAY_TIMEOUTS 5
+#define FLEET_REPLAY_ARRAYS 6
+typedef struct FleetReplayLayout {
+  int32_t struct_bytes;  /* sizeof(FleetReplayLayout) */
+  int32_t alignment;     /* FLEET_REPLAY_ALIGN */
+  int32_t rows;          /* R */
+  int32_t reserved;
+  uint64_t total_bytes;  /* of the allocation, the error word included */
+  uint64_t offset[FLEET_REPLAY_ARRAYS];     /* of array FLEET_REPLAY_*, a multiple of the alignment */
+  uint64_t bytes[FLEET_REPLAY_ARRAYS];      /* R * E * (D | A | 1) * (4 | 1) */
+  uint64_t row_bytes[FLEET_REPLAY_ARRAYS];  /* of one ring row: bytes / R */
+  uint64_t error_offset; /* of the 32-bit error word */
+} FleetReplayLayout;
+typedef struct FleetReplayArrays {  /* base addresses (row 0) of the six arrays, device memory */
+  float* observations;
+  float* next_observations;
+  float* actions;
+  float* rewards;
+  uint8_t* dones;
+  uint8_t* timeouts;
+} FleetReplayArrays;
+typedef struct FleetReplay* fleet_replay_handle;
+
+/* No device needed.  FLEET_ERR_INVALID (fleet_replay_last_error(NULL) says why) for parameters fleet_replay_create refuses. */
+int fleet_replay_layout(const FleetReplayParams* p, FleetReplayLayout* out);
+/* The parameters are validated BEFORE the device is touched: FLEET_ERR_INVALID for E, buffer_size, D or A < 1, R * E >= 2^31, a
+ * wrong struct_bytes, a null pointer.  Then: one allocation, zero-filled (a failure names its byte count). */
+int fleet_replay_create(int device, const FleetReplayParams* p, fleet_replay_handle* out);
+int fleet_replay_destroy(fleet_replay_handle r);
+const char* fleet_replay_last_error(fleet_replay_handle r);  /* r may be NULL: error of the last failed create / layout */
+/* launch on an external hipStream_t (borrowed; NULL = the null stream) from now on instead of the buffer's own stream; waits for
+ * what the previous stream still holds of this buffer's work */
+int fleet_replay_set_stream(fleet_replay_handle r, void* hip_stream);
+int fleet_replay_arrays(fleet_replay_handle r, FleetReplayArrays* out);
+/* One launch: ring row pos <- the step's tensors (device memory), then pos advances and wraps.  obs, next_obs f32[E,D], action
+ * f32[E,A], reward f64[E] (reward_dtype = FLEET_ACT_F64) or f32[E] (FLEET_ACT_F32), rounded ONCE to float32, done u8[E].
+ * terminal f32[E,D] or NULL: next_observations[pos,e] = done[e] ? terminal[e] : next_obs[e]; terminal rows of envs that are not
+ * done are never read.  timeout u8[E] or NULL (zeros are stored).  Rows move as 16-byte words when D (A) is a multiple of 4 and the
+ * source is 16-byte aligned, as single floats otherwise.  The sources are copied, never adopted in place: in a ring a row written
+ * in place would corrupt the oldest transition until the next add. */
+int fleet_replay_add_dev(fleet_replay_handle r, const float* obs, const float* next_obs, const float* action, const void* reward,
+                         int reward_dtype, const uint8_t* done, const float* terminal, const uint8_t* timeout);
+/* One launch, explicit indices: sample b <- transition (rows[b], envs[b]), both i32[batch] in device memory (SB3's _get_samples with
+ * given env_indices; the hook for prioritised replay).  Outputs (any may be NULL): out_obs, out_next_obs f32[batch,D] and
+ * out_rewards f32[batch] normalised as above when `norm` is not NULL (its obs_dim must be D, else FLEET_ERR_INVALID), out_actions
+ * f32[batch,A], out_dones f32[batch] = f32(done) * (1 - f32(timeout)).  A pair outside [0, upper) x [0, E), upper = full ? R : pos,
+ * writes nothing for its sample and sets the buffer's error word (fleet_replay_check_errors). */
+int fleet_replay_gather_dev(fleet_replay_handle r, const int32_t* rows, const int32_t* envs, int batch, fleet_norm_handle norm,
+                            float* out_obs, float* out_actions, float* out_next_obs, float* out_dones, float* out_rewards);
+/* One launch, drawn indices (above); the handle's call counter is used and then incremented: the same seed and the same sequence
+ * of calls give the same minibatches, on any stream.  out_rows / out_envs i32[batch] (or NULL) receive what was drawn.
+ * FLEET_ERR_STATE, before any launch, for an empty buffer. */
+int fleet_replay_sample_dev(fleet_replay_handle r, int batch, fleet_norm_handle norm, float* out_obs, float* out_actions,
+                            float* out_next_obs, float* out_dones, float* out_rewards, int32_t* out_rows, int32_t* out_envs);
+/* Waits for the stream, reads the error word back: FLEET_OK, or FLEET_ERR_STATE (a gather met an index out of range since the last
+ * check) -- the word is cleared, so the next check is clean. */
+int fleet_replay_check_errors(fleet_replay_handle r);
+/* host bookkeeping (any output may be NULL): the next row to be written, whether the ring has wrapped, R, minibatches drawn so far */
+int fleet_replay_size(fleet_replay_handle r, int32_t* pos, int32_t* full, int32_t* rows, uint64_t* calls);
+/* what a caller needs to resume (the arrays themselves are the caller's to fill): 0 <= pos < R, full 0 / 1, the call counter */
+int fleet_replay_set_position(fleet_replay_handle r, int32_t pos, int32_t full, uint64_t calls);
+
 #ifdef __cplusplus
 }
 #endif
