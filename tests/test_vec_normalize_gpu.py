@@ -4,7 +4,7 @@ import contextlib
 import numpy as np
 import pytest
 
-from vecnorm_model import VecNormModel
+from vecnorm_model import VecNormModel, check_stats, close_f32
 
 pytestmark = pytest.mark.gpu
 
@@ -74,25 +74,6 @@ def test_apply_is_bit_exact(E, D, in_place):
     with pytest.raises(Exception) if in_place else contextlib.nullcontext():
         norm.original(obs=True, reward=False)
     norm.close()
-
-
-def check_stats(norm, model, tag):
-    st = norm.get_state()
-    m, v = model.obs_rms.mean, model.obs_rms.var
-    assert np.all(np.abs(st.obs_rms.mean - m) <= 1e-12 * (np.abs(m) + np.sqrt(v))), tag
-    ok = (np.abs(st.obs_rms.var - v) <= 1e-10 * v) | (np.abs(st.obs_rms.var - v) <= 1e-14 * (1 + m * m))
-    assert ok.all(), (tag, np.max(np.abs(st.obs_rms.var - v) / np.maximum(v, 1e-300)))
-    rm, rv = float(model.ret_rms.mean), float(model.ret_rms.var)
-    assert abs(float(st.ret_rms.mean) - rm) <= 1e-12 * (abs(rm) + np.sqrt(rv)), tag
-    assert abs(float(st.ret_rms.var) - rv) <= max(1e-10 * rv, 1e-14 * (1 + rm * rm)), tag
-    assert st.obs_rms.count == model.obs_rms.count and st.ret_rms.count == model.ret_rms.count, tag
-    assert np.array_equal(st.returns.view(np.uint64), model.returns.view(np.uint64)), tag
-
-
-def close_f32(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    ulps = np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
-    return bool(np.all((ulps <= 2) | (np.abs(a - b) <= 1e-6)))
 
 
 @pytest.mark.parametrize("E,D", [(4096, 388), (4096, 1407), (8192, 388), (8192, 1407)])
