@@ -345,7 +345,6 @@ def load_library():
     lib.fleet_norm_create.argtypes = [C.c_int, C.POINTER(FleetNormParams), C.POINTER(vp)]
     lib.fleet_norm_destroy.argtypes = [vp]
     lib.fleet_norm_last_error.argtypes = [vp]
-    lib.fleet_norm_last_error.restype = C.c_char_p
     lib.fleet_norm_set_stream.argtypes = [vp, vp]
     lib.fleet_norm_configure.argtypes = [vp, C.POINTER(FleetNormParams)]
     lib.fleet_norm_reset_dev.argtypes = [vp, f32p, f32p]
@@ -355,15 +354,11 @@ def load_library():
     lib.fleet_norm_original_host.argtypes = [vp, vp, vp]
     lib.fleet_reset_host_norm.argtypes = [vp, vp, f32p]
     lib.fleet_step_host_norm.argtypes = [vp, vp, vp, C.c_int, f32p, f64p, u8p, f32p]
-    for name in NORM_SYMBOLS:
-        if name != "fleet_norm_last_error":
-            getattr(lib, name).restype = C.c_int
     # the rollout buffer (fleet_rollout.hip)
     lib.fleet_rollout_layout.argtypes = [C.POINTER(FleetRolloutParams), C.POINTER(FleetRolloutLayout)]
     lib.fleet_rollout_create.argtypes = [C.c_int, C.POINTER(FleetRolloutParams), C.POINTER(vp)]
     lib.fleet_rollout_destroy.argtypes = [vp]
     lib.fleet_rollout_last_error.argtypes = [vp]
-    lib.fleet_rollout_last_error.restype = C.c_char_p
     lib.fleet_rollout_set_stream.argtypes = [vp, vp]
     lib.fleet_rollout_arrays.argtypes = [vp, C.POINTER(FleetRolloutArrays)]
     lib.fleet_rollout_slot.argtypes = [vp, C.c_int, C.POINTER(FleetRolloutSlot)]
@@ -371,15 +366,11 @@ def load_library():
     lib.fleet_rollout_finish_dev.argtypes = [vp, f32p, u8p]
     lib.fleet_rollout_gather_dev.argtypes = [vp, vp, C.c_int, f32p, f32p, f32p, f32p, f32p, f32p]
     lib.fleet_rollout_check_errors.argtypes = [vp]
-    for name in ROLLOUT_SYMBOLS:
-        if name != "fleet_rollout_last_error":
-            getattr(lib, name).restype = C.c_int
     # the replay buffer (fleet_replay.hip)
     lib.fleet_replay_layout.argtypes = [C.POINTER(FleetReplayParams), C.POINTER(FleetReplayLayout)]
     lib.fleet_replay_create.argtypes = [C.c_int, C.POINTER(FleetReplayParams), C.POINTER(vp)]
     lib.fleet_replay_destroy.argtypes = [vp]
     lib.fleet_replay_last_error.argtypes = [vp]
-    lib.fleet_replay_last_error.restype = C.c_char_p
     lib.fleet_replay_set_stream.argtypes = [vp, vp]
     lib.fleet_replay_arrays.argtypes = [vp, C.POINTER(FleetReplayArrays)]
     lib.fleet_replay_add_dev.argtypes = [vp, f32p, f32p, f32p, vp, C.c_int, u8p, f32p, u8p]
@@ -388,9 +379,9 @@ def load_library():
     lib.fleet_replay_check_errors.argtypes = [vp]
     lib.fleet_replay_size.argtypes = [vp, i32p, i32p, i32p, C.POINTER(C.c_uint64)]
     lib.fleet_replay_set_position.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint64]
-    for name in REPLAY_SYMBOLS:
-        if name != "fleet_replay_last_error":
-            getattr(lib, name).restype = C.c_int
+    for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS)):
+        for name in names:
+            getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
                  "fleet_log_capacity", "fleet_log_read",
                  "fleet_log_clear", "fleet_synchronize", "fleet_set_start_schedule",
@@ -456,28 +447,27 @@ def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, 
     return name.value.decode(), int(grid.value)
 
 
+def _layout(prefix: str, params, out):
+    """fleet_<prefix>_layout of `params` into `out`."""
+    lib = load_library()
+    rc = getattr(lib, f"fleet_{prefix}_layout")(C.byref(params), C.byref(out))
+    if rc != OK:
+        raise FleetHipError(rc, getattr(lib, f"fleet_{prefix}_last_error")(None).decode())
+    return out
+
+
 def rollout_layout(num_envs: int, n_steps: int, obs_dim: int, act_dim: int, gamma: float = 0.99,
                    gae_lambda: float = 0.95) -> FleetRolloutLayout:
     """fleet_rollout_layout: bytes and offsets of the rollout buffer's arrays (needs the library, no GPU)."""
     p = FleetRolloutParams(C.sizeof(FleetRolloutParams), int(num_envs), int(n_steps), int(obs_dim), int(act_dim), 0, float(gamma),
                            float(gae_lambda))
-    out = FleetRolloutLayout()
-    lib = load_library()
-    rc = lib.fleet_rollout_layout(C.byref(p), C.byref(out))
-    if rc != OK:
-        raise FleetHipError(rc, lib.fleet_rollout_last_error(None).decode())
-    return out
+    return _layout("rollout", p, FleetRolloutLayout())
 
 
 def replay_layout(buffer_size: int, num_envs: int, obs_dim: int, act_dim: int) -> FleetReplayLayout:
     """fleet_replay_layout: rows, bytes and offsets of the replay buffer's arrays (needs the library, no GPU)."""
     p = FleetReplayParams(C.sizeof(FleetReplayParams), int(num_envs), int(buffer_size), int(obs_dim), int(act_dim), 0, 0)
-    out = FleetReplayLayout()
-    lib = load_library()
-    rc = lib.fleet_replay_layout(C.byref(p), C.byref(out))
-    if rc != OK:
-        raise FleetHipError(rc, lib.fleet_replay_last_error(None).decode())
-    return out
+    return _layout("replay", p, FleetReplayLayout())
 
 
 def state_layout(params: FleetParams) -> FleetStateLayout:

@@ -1,0 +1,90 @@
+"""What `DeviceNormalizer`, `DeviceRolloutBuffer` and `DeviceReplayBuffer` share: one handle of the C ABI behind a family of entries
+`fleet_<prefix>_*` (create, destroy, last_error, set_stream), its errors as exceptions, its stream, its end -- the Python side of
+fleetrl_amd/csrc/fleet_handle.h."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import FleetHipError
+
+
+class _DeviceArray:
+    """A view of device memory somebody else owns, for torch.as_tensor (the CUDA array interface)."""
+
+    def __init__(self, ptr: int, shape: tuple, typestr: str, owner):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2,
+                                         "strides": None}
+        self._owner = owner  # the tensor made from this object keeps it, and with it the buffer, alive
+
+
+class _DeviceHandle:
+    _prefix = ""  # "rollout": the entries are fleet_rollout_*
+    _tensors = None  # the buffers' zero-copy views, made on first use
+
+    def _entry(self, name: str):
+        return getattr(self.lib, f"fleet_{self._prefix}_{name}")
+
+    def _open(self, device: int, params):
+        """fleet_<prefix>_create on `device` with the family's parameter struct."""
+        self.lib = _capi.load_library()
+        self.device = int(device)
+        h = C.c_void_p()
+        rc = self._entry("create")(self.device, C.byref(params), C.byref(h))
+        if rc != _capi.OK:
+            raise FleetHipError(rc, self._entry("last_error")(None).decode())
+        self.h = h
+        self._stream = None
+
+    def _check(self, rc: int):
+        if rc != _capi.OK:
+            raise FleetHipError(rc, self._entry("last_error")(self.h).decode())
+
+    def set_stream(self, hip_stream: int | None):
+        self._check(self._entry("set_stream")(self.h, hip_stream))
+        self._stream = hip_stream
+
+    def use_torch_stream(self, device=None):
+        """Launch on torch's current stream of `device` (default: the handle's own) from now on (no-op if already there)."""
+        import torch
+
+        cur = torch.cuda.current_stream(device if device is not None else self.device).cuda_stream
+        if cur != self._stream:
+            self.set_stream(cur)
+
+    def _make_views(self, spec: dict) -> dict:
+        """name -> zero-copy tensor over the address `arrays_dev()` gives for it; spec: name -> (shape, typestr)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        ptrs = self.arrays_dev()
+        return {n: torch.as_tensor(_DeviceArray(ptrs[n], shape, typestr, self), device=dev) for n, (shape, typestr) in spec.items()}
+
+    def _tensor(self, t, shape, dtypes):
+        import torch
+
+        if isinstance(t, np.ndarray) or not isinstance(t, torch.Tensor):  # convenience, not the fast path
+            t = torch.as_tensor(np.ascontiguousarray(t)).to(torch.device("cuda", self.device))
+            if t.dtype not in dtypes:
+                t = t.to(dtypes[0])
+        if t.dtype == torch.bool and torch.uint8 in dtypes:
+            t = t.view(torch.uint8)
+        if t.device.type != "cuda" or t.device.index != self.device or t.dtype not in dtypes or t.numel() != int(np.prod(shape)) or \
+                not t.is_contiguous():
+            raise ValueError(f"expected a contiguous tensor of {int(np.prod(shape))} elements {shape}, dtype in {dtypes}, on "
+                             f"cuda:{self.device}; got {tuple(t.shape)} {t.dtype} on {t.device}")
+        return t
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._tensors = None
+            self._entry("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass

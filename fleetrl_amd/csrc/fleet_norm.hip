@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "fleet_handle.h"
 #include "fleet_norm.h"
 
 namespace {
@@ -255,19 +256,14 @@ const char* validate(const FleetNormParams* p) {
   return nullptr;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
-struct FleetNorm {
+// block: everything the pointers below name (no error word)
+struct FleetNorm : FleetHandleBase {
   FleetNormParams p{};
-  int device = 0;
   int E = 0, D = 0, tiles = 0, slabs = 0;
-  hipStream_t stream = nullptr, own_stream = nullptr;
   hipStream_t last_stream = nullptr;  // where the last enqueue went (state access waits for it)
-  std::string error;
   double obs_count = 1e-4, ret_count = 1e-4;
-  void* block = nullptr;  // one device allocation for everything below
   double *obs_mean = nullptr, *obs_var = nullptr, *obs_sd = nullptr, *ret_stat = nullptr, *returns = nullptr, *raw_reward = nullptr;
   double *part_obs = nullptr, *part_ret = nullptr;
   float* out_obs = nullptr;
@@ -278,22 +274,12 @@ struct FleetNorm {
   bool reader_pending = false;
 };
 
-#define NORM_TRY(n, expr)                                                   \
-  do {                                                                      \
-    hipError_t _e = (expr);                                                 \
-    if (_e != hipSuccess) {                                                 \
-      (n)->error = std::string(#expr) + ": " + hipGetErrorString(_e);       \
-      return FLEET_ERR_HIP;                                                 \
-    }                                                                       \
-  } while (0)
-
 namespace {
 
 hipError_t launch_apply(FleetNorm* n, const ApplyArgs& a, hipStream_t s) {
   const bool vec = a.D % 4 == 0 && aligned16(a.raw) && aligned16(a.out) && (!a.raw_term || (aligned16(a.raw_term) && aligned16(a.term)));
   const size_t items = (size_t)a.E * a.D / (vec ? 4 : 1);
-  const size_t want = (items > (size_t)a.E ? items : (size_t)a.E) + kThreads - 1;
-  const unsigned blocks = (unsigned)(want / kThreads < (size_t)kApplyMaxBlocks ? want / kThreads : (size_t)kApplyMaxBlocks);
+  const unsigned blocks = grid_for(items > (size_t)a.E ? items : (size_t)a.E, kThreads, kApplyMaxBlocks);
   if (vec) hipLaunchKernelGGL(norm_apply<true>, dim3(blocks), dim3(kThreads), 0, s, a);
   else hipLaunchKernelGGL(norm_apply<false>, dim3(blocks), dim3(kThreads), 0, s, a);
   (void)n;
@@ -451,45 +437,28 @@ extern "C" {
 
 int fleet_norm_create(int device, const FleetNormParams* p, fleet_norm_handle* out) {
   if (out) *out = nullptr;
-  if (const char* why = validate(p)) {
+  const char* why = validate(p);  // before the device is touched
+  if (!why && !out) why = "null output handle";
+  if (why) {
     g_norm_create_error = why;
-    return FLEET_ERR_INVALID;
-  }
-  if (!out) {
-    g_norm_create_error = "null output handle";
-    return FLEET_ERR_INVALID;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    g_norm_create_error = "no HIP device";
-    return FLEET_ERR_NODEVICE;
-  }
-  if (device < 0 || device >= ndev) {
-    g_norm_create_error = "device index out of range";
     return FLEET_ERR_INVALID;
   }
   FleetNorm* n = new FleetNorm();
   n->p = *p;
-  n->device = device;
   n->E = p->num_envs;
   n->D = p->obs_dim;
   n->tiles = (n->D + 63) / 64;
   n->slabs = (n->E + kRows - 1) / kRows;
-  auto fail = [&](const std::string& msg) {
-    g_norm_create_error = msg;
-    fleet_norm_destroy(n);
-    return FLEET_ERR_HIP;
-  };
-  if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice failed");
-  if (hipStreamCreateWithFlags(&n->own_stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
-  n->stream = n->last_stream = n->own_stream;
   const size_t E = n->E, D = n->D, S = n->slabs;
   // doubles: obs mean / var / sd [D], ret_stat [4], returns [E], raw rewards [E], partials [S,2,D] + [S,2]; then the floats
   const size_t nd = 3 * D + 4 + 2 * E + 2 * S * D + 2 * S;
-  const size_t bytes = nd * 8 + E * D * 4;
-  if (hipMalloc(&n->block, bytes) != hipSuccess) return fail("hipMalloc of the normaliser's " + std::to_string(bytes) + " bytes failed");
-  double* q = static_cast<double*>(n->block);
+  const int rc = handle_open(n, device, nd * 8 + E * D * 4, "normaliser", &g_norm_create_error);
+  if (rc != FLEET_OK) {
+    fleet_norm_destroy(n);
+    return rc;
+  }
+  n->last_stream = n->own_stream;
+  double* q = reinterpret_cast<double*>(n->block);
   n->obs_mean = q, q += D;
   n->obs_var = q, q += D;
   n->obs_sd = q, q += D;
@@ -503,8 +472,11 @@ int fleet_norm_create(int device, const FleetNormParams* p, fleet_norm_handle* o
   for (size_t c = 0; c < D; ++c) init[D + c] = 1.0;  // var = 1
   init[3 * D + 1] = 1.0;                             // ret var = 1
   if (hipMemcpy(n->block, init.data(), init.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      derive(n, n->own_stream) != hipSuccess || hipStreamSynchronize(n->own_stream) != hipSuccess)
-    return fail("initialising the normaliser's state failed");
+      derive(n, n->own_stream) != hipSuccess || hipStreamSynchronize(n->own_stream) != hipSuccess) {
+    g_norm_create_error = "initialising the normaliser's state failed";
+    fleet_norm_destroy(n);
+    return FLEET_ERR_HIP;
+  }
   *out = n;
   return FLEET_OK;
 }
@@ -513,10 +485,8 @@ int fleet_norm_destroy(fleet_norm_handle n) {
   if (!n) return FLEET_OK;
   (void)hipSetDevice(n->device);
   if (n->last_stream) (void)hipStreamSynchronize(n->last_stream);
-  if (n->own_stream) (void)hipStreamSynchronize(n->own_stream);
   if (n->reader_pending) (void)hipEventSynchronize(n->reader_event);
-  if (n->block) (void)hipFree(n->block);
-  if (n->own_stream) (void)hipStreamDestroy(n->own_stream);
+  handle_close(n);
   if (n->writer_event) (void)hipEventDestroy(n->writer_event);
   if (n->reader_event) (void)hipEventDestroy(n->reader_event);
   delete n;
@@ -527,8 +497,8 @@ const char* fleet_norm_last_error(fleet_norm_handle n) { return n ? n->error.c_s
 
 int fleet_norm_set_stream(fleet_norm_handle n, void* hip_stream) {
   if (!n) return FLEET_ERR_INVALID;
-  NORM_TRY(n, hipSetDevice(n->device));
-  NORM_TRY(n, hipStreamSynchronize(n->last_stream));
+  FLEET_HANDLE_TRY(n, hipSetDevice(n->device));
+  FLEET_HANDLE_TRY(n, hipStreamSynchronize(n->last_stream));
   n->stream = static_cast<hipStream_t>(hip_stream);  // (NULL is the null stream: torch's default stream has that handle)
   n->last_stream = n->stream;
   return FLEET_OK;
@@ -544,11 +514,11 @@ int fleet_norm_configure(fleet_norm_handle n, const FleetNormParams* p) {
     n->error = "fleet_norm_configure: num_envs and obs_dim are fixed at creation";
     return FLEET_ERR_INVALID;
   }
-  NORM_TRY(n, hipSetDevice(n->device));
-  NORM_TRY(n, hipStreamSynchronize(n->last_stream));
-  if (n->reader_pending) NORM_TRY(n, wait_reader(n, nullptr, true));
+  FLEET_HANDLE_TRY(n, hipSetDevice(n->device));
+  FLEET_HANDLE_TRY(n, hipStreamSynchronize(n->last_stream));
+  if (n->reader_pending) FLEET_HANDLE_TRY(n, wait_reader(n, nullptr, true));
   n->p = *p;
-  NORM_TRY(n, derive(n, n->stream));
+  FLEET_HANDLE_TRY(n, derive(n, n->stream));
   n->last_stream = n->stream;
   return FLEET_OK;
 }
@@ -559,8 +529,8 @@ int fleet_norm_reset_dev(fleet_norm_handle n, const float* raw_obs, float* obs) 
     n->error = "fleet_norm_reset_dev: null buffer";
     return FLEET_ERR_INVALID;
   }
-  NORM_TRY(n, hipSetDevice(n->device));
-  NORM_TRY(n, fleet_norm_enqueue_reset(n, raw_obs, obs, n->stream));
+  FLEET_HANDLE_TRY(n, hipSetDevice(n->device));
+  FLEET_HANDLE_TRY(n, fleet_norm_enqueue_reset(n, raw_obs, obs, n->stream));
   return FLEET_OK;
 }
 
@@ -571,22 +541,22 @@ int fleet_norm_step_dev(fleet_norm_handle n, const float* raw_obs, const double*
     n->error = "fleet_norm_step_dev: null buffer";
     return FLEET_ERR_INVALID;
   }
-  NORM_TRY(n, hipSetDevice(n->device));
-  NORM_TRY(n, fleet_norm_enqueue_step(n, raw_obs, raw_reward, done, raw_terminal, obs, reward, terminal, n->stream));
+  FLEET_HANDLE_TRY(n, hipSetDevice(n->device));
+  FLEET_HANDLE_TRY(n, fleet_norm_enqueue_step(n, raw_obs, raw_reward, done, raw_terminal, obs, reward, terminal, n->stream));
   return FLEET_OK;
 }
 
 int fleet_norm_get_state(fleet_norm_handle n, double* obs_mean, double* obs_var, double* obs_count, double* ret_mean,
                          double* ret_var, double* ret_count, double* returns) {
   if (!n) return FLEET_ERR_INVALID;
-  NORM_TRY(n, hipSetDevice(n->device));
-  NORM_TRY(n, hipStreamSynchronize(n->last_stream));
+  FLEET_HANDLE_TRY(n, hipSetDevice(n->device));
+  FLEET_HANDLE_TRY(n, hipStreamSynchronize(n->last_stream));
   const size_t D = n->D, E = n->E;
-  if (obs_mean) NORM_TRY(n, hipMemcpy(obs_mean, n->obs_mean, D * 8, hipMemcpyDeviceToHost));
-  if (obs_var) NORM_TRY(n, hipMemcpy(obs_var, n->obs_var, D * 8, hipMemcpyDeviceToHost));
-  if (returns) NORM_TRY(n, hipMemcpy(returns, n->returns, E * 8, hipMemcpyDeviceToHost));
+  if (obs_mean) FLEET_HANDLE_TRY(n, hipMemcpy(obs_mean, n->obs_mean, D * 8, hipMemcpyDeviceToHost));
+  if (obs_var) FLEET_HANDLE_TRY(n, hipMemcpy(obs_var, n->obs_var, D * 8, hipMemcpyDeviceToHost));
+  if (returns) FLEET_HANDLE_TRY(n, hipMemcpy(returns, n->returns, E * 8, hipMemcpyDeviceToHost));
   double rs[4];
-  NORM_TRY(n, hipMemcpy(rs, n->ret_stat, sizeof rs, hipMemcpyDeviceToHost));
+  FLEET_HANDLE_TRY(n, hipMemcpy(rs, n->ret_stat, sizeof rs, hipMemcpyDeviceToHost));
   if (ret_mean) *ret_mean = rs[0];
   if (ret_var) *ret_var = rs[1];
   if (obs_count) *obs_count = n->obs_count;
@@ -612,18 +582,18 @@ int fleet_norm_set_state(fleet_norm_handle n, const double* obs_mean, const doub
     n->error = "fleet_norm_set_state: variances must be >= 0";
     return FLEET_ERR_INVALID;
   }
-  NORM_TRY(n, hipSetDevice(n->device));
-  NORM_TRY(n, hipStreamSynchronize(n->last_stream));
-  if (n->reader_pending) NORM_TRY(n, wait_reader(n, nullptr, true));
-  if (obs_mean) NORM_TRY(n, hipMemcpy(n->obs_mean, obs_mean, D * 8, hipMemcpyHostToDevice));
-  if (obs_var) NORM_TRY(n, hipMemcpy(n->obs_var, obs_var, D * 8, hipMemcpyHostToDevice));
-  if (returns) NORM_TRY(n, hipMemcpy(n->returns, returns, E * 8, hipMemcpyHostToDevice));
-  if (ret_mean) NORM_TRY(n, hipMemcpy(n->ret_stat + 0, ret_mean, 8, hipMemcpyHostToDevice));
-  if (ret_var) NORM_TRY(n, hipMemcpy(n->ret_stat + 1, ret_var, 8, hipMemcpyHostToDevice));
+  FLEET_HANDLE_TRY(n, hipSetDevice(n->device));
+  FLEET_HANDLE_TRY(n, hipStreamSynchronize(n->last_stream));
+  if (n->reader_pending) FLEET_HANDLE_TRY(n, wait_reader(n, nullptr, true));
+  if (obs_mean) FLEET_HANDLE_TRY(n, hipMemcpy(n->obs_mean, obs_mean, D * 8, hipMemcpyHostToDevice));
+  if (obs_var) FLEET_HANDLE_TRY(n, hipMemcpy(n->obs_var, obs_var, D * 8, hipMemcpyHostToDevice));
+  if (returns) FLEET_HANDLE_TRY(n, hipMemcpy(n->returns, returns, E * 8, hipMemcpyHostToDevice));
+  if (ret_mean) FLEET_HANDLE_TRY(n, hipMemcpy(n->ret_stat + 0, ret_mean, 8, hipMemcpyHostToDevice));
+  if (ret_var) FLEET_HANDLE_TRY(n, hipMemcpy(n->ret_stat + 1, ret_var, 8, hipMemcpyHostToDevice));
   if (obs_count) n->obs_count = *obs_count;
   if (ret_count) n->ret_count = *ret_count;
-  NORM_TRY(n, derive(n, n->stream));
-  NORM_TRY(n, hipStreamSynchronize(n->stream));
+  FLEET_HANDLE_TRY(n, derive(n, n->stream));
+  FLEET_HANDLE_TRY(n, hipStreamSynchronize(n->stream));
   n->last_stream = n->stream;
   return FLEET_OK;
 }
@@ -638,10 +608,10 @@ int fleet_norm_original_host(fleet_norm_handle n, float* obs, double* reward) {
     n->error = "fleet_norm_original_host: no raw rewards (no step yet)";
     return FLEET_ERR_STATE;
   }
-  NORM_TRY(n, hipSetDevice(n->device));
-  NORM_TRY(n, hipStreamSynchronize(n->last_stream));
-  if (obs) NORM_TRY(n, hipMemcpy(obs, n->last_raw_obs, (size_t)n->E * n->D * 4, hipMemcpyDeviceToHost));
-  if (reward) NORM_TRY(n, hipMemcpy(reward, n->raw_reward, (size_t)n->E * 8, hipMemcpyDeviceToHost));
+  FLEET_HANDLE_TRY(n, hipSetDevice(n->device));
+  FLEET_HANDLE_TRY(n, hipStreamSynchronize(n->last_stream));
+  if (obs) FLEET_HANDLE_TRY(n, hipMemcpy(obs, n->last_raw_obs, (size_t)n->E * n->D * 4, hipMemcpyDeviceToHost));
+  if (reward) FLEET_HANDLE_TRY(n, hipMemcpy(reward, n->raw_reward, (size_t)n->E * 8, hipMemcpyDeviceToHost));
   return FLEET_OK;
 }
 

@@ -17,6 +17,7 @@
 
 #include <string>
 
+#include "fleet_handle.h"
 #include "fleet_norm.h"
 #include "fleet_replay.h"
 
@@ -192,53 +193,19 @@ void layout_of(const FleetReplayParams* p, FleetReplayLayout* L) {
   L->struct_bytes = (int32_t)sizeof(FleetReplayLayout);
   L->alignment = FLEET_REPLAY_ALIGN;
   L->rows = (int32_t)R;
-  uint64_t off = 0;
-  for (int i = 0; i < FLEET_REPLAY_ARRAYS; ++i) {
-    L->offset[i] = off;
-    L->row_bytes[i] = row[i];
-    L->bytes[i] = row[i] * R;
-    off = (off + L->bytes[i] + FLEET_REPLAY_ALIGN - 1) / FLEET_REPLAY_ALIGN * FLEET_REPLAY_ALIGN;
-  }
-  L->error_offset = off;
-  L->total_bytes = off + FLEET_REPLAY_ALIGN;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-unsigned blocks_for(size_t wave_items) {
-  const size_t want = (wave_items + kReplayWaves - 1) / kReplayWaves;
-  return (unsigned)(want < 1 ? 1 : (want < (size_t)kReplayMaxBlocks ? want : (size_t)kReplayMaxBlocks));
+  handle_layout(row, FLEET_REPLAY_ARRAYS, R, FLEET_REPLAY_ALIGN, L->offset, L->bytes, L->row_bytes, &L->error_offset, &L->total_bytes);
 }
 
 }  // namespace
 
-struct FleetReplay {
+// block: the six arrays, then the error word
+struct FleetReplay : FleetBufferBase<FleetReplayLayout> {
   FleetReplayParams p{};
-  FleetReplayLayout L{};
-  int device = 0;
   int E = 0, R = 0, D = 0, A = 0;
   int pos = 0;
   bool full = false;
   uint64_t calls = 0;  // minibatches drawn so far: the high half of the Philox counter
-  hipStream_t stream = nullptr, own_stream = nullptr;
-  std::string error;
-  char* block = nullptr;  // one device allocation: the six arrays, then the error word
-  uint32_t* err = nullptr;
-
-  template <typename T>
-  T* array(int which, int row = 0) const {
-    return reinterpret_cast<T*>(block + L.offset[which] + (uint64_t)row * L.row_bytes[which]);
-  }
 };
-
-#define REPLAY_TRY(r, expr)                                               \
-  do {                                                                    \
-    hipError_t _e = (expr);                                               \
-    if (_e != hipSuccess) {                                               \
-      (r)->error = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-      return FLEET_ERR_HIP;                                               \
-    }                                                                     \
-  } while (0)
 
 namespace {
 
@@ -259,11 +226,11 @@ int launch_sample(FleetReplay* r, const char* who, const int32_t* rows, const in
   // (the buffer's rows start at multiples of 16 bytes when D % 4 == 0: the arrays are 256-byte aligned)
   a.obs_vec = r->D % 4 == 0 && aligned16(out_obs) && aligned16(out_next_obs);
   a.act_vec = r->A % 4 == 0 && aligned16(out_actions);
-  REPLAY_TRY(r, hipSetDevice(r->device));
+  FLEET_HANDLE_TRY(r, hipSetDevice(r->device));
   bool norm_obs = false;
   if (norm) {
     FleetNormView v{};
-    REPLAY_TRY(r, fleet_norm_begin_read(norm, r->stream, &v));
+    FLEET_HANDLE_TRY(r, fleet_norm_begin_read(norm, r->stream, &v));
     if (v.D != r->D || v.device != r->device) {
       r->error = std::string(who) + ": the normaliser has obs_dim " + std::to_string(v.D) + " on device " + std::to_string(v.device) +
                  ", the buffer " + std::to_string(r->D) + " on device " + std::to_string(r->device);
@@ -276,12 +243,12 @@ int launch_sample(FleetReplay* r, const char* who, const int32_t* rows, const in
   }
   const size_t lds = norm_obs ? (size_t)r->D * 16 : 0;
   const bool use_lds = lds > 0 && lds <= kReplayLdsBytes;
-  const dim3 grid(blocks_for((size_t)batch)), block(kReplayThreads);
+  const dim3 grid(grid_for((size_t)batch, kReplayWaves, kReplayMaxBlocks)), block(kReplayThreads);
   if (!norm_obs) hipLaunchKernelGGL((replay_sample<false, false>), grid, block, 0, r->stream, a);
   else if (use_lds) hipLaunchKernelGGL((replay_sample<true, true>), grid, block, lds, r->stream, a);
   else hipLaunchKernelGGL((replay_sample<true, false>), grid, block, 0, r->stream, a);
-  REPLAY_TRY(r, hipGetLastError());
-  if (norm) REPLAY_TRY(r, fleet_norm_end_read(norm, r->stream));
+  FLEET_HANDLE_TRY(r, hipGetLastError());
+  if (norm) FLEET_HANDLE_TRY(r, fleet_norm_end_read(norm, r->stream));
   return FLEET_OK;
 }
 
@@ -290,12 +257,10 @@ int launch_sample(FleetReplay* r, const char* who, const int32_t* rows, const in
 extern "C" {
 
 int fleet_replay_layout(const FleetReplayParams* p, FleetReplayLayout* out) {
-  if (const char* why = validate(p)) {
+  const char* why = validate(p);
+  if (!why && !out) why = "null FleetReplayLayout";
+  if (why) {
     g_replay_create_error = why;
-    return FLEET_ERR_INVALID;
-  }
-  if (!out) {
-    g_replay_create_error = "null FleetReplayLayout";
     return FLEET_ERR_INVALID;
   }
   layout_of(p, out);
@@ -304,70 +269,35 @@ int fleet_replay_layout(const FleetReplayParams* p, FleetReplayLayout* out) {
 
 int fleet_replay_create(int device, const FleetReplayParams* p, fleet_replay_handle* out) {
   if (out) *out = nullptr;
-  if (const char* why = validate(p)) {  // before the device is touched
+  const char* why = validate(p);  // before the device is touched
+  if (!why && !out) why = "null output handle";
+  if (why) {
     g_replay_create_error = why;
-    return FLEET_ERR_INVALID;
-  }
-  if (!out) {
-    g_replay_create_error = "null output handle";
-    return FLEET_ERR_INVALID;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    g_replay_create_error = "no HIP device";
-    return FLEET_ERR_NODEVICE;
-  }
-  if (device < 0 || device >= ndev) {
-    g_replay_create_error = "device index out of range";
     return FLEET_ERR_INVALID;
   }
   FleetReplay* r = new FleetReplay();
   r->p = *p;
-  r->device = device;
   r->E = p->num_envs, r->R = (int)rows_of(p), r->D = p->obs_dim, r->A = p->act_dim;
   layout_of(p, &r->L);
-  auto fail = [&](const std::string& msg) {
-    g_replay_create_error = msg;
+  const int rc = handle_open_buffer(r, device, "replay buffer", &g_replay_create_error);
+  if (rc != FLEET_OK) {
     fleet_replay_destroy(r);
-    return FLEET_ERR_HIP;
-  };
-  if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice failed");
-  if (hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
-  r->stream = r->own_stream;
-  void* q = nullptr;
-  if (hipMalloc(&q, r->L.total_bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail("hipMalloc of the replay buffer's " + std::to_string(r->L.total_bytes) + " bytes failed");
+    return rc;
   }
-  r->block = static_cast<char*>(q);
-  r->err = reinterpret_cast<uint32_t*>(r->block + r->L.error_offset);
-  if (hipMemset(r->block, 0, r->L.total_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-    return fail("clearing the replay buffer failed");
   *out = r;
   return FLEET_OK;
 }
 
 int fleet_replay_destroy(fleet_replay_handle r) {
   if (!r) return FLEET_OK;
-  (void)hipSetDevice(r->device);
-  if (r->stream) (void)hipStreamSynchronize(r->stream);
-  if (r->own_stream) (void)hipStreamSynchronize(r->own_stream);
-  if (r->block) (void)hipFree(r->block);
-  if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
+  handle_close(r);
   delete r;
   return FLEET_OK;
 }
 
 const char* fleet_replay_last_error(fleet_replay_handle r) { return r ? r->error.c_str() : g_replay_create_error.c_str(); }
 
-int fleet_replay_set_stream(fleet_replay_handle r, void* hip_stream) {
-  if (!r) return FLEET_ERR_INVALID;
-  REPLAY_TRY(r, hipSetDevice(r->device));
-  REPLAY_TRY(r, hipStreamSynchronize(r->stream));
-  r->stream = static_cast<hipStream_t>(hip_stream);  // (NULL is the null stream: torch's default stream has that handle)
-  return FLEET_OK;
-}
+int fleet_replay_set_stream(fleet_replay_handle r, void* hip_stream) { return r ? handle_set_stream(r, hip_stream) : FLEET_ERR_INVALID; }
 
 int fleet_replay_arrays(fleet_replay_handle r, FleetReplayArrays* out) {
   if (!r || !out) return FLEET_ERR_INVALID;
@@ -402,9 +332,9 @@ int fleet_replay_add_dev(fleet_replay_handle r, const float* obs, const float* n
   a.obs_vec = r->D % 4 == 0 && aligned16(obs);
   a.next_vec = r->D % 4 == 0 && aligned16(next_obs) && aligned16(terminal);
   a.act_vec = r->A % 4 == 0 && aligned16(action);
-  REPLAY_TRY(r, hipSetDevice(r->device));
-  hipLaunchKernelGGL(replay_add, dim3(blocks_for((size_t)r->E)), dim3(kReplayThreads), 0, r->stream, a);
-  REPLAY_TRY(r, hipGetLastError());
+  FLEET_HANDLE_TRY(r, hipSetDevice(r->device));
+  hipLaunchKernelGGL(replay_add, dim3(grid_for((size_t)r->E, kReplayWaves, kReplayMaxBlocks)), dim3(kReplayThreads), 0, r->stream, a);
+  FLEET_HANDLE_TRY(r, hipGetLastError());
   if (++r->pos == r->R) {
     r->pos = 0;
     r->full = true;
@@ -446,14 +376,7 @@ int fleet_replay_sample_dev(fleet_replay_handle r, int batch, fleet_norm_handle 
 
 int fleet_replay_check_errors(fleet_replay_handle r) {
   if (!r) return FLEET_ERR_INVALID;
-  REPLAY_TRY(r, hipSetDevice(r->device));
-  uint32_t word = 0;
-  REPLAY_TRY(r, hipMemcpyAsync(&word, r->err, sizeof word, hipMemcpyDeviceToHost, r->stream));
-  REPLAY_TRY(r, hipStreamSynchronize(r->stream));
-  if (!word) return FLEET_OK;
-  REPLAY_TRY(r, hipMemsetAsync(r->err, 0, sizeof word, r->stream));
-  r->error = "a gather met an index pair outside [0, rows filled) x [0, num_envs): its sample was left untouched";
-  return FLEET_ERR_STATE;
+  return handle_check_errors(r, "a gather met an index pair outside [0, rows filled) x [0, num_envs): its sample was left untouched");
 }
 
 int fleet_replay_size(fleet_replay_handle r, int32_t* pos, int32_t* full, int32_t* rows, uint64_t* calls) {

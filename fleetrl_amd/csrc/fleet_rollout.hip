@@ -15,6 +15,7 @@
 #include <cmath>
 #include <string>
 
+#include "fleet_handle.h"
 #include "fleet_rollout.h"
 
 namespace {
@@ -208,61 +209,25 @@ void layout_of(const FleetRolloutParams* p, FleetRolloutLayout* L) {
   *L = FleetRolloutLayout{};
   L->struct_bytes = (int32_t)sizeof(FleetRolloutLayout);
   L->alignment = FLEET_ROLLOUT_ALIGN;
-  uint64_t off = 0;
-  for (int i = 0; i < FLEET_ROLLOUT_ARRAYS; ++i) {
-    L->offset[i] = off;
-    L->row_bytes[i] = row[i];
-    L->bytes[i] = row[i] * K;
-    off = (off + L->bytes[i] + FLEET_ROLLOUT_ALIGN - 1) / FLEET_ROLLOUT_ALIGN * FLEET_ROLLOUT_ALIGN;
-  }
-  L->error_offset = off;
-  L->total_bytes = off + FLEET_ROLLOUT_ALIGN;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-unsigned blocks_for(size_t items) {
-  const size_t want = (items + kRolloutThreads - 1) / kRolloutThreads;
-  return (unsigned)(want < 1 ? 1 : (want < (size_t)kRolloutMaxBlocks ? want : (size_t)kRolloutMaxBlocks));
+  handle_layout(row, FLEET_ROLLOUT_ARRAYS, K, FLEET_ROLLOUT_ALIGN, L->offset, L->bytes, L->row_bytes, &L->error_offset, &L->total_bytes);
 }
 
 }  // namespace
 
-struct FleetRollout {
+// block: the eight arrays, then the error word
+struct FleetRollout : FleetBufferBase<FleetRolloutLayout> {
   FleetRolloutParams p{};
-  FleetRolloutLayout L{};
-  int device = 0;
   int E = 0, K = 0, D = 0, A = 0;
   float g = 0.f, gl = 0.f;
-  hipStream_t stream = nullptr, own_stream = nullptr;
-  std::string error;
-  char* block = nullptr;  // one device allocation: the eight arrays, then the error word
-  uint32_t* err = nullptr;
-
-  template <typename T>
-  T* array(int which, int t = 0) const {
-    return reinterpret_cast<T*>(block + L.offset[which] + (uint64_t)t * L.row_bytes[which]);
-  }
 };
-
-#define ROLLOUT_TRY(r, expr)                                              \
-  do {                                                                    \
-    hipError_t _e = (expr);                                               \
-    if (_e != hipSuccess) {                                               \
-      (r)->error = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-      return FLEET_ERR_HIP;                                               \
-    }                                                                     \
-  } while (0)
 
 extern "C" {
 
 int fleet_rollout_layout(const FleetRolloutParams* p, FleetRolloutLayout* out) {
-  if (const char* why = validate(p)) {
+  const char* why = validate(p);
+  if (!why && !out) why = "null FleetRolloutLayout";
+  if (why) {
     g_rollout_create_error = why;
-    return FLEET_ERR_INVALID;
-  }
-  if (!out) {
-    g_rollout_create_error = "null FleetRolloutLayout";
     return FLEET_ERR_INVALID;
   }
   layout_of(p, out);
@@ -271,70 +236,37 @@ int fleet_rollout_layout(const FleetRolloutParams* p, FleetRolloutLayout* out) {
 
 int fleet_rollout_create(int device, const FleetRolloutParams* p, fleet_rollout_handle* out) {
   if (out) *out = nullptr;
-  if (const char* why = validate(p)) {  // before the device is touched
+  const char* why = validate(p);  // before the device is touched
+  if (!why && !out) why = "null output handle";
+  if (why) {
     g_rollout_create_error = why;
-    return FLEET_ERR_INVALID;
-  }
-  if (!out) {
-    g_rollout_create_error = "null output handle";
-    return FLEET_ERR_INVALID;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    g_rollout_create_error = "no HIP device";
-    return FLEET_ERR_NODEVICE;
-  }
-  if (device < 0 || device >= ndev) {
-    g_rollout_create_error = "device index out of range";
     return FLEET_ERR_INVALID;
   }
   FleetRollout* r = new FleetRollout();
   r->p = *p;
-  r->device = device;
   r->E = p->num_envs, r->K = p->n_steps, r->D = p->obs_dim, r->A = p->act_dim;
   r->g = (float)p->gamma;
   r->gl = (float)(p->gamma * p->gae_lambda);  // the product in float64 first, as Python forms it
   layout_of(p, &r->L);
-  auto fail = [&](const std::string& msg) {
-    g_rollout_create_error = msg;
+  const int rc = handle_open_buffer(r, device, "rollout buffer", &g_rollout_create_error);
+  if (rc != FLEET_OK) {
     fleet_rollout_destroy(r);
-    return FLEET_ERR_HIP;
-  };
-  if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice failed");
-  if (hipStreamCreateWithFlags(&r->own_stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
-  r->stream = r->own_stream;
-  void* q = nullptr;
-  if (hipMalloc(&q, r->L.total_bytes) != hipSuccess)
-    return fail("hipMalloc of the rollout buffer's " + std::to_string(r->L.total_bytes) + " bytes failed");
-  r->block = static_cast<char*>(q);
-  r->err = reinterpret_cast<uint32_t*>(r->block + r->L.error_offset);
-  if (hipMemset(r->block, 0, r->L.total_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-    return fail("clearing the rollout buffer failed");
+    return rc;
+  }
   *out = r;
   return FLEET_OK;
 }
 
 int fleet_rollout_destroy(fleet_rollout_handle r) {
   if (!r) return FLEET_OK;
-  (void)hipSetDevice(r->device);
-  if (r->stream) (void)hipStreamSynchronize(r->stream);
-  if (r->own_stream) (void)hipStreamSynchronize(r->own_stream);
-  if (r->block) (void)hipFree(r->block);
-  if (r->own_stream) (void)hipStreamDestroy(r->own_stream);
+  handle_close(r);
   delete r;
   return FLEET_OK;
 }
 
 const char* fleet_rollout_last_error(fleet_rollout_handle r) { return r ? r->error.c_str() : g_rollout_create_error.c_str(); }
 
-int fleet_rollout_set_stream(fleet_rollout_handle r, void* hip_stream) {
-  if (!r) return FLEET_ERR_INVALID;
-  ROLLOUT_TRY(r, hipSetDevice(r->device));
-  ROLLOUT_TRY(r, hipStreamSynchronize(r->stream));
-  r->stream = static_cast<hipStream_t>(hip_stream);  // (NULL is the null stream: torch's default stream has that handle)
-  return FLEET_OK;
-}
+int fleet_rollout_set_stream(fleet_rollout_handle r, void* hip_stream) { return r ? handle_set_stream(r, hip_stream) : FLEET_ERR_INVALID; }
 
 int fleet_rollout_arrays(fleet_rollout_handle r, FleetRolloutArrays* out) {
   if (!r || !out) return FLEET_ERR_INVALID;
@@ -416,9 +348,9 @@ int fleet_rollout_add_dev(fleet_rollout_handle r, int t, const float* obs, const
   size_t items = (size_t)r->E;
   if (a.obs && a.n_obs > items) items = a.n_obs;
   if (a.act && a.n_act > items) items = a.n_act;
-  ROLLOUT_TRY(r, hipSetDevice(r->device));
-  hipLaunchKernelGGL(rollout_add, dim3(blocks_for(items)), dim3(kRolloutThreads), 0, r->stream, a);
-  ROLLOUT_TRY(r, hipGetLastError());
+  FLEET_HANDLE_TRY(r, hipSetDevice(r->device));
+  hipLaunchKernelGGL(rollout_add, dim3(grid_for(items, kRolloutThreads, kRolloutMaxBlocks)), dim3(kRolloutThreads), 0, r->stream, a);
+  FLEET_HANDLE_TRY(r, hipGetLastError());
   return FLEET_OK;
 }
 
@@ -428,12 +360,12 @@ int fleet_rollout_finish_dev(fleet_rollout_handle r, const float* last_values, c
     r->error = "fleet_rollout_finish_dev: null buffer";
     return FLEET_ERR_INVALID;
   }
-  ROLLOUT_TRY(r, hipSetDevice(r->device));
+  FLEET_HANDLE_TRY(r, hipSetDevice(r->device));
   hipLaunchKernelGGL(rollout_gae, dim3((r->E + kGaeThreads - 1) / kGaeThreads), dim3(kGaeThreads), 0, r->stream,
                      r->array<float>(FLEET_ROLLOUT_REWARDS), r->array<float>(FLEET_ROLLOUT_VALUES),
                      r->array<uint8_t>(FLEET_ROLLOUT_EPISODE_STARTS), last_values, dones, r->array<float>(FLEET_ROLLOUT_ADVANTAGES),
                      r->array<float>(FLEET_ROLLOUT_RETURNS), r->E, r->K, r->g, r->gl);
-  ROLLOUT_TRY(r, hipGetLastError());
+  FLEET_HANDLE_TRY(r, hipGetLastError());
   return FLEET_OK;
 }
 
@@ -467,22 +399,15 @@ int fleet_rollout_gather_dev(fleet_rollout_handle r, const int32_t* indices, int
   size_t items = (size_t)batch;
   if (out_obs && a.n_obs > items) items = a.n_obs;
   if (out_actions && a.n_act > items) items = a.n_act;
-  ROLLOUT_TRY(r, hipSetDevice(r->device));
-  hipLaunchKernelGGL(rollout_gather, dim3(blocks_for(items)), dim3(kRolloutThreads), 0, r->stream, a);
-  ROLLOUT_TRY(r, hipGetLastError());
+  FLEET_HANDLE_TRY(r, hipSetDevice(r->device));
+  hipLaunchKernelGGL(rollout_gather, dim3(grid_for(items, kRolloutThreads, kRolloutMaxBlocks)), dim3(kRolloutThreads), 0, r->stream, a);
+  FLEET_HANDLE_TRY(r, hipGetLastError());
   return FLEET_OK;
 }
 
 int fleet_rollout_check_errors(fleet_rollout_handle r) {
   if (!r) return FLEET_ERR_INVALID;
-  ROLLOUT_TRY(r, hipSetDevice(r->device));
-  uint32_t word = 0;
-  ROLLOUT_TRY(r, hipMemcpyAsync(&word, r->err, sizeof word, hipMemcpyDeviceToHost, r->stream));
-  ROLLOUT_TRY(r, hipStreamSynchronize(r->stream));
-  if (!word) return FLEET_OK;
-  ROLLOUT_TRY(r, hipMemsetAsync(r->err, 0, sizeof word, r->stream));
-  r->error = "a gather met an index outside [0, n_steps * num_envs): its output rows were left untouched";
-  return FLEET_ERR_STATE;
+  return handle_check_errors(r, "a gather met an index outside [0, n_steps * num_envs): its output rows were left untouched");
 }
 
 }  // extern "C"

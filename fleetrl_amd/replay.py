@@ -13,11 +13,8 @@ from __future__ import annotations
 import ctypes as C
 from collections import namedtuple
 
-import numpy as np
-
 from . import _capi
-from ._capi import FleetHipError
-from .rollout import _DeviceArray
+from ._handle import _DeviceHandle
 
 __all__ = ["DeviceReplayBuffer", "ReplayBatch"]
 
@@ -36,44 +33,21 @@ def _norm_handle(env):
     return h
 
 
-class DeviceReplayBuffer:
+class DeviceReplayBuffer(_DeviceHandle):
     """One `fleet_replay_*` handle.  The `*_dev` methods take raw device addresses; every other method takes torch tensors on
     the buffer's device and launches on torch's current stream."""
+    _prefix = "replay"
 
     def __init__(self, buffer_size: int, num_envs: int, obs_dim: int, act_dim: int, seed: int = 0, device: int = 0):
-        self.lib = _capi.load_library()
         self.buffer_size, self.num_envs, self.obs_dim, self.act_dim = int(buffer_size), int(num_envs), int(obs_dim), int(act_dim)
-        self.seed, self.device = int(seed) & (2 ** 64 - 1), int(device)
+        self.seed = int(seed) & (2 ** 64 - 1)
         for name in ("buffer_size", "num_envs", "obs_dim", "act_dim"):
             if not -2 ** 31 <= getattr(self, name) < 2 ** 31:
                 raise ValueError(f"{name} must fit a 32-bit integer, got {getattr(self, name)}")
         p = _capi.FleetReplayParams(C.sizeof(_capi.FleetReplayParams), self.num_envs, self.buffer_size, self.obs_dim, self.act_dim, 0,
                                     self.seed)
-        h = C.c_void_p()
-        rc = self.lib.fleet_replay_create(self.device, C.byref(p), C.byref(h))
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_replay_last_error(None).decode())
-        self.h = h
+        self._open(device, p)
         self.rows = max(self.buffer_size // self.num_envs, 1)
-        self._stream = None
-        self._tensors = None
-
-    def _check(self, rc: int):
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_replay_last_error(self.h).decode())
-
-    # ---- streams ------------------------------------------------------------------------------------------------------
-    def set_stream(self, hip_stream: int | None):
-        self._check(self.lib.fleet_replay_set_stream(self.h, hip_stream))
-        self._stream = hip_stream
-
-    def use_torch_stream(self, device=None):
-        """Launch on torch's current stream of the buffer's device from now on (no-op if already there)."""
-        import torch
-
-        cur = torch.cuda.current_stream(device if device is not None else self.device).cuda_stream
-        if cur != self._stream:
-            self.set_stream(cur)
 
     # ---- bookkeeping (the host's) -------------------------------------------------------------------------------------------
     def _size(self):
@@ -125,14 +99,10 @@ class DeviceReplayBuffer:
     # ---- the arrays as torch tensors (zero-copy views of the buffer's memory) -------------------------------------------------
     def _views(self) -> dict:
         if self._tensors is None:
-            import torch
-
             R, E, D, A = self.rows, self.num_envs, self.obs_dim, self.act_dim
             shapes = {"observations": (R, E, D), "next_observations": (R, E, D), "actions": (R, E, A)}
-            dev = torch.device("cuda", self.device)
-            ptrs = self.arrays_dev()
-            self._tensors = {n: torch.as_tensor(_DeviceArray(ptrs[n], shapes.get(n, (R, E)), "|u1" if n in ("dones", "timeouts") else "<f4",
-                                                             self), device=dev) for n in _capi.REPLAY_ARRAY_NAMES}
+            self._tensors = self._make_views({n: (shapes.get(n, (R, E)), "|u1" if n in ("dones", "timeouts") else "<f4")
+                                              for n in _capi.REPLAY_ARRAY_NAMES})
         return self._tensors
 
     observations = property(lambda self: self._views()["observations"], doc="f32 [rows, num_envs, obs_dim], raw")
@@ -143,21 +113,6 @@ class DeviceReplayBuffer:
     timeouts = property(lambda self: self._views()["timeouts"], doc="u8 [rows, num_envs]")
 
     # ---- SB3's surface ----------------------------------------------------------------------------------------------------
-    def _tensor(self, t, shape, dtypes):
-        import torch
-
-        if isinstance(t, np.ndarray) or not isinstance(t, torch.Tensor):  # convenience, not the fast path
-            t = torch.as_tensor(np.ascontiguousarray(t)).to(torch.device("cuda", self.device))
-            if t.dtype not in dtypes:
-                t = t.to(dtypes[0])
-        if t.dtype == torch.bool and torch.uint8 in dtypes:
-            t = t.view(torch.uint8)
-        if t.device.type != "cuda" or t.device.index != self.device or t.dtype not in dtypes or t.numel() != int(np.prod(shape)) or \
-                not t.is_contiguous():
-            raise ValueError(f"expected a contiguous tensor of {int(np.prod(shape))} elements {shape}, dtype in {dtypes}, on "
-                             f"cuda:{self.device}; got {tuple(t.shape)} {t.dtype} on {t.device}")
-        return t
-
     def add(self, obs, next_obs, action, reward, done, terminal=None, timeout=None):
         """SB3's add: ring row `pos` <- one transition per env.  obs / next_obs f32 [E, D] RAW (not normalised), action f32 [E, A],
         reward f64 or f32 [E] raw (rounded once to float32), done u8 / bool [E].  terminal f32 [E, D]: the raw terminal observations;
@@ -215,15 +170,3 @@ class DeviceReplayBuffer:
             ei = self._tensor(indices_out[1], (B,), (torch.int32,)).data_ptr()
         self.sample_dev(B, env, *ptrs, ri, ei)
         return out
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._tensors = None
-            self.lib.fleet_replay_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter shutdown
-            pass

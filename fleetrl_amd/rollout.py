@@ -12,10 +12,9 @@ from __future__ import annotations
 import ctypes as C
 from collections import namedtuple
 
-import numpy as np
-
 from . import _capi
 from ._capi import FleetHipError
+from ._handle import _DeviceHandle
 
 __all__ = ["DeviceRolloutBuffer", "RolloutBatch", "RolloutSlot"]
 
@@ -24,51 +23,19 @@ RolloutBatch = namedtuple("RolloutBatch", ["observations", "actions", "old_value
 RolloutSlot = namedtuple("RolloutSlot", ["obs", "actions", "reward", "episode_start", "value", "log_prob"])
 
 
-class _DeviceArray:
-    """A view of device memory somebody else owns, for torch.as_tensor (the CUDA array interface)."""
-
-    def __init__(self, ptr: int, shape: tuple, typestr: str, owner):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2,
-                                         "strides": None}
-        self._owner = owner  # the tensor made from this object keeps it, and with it the buffer, alive
-
-
-class DeviceRolloutBuffer:
+class DeviceRolloutBuffer(_DeviceHandle):
     """One `fleet_rollout_*` handle.  The `*_dev` methods take raw device addresses; every other method takes torch tensors on
     the buffer's device and launches on torch's current stream."""
+    _prefix = "rollout"
 
     def __init__(self, num_envs: int, n_steps: int, obs_dim: int, act_dim: int, gamma: float = 0.99, gae_lambda: float = 0.95,
                  device: int = 0):
-        self.lib = _capi.load_library()
         self.num_envs, self.n_steps, self.obs_dim, self.act_dim = int(num_envs), int(n_steps), int(obs_dim), int(act_dim)
-        self.gamma, self.gae_lambda, self.device = float(gamma), float(gae_lambda), int(device)
+        self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
         p = _capi.FleetRolloutParams(C.sizeof(_capi.FleetRolloutParams), self.num_envs, self.n_steps, self.obs_dim, self.act_dim, 0,
                                      self.gamma, self.gae_lambda)
-        h = C.c_void_p()
-        rc = self.lib.fleet_rollout_create(self.device, C.byref(p), C.byref(h))
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_rollout_last_error(None).decode())
-        self.h = h
-        self._stream = None
+        self._open(device, p)
         self.pos, self.full = 0, False
-        self._tensors = None
-
-    def _check(self, rc: int):
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_rollout_last_error(self.h).decode())
-
-    # ---- streams ------------------------------------------------------------------------------------------------------
-    def set_stream(self, hip_stream: int | None):
-        self._check(self.lib.fleet_rollout_set_stream(self.h, hip_stream))
-        self._stream = hip_stream
-
-    def use_torch_stream(self, device=None):
-        """Launch on torch's current stream of the buffer's device from now on (no-op if already there)."""
-        import torch
-
-        cur = torch.cuda.current_stream(device if device is not None else self.device).cuda_stream
-        if cur != self._stream:
-            self.set_stream(cur)
 
     # ---- device pointers ------------------------------------------------------------------------------------------------
     def arrays_dev(self) -> dict:
@@ -102,14 +69,10 @@ class DeviceRolloutBuffer:
     # ---- the arrays as torch tensors (zero-copy views of the buffer's memory) -------------------------------------------------
     def _views(self) -> dict:
         if self._tensors is None:
-            import torch
-
             K, E, D, A = self.n_steps, self.num_envs, self.obs_dim, self.act_dim
             shapes = {"obs": (K, E, D), "actions": (K, E, A)}
-            dev = torch.device("cuda", self.device)
-            ptrs = self.arrays_dev()
-            self._tensors = {n: torch.as_tensor(_DeviceArray(ptrs[n], shapes.get(n, (K, E)), "|u1" if n == "episode_starts" else "<f4", self),
-                                                device=dev) for n in _capi.ROLLOUT_ARRAY_NAMES}
+            self._tensors = self._make_views({n: (shapes.get(n, (K, E)), "|u1" if n == "episode_starts" else "<f4")
+                                              for n in _capi.ROLLOUT_ARRAY_NAMES})
         return self._tensors
 
     observations = property(lambda self: self._views()["obs"], doc="f32 [n_steps, num_envs, obs_dim]")
@@ -133,21 +96,6 @@ class DeviceRolloutBuffer:
     def reset(self):
         """Start a new rollout at row 0 (the rows are overwritten as they are added, not cleared)."""
         self.pos, self.full = 0, False
-
-    def _tensor(self, t, shape, dtypes):
-        import torch
-
-        if isinstance(t, np.ndarray) or not isinstance(t, torch.Tensor):  # convenience, not the fast path
-            t = torch.as_tensor(np.ascontiguousarray(t)).to(torch.device("cuda", self.device))
-            if t.dtype not in dtypes:
-                t = t.to(dtypes[0])
-        if t.dtype == torch.bool and torch.uint8 in dtypes:
-            t = t.view(torch.uint8)
-        if t.device.type != "cuda" or t.device.index != self.device or t.dtype not in dtypes or t.numel() != int(np.prod(shape)) or \
-                not t.is_contiguous():
-            raise ValueError(f"expected a contiguous tensor of {int(np.prod(shape))} elements {shape}, dtype in {dtypes}, on "
-                             f"cuda:{self.device}; got {tuple(t.shape)} {t.dtype} on {t.device}")
-        return t
 
     def add(self, obs, action, reward, episode_start, value, log_prob, terminal_value=None, done=None):
         """SB3's add: row `pos` <- the step's tensors (value may be [E, 1] as a critic returns it; reward float64 or float32,
@@ -211,15 +159,3 @@ class DeviceRolloutBuffer:
         batch_size = n if batch_size is None else int(batch_size)
         for start in range(0, n, batch_size):
             yield self.gather(perm[start:start + batch_size])
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._tensors = None
-            self.lib.fleet_rollout_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter shutdown
-            pass

@@ -24,6 +24,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import FleetHipError
+from ._handle import _DeviceHandle
 
 __all__ = ["DeviceNormalizer", "FleetVecNormalize", "RunningStats", "sync_normalization", "NormSettings", "NormState",
            "save_state", "load_state", "state_from_sb3"]
@@ -139,31 +140,22 @@ def normalize_obs_np(obs, rms: RunningStats, clip_obs: float, epsilon: float) ->
     return np.clip((x - rms.mean) / np.sqrt(rms.var + epsilon), -clip_obs, clip_obs).astype(np.float32)
 
 
-class DeviceNormalizer:
+class DeviceNormalizer(_DeviceHandle):
     """One `fleet_norm_*` handle: SB3 VecNormalize's state and arithmetic for a batch of `num_envs` observations of `obs_dim`
     floats on `device`.  The `*_dev` calls take raw device addresses and are asynchronous on the normaliser's stream (its own
     unless `set_stream` / `use_torch_stream` adopted another)."""
+    _prefix = "norm"
 
     def __init__(self, num_envs: int, obs_dim: int, device: int = 0, **settings):
         self.settings = NormSettings(**settings).validate()
-        self.lib = _capi.load_library()
-        self.E, self.D, self.device = int(num_envs), int(obs_dim), int(device)
-        h = C.c_void_p()
-        rc = self.lib.fleet_norm_create(self.device, C.byref(self._params()), C.byref(h))
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_norm_last_error(None).decode())
-        self.h = h
-        self._stream = None
+        self.E, self.D = int(num_envs), int(obs_dim)
+        self._open(device, self._params())
 
     def _params(self) -> _capi.FleetNormParams:
         s = self.settings
         return _capi.FleetNormParams(C.sizeof(_capi.FleetNormParams), self.E, self.D, int(bool(s.training)), int(bool(s.norm_obs)),
                                      int(bool(s.norm_reward)), float(s.clip_obs), float(s.clip_reward), float(s.gamma),
                                      float(s.epsilon))
-
-    def _check(self, rc: int):
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_norm_last_error(self.h).decode())
 
     def configure(self, **changes):
         """Change flags / constants (training, norm_obs, norm_reward, clip_obs, clip_reward, gamma, epsilon)."""
@@ -173,18 +165,6 @@ class DeviceNormalizer:
         if rc != _capi.OK:
             self.settings = old
             self._check(rc)
-
-    def set_stream(self, hip_stream: int | None):
-        self._check(self.lib.fleet_norm_set_stream(self.h, hip_stream))
-        self._stream = hip_stream
-
-    def use_torch_stream(self, device=None):
-        """Launch on torch's current stream of `device` from now on (no-op if already there)."""
-        import torch
-
-        cur = torch.cuda.current_stream(device if device is not None else self.device).cuda_stream
-        if cur != self._stream:
-            self.set_stream(cur)
 
     # ---- device pointers --------------------------------------------------------------------------------------------
     def reset_dev(self, raw_obs_ptr: int, obs_ptr: int):
@@ -196,7 +176,7 @@ class DeviceNormalizer:
                                                  reward_ptr, terminal_ptr))
 
     # ---- torch tensors (on torch's current stream) ----------------------------------------------------------------
-    def _tensor(self, t, shape, dtype):
+    def _tensor(self, t, shape, dtype):  # stricter than the buffers': nothing is converted, and the address comes back
         import torch
 
         if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or \
@@ -262,17 +242,6 @@ class DeviceNormalizer:
         r = np.empty(self.E) if reward else None
         self._check(self.lib.fleet_norm_original_host(self.h, None if o is None else o.ctypes.data, None if r is None else r.ctypes.data))
         return o, r
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.fleet_norm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter shutdown
-            pass
 
 
 class FleetVecNormalize(_SB3VecEnvWrapper):

@@ -134,7 +134,7 @@ def measure_gae(torch, buf, reps, variants):
             assert lib.fleet_rollout_set_stream(h, stream) == 0
             arr = _capi.FleetRolloutArrays()
             lib.fleet_rollout_arrays(h, C.byref(arr))
-            from fleetrl_amd.rollout import _DeviceArray
+            from fleetrl_amd._handle import _DeviceArray
 
             view = lambda ptr, ts: torch.as_tensor(_DeviceArray(ptr, (K, E), ts, None), device=torch.device("cuda", 0))  # noqa: E731
             view(arr.rewards, "<f4").copy_(buf.rewards)
