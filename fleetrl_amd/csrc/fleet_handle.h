@@ -1,8 +1,7 @@
 // fleet_handle.h -- the host scaffold the normaliser (fleet_norm.hip), the rollout buffer (fleet_rollout.hip) and the replay buffer
 // (fleet_replay.hip) share: what such a handle holds, how it is opened and closed, how it changes streams, how its HIP errors and
 // its device error word become messages, and how a buffer's arrays are laid out.  Host code only; nothing here launches a kernel,
-// and nothing here builds a string outside an error branch.  (The env's own handle, `fleet_handle` of fleet_capi.hip, is not one of
-// these.)
+// and nothing here builds a string outside an error branch.  (The env's own handle, `fleet_handle`, is not one of these: fleet_batch.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // fleet_lp.h -- the linear-optimisation benchmark's per-(env, EV) planner (fleet_lp.hip), called by fleet_lp_plan_dev
-// (fleet_capi.hip).  DESIGN.md section 8 "The linear-optimisation benchmark" derives the model and the method.
+// (fleet_capi.hip, the handle: fleet_batch.h).  DESIGN.md section 8 "The linear-optimisation benchmark" derives the model and the method.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

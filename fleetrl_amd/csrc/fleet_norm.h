@@ -1,4 +1,4 @@
-// fleet_norm.h -- what the env's host path (fleet_capi.hip) needs of the normaliser (fleet_norm.hip).
+// fleet_norm.h -- what the env's host path (fleet_hostpath.hip) needs of the normaliser (fleet_norm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,6 +1,6 @@
 // fleet_state.h -- env state in the caller's hands (fleet_state.hip): the blob layout, the fingerprint that decides whether a state
 // fits a handle, whole-handle save / load as one copy per section, and the fork kernel that copies chosen envs within a handle or
-// between two.  Called by the fleet_state_* / fleet_fork_envs entry points (fleet_capi.hip owns the handle).  What "the state" is:
+// between two.  Called by the fleet_state_* / fleet_fork_envs entry points (fleet_capi.hip; the handle: fleet_batch.h).  What "the state" is:
 // fleet_device.h, beside FleetDev.  DESIGN.md "Env state in the caller's hands".
 #pragma once
 #include <hip/hip_runtime.h>

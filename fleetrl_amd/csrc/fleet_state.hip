@@ -6,7 +6,7 @@
 #include <cstring>
 #include <vector>
 
-void fleet_set_create_error(const std::string& why);  // fleet_capi.hip: what fleet_last_error(NULL) returns
+void fleet_set_create_error(const std::string& why);  // fleet_capi.hip (declared in fleet_batch.h too): what fleet_last_error(NULL) returns
 
 namespace {
 

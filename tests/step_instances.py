@@ -41,7 +41,7 @@ class Launch:
 
 def abi_accepts(real_time: bool, act_mode: int, K: int, has_done_count: bool) -> bool:
     """Which (configuration, call) combinations an entry point of the C ABI lets through to the planner, on a handle with auto_reset = 1
-    (fleet_capi.hip): fleet_step_dev / fleet_step_host / the tape replays launch K = 1 without a done_count buffer, with any
+    (fleet_capi.hip, fleet_hostpath.hip, fleet_tape.hip): fleet_step_dev / fleet_step_host / the tape replays launch K = 1 without a done_count buffer, with any
     configuration; fleet_step_many_dev (an action dtype, K >= 1, done_count or not) and fleet_rollout_policy_dev (a policy, K >= 1,
     done_count or not) refuse real_time = 1.  (Both also need auto_reset = 1, which the planner does not read.)"""
     if real_time:

@@ -312,3 +312,15 @@ def test_library_and_code_object_carry_the_same_source_hash():
     sha = build.source_sha().encode()
     assert sha in open(build.lib_path(), "rb").read()
     assert sha in open(build.code_object_path(), "rb").read()
+
+
+def test_the_build_lists_name_every_source_and_header():
+    """Every *.hip under csrc/ is compiled and every *.h there is a dependency: a header missing from HEADERS means no rebuild when
+    it changes, and a `FLEET_SRC_SHA` that does not see it."""
+    from fleetrl_amd import build
+
+    csrc = os.path.join(os.path.dirname(os.path.abspath(build.__file__)), "csrc")
+    names = sorted(os.listdir(csrc))
+    assert sorted(build.SOURCES) == [f for f in names if f.endswith(".hip")]
+    assert sorted(h for h in build.HEADERS if os.sep not in h) == [f for f in names if f.endswith(".h")]
+    assert len(set(build.SOURCES)) == len(build.SOURCES) and len(set(build.HEADERS)) == len(build.HEADERS)
