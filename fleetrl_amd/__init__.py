@@ -4,6 +4,7 @@
     from fleetrl_amd import FleetVecNormalize, DeviceNormalizer, sync_normalization
     from fleetrl_amd import plan_linear_optimization, run_linear_optimization
     from fleetrl_amd import DeviceRolloutBuffer, DeviceReplayBuffer
+    from fleetrl_amd import DevicePolicy, evaluate_policy
 """
 __version__ = "0.1.0"
 
@@ -29,6 +30,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import replay
 
         return getattr(replay, name)
+    if name in ("DevicePolicy", "evaluate_policy"):
+        from . import policy
+
+        return getattr(policy, name)
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

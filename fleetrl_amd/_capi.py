@@ -145,6 +145,22 @@ class FleetReplayArrays(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in REPLAY_ARRAY_NAMES]
 
 
+# ---- MLP policy (include/fleet_hip.h "MLP policy on the device", fleet_policy_*) -------------------------------------------------
+POLICY_MAX_HEADS, POLICY_MAX_LAYERS, POLICY_MAX_WIDTH, POLICY_MAX_OBS_DIM = 2, 4, 512, 8192
+POLICY_ACT_TANH, POLICY_ACT_RELU = 0, 1
+POLICY_OUT_NONE, POLICY_OUT_CLIP, POLICY_OUT_TANH = 0, 1, 2
+
+
+class FleetPolicyHead(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("width", C.c_int32 * POLICY_MAX_LAYERS), ("activation", C.c_int32), ("output", C.c_int32),
+                ("reserved", C.c_int32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class FleetPolicyParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("obs_dim", C.c_int32), ("n_heads", C.c_int32), ("tile_rows", C.c_int32),
+                ("head", FleetPolicyHead * POLICY_MAX_HEADS)]
+
+
 # ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
 STATE_MAGIC = 0x4554415453544C46
 STATE_ALIGN = 256
@@ -379,7 +395,16 @@ def load_library():
     lib.fleet_replay_check_errors.argtypes = [vp]
     lib.fleet_replay_size.argtypes = [vp, i32p, i32p, i32p, C.POINTER(C.c_uint64)]
     lib.fleet_replay_set_position.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint64]
-    for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS)):
+    # the MLP policy (fleet_policy.hip)
+    lib.fleet_policy_create.argtypes = [C.c_int, C.POINTER(FleetPolicyParams), f32p, C.POINTER(vp)]
+    lib.fleet_policy_destroy.argtypes = [vp]
+    lib.fleet_policy_last_error.argtypes = [vp]
+    lib.fleet_policy_set_stream.argtypes = [vp, vp]
+    lib.fleet_policy_load_host.argtypes = [vp, f32p]
+    lib.fleet_policy_load_dev.argtypes = [vp, C.POINTER(vp), C.c_int]
+    lib.fleet_policy_forward_dev.argtypes = [vp, f32p, C.c_int, vp, f32p, f32p]
+    lib.fleet_policy_describe.argtypes = [vp, C.POINTER(FleetPolicyParams)]
+    for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS)):
         for name in names:
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
@@ -419,6 +444,11 @@ REPLAY_SYMBOLS = (
     "fleet_replay_size", "fleet_replay_set_position",
 )
 
+POLICY_SYMBOLS = (
+    "fleet_policy_create", "fleet_policy_destroy", "fleet_policy_last_error", "fleet_policy_set_stream", "fleet_policy_load_host",
+    "fleet_policy_load_dev", "fleet_policy_forward_dev", "fleet_policy_describe",
+)
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -431,7 +461,7 @@ EXPORTED_SYMBOLS = (
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

@@ -1,0 +1,426 @@
+// fleet_policy.hip -- the deterministic forward pass of a trained MLP policy on the device (include/fleet_hip.h "MLP policy on the
+// device"): what stable-baselines3's `predict(obs, deterministic=True)` computes for an MlpPolicy, in one launch whose output
+// fleet_step_dev reads directly.
+//
+// One allocation holds the network's record (PolicyDesc, fleet_policy.h) and every layer's weights, re-laid at upload as
+// Wt[in][out] with `out` padded to whole wavefronts: the lanes of a wavefront read consecutive addresses.  Two kernels:
+//   policy_forward  grid (ceil(E / 16), heads).  A workgroup takes 16 env rows through every layer of one head; the activations
+//                   ping-pong between two buffers in the LDS.  A lane owns ONE output column and keeps one accumulator per row in
+//                   registers; an activation is read from the LDS by all lanes at the same address (a broadcast), four inputs per
+//                   read.  acc = fmaf(x[k], w[k], acc) in ascending k, then + bias: a result depends on its own row and on nothing
+//                   else.  The first layer's input is staged 128 columns at a time -- and normalised while it is staged, with
+//                   fleet_norm_obs1 (fleet_norm.h), when a normaliser is given -- so D = 1438 needs no whole row in the LDS.
+//                   A wavefront works on units of 64 columns x R rows, at most two, which share their LDS reads: R = 16 for layers
+//                   of 4..8 column groups, 8 for 2..3, 4 for one (four wavefronts split the rows of a 64-wide layer).
+//   policy_relay    load_dev: torch's [out, in] tensors -> the padded [in][out] image, one launch for all of them.
+// Launch boundaries are the only visibility mechanism.  float32 throughout (the normalisation in float64, as everywhere).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "fleet_handle.h"
+#include "fleet_norm.h"
+#include "fleet_policy.h"
+
+namespace {
+
+struct ForwardArgs {
+  const PolicyDesc* desc;
+  const float* base;  // the block: offsets of PolicyLayer count from here
+  const float* obs;
+  float *actions, *values;
+  const double *mean, *sd;  // the normaliser's statistics (kNorm)
+  double clip;
+  int E;
+};
+
+// columns [k0, k0 + kPolicyChunk) of the tile's rows -> xs[row][col]; zeros past D and past E
+template <bool kNorm>
+__device__ __forceinline__ void stage(const ForwardArgs& a, float* xs, int row0, int k0, int D) {
+  const int col = threadIdx.x % kPolicyChunk, r0 = threadIdx.x / kPolicyChunk;
+  const int k = k0 + col;
+  double m = 0.0, s = 1.0;
+  if (kNorm && k < D) {
+    m = a.mean[k];
+    s = a.sd[k];
+  }
+#pragma unroll
+  for (int r = r0; r < kPolicyRows; r += kPolicyThreads / kPolicyChunk) {
+    const int row = row0 + r;
+    float v = 0.0f;
+    if (k < D && row < a.E) {
+      v = a.obs[(size_t)row * D + k];
+      if (kNorm) v = fleet_norm_obs1(v, m, s, a.clip);
+    }
+    xs[r * kPolicyChunk + col] = v;
+  }
+}
+
+// acc[r] += sum over k < kn (a multiple of 4) of xs[r][k] * W[k][j], ascending k, for column j0 (and j1 when kTwo)
+template <int R, bool kTwo>
+__device__ __forceinline__ void accumulate(const float* xs, int stride, int kn, const float* __restrict__ W, int O, int j0, int j1,
+                                           float (&acc0)[R], float (&acc1)[R]) {
+  for (int k = 0; k < kn; k += 4) {
+    const float* w = W + (size_t)k * O;
+    const float a0 = w[j0], a1 = w[O + j0], a2 = w[2 * O + j0], a3 = w[3 * O + j0];
+    float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;
+    if (kTwo) b0 = w[j1], b1 = w[O + j1], b2 = w[2 * O + j1], b3 = w[3 * O + j1];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float4 x = *reinterpret_cast<const float4*>(xs + r * stride + k);  // every lane the same address
+      acc0[r] = fmaf(x.w, a3, fmaf(x.z, a2, fmaf(x.y, a1, fmaf(x.x, a0, acc0[r]))));
+      if (kTwo) acc1[r] = fmaf(x.w, b3, fmaf(x.z, b2, fmaf(x.y, b1, fmaf(x.x, b0, acc1[r]))));
+    }
+  }
+}
+
+__device__ __forceinline__ float hidden_act(float y, int activation) {
+  return activation == FLEET_POLICY_ACT_RELU ? (y < 0.0f ? 0.0f : y) : tanhf(y);  // (a NaN stays one)
+}
+
+__device__ __forceinline__ float output_of(float y, int output, float lo, float hi) {
+  if (output == FLEET_POLICY_OUT_CLIP) return y < lo ? lo : (y > hi ? hi : y);
+  return output == FLEET_POLICY_OUT_TANH ? tanhf(y) : y;
+}
+
+// one layer for the tile: `in` -> `out` (activation buffers in the LDS, row stride S), or the staged input -> ... -> global memory
+template <int R, bool kNorm>
+__device__ __forceinline__ void run_layer(const ForwardArgs& a, const PolicyHeadDesc* H, const PolicyLayer& L, bool first, bool last,
+                                          const float* in, float* out, float* xs, int S, int row0, float* gout) {
+  constexpr int kSplit = kPolicyRows / R;  // row groups per column group
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int units = (L.out64 / 64) * kSplit;
+  const bool has0 = w < units, has1 = w + kPolicyWaves < units;
+  const int q = w % kSplit;  // (kPolicyWaves % kSplit == 0: both units of a wavefront take the same rows)
+  const int j0 = (w / kSplit) * 64 + lane, j1 = ((w + kPolicyWaves) / kSplit) * 64 + lane;
+  float acc0[R], acc1[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc0[r] = acc1[r] = 0.0f;
+  const float* W = a.base + L.w_off;
+  if (first) {
+    for (int k0 = 0; k0 < L.in; k0 += kPolicyChunk) {
+      const int kn = L.in4 - k0 < kPolicyChunk ? L.in4 - k0 : kPolicyChunk;
+      __syncthreads();  // the readers of the chunk before are done
+      stage<kNorm>(a, xs, row0, k0, L.in);
+      __syncthreads();
+      const float* x = xs + q * R * kPolicyChunk;
+      const float* wk = W + (size_t)k0 * L.out64;
+      if (has1) accumulate<R, true>(x, kPolicyChunk, kn, wk, L.out64, j0, j1, acc0, acc1);
+      else if (has0) accumulate<R, false>(x, kPolicyChunk, kn, wk, L.out64, j0, j1, acc0, acc1);
+    }
+  } else if (has1) {
+    accumulate<R, true>(in + q * R * S, S, L.in4, W, L.out64, j0, j1, acc0, acc1);
+  } else if (has0) {
+    accumulate<R, false>(in + q * R * S, S, L.in4, W, L.out64, j0, j1, acc0, acc1);
+  }
+  const int activation = H->activation, output = H->output;
+  const float lo = H->lo, hi = H->hi;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (!(u ? has1 : has0)) continue;
+    const int j = u ? j1 : j0;
+    const float b = a.base[L.b_off + j];  // (padded like the columns: zero past `out`)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float y = (u ? acc1[r] : acc0[r]) + b;
+      const int rr = q * R + r;
+      if (!last) {
+        out[rr * S + j] = hidden_act(y, activation);  // (a padding column gets act(0) = 0: the next layer's padded inputs)
+      } else if (j < L.out && row0 + rr < a.E) {
+        gout[(size_t)(row0 + rr) * L.out + j] = output_of(y, output, lo, hi);
+      }
+    }
+  }
+}
+
+template <bool kNorm>
+__global__ __launch_bounds__(kPolicyThreads) void policy_forward(ForwardArgs a) {
+  extern __shared__ float lds[];  // two activation buffers [16][S], then the staged input [16][kPolicyChunk]
+  const PolicyDesc* __restrict__ d = a.desc;
+  const PolicyHeadDesc* __restrict__ H = &d->head[blockIdx.y];
+  const int S = d->stride;
+  float *cur = lds, *nxt = lds + kPolicyRows * S, *xs = lds + 2 * kPolicyRows * S;
+  const int row0 = blockIdx.x * kPolicyRows;
+  float* gout = blockIdx.y ? a.values : a.actions;
+  const int n = H->n_layers;
+  for (int l = 0; l < n; ++l) {
+    const PolicyLayer L = H->layer[l];
+    const int groups = L.out64 / 64;
+    if (groups >= 4) run_layer<16, kNorm>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout);
+    else if (groups >= 2) run_layer<8, kNorm>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout);
+    else run_layer<4, kNorm>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout);
+    __syncthreads();
+    float* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+}
+
+// ---- policy_relay ----------------------------------------------------------------------------------------------------------------
+constexpr int kPolicyTensors = 2 * FLEET_POLICY_MAX_HEADS * FLEET_POLICY_MAX_LAYERS;
+struct RelayArgs {
+  const float* src[kPolicyTensors];
+  const PolicyDesc* desc;
+  float* base;
+};
+
+// tensor blockIdx.y (W, b per layer, head 0 then head 1): W[out][in] -> Wt[in][out64], b -> b; the padding stays what create made it
+__global__ __launch_bounds__(256) void policy_relay(RelayArgs a) {
+  const PolicyDesc* __restrict__ d = a.desc;
+  int t = blockIdx.y, h = 0;
+  if (t >= 2 * d->head[0].n_layers) {
+    t -= 2 * d->head[0].n_layers;
+    h = 1;
+  }
+  const PolicyLayer L = d->head[h].layer[t >> 1];
+  const float* __restrict__ src = a.src[blockIdx.y];
+  const unsigned stride = gridDim.x * 256, gid = blockIdx.x * 256 + threadIdx.x;
+  if (t & 1) {
+    for (unsigned j = gid; j < (unsigned)L.out; j += stride) a.base[L.b_off + j] = src[j];
+  } else {
+    const unsigned count = (unsigned)L.in * (unsigned)L.out;  // <= 8192 * 512
+    for (unsigned i = gid; i < count; i += stride) {
+      const unsigned k = i / (unsigned)L.out, j = i - k * (unsigned)L.out;
+      a.base[L.w_off + (size_t)k * L.out64 + j] = src[(size_t)j * L.in + k];
+    }
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+thread_local std::string g_policy_create_error;
+
+std::string validate(const FleetPolicyParams* p) {
+  if (!p) return "null FleetPolicyParams";
+  if (p->struct_bytes != (int32_t)sizeof(FleetPolicyParams)) return "FleetPolicyParams.struct_bytes does not match this library";
+  if (p->obs_dim < 1 || p->obs_dim > FLEET_POLICY_MAX_OBS_DIM)
+    return "obs_dim must be in 1.." + std::to_string(FLEET_POLICY_MAX_OBS_DIM) + ", got " + std::to_string(p->obs_dim);
+  if (p->n_heads < 1 || p->n_heads > FLEET_POLICY_MAX_HEADS) return "n_heads must be 1 or 2, got " + std::to_string(p->n_heads);
+  for (int h = 0; h < p->n_heads; ++h) {
+    const FleetPolicyHead& H = p->head[h];
+    const std::string who = "head " + std::to_string(h) + ": ";
+    if (H.n_layers < 1 || H.n_layers > FLEET_POLICY_MAX_LAYERS)
+      return who + "n_layers must be in 1.." + std::to_string(FLEET_POLICY_MAX_LAYERS) + ", got " + std::to_string(H.n_layers);
+    for (int l = 0; l < H.n_layers; ++l)
+      if (H.width[l] < 1 || H.width[l] > FLEET_POLICY_MAX_WIDTH)
+        return who + "width of layer " + std::to_string(l) + " must be in 1.." + std::to_string(FLEET_POLICY_MAX_WIDTH) + ", got " +
+               std::to_string(H.width[l]);
+    if (H.activation != FLEET_POLICY_ACT_TANH && H.activation != FLEET_POLICY_ACT_RELU) return who + "unknown activation";
+    if (H.output != FLEET_POLICY_OUT_NONE && H.output != FLEET_POLICY_OUT_CLIP && H.output != FLEET_POLICY_OUT_TANH)
+      return who + "unknown output transform";
+    if (H.output == FLEET_POLICY_OUT_CLIP && !(H.lo <= H.hi)) return who + "clip bounds need lo <= hi";
+  }
+  return "";
+}
+
+int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// the record of the network and the size of the block (floats)
+size_t describe_layout(const FleetPolicyParams& p, PolicyDesc* d) {
+  *d = PolicyDesc{};
+  d->obs_dim = p.obs_dim, d->n_heads = p.n_heads, d->stride = 64;
+  size_t off = round_up((int)sizeof(PolicyDesc), 256) / 4;
+  for (int h = 0; h < p.n_heads; ++h) {
+    const FleetPolicyHead& H = p.head[h];
+    PolicyHeadDesc& o = d->head[h];
+    o.n_layers = H.n_layers, o.activation = H.activation, o.output = H.output, o.lo = H.lo, o.hi = H.hi;
+    for (int l = 0; l < H.n_layers; ++l) {
+      PolicyLayer& L = o.layer[l];
+      L.in = l ? H.width[l - 1] : p.obs_dim, L.out = H.width[l];
+      L.in4 = round_up(L.in, 4), L.out64 = round_up(L.out, 64);
+      L.w_off = (uint32_t)off;
+      off += (size_t)L.in4 * L.out64;
+      L.b_off = (uint32_t)off;
+      off += (size_t)L.out64;
+      if (l < H.n_layers - 1 && L.out64 > d->stride) d->stride = L.out64;
+    }
+  }
+  return off;  // <= 256 + 2 * 4 * (8192 * 512 + 512) floats: fits the 32-bit offsets
+}
+
+}  // namespace
+
+struct FleetPolicy : FleetHandleBase {
+  FleetPolicyParams p{};
+  PolicyDesc desc{};
+  size_t floats = 0;     // of the block
+  size_t lds_bytes = 0;  // of one workgroup of policy_forward
+  int n_tensors = 0;
+};
+
+namespace {
+
+// the packed weights -> the block's image (the record included); "" or why not
+std::string build_image(const FleetPolicy* h, const float* weights, std::vector<float>* image) {
+  image->assign(h->floats, 0.0f);
+  memcpy(image->data(), &h->desc, sizeof(PolicyDesc));
+  const float* src = weights;
+  for (int hd = 0; hd < h->desc.n_heads; ++hd)
+    for (int l = 0; l < h->desc.head[hd].n_layers; ++l) {
+      const PolicyLayer& L = h->desc.head[hd].layer[l];
+      const size_t count = (size_t)L.in * L.out + L.out;
+      for (size_t i = 0; i < count; ++i)
+        if (!std::isfinite(src[i]))
+          return "head " + std::to_string(hd) + ", layer " + std::to_string(l) + ": " + (i < count - L.out ? "weight " : "bias ") +
+                 std::to_string(i < count - L.out ? i : i - (count - L.out)) + " is not finite";
+      for (int j = 0; j < L.out; ++j)
+        for (int k = 0; k < L.in; ++k) (*image)[L.w_off + (size_t)k * L.out64 + j] = src[(size_t)j * L.in + k];
+      src += (size_t)L.in * L.out;
+      for (int j = 0; j < L.out; ++j) (*image)[L.b_off + j] = src[j];
+      src += L.out;
+    }
+  return "";
+}
+
+int upload(FleetPolicy* h, const std::vector<float>& image) {
+  FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
+  FLEET_HANDLE_TRY(h, hipMemcpyAsync(h->block, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  FLEET_HANDLE_TRY(h, hipStreamSynchronize(h->stream));  // (the image is the caller's stack from here on)
+  return FLEET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fleet_policy_create(int device, const FleetPolicyParams* p, const float* host_weights, fleet_policy_handle* out) {
+  if (out) *out = nullptr;
+  std::string why = validate(p);  // before the device is touched
+  if (why.empty() && !host_weights) why = "null host_weights";
+  if (why.empty() && !out) why = "null output handle";
+  if (!why.empty()) {
+    g_policy_create_error = why;
+    return FLEET_ERR_INVALID;
+  }
+  FleetPolicy* h = new FleetPolicy();
+  h->p = *p;
+  h->p.tile_rows = kPolicyRows;
+  h->floats = describe_layout(*p, &h->desc);
+  h->lds_bytes = ((size_t)2 * kPolicyRows * h->desc.stride + (size_t)kPolicyRows * kPolicyChunk) * sizeof(float);
+  for (int hd = 0; hd < p->n_heads; ++hd) h->n_tensors += 2 * p->head[hd].n_layers;
+  std::vector<float> image;
+  why = build_image(h, host_weights, &image);
+  if (!why.empty()) {
+    g_policy_create_error = why;
+    delete h;
+    return FLEET_ERR_INVALID;
+  }
+  int rc = handle_open(h, device, h->floats * sizeof(float), "policy", &g_policy_create_error);
+  if (rc == FLEET_OK) {
+    // more than the 64 KiB a launch gets unasked when a hidden layer is wider than 448; the attribute belongs to the kernel, not
+    // to the handle, so every policy asks for what the widest one needs
+    constexpr int kMaxLds = (2 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk) * (int)sizeof(float);
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
+      (void)hipGetLastError();
+      g_policy_create_error = "hipFuncSetAttribute failed for the policy kernel's " + std::to_string(kMaxLds) + " bytes of LDS";
+      rc = FLEET_ERR_HIP;
+    }
+  }
+  if (rc == FLEET_OK && (rc = upload(h, image)) != FLEET_OK) g_policy_create_error = h->error;
+  if (rc != FLEET_OK) {
+    fleet_policy_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return FLEET_OK;
+}
+
+int fleet_policy_destroy(fleet_policy_handle h) {
+  if (!h) return FLEET_OK;
+  handle_close(h);
+  delete h;
+  return FLEET_OK;
+}
+
+const char* fleet_policy_last_error(fleet_policy_handle h) { return h ? h->error.c_str() : g_policy_create_error.c_str(); }
+
+int fleet_policy_set_stream(fleet_policy_handle h, void* hip_stream) { return h ? handle_set_stream(h, hip_stream) : FLEET_ERR_INVALID; }
+
+int fleet_policy_load_host(fleet_policy_handle h, const float* weights) {
+  if (!h) return FLEET_ERR_INVALID;
+  if (!weights) {
+    h->error = "fleet_policy_load_host: null weights";
+    return FLEET_ERR_INVALID;
+  }
+  std::vector<float> image;
+  const std::string why = build_image(h, weights, &image);
+  if (!why.empty()) {
+    h->error = "fleet_policy_load_host: " + why;
+    return FLEET_ERR_INVALID;
+  }
+  return upload(h, image);
+}
+
+int fleet_policy_load_dev(fleet_policy_handle h, const float* const* tensors, int count) {
+  if (!h) return FLEET_ERR_INVALID;
+  if (!tensors || count != h->n_tensors) {
+    h->error = "fleet_policy_load_dev: expected " + std::to_string(h->n_tensors) + " tensors (W, b per layer), got " +
+               (tensors ? std::to_string(count) : std::string("a null array"));
+    return FLEET_ERR_INVALID;
+  }
+  RelayArgs a{};
+  for (int i = 0; i < count; ++i) {
+    if (!tensors[i]) {
+      h->error = "fleet_policy_load_dev: tensor " + std::to_string(i) + " is null";
+      return FLEET_ERR_INVALID;
+    }
+    a.src[i] = tensors[i];
+  }
+  a.desc = reinterpret_cast<const PolicyDesc*>(h->block);
+  a.base = reinterpret_cast<float*>(h->block);
+  FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
+  hipLaunchKernelGGL(policy_relay, dim3(64, count), dim3(256), 0, h->stream, a);
+  FLEET_HANDLE_TRY(h, hipGetLastError());
+  return FLEET_OK;
+}
+
+int fleet_policy_forward_dev(fleet_policy_handle h, const float* obs, int E, fleet_norm_handle norm, float* actions, float* values) {
+  if (!h) return FLEET_ERR_INVALID;
+  if (!obs || !actions) {
+    h->error = "fleet_policy_forward_dev: null obs or actions";
+    return FLEET_ERR_INVALID;
+  }
+  if (E < 1) {
+    h->error = "fleet_policy_forward_dev: E must be >= 1, got " + std::to_string(E);
+    return FLEET_ERR_INVALID;
+  }
+  if (values && h->p.n_heads < 2) {
+    h->error = "fleet_policy_forward_dev: values asked of a policy without a critic head";
+    return FLEET_ERR_INVALID;
+  }
+  ForwardArgs a{};
+  a.desc = reinterpret_cast<const PolicyDesc*>(h->block);
+  a.base = reinterpret_cast<const float*>(h->block);
+  a.obs = obs, a.actions = actions, a.values = values, a.E = E;
+  FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
+  bool norm_obs = false;
+  if (norm) {
+    FleetNormView v{};
+    FLEET_HANDLE_TRY(h, fleet_norm_begin_read(norm, h->stream, &v));
+    if (v.D != h->p.obs_dim || v.device != h->device) {
+      h->error = "fleet_policy_forward_dev: the normaliser has obs_dim " + std::to_string(v.D) + " on device " + std::to_string(v.device) +
+                 ", the policy " + std::to_string(h->p.obs_dim) + " on device " + std::to_string(h->device);
+      return FLEET_ERR_INVALID;
+    }
+    a.mean = v.obs_mean, a.sd = v.obs_sd, a.clip = v.clip_obs;
+    norm_obs = v.norm_obs != 0;
+  }
+  const dim3 grid((unsigned)(((size_t)E + kPolicyRows - 1) / kPolicyRows), values ? 2 : 1), block(kPolicyThreads);
+  if (norm_obs) hipLaunchKernelGGL(policy_forward<true>, grid, block, h->lds_bytes, h->stream, a);
+  else hipLaunchKernelGGL(policy_forward<false>, grid, block, h->lds_bytes, h->stream, a);
+  FLEET_HANDLE_TRY(h, hipGetLastError());
+  if (norm) FLEET_HANDLE_TRY(h, fleet_norm_end_read(norm, h->stream));
+  return FLEET_OK;
+}
+
+int fleet_policy_describe(fleet_policy_handle h, FleetPolicyParams* out) {
+  if (!h || !out) return FLEET_ERR_INVALID;
+  *out = h->p;
+  return FLEET_OK;
+}
+
+}  // extern "C"

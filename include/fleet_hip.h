@@ -816,6 +816,72 @@ int fleet_replay_size(fleet_replay_handle r, int32_t* pos, int32_t* full, int32_
 /* what a caller needs to resume (the arrays themselves are the caller's to fill): 0 <= pos < R, full 0 / 1, the call counter */
 int fleet_replay_set_position(fleet_replay_handle r, int32_t pos, int32_t full, uint64_t calls);
 
+/* ---- MLP policy on the device (fleet_policy.hip; DESIGN.md "The agent's forward pass on the device") ---------------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * The deterministic forward pass of a trained stable-baselines3 MLP policy, float32 throughout, ONE launch per forward.  A policy
+ * is one or two heads over the same [E,D] float32 input: head 0 the actor, head 1 an optional critic.  A head is a chain of
+ * 1..FLEET_POLICY_MAX_LAYERS linear layers y = W x + b (W float32 [out, in], torch's layout), a hidden activation after every
+ * layer but the last, and an output transform after the last:
+ *   NONE  y        CLIP  min(max(y, lo), hi) (SB3's clip of a Gaussian policy's mean to the action space)        TANH  tanh(y)
+ * Every output element is one chain acc = 0; acc = fmaf(x[k], W[j][k], acc) for k = 0 .. in-1; y = acc + b[j], evaluated by one
+ * lane: a row's result does not depend on E, on the row's position in the batch, on the stream or on the other head.
+ * Input normalisation (a fleet_norm_handle given): the input is the RAW observation and each element goes through the normaliser's
+ * own arithmetic first, x' = (float)clip(((double)x - mean[col]) / sd[col], +-clip_obs), with its statistics as they are when the
+ * launch RUNS, behind the normaliser's last enqueued launch; with its norm_obs off the input passes through.  Nothing is updated.
+ * Every *_dev call takes device pointers, only enqueues (no host synchronisation) and runs on the policy's stream: its own, or the
+ * one fleet_policy_set_stream borrowed.  Calls on one policy are serialised by the caller.  No atomics, no random numbers. */
+#define FLEET_POLICY_MAX_HEADS 2
+#define FLEET_POLICY_MAX_LAYERS 4
+#define FLEET_POLICY_MAX_WIDTH 512
+#define FLEET_POLICY_MAX_OBS_DIM 8192
+#define FLEET_POLICY_ACT_TANH 0
+#define FLEET_POLICY_ACT_RELU 1
+#define FLEET_POLICY_OUT_NONE 0
+#define FLEET_POLICY_OUT_CLIP 1
+#define FLEET_POLICY_OUT_TANH 2
+typedef struct FleetPolicyHead {
+  int32_t n_layers;                        /* linear layers, 1..FLEET_POLICY_MAX_LAYERS */
+  int32_t width[FLEET_POLICY_MAX_LAYERS];  /* outputs of layer l, 1..FLEET_POLICY_MAX_WIDTH; the last one is the head's output width */
+  int32_t activation;                      /* FLEET_POLICY_ACT_*, after every layer but the last */
+  int32_t output;                          /* FLEET_POLICY_OUT_*, after the last layer */
+  int32_t reserved;                        /* 0 */
+  float lo, hi;                            /* FLEET_POLICY_OUT_CLIP: lo <= hi */
+} FleetPolicyHead;
+typedef struct FleetPolicyParams {
+  int32_t struct_bytes;  /* sizeof(FleetPolicyParams) */
+  int32_t obs_dim;       /* D, 1..FLEET_POLICY_MAX_OBS_DIM */
+  int32_t n_heads;       /* 1 (actor) or 2 (actor, critic) */
+  int32_t tile_rows;     /* out (fleet_policy_describe): env rows one workgroup takes through every layer; ignored by create */
+  FleetPolicyHead head[FLEET_POLICY_MAX_HEADS];
+} FleetPolicyParams;
+typedef struct FleetPolicy* fleet_policy_handle;
+
+/* The parameters and the weights are validated BEFORE the device is touched: FLEET_ERR_INVALID (fleet_policy_last_error(NULL)
+ * says why) for obs_dim outside 1..8192, a width outside 1..512, a layer count outside 1..4, n_heads outside 1..2, an unknown
+ * activation or output transform, lo > hi or a NaN bound, a wrong struct_bytes, a null pointer, a weight that is not finite.
+ * host_weights: packed float32 in declaration order -- for head 0 then head 1, for each layer W[out, in] (row-major) then b[out]. */
+int fleet_policy_create(int device, const FleetPolicyParams* p, const float* host_weights, fleet_policy_handle* out);
+int fleet_policy_destroy(fleet_policy_handle h);
+const char* fleet_policy_last_error(fleet_policy_handle h);  /* h may be NULL: error of the last failed fleet_policy_create */
+/* launch on an external hipStream_t (borrowed; NULL = the null stream) from now on instead of the policy's own stream; waits for
+ * what the previous stream still holds of this policy's work */
+int fleet_policy_set_stream(fleet_policy_handle h, void* hip_stream);
+/* New weights from HOST memory, packed as for create; FLEET_ERR_INVALID (nothing changes) when one is not finite.  The upload is
+ * enqueued behind the policy's earlier forwards, and the host waits for it. */
+int fleet_policy_load_host(fleet_policy_handle h, const float* weights);
+/* New weights from DEVICE memory: `tensors` is a host array of `count` device pointers, torch's parameter tensors in declaration
+ * order (W, b per layer, head 0 then head 1; count must be twice the number of layers).  One launch on the policy's stream copies
+ * and re-lays them, no host synchronisation: a training loop refreshes the device policy after an optimiser step.  The values are
+ * not inspected (that would need the host): a weight that is not finite shows in the outputs. */
+int fleet_policy_load_dev(fleet_policy_handle h, const float* const* tensors, int count);
+/* One launch: actions f32[E, width of head 0] <- head 0 of obs f32[E,D]; values f32[E, width of head 1] <- head 1 when `values` is
+ * not NULL (FLEET_ERR_INVALID on a one-head policy).  norm: NULL, or the normaliser whose statistics the input goes through (its
+ * obs_dim must be D and its device the policy's, else FLEET_ERR_INVALID; its num_envs is not looked at).  FLEET_ERR_INVALID for
+ * E < 1 or a null obs / actions.  The outputs may feed fleet_step_dev directly (FLEET_ACT_F32). */
+int fleet_policy_forward_dev(fleet_policy_handle h, const float* obs, int E, fleet_norm_handle norm, float* actions, float* values);
+/* the parameters the policy was created with, and tile_rows */
+int fleet_policy_describe(fleet_policy_handle h, FleetPolicyParams* out);
+
 #ifdef __cplusplus
 }
 #endif
