@@ -8,7 +8,8 @@
 //                   ping-pong between two buffers in the LDS.  A lane owns ONE output column and keeps one accumulator per row in
 //                   registers; an activation is read from the LDS by all lanes at the same address (a broadcast), four inputs per
 //                   read.  acc = fmaf(x[k], w[k], acc) in ascending k, then + bias: a result depends on its own row and on nothing
-//                   else.  The first layer's input is staged 128 columns at a time -- and normalised while it is staged, with
+//                   else, and for finite inputs it is that chain bit for bit (tests/policy_bits.py restates it; an infinite input
+//                   turns a hidden layer's padded columns into inf * 0 = NaN, and with them its row).  The first layer's input is staged 128 columns at a time -- and normalised while it is staged, with
 //                   fleet_norm_obs1 (fleet_norm.h), when a normaliser is given -- so D = 1438 needs no whole row in the LDS.
 //                   A wavefront works on units of 64 columns x R rows, at most two, which share their LDS reads: R = 16 for layers
 //                   of 4..8 column groups, 8 for 2..3, 4 for one (four wavefronts split the rows of a 64-wide layer).

@@ -824,7 +824,11 @@ int fleet_replay_set_position(fleet_replay_handle r, int32_t pos, int32_t full, 
  * layer but the last, and an output transform after the last:
  *   NONE  y        CLIP  min(max(y, lo), hi) (SB3's clip of a Gaussian policy's mean to the action space)        TANH  tanh(y)
  * Every output element is one chain acc = 0; acc = fmaf(x[k], W[j][k], acc) for k = 0 .. in-1; y = acc + b[j], evaluated by one
- * lane: a row's result does not depend on E, on the row's position in the batch, on the stream or on the other head.
+ * lane: a row's result does not depend on E, on the row's position in the batch, on the stream or on the other head.  For finite
+ * inputs that chain is the result bit for bit (ReLU is y < 0 ? 0 : y, CLIP y < lo ? lo : (y > hi ? hi : y)).  An input element that
+ * is not finite reaches no other row; in its own row the result is the chain's or NaN, because the layout's zero padding meets it
+ * (inf * 0 in a padded column of a hidden layer, read by the next layer when its `in` is no multiple of 4): 20-1-3 with one +inf
+ * input gives NaN where the chain gives the bias or an infinity.
  * Input normalisation (a fleet_norm_handle given): the input is the RAW observation and each element goes through the normaliser's
  * own arithmetic first, x' = (float)clip(((double)x - mean[col]) / sd[col], +-clip_obs), with its statistics as they are when the
  * launch RUNS, behind the normaliser's last enqueued launch; with its norm_obs off the input passes through.  Nothing is updated.
