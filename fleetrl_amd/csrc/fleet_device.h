@@ -1,5 +1,5 @@
 // fleet_device.h -- device-side view of one env batch (kernel argument block) shared by the kernels
-// (fleet_kernels.hip) and the host side of the C ABI (fleet_capi.hip).  gfx950 only.
+// (fleet_kernels.hip and the headers it includes) and the host side of the C ABI (fleet_capi.hip).  gfx950 only.
 //
 // Layout rules (DESIGN.md "Data layout in HBM"):
 //   * everything a lane reads AND writes every step sits in one dense 16-byte record per (env, EV): one 16-byte load /
@@ -19,7 +19,7 @@
 #include "../../include/fleet_hip.h"
 
 // ---- read-only tables ---------------------------------------------------------------------------------------
-// Physics row of time row t (72 B): per-time scalars pre-combined on the host (fleet_capi.hip build_phys_rows()).
+// Physics row of time row t (72 B): per-time scalars pre-combined on the host (fleet_tables.hip build_phys_rows()).
 // k_charge / k_discharge / pv_share use exactly the reference's float64 operations (bit-identical); k_cost / k_rev
 // re-associate two multiplications of the money terms (cashflow differs from the reference by <= 1 ulp per EV).
 struct PhysRow {
@@ -42,7 +42,7 @@ struct PhysRow {
 // falls by dt per row, so consecutive rows form a SEGMENT and every row of a segment holds the SAME record: the two constant
 // columns, the departure row `time_left` counts down to, and the first row after the segment.  A lane that holds the record
 // of one row therefore holds the record of every row up to `seg_end` and only has to touch the table when it crosses a
-// segment boundary (about four times per EV and day).  Built by fleet_create (fleet_capi.hip build_seg_rows), which checks
+// segment boundary (about four times per EV and day).  Built by fleet_create (fleet_tables.hip build_seg_rows), which checks
 // row by row that the float32 `time_left` the table holds is exactly what `seg_tl` derives; a row where it is not (irregular
 // time grids, hand-made tables) becomes a one-row segment that carries its `time_left` verbatim (SEG_RAW).
 struct SegRec {
@@ -225,7 +225,7 @@ struct FleetDev {
   // auxiliary observation slots (observer_*.py:85-91), computed per lane from the carried schedule record:
   // hn_scale = nominal capacity / (evse * eta_c); the normaliser's reciprocals are in FleetCold
   double hn_scale;
-  double inv_eta_c;  // 1 / eta_c, correctly rounded (host): `need / eta_c` as div_rcp (fleet_kernels.hip)
+  double inv_eta_c;  // 1 / eta_c, correctly rounded (host): `need / eta_c` as div_rcp (fleet_wave.h)
   // ---- read-only tables ---------------------------------------------------------------------------------
   const SegRec* seg;          // [T,N] schedule records in run-length form
   const PhysRow* tab_phys;    // [T]
@@ -260,7 +260,7 @@ struct FleetDev {
   int rf_row_stride;  // doubles per row (multiple of 16)
 };
 
-// launchers implemented in fleet_kernels.hip
+// launchers implemented in fleet_step_plan.h (the host half of fleet_kernels.hip, which includes it)
 hipError_t fleet_launch_reset(const FleetDev& d, const uint8_t* mask, float* obs, hipStream_t s);
 // (fleet_max_evs_per_lane_group, include/fleet_hip.h: up to this many EVs per env the single-step kernel gives every EV a lane,
 // fleet_kernels.hip kMaxGroup)
@@ -300,5 +300,5 @@ hipError_t fleet_launch_gather_field(const FleetDev& d, int field, void* out, hi
 // div_rcp (the charge arithmetic's divisions by a reciprocal) against the IEEE sequence on n random operand pairs: bad_dev[0..1]
 // cycle_stress against library double precision on n random triples: worst_dev[0] = bits of the largest relative difference
 hipError_t fleet_launch_selftest_stress(unsigned long long n, unsigned long long seed, unsigned long long* worst_dev, hipStream_t s);
-const char* fleet_kernels_src_sha();  // FLEET_SRC_SHA as compiled into the library's kernels (fleet_kernels.hip)
+const char* fleet_kernels_src_sha();  // FLEET_SRC_SHA as compiled into the library's kernels (fleet_kernels.hip; build.py hashes every source and header)
 hipError_t fleet_launch_selftest_division(unsigned long long n, unsigned long long seed, unsigned long long* bad_dev, hipStream_t s);

@@ -30,7 +30,8 @@
 //     A run whose queue moved in its middle is void and says so; between runs a move is harmless;
 //   * the agent is the one with the HIP device's PCI address -- never "the n-th GPU agent" (HIP and HSA enumerate differently under
 //     *_VISIBLE_DEVICES);
-//   * the code object must carry the source hash the library was compiled with.
+//   * the code object must carry the source hash the library was compiled with (fleetrl_amd/build.py source_sha: every source and
+//     header, the headers fleet_kernels.hip is made of included).
 //
 // What a caller may rely on: nothing of the run is visible before it has completed (fleet_synchronize / the next call on the handle
 // waits for it), everything after.  What the library relies on beside the placement: the single-step kernels touch an env's state only

@@ -1,16 +1,22 @@
 // fleet_kernels.hip -- the FleetEnv step / reset hot path as hand-written HIP for gfx950 (MI355X, CDNA4).
 //
-// What runs here (reference: /root/reference/fleetrl, float64 in the reference's operation order):
+// What runs here (reference: the fleetrl package, float64 in the reference's operation order):
 //   EvCharger.charge            utils/ev_charging/ev_charger.py:39-231
 //   LoadCalculation.check_violation + ScoreConfig.overloading_penalty
 //                               utils/load_calculation/load_calculation.py:83-94, fleet_env/config/score_config.py:33-41
 //   arrival/departure state machine + ScoreConfig.soc_violation_penalty
 //                               fleet_env/fleet_environment.py:528-623, score_config.py:26-30
-//   Observer*.get_obs + Unit/OracleNormalization.normalize_obs
-//                               utils/observation/observer_*.py, utils/normalization/*.py
-//   LogDataDeg.log_soc, RainflowSeiDegradation / EmpiricalDegradation.calculate_degradation
-//                               utils/battery_degradation/*.py  (+ third-party rainflow.extract_cycles)
-//   FleetEnv.reset (incl. the vec-env auto-reset)  fleet_environment.py:330-434
+// and, in the headers this file includes (each opens with what it provides, what it restates and what it expects of its caller):
+//   fleet_stamps.h       diagnostic time stamps (FLEET_STAMPS builds only)
+//   fleet_wave.h         lane-group reductions, the start-row sampler, division by a reciprocal, the sigmoid penalties
+//   fleet_obs.h          state addressing and stores; Observer*.get_obs + Unit/OracleNormalization.normalize_obs
+//   fleet_rainflow.h     LogDataDeg.log_soc, RainflowSeiDegradation / EmpiricalDegradation.calculate_degradation
+//                        ("Rainflow without a history replay" is described there)
+//   fleet_reset.h        FleetEnv.reset (incl. the vec-env auto-reset) and fleet_reset_kernel
+//   fleet_aux_kernels.h  dist factor, field gather, terminal-observation compaction, the two self-test kernels
+//   fleet_step_plan.h    the host half: instance selection and every launcher
+// This file stays the ONE translation unit (compiled into the library and, once more, into the code object of the direct-launch
+// queue): it keeps the step -- ev_finish, ev_physics, the kernel-argument structs and fleet_step_kernel.
 //
 // Mapping.  One *group* of G lanes owns one env.  Up to 256 EVs per env every EV has a lane of its own: G = the smallest power
 // of two >= N up to 64 (a 64-lane wavefront holds 64/G envs, a 256-thread workgroup 256/G), and two or four whole wavefronts of
@@ -27,73 +33,23 @@
 // the table when row t+2 crosses a schedule event of its EV (about 4 % of the EV-steps), for the NEXT launch.  The row
 // flags the state machine needs travel in the env head; the physics record of the time row is requested when the head
 // arrives and consumed late (money terms); the four table-derived auxiliary observation slots are computed per lane from the
-// carried record (one reciprocal, no division; write_obs_ev).
-//
-// Rainflow without a history replay.  The reference re-runs rainflow over the whole episode history every
-// simulated day.  Three-point rainflow is a streaming algorithm, so the kernel keeps its state per EV (a row in HBM:
-// closed-cycle count, sum of cycle means, the two newest stack entries, stress sum of the closed cycles that fall into the
-// reference's slice, reversal stack; slope sign and stack size in the hot record) and feeds it ONE sample per step; the row
-// is only touched by a step that pushes a reversal point, requested in the middle of the step and consumed at its end.  On the daily 14:45 row
-// the forced last point and the residual half cycles are evaluated on a *virtual* copy of the stack (registers
-// only), which reproduces the reference's full recount, including its cross-episode bookkeeping
-// (rainflow_length, quirk Q6), at O(stack depth) instead of O(history).
+// carried record (one reciprocal, no division; write_obs_ev in fleet_obs.h).
 #include "fleet_device.h"
 #include <cstddef>
-#include <cstdio>
-#include <cstring>
 
-#ifdef FLEET_STAMPS
-// Diagnostic build only (tools/stamps.py): s_memtime stamps of every wave (the first 4096) at fixed points of the step,
-// written to a buffer nothing else reads.  Never compiled into the product library.
-__device__ unsigned long long fleet_stamp_buf[4096 * 32];
-#define FLEET_STAMP(k)                                                                                   \
-  do {                                                                                                   \
-    __builtin_amdgcn_sched_barrier(0);                                                                   \
-    unsigned long long _t;                                                                               \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");                           \
-    __builtin_amdgcn_sched_barrier(0);                                                                   \
-    const unsigned _w = blockIdx.x * (FLEET_KBLOCK / 64) + threadIdx.x / 64;                             \
-    if ((threadIdx.x & 63) == 0 && _w < 4096) fleet_stamp_buf[_w * 32 + (k)] = _t;                       \
-  } while (0)
-// wall-clock stamps (s_memrealtime: 100 MHz, one counter for the whole chip) at a wave's entry (slot 9) and exit (slot 10):
-// the launch's timeline across dies, which the per-die shader-clock stamps cannot give
-#define FLEET_STAMP_RT(k)                                                                                \
-  do {                                                                                                   \
-    const unsigned long long _t = __builtin_amdgcn_s_memrealtime();                                      \
-    const unsigned _w = blockIdx.x * (FLEET_KBLOCK / 64) + threadIdx.x / 64;                             \
-    if ((threadIdx.x & 63) == 0 && _w < 4096) fleet_stamp_buf[_w * 32 + (k)] = _t;                       \
-  } while (0)
-// where the wavefront runs (slot 16: HW_REG_HW_ID = wave / SIMD / CU / SH / SE ids; slot 17: HW_REG_XCC_ID): does the tail of slow
-// wavefronts belong to a die, a CU, a SIMD?
-#define FLEET_STAMP_WHERE()                                                                              \
-  do {                                                                                                   \
-    const unsigned _hw = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));                         \
-    const unsigned _xc = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));                        \
-    const unsigned _w = blockIdx.x * (FLEET_KBLOCK / 64) + threadIdx.x / 64;                             \
-    if ((threadIdx.x & 63) == 0 && _w < 4096) {                                                          \
-      fleet_stamp_buf[_w * 32 + 16] = _hw;                                                               \
-      fleet_stamp_buf[_w * 32 + 17] = _xc;                                                               \
-    }                                                                                                    \
-  } while (0)
-extern "C" int fleet_debug_read_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(fleet_stamp_buf), sizeof(fleet_stamp_buf));
-}
-#else
-#define FLEET_STAMP(k) do {} while (0)
-#define FLEET_STAMP_RT(k) do {} while (0)
-#define FLEET_STAMP_WHERE() do {} while (0)
-#endif
+#include "fleet_stamps.h"
 
 namespace {
 
-// Minimum workgroups per CU the kernels are compiled for (= waves per SIMD; register budget 512 / this).  The single-step
-// kernel needs 97 VGPRs.  The multi-step kernel wants ~150; its wavefronts advance independently and are bound by their own
-// dependent round trips, so what counts is that all of a 4096-env batch's wavefronts are resident at once: it is compiled for
-// four per SIMD (128 VGPRs, a few dozen bytes of spills) -- +21 % env-steps/s over the three its natural register count
-// allows (profiles/r03_experiments/ab_multiwaves.log).  With several EVs per lane it stays at two.
+// Minimum workgroups per CU the kernels are compiled for (= waves per SIMD; register budget 512 / this).  What the instances
+// need is tabulated in DESIGN.md section 4 ("Registers and occupancy", from tools/kres.sh).  The multi-step kernel wants ~150
+// VGPRs; its wavefronts advance independently and are bound by their own dependent round trips, so what counts is that all of a
+// 4096-env batch's wavefronts are resident at once: it is compiled for four per SIMD (128 VGPRs, a few dozen bytes of spills) --
+// +21 % env-steps/s over the three its natural register count allows (profiles/r03_experiments/ab_multiwaves.log).  With several
+// EVs per lane it stays at two.
 constexpr int kSingleWaves = 4, kMultiWaves = 4, kMultiWideWaves = 2;
 #ifndef FLEET_KBLOCK
-#define FLEET_KBLOCK 256  // (a macro only because the diagnostic stamp code above indexes its buffer with it)
+#define FLEET_KBLOCK 256  // (a macro only because the diagnostic stamp code of fleet_stamps.h indexes its buffer with it)
 #endif
 constexpr int kBlock = FLEET_KBLOCK;  // threads per workgroup
 // Largest lane group of one env in the single-step kernel: up to this many EVs every EV has a lane of its own.  Groups above 64
@@ -103,716 +59,14 @@ constexpr int kBlock = FLEET_KBLOCK;  // threads per workgroup
 constexpr int kMaxGroup = 256;
 static_assert(kMaxGroup <= kBlock && kBlock % 64 == 0, "a lane group is a whole number of a workgroup's wavefronts");
 
-// ---------------------------------------------------------------------------------------------------------
-// wavefront helpers
-// ---------------------------------------------------------------------------------------------------------
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_add(double v) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  // old = 0 and bound_ctrl = 1: lanes whose source is out of range (or whose row is masked off) add 0.0
-  int l2 = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xF, true);
-  int h2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xF, true);
-  return v + __hiloint2double(h2, l2);
-}
+}  // namespace
 
-// Sum over the G lanes of an aligned group; the result is valid in the LAST lane of the group.
-// row_shr:1/2/4/8 (0x111..0x118) scan inside a 16-lane row, row_bcast:15 (0x142) and row_bcast:31 (0x143)
-// carry row totals across rows.  All 64 lanes must execute this (uniform control flow).
-// true in every lane of the group if `v` holds in any of its lanes (real_time event test)
-template <int G>
-__device__ __forceinline__ bool group_any(bool v) {
-  const unsigned long long m = __ballot(v);
-  if (G >= 64) return m != 0ull;  // (groups of several wavefronts never run the event-skipping loop: plan_step_gd)
-  const int base = (int)(threadIdx.x % 64) & ~(G - 1);
-  return ((m >> base) & ((1ull << (G % 64)) - 1ull)) != 0ull;
-}
+#include "fleet_wave.h"
+#include "fleet_obs.h"
+#include "fleet_rainflow.h"
+#include "fleet_reset.h"
 
-template <int G>
-__device__ __forceinline__ double group_sum_to_last(double v) {
-  if (G >= 2) v = dpp_add<0x111, 0xF>(v);
-  if (G >= 4) v = dpp_add<0x112, 0xF>(v);
-  if (G >= 8) v = dpp_add<0x114, 0xF>(v);
-  if (G >= 16) v = dpp_add<0x118, 0xF>(v);
-  if (G >= 32) v = dpp_add<0x142, 0xA>(v);
-  if (G >= 64) v = dpp_add<0x143, 0xC>(v);
-  return v;
-}
-
-// Four per-env sums at once for one env per wavefront (G == 64); the totals are valid in the LAST lane.  The quantities are
-// folded pairwise with the gfx950 lane-swap instructions -- after `v_permlane32_swap` one register holds the lower half's
-// values of a AND b, the other the upper half's, so ONE add folds two quantities from 64 to 32 lanes; `v_permlane16_swap`
-// does the same from 32 to 16 -- which leaves each quantity spread over one 16-lane row; four DPP row shifts finish the rows
-// and three lane reads bring the other rows' totals to the last lane: 27 vector instructions instead of 18 per quantity.
-__device__ __forceinline__ double swap_fold32(double a, double b) {
-  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);  // lanes 0-31: a folded, 32-63: b folded
-}
-__device__ __forceinline__ double swap_fold16(double x, double y) {
-  const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
-  const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
-  return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);  // rows: x.r0+x.r1, y.r0+y.r1, x.r2+x.r3, y.r2+y.r3
-}
-__device__ __forceinline__ double lane_read(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-__device__ __forceinline__ void wave_sum4_to_last(double& a, double& b, double& c, double& dd) {
-  double z = swap_fold16(swap_fold32(a, b), swap_fold32(c, dd));  // row 0: a, row 1: c, row 2: b, row 3: dd (16 partial sums each)
-  z = dpp_add<0x111, 0xF>(z);
-  z = dpp_add<0x112, 0xF>(z);
-  z = dpp_add<0x114, 0xF>(z);
-  z = dpp_add<0x118, 0xF>(z);  // row totals in lanes 15, 31, 47, 63
-  a = lane_read(z, 15);
-  c = lane_read(z, 31);
-  b = lane_read(z, 47);
-  dd = z;  // the last lane's own row
-}
-
-// Philox4x32-10 start-row sampler; same specification as the oracle's (counter = (global env, episode, 0, 0)).
-__device__ __forceinline__ uint32_t philox_start(unsigned long long seed, uint32_t env, uint32_t episode) {
-  uint32_t c0 = env, c1 = episode, c2 = 0, c3 = 0;
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c0;
-}
-
-__device__ __forceinline__ int choose_start(const FleetCold* cd, int E, int e, int episode) {
-  if (cd->sched_n > 0) return cd->sched[(size_t)(episode % cd->sched_n) * E + e];
-  int k = cd->start_lo;
-  if (cd->picker_mode != FLEET_PICK_STATIC) {
-    const uint32_t range = (uint32_t)(cd->start_hi - cd->start_lo + 1);
-    const uint32_t x = philox_start(cd->seed, (uint32_t)(cd->env_id_offset + e), (uint32_t)episode);
-    k += (int)__umulhi(x, range);
-  }
-  return cd->pick_rows ? cd->pick_rows[k] : k;  // candidate list of the pickers' date_range on an irregular grid
-}
-
-// 1 / x for the auxiliary slots' one division: hardware reciprocal seed (v_rcp_f64, ~26 good bits) + two Newton steps = full
-// float64 accuracy (<= 1 ulp) in five instructions, against ~14 of the IEEE division sequence with its special-case handling.
-__device__ __forceinline__ double rcp_newton(double x) {
-  double r = __builtin_amdgcn_rcp(x);
-  r = fma(fma(-x, r, 1.0), r, r);
-  r = fma(fma(-x, r, 1.0), r, r);
-  return r;
-}
-// The same with ONE Newton step: relative error <= ~2^-44 (the seed is good to ~2^-23).  Enough wherever the result is rounded
-// to float32 afterwards or feeds div_rcp's residual correction (which squares the reciprocal's error once more).
-__device__ __forceinline__ double rcp_newton1(double x) {
-  const double r = __builtin_amdgcn_rcp(x);
-  return fma(fma(-x, r, 1.0), r, r);
-}
-// x / c, IEEE-correctly rounded, from a reciprocal rc ~ 1 / c (Markstein's residual correction): q0 = x * rc is within a few
-// ulp of the quotient, e = x - q0 * c is EXACT in one fma, and q0 + e * rc is the quotient to a relative 2 * |rc * c - 1|^2
-// (2^-104 for a correctly rounded rc, 2^-87 for rcp_newton1) before the final rounding -- i.e. the correctly rounded quotient
-// unless x / c lies that close to a rounding boundary, which no pair of float64 operands of these magnitudes does in practice
-// (tests/test_capi_gpu.py::test_division_by_reciprocal_is_bit_exact: 2^30 operand pairs of the charge arithmetic's ranges
-// against the IEEE sequence, 0 differences).  `v_div_fixup` restores what the three fmas lose at the edges (x = +-0, inf, NaN,
-// c = 0): 5 vector instructions instead of the 11 of the IEEE division sequence, none of them quarter-rate.
-__device__ __forceinline__ double div_rcp(double x, double c, double rc) {
-  const double q0 = x * rc;
-  const double e = fma(-q0, c, x);
-  return __builtin_amdgcn_div_fixup(fma(e, rc, q0), c, x);
-}
-
-// ScoreConfig.soc_violation_penalty (score_config.py:26-30)
-__device__ __forceinline__ double soc_violation_penalty(double missing) {
-  return -500.0 * rcp_newton(1.0 + exp(-16.48461585 * (missing - 0.29229767))) + 1.0;  // (<= 2 ulp of the quotient)
-}
-
-// ScoreConfig.overloading_penalty (score_config.py:33-41)
-__device__ __forceinline__ double overloading_penalty(double rel, double scale) {
-  const double pen = (rel < 1.1) ? 0.0 : -700.0 / (1.0 + exp(-15.77350877 * (rel - 1.33298382)));
-  return pen * scale;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// observation assembly (observer_*.py + normalization/*.py); layout: DESIGN.md "Observation row"
-// ---------------------------------------------------------------------------------------------------------
-typedef float fleet_v4f __attribute__((ext_vector_type(4)));
-// Observation rows are written once and read by nobody on the chip: non-temporal stores (-1.5 % per launch, r03 ab_nt.log).
-// Everything else is stored plain: write-through (`sc1`) and non-temporal state stores were measured on every class of store
-// and lose everywhere (profiles/r03_experiments/ab_stores.log).
-__device__ __forceinline__ void st_obs(float* p, float v) { __builtin_nontemporal_store(v, p); }
-template <typename T>
-__device__ __forceinline__ void st_rec16(T* p, const T& v) {  // a 16-byte record as ONE store
-  static_assert(sizeof(T) == 16, "16-byte record");
-  fleet_v4f w;
-  __builtin_memcpy(&w, &v, 16);
-  *reinterpret_cast<fleet_v4f*>(p) = w;
-}
-// base + 32-bit byte offset.  The offset is made opaque at every use: its 64-bit zero-extension must be formed in the basic
-// block of the access for the instruction selector to see "uniform base + 32-bit lane offset" (scalar-base addressing); a
-// zero-extension hoisted into an earlier block arrives as an anonymous 64-bit vector value and costs a 64-bit vector add.
-// (in place: the caller's variable is the one register all its uses share)
-template <typename T>
-__device__ __forceinline__ T* at_off(T* base, unsigned& byte_off) {
-  asm volatile("" : "+v"(byte_off));
-  return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + byte_off);
-}
-template <typename T>
-__device__ __forceinline__ const T* at_off(const T* base, unsigned& byte_off) {
-  asm volatile("" : "+v"(byte_off));
-  return reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-}
-template <typename T>
-__device__ __forceinline__ void st_plain(T* p, const T& v) { *p = v; }
-__device__ __forceinline__ void st_obs_at(float* base, unsigned& byte_off, float v) { st_obs(at_off(base, byte_off), v); }
-
-// One EV of one env: the planes [E, N] are addressed as (plane + e * N) + c -- the first part is wave-uniform when a
-// wavefront is one env (G == 64) and lives in scalar registers.
-struct EvIx {
-  size_t eN;   // e * N
-  unsigned c;  // EV of the env
-  __device__ __forceinline__ size_t flat() const { return eN + c; }
-};
-template <typename T>
-__device__ __forceinline__ T* ev_at(T* plane, const EvIx& ix) {
-  unsigned off = ix.c * (unsigned)sizeof(T);
-  return at_off(plane + ix.eN, off);
-}
-// the EV's rainflow row (row stride in float64 words; one env's rows stay below 4 GiB: fleet_create checks)
-__device__ __forceinline__ double* rf_row_of(const FleetDev& d, const EvIx& ix, unsigned word = 0) {
-  unsigned off = (ix.c * (unsigned)d.rf_row_stride + word) * 8u;
-  return at_off(d.rf_rows + ix.eN * (size_t)d.rf_row_stride, off);
-}
-
-// The three schedule columns of one (row, EV), decoded from the record of the row's segment.
-struct RowRec {
-  double sor;      // db["SOC_on_return"]
-  float tl;        // db["time_left"]
-  uint32_t there;  // db["There"]
-};
-__device__ __forceinline__ RowRec seg_row(const SegRec& s, int r, double dt) {
-  RowRec o;
-  o.sor = s.sor;
-  o.tl = seg_tl(s, r, dt);
-  o.there = SEG_THERE(s.se);
-  return o;
-}
-
-// Per-EV slots of EV c.  soc / hours_left come from live state; the five auxiliary slots from the TABLE row the step
-// advanced to (quirk Q10): there | target_soc * there | charging_left | hours_needed | laxity (observer_bl_pv.py:85-91), each
-// divided by the normaliser's constant when normalize_in_env (oracle_normalization.py:127-131).  They are computed per lane
-// from the carried schedule record in float64 and rounded to float32 like the reference's; `cl * cap / (evse * eta)` and the
-// normaliser's divisions are multiplications by the correctly rounded quotient / reciprocal and `time_left / (hours_needed +
-// 0.001)` uses rcp_newton: <= 2 ulp of float64 before the rounding to float32, i.e. the float32 word is the reference's
-// except when the float64 value lies within ~2e-16 relative of a rounding boundary (tests/test_hip_parity.py reports the
-// exact-match fraction; the north-star tolerance is 1e-5).  Round 3 read these four words from a [T, N] table: 16 bytes per EV
-// and step, 7 of a wavefront's 44 line requests; the two float64 divisions that had made the per-lane form lose in round 3
-// (ab_seg3.log) are gone.
-__device__ __forceinline__ void write_obs_ev(const FleetDev& d, float* __restrict__ row, int c, double soc, float hl, double tgt,
-                                             const RowRec& tb) {
-  const int N = d.N;
-  // one 32-bit lane offset for all seven slots; the slot arrays' bases are wave-uniform when a wavefront is one env (scalar
-  // registers, `global_store ... s[base]` addressing: no 64-bit vector address per slot)
-  unsigned o4 = (unsigned)c * 4u;
-  st_obs_at(row, o4, (float)soc);
-  st_obs_at(row + N, o4, d.normalize ? (float)((double)hl / d.self->max_time_left) : hl);
-  if (!d.aux) return;
-  float* a = row + 2 * N + d.tail_a_len;
-  const double th = (double)tb.there;
-  const double tgt_th = tgt * th;
-  const double cl = tgt_th - tb.sor;
-  const double hn = cl * d.hn_scale;
-  double lax = ((double)tb.tl * rcp_newton1(hn + 0.001) - 1.0) * th;
-  lax = lax < 0.0 ? 0.0 : (lax > 5.0 ? 5.0 : lax);  // np.clip(., 0, 5): keeps -0.0 (an absent EV) and NaN like numpy does
-  st_obs_at(a, o4, (float)tb.there);
-  if (d.normalize) {
-    const FleetCold* cd = d.self->cold;
-    st_obs_at(a + N, o4, (float)(tgt_th * cd->inv_max_soc));
-    st_obs_at(a + 2 * N, o4, (float)(cl * cd->inv_max_soc));
-    st_obs_at(a + 3 * N, o4, (float)(hn * cd->inv_max_hours_needed));
-    st_obs_at(a + 4 * N, o4, (float)(lax * cd->inv_max_laxity));
-  } else {
-    st_obs_at(a + N, o4, (float)tgt_th);
-    st_obs_at(a + 2 * N, o4, (float)cl);
-    st_obs_at(a + 3 * N, o4, (float)hn);
-    st_obs_at(a + 4 * N, o4, (float)lax);
-  }
-}
-
-// env-level blocks: a pure function of the table row, pre-assembled (and pre-normalised) on the host.  Lane j copies
-// tail float j to its slot (block A right after the 2N state slots, block B after the 5N auxiliary slots).  The load
-// is issued early (with the other time-row loads) and the store late: `tail_load` / `tail_store`; for the usual
-// sizes (<= G floats) that is one predicated load and one store per lane, no loop.
-template <int G>
-__device__ __forceinline__ float tail_load(const FleetDev& d, int t, int g) {
-  const int total = d.tail_a_len + d.tail_b_len;
-  return (g < total) ? d.tab_tail[(size_t)t * d.tail_stride + g] : 0.0f;
-}
-
-template <int G>
-__device__ __forceinline__ void tail_store(const FleetDev& d, float* __restrict__ row, int t, int g, float first) {
-  const float* __restrict__ src = d.tab_tail + (size_t)t * d.tail_stride;
-  const int na = d.tail_a_len, total = d.tail_a_len + d.tail_b_len;
-  const unsigned base_a = 2u * (unsigned)d.N, base_b = 7u * (unsigned)d.N;  // block B: 2N + na + 5N + (j - na) = 7N + j
-  int j = g;
-  if (j < total) st_obs(row + ((j < na ? base_a : base_b) + (unsigned)j), first);
-  if (total > G) {
-    for (j += G; j < total; j += G) row[(j < na ? base_a : base_b) + (unsigned)j] = src[j];
-  }
-}
-
-template <int G>
-__device__ __forceinline__ void write_obs_tail(const FleetDev& d, float* __restrict__ row, int t, int g) {
-  tail_store<G>(d, row, t, g, tail_load<G>(d, t, g));
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// battery degradation
-// ---------------------------------------------------------------------------------------------------------
-// exp(z) by its Taylor polynomial of degree 14: truncation < 2e-15 relative for |z| <= 0.55 (a mean SOC in [0, 1]) and
-// < 8e-13 for |z| <= 1; beyond that -- a mean SOC far outside [0, 1], which the reference does not clip (quirk Q9) and a
-// schedule whose trips use more than a battery charge can produce -- the library exp takes over.
-__device__ __forceinline__ double exp_small(double z) {
-  if (fabs(z) > 1.0) return exp(z);
-  double r = 1.0 / 87178291200.0;  // 1/14!
-  r = fma(r, z, 1.0 / 6227020800.0);
-  r = fma(r, z, 1.0 / 479001600.0);
-  r = fma(r, z, 1.0 / 39916800.0);
-  r = fma(r, z, 1.0 / 3628800.0);
-  r = fma(r, z, 1.0 / 362880.0);
-  r = fma(r, z, 1.0 / 40320.0);
-  r = fma(r, z, 1.0 / 5040.0);
-  r = fma(r, z, 1.0 / 720.0);
-  r = fma(r, z, 1.0 / 120.0);
-  r = fma(r, z, 1.0 / 24.0);
-  r = fma(r, z, 1.0 / 6.0);
-  r = fma(r, z, 0.5);
-  r = fma(r, z, 1.0);
-  r = fma(r, z, 1.0);
-  return r;
-}
-
-// x^(-0.501) for 0 < x <= 1, as x^(-1/2) * exp(-0.001 * ln x):
-//   x^(-1/2): hardware reciprocal-square-root seed + two Newton steps (full float64 accuracy);
-//   ln x    : hardware float32 log2 (relative error ~1e-7, i.e. <= 4e-6 absolute for x >= 1e-17); multiplied by
-//             0.001 that leaves <= 4e-9 relative error in the result; exp of an argument <= 0.04 by Taylor.
-// The library pow() would be exact to 1 ulp but costs several hundred instructions inside a divergent branch.
-__device__ __forceinline__ double pow_m0501(double x) {
-  double y = __builtin_amdgcn_rsq(x);
-  y = y * fma(-0.5 * x * y, y, 1.5);
-  y = y * fma(-0.5 * x * y, y, 1.5);
-  const double lnx = (double)(__builtin_amdgcn_logf((float)x)) * 0.6931471805599453;  // log2 -> ln
-  const double z = -0.001 * lnx;
-  double r = 1.0 / 720.0;
-  r = fma(r, z, 1.0 / 120.0);
-  r = fma(r, z, 1.0 / 24.0);
-  r = fma(r, z, 1.0 / 6.0);
-  r = fma(r, z, 0.5);
-  r = fma(r, z, 1.0);
-  r = fma(r, z, 1.0);
-  return y * r;
-}
-
-// stress of one rainflow cycle: deg_rate_cycle(dod, avg_soc, temp) (rainflow_sei_degradation.py:68-80) for
-// effective_dod = clip(range*count, 0, 1) (:170).  Relative accuracy ~1e-8 (see pow_m0501), which moves SoH by
-// < 1e-12 relative (the degradation is a 1e-5-sized correction to 1.0); DESIGN.md "Numerics".
-__device__ __forceinline__ double cycle_stress(double rng, double mean, double count, double stress_temp) {
-  double eff = rng * count;
-  eff = eff > 1.0 ? 1.0 : eff;
-  if (!(eff > 0.0)) return 0.0;  // pow(0, -0.501) = inf -> 1/inf = 0
-  const double s_dod = 1.0 / (1.4E5 * pow_m0501(eff) + -1.23E5);   // (kd1 * dod**kd2 + kd3) ** -1
-  const double s_soc = exp_small(1.04 * (mean - 0.5));              // e ** (k_sigma * (soc - sigma_ref)), |arg| <= 0.55
-  return s_dod * s_soc * stress_temp;
-}
-
-// A real reversal point `p` arrives (rainflow.reversals yielded it): push it and close every cycle the
-// three-point rule allows (rainflow.extract_cycles, the `while len(points) >= 3` loop).
-// The stack of the EV always starts at slot 0 (`tail` = its size; when the three-point rule drops the FIRST point -- the
-// stack is exactly [a, b, p] then -- the survivor below the top is rewritten to slot 0, so no head index exists and the size
-// alone describes it).  Its newest entry lives in the row header only (s2; s1 caches the one below), the entries below it in
-// the stack words behind the header (struct RfHdr in fleet_device.h).
-// The push is split in two so that its memory round trip hides behind the rest of the step: `rf_begin`, right after the
-// state machine, knows the new sample and therefore whether a reversal point is pushed, and REQUESTS the EV's row (header
-// head, stack top, the two entries below the top two: three 16-byte loads of one cache line); `rf_finish`, after the
-// observation stores and the money terms, consumes it.  A step that pushes nothing -- three in four -- never touches the row.
-struct RfReq {
-  double p;        // the reversal point to push
-  RfAccHead acc;   // requested when a point is pushed
-  RfTop top;       // stack[tail-2], stack[tail-1]
-  double w0, w1;   // stack[tail-3], [tail-4] (before the push)
-  bool push;
-  bool win;        // w0 / w1 were requested (else the pops read the stack words)
-};
-// `early`: the row's header and the entries below the top two were already requested at the start of the EV's step (K steps
-// per launch: the same row lines serve all K steps of the launch from the cache, and a wavefront that advances on its own is
-// bound by its own dependent round trips, which this removes from every step that pushes).
-__device__ __forceinline__ void rf_request(const FleetDev& d, const EvIx& i, int tail, RfReq& q) {
-  const double* row = rf_row_of(d, i);
-  q.acc = *reinterpret_cast<const RfAccHead*>(row);
-  q.top = *reinterpret_cast<const RfTop*>(row + 2);
-  // stack[tail-4], stack[tail-3]; for a shallow stack they fall into the row's own header (never used: `nwin`)
-  const double* w = rf_row_of(d, i, (unsigned)(RF_HDR_WORDS + tail - 4));  // tail >= 1
-  q.w1 = w[0];
-  q.w0 = w[1];
-  q.win = true;
-}
-__device__ __forceinline__ void rf_begin(const FleetDev& d, const EvIx& i, double old_deg, double soc_deg, int tail, int& sgn, RfReq& q,
-                                         bool early = false) {
-  q.push = false;
-  q.p = old_deg;
-  // rainflow.reversals, one sample per step: equal samples are skipped, a strict slope sign change makes the previous
-  // sample a reversal point
-  if (soc_deg != old_deg) {
-    const int s_next = (soc_deg > old_deg) ? 1 : 2;
-    q.push = (sgn != 0 && sgn != s_next);
-    sgn = s_next;
-  }
-  if (q.push && !early) rf_request(d, i, tail, q);
-}
-// `top`: the stack top after the push (only written when a point was pushed)
-// `acc_out`: the accumulator head after the push (only written when the push closed a cycle)
-// Shape (round 5): the push that closes nothing, the half cycle and the FIRST full cycle are one straight line of selects -- the
-// only memory they need is what rf_request brought (top two entries, the two below, the accumulators) -- and only a second closure
-// of the same push (the new top against what lies below: rare) enters a loop that reads stack words.  The general loop of rounds
-// 2-4 walked every push through its loop control and the first-point test: 8.3 -> 7.9 us per 4096x50 launch for the same
-// algorithm (profiles/r05_experiments/ab7_rf_finish_peeled.log).
-__device__ __forceinline__ void rf_finish(const FleetDev& d, const EvIx& i, const RfReq& q, int& tail, RfTop& top, RfAccHead& acc_out,
-                                          uint32_t& err) {
-  if (!q.push) return;
-  double* row = rf_row_of(d, i);
-  double* stk = row + RF_HDR_WORDS;
-  // Within an episode this cannot happen (pushes <= samples < stack_cap).  Past the finish row (no auto-reset) the samples keep
-  // coming while the workspace stays sized for one episode: what must fit then is the stack depth, which only a long run of
-  // ever smaller swings makes grow.  Refuse instead of overrunning -- the step that would overflow raises the error bit.
-  if (tail >= d.stack_cap) {
-    err |= FLEET_DEVERR_TABLE_END;
-    return;
-  }
-  const double p = q.p;
-  const double a0 = q.top.s1, b0 = q.top.s2;  // stack[tail-2] (also in the stack words), stack[tail-1] (only in the header)
-  const int size = tail + 1;                  // points on the stack with p pushed
-  const bool closes = (size >= 3) && !(fabs(p - b0) < fabs(b0 - a0));
-  const bool half = closes && (size == 3);    // Y contains the starting point: half cycle, the first point is dropped
-  // ONE store for b0: it joins the stack words when nothing closes (slot tail-1) and is rewritten to slot 0 when the first point
-  // is dropped; a full cycle leaves the stack words as they are
-  if (!closes || half) st_plain(rf_row_of(d, i, (unsigned)(RF_HDR_WORDS + (half ? 0 : tail - 1))), b0);
-  const int L = q.acc.rf_len;
-  int nc = q.acc.nc;
-  double mean_sum = q.acc.mean_sum, dcsum = 0.0;
-  bool has_csum = false;
-  double a = a0, b = b0;
-  int t = size;
-  if (closes) {
-    if (nc >= L - 1) {  // only the closed cycles beyond the last evaluation's count carry stress: none in the steady state
-      dcsum = cycle_stress(fabs(a0 - b0), 0.5 * (a0 + b0), half ? 0.5 : 1.0, d.self->stress_temp);
-      has_csum = true;
-    }
-    mean_sum += 0.5 * (a0 + b0);
-    nc += 1;
-    if (half) {
-      t = 2;  // stack = [b0, p]
-    } else {  // full cycle: its two points vanish, p lives in s2, the entries below come from the request
-      t = size - 2;
-      const int nwin = q.win ? (tail - 2 > 2 ? 2 : tail - 2) : 0;
-      b = (nwin >= 1) ? q.w0 : stk[t - 2];
-      a = (t >= 3) ? ((nwin >= 2) ? q.w1 : stk[t - 3]) : 0.0;
-      while (t >= 3) {  // further closures of the new top against what lies below: rare, from the stack words
-        if (fabs(p - b) < fabs(b - a)) break;
-        if (nc >= L - 1) {
-          dcsum += cycle_stress(fabs(a - b), 0.5 * (a + b), (t == 3) ? 0.5 : 1.0, d.self->stress_temp);
-          has_csum = true;
-        }
-        mean_sum += 0.5 * (a + b);
-        nc += 1;
-        if (t == 3) {
-          stk[0] = b;
-          t = 2;
-        } else {
-          t -= 2;
-          b = stk[t - 2];
-          a = (t >= 3) ? stk[t - 3] : 0.0;
-        }
-      }
-    }
-  }
-  tail = t;
-  top.s1 = b;  // stack[tail-2]
-  top.s2 = p;  // stack[tail-1]
-  st_plain(reinterpret_cast<RfTop*>(row + 2), top);
-  if (closes) {
-    RfAccHead out;
-    out.mean_sum = mean_sum;
-    out.nc = nc;
-    out.rf_len = L;
-    acc_out = out;
-    st_plain(reinterpret_cast<RfAccHead*>(row), out);
-    if (has_csum) reinterpret_cast<RfHdr*>(row)->csum += dcsum;
-  }
-}
-// RainflowSeiDegradation.calculate_degradation for one EV on the daily row (rainflow_sei_degradation.py:91-212).
-// `v` = the sample just logged (forced last reversal), `n` = number of logged samples.  The forced point and the
-// residual half cycles are evaluated on a virtual stack (vt, vh, registers a/b); nothing of the streaming state
-// is modified except rainflow_length / fd_cyc / fd_cal / l / csum when the reference would update them.
-// `top` / `have_top`: the stack top when this step's push has just written it (registers are newer than the row).
-__device__ __forceinline__ double sei_evaluate(const FleetDev& d, const EvIx& ix, double v, int n, int tail, const RfTop& top, bool have_top,
-                                             uint32_t& err, double dt_hours, int* new_len = nullptr) {
-  const size_t i = ix.flat();
-  double* row = d.rf_rows + i * (size_t)d.rf_row_stride;
-  const double* stk = row + RF_HDR_WORDS;
-  // everything this needs from memory is requested up front (one round trip)
-  const RfHdr hd = *reinterpret_cast<const RfHdr*>(row);
-  SeiRec sr = d.sei[i];
-  const int L = hd.rf_len;
-  const int nc = hd.nc;
-  const double mean_sum0 = hd.mean_sum, csum0 = hd.csum, fd_cyc0 = sr.fd_cyc, sei_l0 = sr.sei_l, sei_soh0 = sr.sei_soh;
-  const double st = d.stress_temp;
-#ifdef FLEET_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-  FLEET_STAMP(11);  // records arrived
-
-  // The walk below emits at most one cycle per stack entry (`tail` entries and the forced last point make at most `tail`
-  // ranges), and the model is only updated when the cycle count passes rainflow_length (`len > L` below): an EV whose closed
-  // cycles plus stack entries stay within it -- typically the first 14:45 row of an episode, whose rainflow_length still is the
-  // previous episode's (quirk Q6) -- gets no update whatever the walk finds: degradation 0, records as they are.  Nothing to
-  // walk, nothing to store.  (These wavefronts end their launch: -1.3 % per launch at 4096 x 50, -16 % at 2048 x 50.)
-  if (nc + tail <= L) return 0.0;
-  int nv = 0;
-  double vmean = 0.0, vsum = 0.0, pend = 0.0, max_dod = 0.0;
-  bool has_pend = false;
-  auto emit = [&](double x1, double x2, double count) {
-    if (has_pend) vsum += pend;  // the previous cycle is not the last one
-    has_pend = false;
-    const double rng = fabs(x1 - x2), mean = 0.5 * (x1 + x2);
-    if (nc + nv >= L - 1) {
-      pend = cycle_stress(rng, mean, count, st);
-      has_pend = true;
-      max_dod = rng > max_dod ? rng : max_dod;
-    }
-    vmean += mean;
-    nv += 1;
-  };
-  if (n >= 3) {  // with two samples rainflow.reversals yields only the first point: no cycle at all
-    int vt = tail, vh = 0;
-    int size = vt - vh + 1;
-    double a = have_top ? top.s1 : hd.s1, b = have_top ? top.s2 : hd.s2;
-    while (size >= 3) {
-      const double X = fabs(v - b), Y = fabs(b - a);
-      if (X < Y) break;
-      emit(a, b, (size == 3) ? 0.5 : 1.0);
-      if (size == 3) {
-        vh += 1;
-        size = 2;
-      } else {
-        vt -= 2;
-        size -= 2;
-        b = stk[vt - 1];
-        a = (size >= 3) ? stk[vt - 2] : 0.0;
-      }
-    }
-    // remaining ranges are half cycles: stack[vh..vt) followed by the forced point
-    double prev = (vt - vh >= 2) ? stk[vh] : b;
-    for (int j = vh + 1; j < vt; ++j) {
-      const double cur = (j == vt - 1) ? b : stk[j];
-      emit(prev, cur, 0.5);
-      prev = cur;
-    }
-    emit(b, v, 0.5);
-  }
-
-  FLEET_STAMP(12);  // stack walked, cycle stresses evaluated
-  double degradation = 0.0;
-  double sei_l = sei_l0;
-  const int len = nc + nv;
-  if (len > 0 && len > L) {
-    if (max_dod > 5.0) err |= FLEET_DEVERR_DOD_RANGE;
-    const double battery_age = (double)(n - 1) * dt_hours * 3600.0;  // max(End) is always the last sample's index
-    const double mean_soc_cal = (mean_sum0 + vmean) / (double)len;
-    const double fd_cyc = fd_cyc0 + (csum0 + vsum);
-    const double fd_cal = (4.14E-10 * battery_age) * exp(1.04 * (mean_soc_cal - 0.5)) * st;
-    const double fd = fd_cyc + fd_cal;
-    const double alpha = 5.75E-2, beta = 121.0;
-    sei_l = 1.0 - alpha * exp(-beta * fd) - (1.0 - alpha) * exp(-fd);
-    if (sei_l < 0.0) err |= FLEET_DEVERR_NEG_LIFE;
-    degradation = sei_l - sei_l0;
-    sr.fd_cyc = fd_cyc;
-    sr.fd_cal = fd_cal;
-    sr.sei_l = sei_l;
-    RfAccHead out;  // rainflow_length moves on; every closed cycle so far now lies below the new rainflow_length-1
-    out.mean_sum = mean_sum0;
-    out.nc = nc;
-    out.rf_len = len;
-    *reinterpret_cast<RfAccHead*>(row) = out;
-    reinterpret_cast<RfHdr*>(row)->csum = 0.0;
-    if (new_len) *new_len = len;
-  }
-  FLEET_STAMP(13);  // SEI model evaluated
-  const double s = sei_soh0 - degradation;
-  sr.sei_soh = s;
-  d.sei[i] = sr;
-  if (fabs(s - (1.0 - sei_l)) > 0.0001) err |= FLEET_DEVERR_SOH_MISMATCH;
-  return degradation;
-}
-
-// EmpiricalDegradation.calculate_degradation for one EV (empirical_degradation.py:29-99; quirks Q1, Q5):
-// the last two log entries are the SOC sample before and after this step.
-__device__ __forceinline__ double linear_degradation(const FleetDev& d, double old_soc, double new_soc, double dt_hours) {
-  const double avg = (old_soc + new_soc) / 2.0;
-  // nearest of {0, 40, 90} to a SOC on a [0,1] scale -- replicated literally (argmin, first wins ties)
-  int best = 0;
-  double bd = fabs(0.0 - avg);
-  if (fabs(40.0 - avg) < bd) { best = 1; bd = fabs(40.0 - avg); }
-  if (fabs(90.0 - avg) < bd) best = 2;
-  const double cal = (best == 0 ? 0.0065 : best == 1 ? 0.0293 : 0.065) * dt_hours / 8760.0;
-  const double dod = fabs(new_soc - old_soc);
-  const double cyc = (d.evse_power <= 22.0) ? dod * 0.000125 / 2.0 : dod * 0.000167 / 2.0;
-  return cal + cyc;
-}
-
-// The hot record of an EV whose soc / soc_deg / hours_left are given (struct Hot in fleet_device.h): the shared float64
-// field, the FROZEN / INPLANE flags, and the soc_deg plane entry in the one case that needs it.  `plane_has` = the
-// plane already holds this soc_deg (the EV was INPLANE before and soc_deg has not changed since).
-__device__ __forceinline__ Hot hot_encode(const FleetDev& d, const EvIx& i, double soc, double soc_deg, float hl, int tail, int sgn,
-                                          uint32_t there, bool t090, bool plane_has) {
-  Hot h;
-  h.hl = hl;
-  bool frozen = false, inplane = false;
-  h.x = soc;
-  if (__double_as_longlong(soc_deg) != __double_as_longlong(soc)) {
-    frozen = true;
-    if (__double_as_longlong(soc) == 0ll) {
-      h.x = soc_deg;  // soc == +0.0 is implied
-    } else {
-      inplane = true;
-      if (!plane_has) d.soc_deg[i.flat()] = soc_deg;
-    }
-  }
-  h.bits = HOT_PACK(tail, sgn, frozen, inplane, there, t090);
-  return h;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// reset of one env by its group (FleetEnv.reset, fleet_environment.py:330-434)
-// ---------------------------------------------------------------------------------------------------------
-// FleetEnv.reset in two parts -- what each EV of the env does for itself, and what is done once per env -- so that both lane
-// parts can be placed independently (reset_env below runs them for a group of G lanes; round 5's flat-mapping experiment ran the
-// env's part on another thread than its EVs').
-// The EV's part (fleet_environment.py:345-399): state of health, SOC / hours_left from the start row, laxity fix-up, first SOC
-// sample, the carried schedule record, the observation slots.  `log_obs_row` / `log_ev_soh`: the data log's row reset() writes.
-__device__ __forceinline__ void reset_ev(const FleetDev& d, int e, int c, int start, float* __restrict__ obs_row,
-                                         float* __restrict__ log_obs_row, double* __restrict__ log_ev) {
-  const int N = d.N;
-  const FleetCold* cd = d.cold;
-  const int next = start + 1 > d.T - 1 ? d.T - 1 : start + 1;
-  const EvIx ix = {(size_t)e * N, (unsigned)c};
-  const size_t i = ix.flat();
-  const SegRec s0 = d.seg[(size_t)start * N + c];
-  d.run[i] = d.seg[(size_t)next * N + c];  // the record the first step of the episode advances to
-  const RowRec tb = seg_row(s0, start, d.dt);
-  const bool t090 = HOT_T090(d.hot[i].bits);  // target_soc survives reset (quirk Q7)
-  const double soh = 1.0 * cd->init_soh;
-  const double cap = soh * d.init_cap;
-  double soc = tb.sor;
-  const float hl = tb.tl;
-  const double tgt = t090 ? 0.9 : d.target_soc;
-  const double time_needed = (tgt - soc) * cap / d.p_avail;              // :384
-  if ((hl > 0.0f) && (cd->min_laxity * time_needed > (double)hl))        // :388
-    soc = tgt - (time_needed * d.p_avail / cap) / cd->min_laxity;        // :389-390
-  const double soc_deg = (soc == 0.0) ? cd->def_soc : soc;               // :395-399
-  d.hot[i] = hot_encode(d, ix, soc, soc_deg, hl, 1, 0, tb.there, t090, false);  // rainflow: the first sample is the first reversal point
-  d.soh[i] = soh;
-  if (d.deg_mode == FLEET_DEG_RAINFLOW) {  // LogDataDeg restarts; the SEI bookkeeping does NOT (quirk Q6)
-    RfHdr* hp = reinterpret_cast<RfHdr*>(d.rf_rows + i * (size_t)d.rf_row_stride);
-    RfHdr hd = *hp;  // rainflow_length survives
-    hd.mean_sum = 0.0;
-    hd.csum = 0.0;
-    hd.nc = 0;
-    hd.s1 = 0.0;
-    hd.s2 = soc_deg;  // the stack is [soc_deg]: its only entry lives in the header
-    *hp = hd;
-  }
-  if (obs_row) write_obs_ev(d, obs_row, c, soc, hl, tgt, tb);
-  if (log_obs_row) {
-    write_obs_ev(d, log_obs_row, c, soc, hl, tgt, tb);
-    double* lev = log_ev + c;
-    lev[0] = 0.0;
-    lev[N] = 0.0;
-    lev[2 * N] = 0.0;
-    lev[3 * N] = soh;
-  }
-}
-// Start row, finish row and sample count of the env's next episode (time pickers, :351-355) -- every lane of the env computes
-// them for itself (registers, no exchange).
-// `rf_until`: the last row of the new episode on which the degradation model runs (EnvRec::rf_until).  Without auto-reset the
-// env may be stepped past its finish row (gymnasium.Env path: the reference keeps logging and evaluating, :655-671), so the
-// count never stops there.
-__device__ __forceinline__ int reset_times(const FleetDev& d, int e, EnvHead& r, int& rf_until) {
-  const FleetCold* cd = d.cold;
-  const int start = choose_start(cd, d.E, e, r.episodes);
-  r.t = start;
-  r.t_end = d.tab_finish ? d.tab_finish[start] : start + d.episode_steps;  // :355 (exact date match on an irregular grid)
-  r.nsamp = (d.deg_mode != FLEET_DEG_NONE) ? 1 : 0;
-  // the degradation model is evaluated on the rows (start, t_end] that carry FLEET_TFLAG_DEG; what is logged after the last of
-  // them is cleared by the next reset() unread
-  const int last = cd->tab_last_deg[r.t_end > d.T - 1 ? d.T - 1 : r.t_end];
-  rf_until = (cd->rf_count_all || !d.auto_reset) ? INT32_MAX : (last > start ? last : -1);
-  return start;
-}
-// The env's part: its record (episode counters zeroed :402-404, the head with the row flags the episode's first step needs).
-__device__ __forceinline__ void reset_head(const FleetDev& d, int e, const EnvHead& r, int start, int rf_until) {
-  EnvRec* er = d.env + e;
-  EnvHead hd = r;
-  hd.nsamp = HEAD_PACK(r.nsamp, d.tab_phys[start].flags_next, start < rf_until);
-  er->h = hd;
-  er->rf_until = rf_until;
-  er->ep_return = 0.0;
-  er->ep_len = 0;
-  er->penalty_record = 0.0;
-  er->start_done = start;  // bit 31 (episode.done) cleared
-  // (an episode whose finish row lies beyond the table is legal until a step leaves the table: FLEET_DEVERR_TABLE_END is raised
-  // there, like the KeyError of the reference's `db.loc[...]`)
-}
-
-// `lp`: the env's data-log cursor (rows written so far; only used when the log is on), advanced by the row reset() writes.
-template <int G, bool LOG>
-__device__ __forceinline__ void reset_env(const FleetDev& d, int e, int g, bool leader, EnvHead& r, float* __restrict__ obs_row, int& lp,
-                                          int& rf_until) {
-  const bool log_on = LOG && (d.log_pos != nullptr);
-  const int N = d.N;
-  const int start = reset_times(d, e, r, rf_until);
-  // data log: the row reset() writes -- time, observation and SoH, zeros for everything else (:420-432)
-  const size_t lrow = log_on ? (size_t)(lp % d.log_cap) * d.E + e : 0;
-  float* const log_obs_row = log_on ? d.log_obs + lrow * d.obs_dim : nullptr;
-  double* const log_ev = log_on ? d.log_ev + lrow * 4 * N : nullptr;
-  for (int c = g; c < N; c += G) reset_ev(d, e, c, start, obs_row, log_obs_row, log_ev);
-  if (obs_row) write_obs_tail<G>(d, obs_row, start, g);
-  if (log_on) {
-    write_obs_tail<G>(d, log_obs_row, start, g);
-    if (leader) {
-      d.log_row[lrow] = (int32_t)((uint32_t)start | 0x80000000u);
-      double* le = d.log_env + lrow * 4;
-      le[0] = le[1] = le[2] = le[3] = 0.0;
-    }
-    lp += 1;
-  }
-  if (leader) reset_head(d, e, r, start, rf_until);
-}
-
-template <int G>
-__global__ __launch_bounds__(kBlock) void fleet_reset_kernel(FleetDev d, const uint8_t* __restrict__ mask, float* __restrict__ obs) {
-  const int g = threadIdx.x % G;
-  const int e = blockIdx.x * (kBlock / G) + threadIdx.x / G;
-  if (e >= d.E) return;
-  if (mask && !mask[e]) return;
-  EnvHead r = d.env[e].h;
-  r.nsamp = HEAD_NSAMP(r.nsamp);
-  // an explicit reset of an episode that is in progress abandons it: count it so the next start row differs
-  if (d.env[e].ep_len > 0 && d.env[e].start_done >= 0) r.episodes += 1;
-  int lp = d.log_pos ? d.log_pos[e] : 0;
-  int rf_until;
-  reset_env<G, true>(d, e, g, g == G - 1, r, obs ? obs + (size_t)e * d.obs_dim : nullptr, lp, rf_until);
-  if (d.log_pos && g == G - 1) d.log_pos[e] = lp;
-}
+namespace {
 
 // The tail of an EV's step: the rainflow push (second half), the linear model's daily update, the data-log row, and the
 // stores of the state records that changed.
@@ -1570,253 +824,9 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   FLEET_STAMP_WHERE();
 }
 
-// FleetEnv.get_dist_factor (fleet_environment.py:782-799)
-__global__ void fleet_dist_factor_kernel(FleetDev d, double* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)d.E * d.N) return;
-  const int e = (int)(i / d.N), c = (int)(i % d.N);
-  const int t = d.env[e].h.t;
-  const RowRec tb = seg_row(d.seg[(size_t)t * d.N + c], t, d.dt);
-  const double th = (double)tb.there;
-  const double tgt = HOT_T090(d.hot[i].bits) ? 0.9 : d.target_soc;
-  const double cl = tgt * th - tb.sor;
-  const double hn = cl * d.cold->batt_cap_nominal / d.cold->hn_denominator;
-  out[i] = hn / ((double)tb.tl + 0.001);
-}
-
-// fleet_get: unpack one field into a contiguous buffer (types as documented in include/fleet_hip.h)
-__global__ void fleet_gather_field_kernel(FleetDev d, int field, void* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t E = d.E, EN = (size_t)d.E * d.N;
-  const bool per_car = field == FLEET_F_SOC || field == FLEET_F_HOURS_LEFT || field == FLEET_F_SOH || field == FLEET_F_SOC_DEG ||
-                       field == FLEET_F_TARGET_SOC || field == FLEET_F_RF_LEN || field == FLEET_F_RF_CYCLES || field == FLEET_F_RF_STACK ||
-                       field == FLEET_F_FD_CYC ||
-                       field == FLEET_F_FD_CAL || field == FLEET_F_SEI_L;
-  if (i >= (per_car ? EN : E)) return;
-  switch (field) {
-    case FLEET_F_SOC: ((double*)out)[i] = HOT_SOC(d.hot[i]); break;
-    case FLEET_F_HOURS_LEFT: ((float*)out)[i] = d.hot[i].hl; break;
-    case FLEET_F_SOH: ((double*)out)[i] = d.soh[i]; break;
-    case FLEET_F_SOC_DEG: ((double*)out)[i] = HOT_INPLANE(d.hot[i].bits) ? d.soc_deg[i] : d.hot[i].x; break;
-    case FLEET_F_TARGET_SOC: ((double*)out)[i] = HOT_T090(d.hot[i].bits) ? 0.9 : d.target_soc; break;
-    case FLEET_F_RF_LEN:
-      ((int32_t*)out)[i] = d.rf_rows ? reinterpret_cast<const RfHdr*>(d.rf_rows + i * (size_t)d.rf_row_stride)->rf_len : 1;
-      break;
-    case FLEET_F_RF_CYCLES:
-      ((int32_t*)out)[i] = d.rf_rows ? reinterpret_cast<const RfHdr*>(d.rf_rows + i * (size_t)d.rf_row_stride)->nc : 0;
-      break;
-    case FLEET_F_RF_STACK: ((int32_t*)out)[i] = d.rf_rows ? HOT_TAIL(d.hot[i].bits) : 0; break;
-    case FLEET_F_FD_CYC: ((double*)out)[i] = d.sei[i].fd_cyc; break;
-    case FLEET_F_FD_CAL: ((double*)out)[i] = d.sei[i].fd_cal; break;
-    case FLEET_F_SEI_L: ((double*)out)[i] = d.sei[i].sei_l; break;
-    case FLEET_F_TIME_IDX: ((int32_t*)out)[i] = d.env[i].h.t; break;
-    case FLEET_F_START_IDX: ((int32_t*)out)[i] = d.env[i].start_done & 0x7FFFFFFF; break;
-    case FLEET_F_CASHFLOW: ((double*)out)[i] = d.env[i].cashflow; break;
-    case FLEET_F_EP_RETURN: ((double*)out)[i] = d.env[i].ep_return; break;
-    case FLEET_F_EP_LEN: ((int32_t*)out)[i] = d.env[i].ep_len; break;
-    case FLEET_F_LAST_EP_RETURN: ((double*)out)[i] = d.env[i].last_ep_return; break;
-    case FLEET_F_LAST_EP_LEN: ((int32_t*)out)[i] = d.cold->last_len[i]; break;
-    case FLEET_F_LAST_EP_LEN_F64: ((double*)out)[i] = (double)d.cold->last_len[i]; break;
-    case FLEET_F_RF_UNTIL: ((int32_t*)out)[i] = d.env[i].rf_until; break;
-    case FLEET_F_ERROR_BITS: ((uint32_t*)out)[i] = d.env[i].err; break;
-    case FLEET_F_DONE: ((uint8_t*)out)[i] = (uint8_t)(d.env[i].start_done < 0); break;
-    case FLEET_F_EPISODES: ((int32_t*)out)[i] = d.env[i].h.episodes; break;
-    case FLEET_F_PENALTY_RECORD: ((double*)out)[i] = d.env[i].penalty_record; break;
-    default: break;
-  }
-}
-
-// Host path: the terminal observations of the envs that finished in this step, compacted (fleet_step_host moves only these
-// rows over PCIe instead of the whole [E, obs_dim] buffer).  One workgroup: a serial-over-chunks scan of the done flags in
-// env order (deterministic), then the rows are copied by the whole launch.
-__global__ __launch_bounds__(1024) void fleet_term_scan_kernel(const uint8_t* __restrict__ done, int E, int32_t* __restrict__ idx,
-                                                               int32_t* __restrict__ count, const EnvRec* __restrict__ env,
-                                                               const FleetCold* __restrict__ cold, double* __restrict__ ep_ret,
-                                                               int32_t* __restrict__ ep_len) {
-  __shared__ int s_wave[16];
-  __shared__ int s_base;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_base = 0;
-  __syncthreads();
-  for (int e0 = 0; e0 < E; e0 += 1024) {
-    const int e = e0 + (int)threadIdx.x;
-    const bool f = (e < E) && done[e] != 0;
-    const unsigned long long m = __ballot(f);
-    const int before = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int off = s_base;
-    for (int w = 0; w < wave; ++w) off += s_wave[w];
-    if (f) {  // the finished episode's return / length travel with the index (what SB3's Monitor would report)
-      idx[off + before] = e;
-      ep_ret[off + before] = env[e].last_ep_return;
-      ep_len[off + before] = cold->last_len[e];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int tot = 0;
-      for (int w = 0; w < 16; ++w) tot += s_wave[w];
-      s_base += tot;
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *count = s_base;
-}
-
-__global__ void fleet_term_gather_kernel(const float* __restrict__ term, int obs_dim, const int32_t* __restrict__ idx,
-                                         const int32_t* __restrict__ count, float* __restrict__ compact) {
-  const int n = *count;
-  for (int k = blockIdx.x; k < n; k += gridDim.x) {
-    const float* src = term + (size_t)idx[k] * obs_dim;
-    float* dst = compact + (size_t)k * obs_dim;
-    for (int j = threadIdx.x; j < obs_dim; j += blockDim.x) dst[j] = src[j];
-  }
-}
-
-// Self-test of div_rcp (fleet_selftest_division): operand pairs drawn the way the charge arithmetic forms them, the IEEE division
-// sequence beside the reciprocal form, bit for bit.  case 0: need / eta_c with the host's correctly rounded 1 / eta_c;
-// case 1: energy / cap with rcp_newton1(cap).  A few lanes in a thousand carry the edge values (+-0, a denormal-sized residue).
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ double u01(unsigned long long h) { return (double)(h >> 11) * (1.0 / 9007199254740992.0); }
-__global__ void fleet_selftest_division_kernel(unsigned long long n, unsigned long long seed, unsigned long long* __restrict__ bad) {
-  unsigned long long b0 = 0, b1 = 0;
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x) {
-    const unsigned long long h = mix64(seed + i * 4ull);
-    const double soc = -0.25 + 1.5 * u01(h), soh = 0.8 + 0.2 * u01(mix64(h)), init_cap = 10.0 + 90.0 * u01(mix64(h + 1));
-    const double eta = 0.5 + 0.5 * u01(mix64(h + 2)), tgt = (h & 1) ? 0.85 : 0.9;
-    const double a = 2.0 * u01(mix64(h + 3)) - 1.0, p_avail = 2.0 + 20.0 * u01(mix64(h + 4));
-    const double cap = soh * init_cap;
-    double need = (tgt - soc) * cap;
-    double en = p_avail * a * 0.25;
-    const unsigned sel = (unsigned)(h >> 40) % 1000u;
-    if (sel == 0) need = 0.0;
-    if (sel == 1) need = -0.0;
-    if (sel == 2) en = -0.0;
-    if (sel == 3) en = 7e-18 * cap;
-    const double inv_eta = 1.0 / eta;  // IEEE: correctly rounded, like the host's
-    const double q0 = need / eta, r0 = div_rcp(need, eta, inv_eta);
-    const double x1 = (a >= 0.0) ? en * eta : en;
-    const double q1 = x1 / cap, r1 = div_rcp(x1, cap, rcp_newton1(cap));
-    b0 += (__double_as_longlong(q0) != __double_as_longlong(r0));
-    b1 += (__double_as_longlong(q1) != __double_as_longlong(r1));
-  }
-  if (b0) atomicAdd(bad, b0);
-  if (b1) atomicAdd(bad + 1, b1);
-}
-
-// cycle_stress (hardware float32 log2 inside x^-0.501, Taylor exp) against the same expression in library double precision, on n
-// pseudo-random (range, mean, weight) triples of the reachable domain: worst[0] = largest relative difference as the bits of a double
-__global__ void fleet_selftest_stress_kernel(unsigned long long n, unsigned long long seed, unsigned long long* __restrict__ worst) {
-  double w = 0.0;
-  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x) {
-    const unsigned long long h = mix64(seed + i * 3ull);
-    // depth of discharge: half of the samples log-uniform over 1e-9 ... 1 (tiny cycles are the common ones), half uniform
-    const double u = u01(h), v = u01(mix64(h + 1));
-    const double rng = (h & 1) ? exp(-20.7232658 * u) : u;
-    const double mean = -0.25 + 1.5 * v;  // a mean SOC a little outside [0, 1] too (quirk Q9: the reference does not clip it)
-    const double count = (h & 2) ? 1.0 : 0.5;
-    const double st = 0.9 + 0.2 * u01(mix64(h + 2));
-    const double got = cycle_stress(rng, mean, count, st);
-    double eff = rng * count;
-    eff = eff > 1.0 ? 1.0 : eff;
-    const double want = (eff > 0.0) ? (1.0 / (1.4E5 * pow(eff, -0.501) + -1.23E5)) * exp(1.04 * (mean - 0.5)) * st : 0.0;
-    const double rel = (want != 0.0) ? fabs(got - want) / fabs(want) : fabs(got);
-    w = rel > w ? rel : w;
-  }
-  atomicMax(worst, (unsigned long long)__double_as_longlong(w));  // non-negative doubles order like their bit patterns
-}
-
-int group_size(int N) {
-  int G = 1;
-  while (G < N && G < 64) G <<= 1;
-  return G;
-}
-
-// The launch a step configuration takes: the instance of fleet_step_kernel, its grid of kBlock-thread workgroups, and whether it is
-// the single-step instance (the only kind fleet_describe_step writes down).  Every instance has the same signature.
-using StepKernelFn = decltype(&fleet_step_kernel<1, FLEET_DEG_NONE, false, false>);
-struct StepPlan {
-  StepKernelFn fn;
-  unsigned grid;
-  bool single;
-  const FleetStepInstance* id;  // the template arguments of `fn` (fleet_step_instance: which kernel a configuration takes)
-};
-// The one place that takes an instance's address: the description is formed from the same template arguments as the pointer, so
-// the two cannot disagree.
-template <int G, int DEG, bool MULTI, bool WIDE, bool LOG = false, bool A64 = false, int MODE = kModeAll>
-StepPlan step_instance(unsigned grid, bool single) {
-  static constexpr FleetStepInstance id{G, DEG, MULTI, WIDE, LOG, A64, MODE};
-  return {&fleet_step_kernel<G, DEG, MULTI, WIDE, LOG, A64, MODE>, grid, single, &id};
-}
-
-// Instance selection.  G (EVs per env rounded up to a power of two, at most 64) and DEG come from the switches of plan_step; an env
-// of 65 ... kMaxGroup EVs re-enters with a group of two or four wavefronts (G = 128 / 256), one of more EVs than lanes (or that needs
-// the real_time or data-log code) with WIDE: every lane walks several EVs.  The `if constexpr` tests keep kernels that a (G, WIDE)
-// never launches from being instantiated at all.
-template <int G, int DEG, bool WIDE = false>
-StepPlan plan_step_gd(const FleetDev& d, int act_mode, int K, bool has_done_count) {
-  if constexpr (G == 64 && !WIDE) {
-    if (d.N > kMaxGroup || (d.N > 64 && (d.real_time || d.log_pos))) return plan_step_gd<64, DEG, true>(d, act_mode, K, has_done_count);
-    if (d.N > 128) return plan_step_gd<256, DEG>(d, act_mode, K, has_done_count);
-    if (d.N > 64) return plan_step_gd<128, DEG>(d, act_mode, K, has_done_count);
-  }
-  const int epb = kBlock / G;
-  const unsigned grid = (unsigned)((d.E + epb - 1) / epb);
-  // the single-step kernel carries neither the policies, nor the event-skipping loop, nor the data-log code; with WIDE it reads
-  // either action dtype at run time
-  if (K == 1 && !has_done_count && act_mode < FLEET_ACT_POLICY_UNCONTROLLED && !d.real_time && !d.log_pos) {
-    if constexpr (!WIDE)
-      if (act_mode == FLEET_ACT_F64) return step_instance<G, DEG, false, false, false, true>(grid, true);
-    return step_instance<G, DEG, false, WIDE>(grid, true);
-  }
-  // K steps per launch: the data log (groups of one wavefront or less); from 32 lanes on the instance that carries what the launch
-  // uses -- the event-skipping loop, the built-in policies, or the tape only; smaller groups keep ONE instance with everything behind
-  // run-time tests
-  if constexpr (G <= 64)
-    if (d.log_pos) return step_instance<G, DEG, true, WIDE, true>(grid, false);
-  if constexpr (G >= 32) {
-    if (d.real_time) return step_instance<G, DEG, true, WIDE, false, false, kModeRt>(grid, false);
-    if (act_mode >= FLEET_ACT_POLICY_UNCONTROLLED) return step_instance<G, DEG, true, WIDE, false, false, kModePolicy>(grid, false);
-    return step_instance<G, DEG, true, WIDE, false, false, kModeTape>(grid, false);
-  }
-  // (no `else` above: this instance stays instantiated for every group, and kModeRt for G = 128 / 256, though no launch takes them --
-  // the set of instances this selection has always compiled)
-  return step_instance<G, DEG, true, WIDE, false, false, kModeAll>(grid, false);
-}
-
-template <int G>
-StepPlan plan_step_g(const FleetDev& d, int act_mode, int K, bool has_done_count) {
-  switch (d.deg_mode) {
-    case FLEET_DEG_NONE: return plan_step_gd<G, FLEET_DEG_NONE>(d, act_mode, K, has_done_count);
-    case FLEET_DEG_LINEAR: return plan_step_gd<G, FLEET_DEG_LINEAR>(d, act_mode, K, has_done_count);
-    default: return plan_step_gd<G, FLEET_DEG_RAINFLOW>(d, act_mode, K, has_done_count);
-  }
-}
-
-// The argument block of a step launch, as issued on a HIP stream; a run on the library's own queue fills in the placement record's
-// fields itself (fleet_direct_prepare).
-StepKernargs step_args(const FleetDev& d, const void* actions, int act_mode, int K, float* obs, double* reward, uint8_t* done,
-                       float* terminal_obs, int32_t* done_count) {
-  StepKernargs a{};
-  a.p_hot = d.hot; a.p_run = d.run; a.p_soh = d.soh; a.p_actions = actions; a.p_E = d.E; a.p_N = d.N; a.p_env = d.env;
-  a.d_arg = d; a.actions = actions; a.act_mode = act_mode; a.K = K;
-  a.obs = obs; a.reward = reward; a.done = done; a.terminal_obs = terminal_obs; a.done_count = done_count;
-  return a;
-}
-
-template <int G>
-hipError_t launch_reset_g(const FleetDev& d, const uint8_t* mask, float* obs, hipStream_t s) {
-  const int epb = kBlock / G;
-  hipLaunchKernelGGL((fleet_reset_kernel<G>), dim3((d.E + epb - 1) / epb), dim3(kBlock), 0, s, d, mask, obs);
-  return hipGetLastError();
-}
-
 }  // namespace
+
+#include "fleet_aux_kernels.h"
 
 // What fleet_direct_open launches on its queue before it accepts the mode: every workgroup writes down the die it runs on
 // (HW_REG_XCC_ID, all bits).  A symbol with C linkage: resolved by name in the code object the HSA loader holds.
@@ -1831,99 +841,4 @@ extern "C" __global__ void fleet_probe_xcc_kernel(uint32_t* __restrict__ out) {
 extern "C" __device__ __attribute__((used)) const char fleet_src_sha[32] = FLEET_SRC_SHA;
 const char* fleet_kernels_src_sha() { return FLEET_SRC_SHA; }
 
-#define FLEET_DISPATCH_G(N, CALL)          \
-  switch (group_size(N)) {                 \
-    case 1: return CALL(1);                \
-    case 2: return CALL(2);                \
-    case 4: return CALL(4);                \
-    case 8: return CALL(8);                \
-    case 16: return CALL(16);              \
-    case 32: return CALL(32);              \
-    default: return CALL(64);              \
-  }
-
-// Up to this many EVs per env a single-step launch gives every EV a lane of its own (groups of 1 ... 4 wavefronts per env) and reads
-// the carried schedule records; beyond it the lanes walk several EVs each and read the table.
-int fleet_max_evs_per_lane_group() { return kMaxGroup; }
-
-hipError_t fleet_launch_reset(const FleetDev& d, const uint8_t* mask, float* obs, hipStream_t s) {
-#define CALL(Gv) launch_reset_g<Gv>(d, mask, obs, s)
-  FLEET_DISPATCH_G(d.N, CALL)
-#undef CALL
-}
-
-static StepPlan plan_step(const FleetDev& d, int act_mode, int K, bool has_done_count) {
-#define CALL(Gv) plan_step_g<Gv>(d, act_mode, K, has_done_count)
-  FLEET_DISPATCH_G(d.N, CALL)
-#undef CALL
-}
-
-hipError_t fleet_launch_step(const FleetDev& d, const void* actions, int act_dtype, int K, float* obs, double* reward,
-                             uint8_t* done, float* terminal_obs, int32_t* done_count, hipStream_t s) {
-  const StepPlan p = plan_step(d, act_dtype, K, done_count != nullptr);
-  const StepKernargs a = step_args(d, actions, act_dtype, K, obs, reward, done, terminal_obs, done_count);
-  hipLaunchKernelGGL(p.fn, dim3(p.grid), dim3(kBlock), 0, s, a.p_hot, a.p_run, a.p_soh, a.p_actions, a.p_E, a.p_N, a.p_env, a.d_arg,
-                     a.actions, a.act_mode, a.K, a.obs, a.reward, a.done, a.terminal_obs, a.done_count, a.guard_bytes, a.rec_blocks,
-                     a.rec_rows, a.rec_rotate);
-  return hipGetLastError();
-}
-
-// "G64.rainflow.multi.policy": lanes per env (with `w` where every lane walks several EVs), degradation model, single step or K
-// steps per launch, then what the instance carries -- the data log, or the part of the K-step code it was cut to (`all`: everything
-// behind run-time tests); a single-step instance the action dtype it reads (`any`: either, chosen at run time).  Combinations of
-// template arguments no launch takes today get every tag that applies, so that two instances never share a name.
-int fleet_describe_step_instance(const FleetDev& d, int act_mode, int K, bool has_done_count, char* name, size_t name_bytes,
-                                 unsigned* grid) {
-  const StepPlan p = plan_step(d, act_mode, K, has_done_count);
-  const FleetStepInstance& i = *p.id;
-  static const char* const deg[] = {"none", "linear", "rainflow"};
-  static const char* const mode[] = {".all", ".tape", ".policy", ".rt"};
-  const char* dtype = i.a64 ? ".f64" : i.multi ? "" : i.wide ? ".any" : ".f32";
-  const char* part = (i.multi && !i.log) || i.mode != kModeAll ? mode[i.mode] : "";
-  *grid = p.grid;
-  return snprintf(name, name_bytes, "G%d%s.%s.%s%s%s%s", i.G, i.wide ? "w" : "", deg[i.deg], i.multi ? "multi" : "single",
-                  i.log ? ".log" : "", part, dtype);
-}
-
-hipError_t fleet_describe_step(const FleetDev& d, const void* actions, int act_dtype, float* obs, double* reward, uint8_t* done,
-                               float* terminal_obs, FleetStepLaunch* out) {
-  const StepPlan p = plan_step(d, act_dtype, 1, false);
-  if (!p.single) return hipErrorNotSupported;
-  const StepKernargs a = step_args(d, actions, act_dtype, 1, obs, reward, done, terminal_obs, nullptr);
-  out->host_fn = (const void*)p.fn; out->grid = p.grid; out->block = kBlock; out->args_bytes = (unsigned)sizeof a;
-  out->actions_offset[0] = (unsigned)offsetof(StepKernargs, p_actions); out->actions_offset[1] = (unsigned)offsetof(StepKernargs, actions);
-  out->packed_n_offset = (unsigned)offsetof(StepKernargs, p_N);
-  out->guard_offset = (unsigned)offsetof(StepKernargs, guard_bytes);
-  out->rec_offset = (unsigned)offsetof(StepKernargs, rec_blocks);  // (then rec_rows and rec_rotate)
-  memcpy(out->args, &a, sizeof a);
-  return hipSuccess;
-}
-
-hipError_t fleet_launch_term_compact(const FleetDev& d, const uint8_t* done, const float* term, int32_t* idx, int32_t* count,
-                                     double* ep_ret, int32_t* ep_len, float* compact, hipStream_t s) {
-  hipLaunchKernelGGL(fleet_term_scan_kernel, dim3(1), dim3(1024), 0, s, done, d.E, idx, count, d.env, d.cold, ep_ret, ep_len);
-  hipLaunchKernelGGL(fleet_term_gather_kernel, dim3(256), dim3(256), 0, s, term, d.obs_dim, idx, count, compact);
-  return hipGetLastError();
-}
-
-hipError_t fleet_launch_dist_factor(const FleetDev& d, double* out, hipStream_t s) {
-  const size_t n = (size_t)d.E * d.N;
-  hipLaunchKernelGGL(fleet_dist_factor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, out);
-  return hipGetLastError();
-}
-
-hipError_t fleet_launch_gather_field(const FleetDev& d, int field, void* out, hipStream_t s) {
-  const size_t n = (size_t)d.E * d.N;
-  hipLaunchKernelGGL(fleet_gather_field_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d, field, out);
-  return hipGetLastError();
-}
-
-hipError_t fleet_launch_selftest_stress(unsigned long long n, unsigned long long seed, unsigned long long* worst_dev, hipStream_t s) {
-  hipLaunchKernelGGL(fleet_selftest_stress_kernel, dim3(2048), dim3(256), 0, s, n, seed, worst_dev);
-  return hipGetLastError();
-}
-
-hipError_t fleet_launch_selftest_division(unsigned long long n, unsigned long long seed, unsigned long long* bad_dev, hipStream_t s) {
-  hipLaunchKernelGGL(fleet_selftest_division_kernel, dim3(2048), dim3(256), 0, s, n, seed, bad_dev);
-  return hipGetLastError();
-}
+#include "fleet_step_plan.h"

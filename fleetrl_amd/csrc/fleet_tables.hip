@@ -25,7 +25,7 @@ const char* fleet_validate(const FleetParams* p, const FleetTables* t) {
   if (p->abi_version != FLEET_ABI_VERSION) return "abi_version mismatch";
   if (p->struct_bytes != (int)sizeof(FleetParams)) return "FleetParams size mismatch";
   if (p->num_envs < 1 || p->num_cars < 1 || p->table_rows < 2) return "num_envs/num_cars/table_rows out of range";
-  if (p->num_cars > 65535) return "num_cars: at most 65535 EVs per env";  // (the step kernel's packed argument, fleet_kernels.hip `p_N`)
+  if (p->num_cars > 65535) return "num_cars: at most 65535 EVs per env";  // (the step kernel's packed argument, fleet_kernels.hip `p_N`; filled by step_args, fleet_step_plan.h)
   if (p->episode_steps < 1 || p->steps_per_hour < 1) return "episode_steps/steps_per_hour out of range";
   if (p->episode_steps >= FLEET_MAX_EPISODE_STEPS) return "episode_steps exceeds 2^29 - 1 (the env head's sample count is 29 bits wide)";
   if (p->price_lookahead < 0 || p->bl_pv_lookahead < 0) return "negative look-ahead";

@@ -7,7 +7,7 @@ A case is (instance, uses): a single-step instance has one use; an instance of t
 different launches -- an action tape with K = 1 or K > 1, each built-in policy, the event-skipping loop of real_time -- and a fault in
 the code of one use does not show in another.  A use is named after the launch that asks for it (`use_of`).
 
-Adding an instance to `plan_step_gd` (fleet_kernels.hip): give it a case here (a width N that selects it in `GROUP_WIDTHS` if it is a
+Adding an instance to `plan_step_gd` (fleet_step_plan.h, the host half of fleet_kernels.hip): give it a case here (a width N that selects it in `GROUP_WIDTHS` if it is a
 new lane group; `cases()` derives the rest), or the CPU test fails and names it."""
 from __future__ import annotations
 

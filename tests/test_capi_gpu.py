@@ -339,7 +339,7 @@ def test_rccl_gather_of_episode_stats_through_the_c_abi():
 
 def test_division_by_reciprocal_is_bit_exact():
     """The charge arithmetic's two divisions (ev_charger.py:114 `need / eta_c`, :128 / :189 `energy / cap`) are formed from a
-    reciprocal with a residual correction (fleet_kernels.hip div_rcp).  2^30 pseudo-random operand pairs of the charge
+    reciprocal with a residual correction (fleet_wave.h div_rcp).  2^30 pseudo-random operand pairs of the charge
     arithmetic's ranges -- incl. +-0 and a 7e-18-sized residue -- against the IEEE division sequence on the device: not one
     quotient may differ in any bit."""
     lib = _capi.load_library()

@@ -71,7 +71,7 @@ def _compare(uc, n_evs, num_envs, deg, norm, steps, aux=True, building=True, pv=
             np.testing.assert_allclose(hip.get("ep_return"), cpu.get("ep_return"), rtol=1e-9, atol=1e-8)
             if deg == "rainflow":
                 # (same bounds as the replay of the reference's golden traces, tests/golden_util.py: the cycle stress uses a
-                # hardware float32 logarithm inside x^-0.501, <= 4e-9 relative, see pow_m0501 in fleet_kernels.hip)
+                # hardware float32 logarithm inside x^-0.501, <= 4e-9 relative, see pow_m0501 in fleet_rainflow.h)
                 np.testing.assert_array_equal(hip.get("rf_len"), cpu.get("rf_len"))
                 np.testing.assert_allclose(hip.get("fd_cyc"), cpu.get("fd_cyc"), rtol=1e-8, atol=1e-18)
                 np.testing.assert_allclose(hip.get("sei_l"), cpu.get("sei_l"), rtol=1e-9, atol=1e-18)

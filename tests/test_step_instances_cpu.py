@@ -40,7 +40,7 @@ def test_the_entry_names_instances_and_refuses_nonsense():
 
 
 def test_reachable_set_is_the_one_the_selection_code_describes(reachable):
-    """10 lane groups x 3 degradation models x the launch kinds each group admits (fleet_kernels.hip plan_step_gd)."""
+    """10 lane groups x 3 degradation models x the launch kinds each group admits (fleet_step_plan.h plan_step_gd)."""
     groups = collections.Counter(name.split(".")[0] for name in reachable)
     assert set(groups) == {"G1", "G2", "G4", "G8", "G16", "G32", "G64", "G128", "G256", "G64w"}
     assert all(n % 3 == 0 for n in groups.values())

@@ -17,7 +17,10 @@ import pandas as pd
 out = sys.argv[1]
 sys.path.insert(0, os.environ["GRAFT_REPO_ROOT"])
 import bench
-res = {"kernel_src_sha": bench.kernel_source_sha(), "bench_args": sys.argv[2:]}
+from fleetrl_amd import build
+# kernel_src_sha is the key bench.py looks a profile up by (fleet_kernels.hip + fleet_device.h); library_src_sha covers every source and
+# header, the headers fleet_kernels.hip includes among them: what the measured library was really compiled from
+res = {"kernel_src_sha": bench.kernel_source_sha(), "library_src_sha": build.source_sha(), "bench_args": sys.argv[2:]}
 n_groups = 1
 lines = [l for l in open(f"{out}/bench_fetch.log") if l.startswith("{")]
 if lines:
