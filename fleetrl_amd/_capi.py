@@ -161,6 +161,19 @@ class FleetPolicyParams(C.Structure):
                 ("head", FleetPolicyHead * POLICY_MAX_HEADS)]
 
 
+# ---- exploration actions (include/fleet_hip.h "exploration actions on the device", fleet_explore_*) ---------------------------------
+EXPLORE_GAUSSIAN, EXPLORE_ACTION_NOISE, EXPLORE_UNIFORM = 0, 1, 2
+EXPLORE_NOISE_DRAW, EXPLORE_NOISE_GIVEN = 0, 1
+
+
+class FleetExploreArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("mode", C.c_int32), ("noise_mode", C.c_int32), ("reserved0", C.c_int32),
+                ("seed", C.c_uint64), ("step", C.c_uint64), ("env_id_offset", C.c_int32), ("reserved1", C.c_int32),
+                ("scale", C.c_void_p), ("shift", C.c_void_p), ("noise_lo", C.c_float), ("noise_hi", C.c_float),
+                ("noise", C.c_void_p), ("actions", C.c_void_p), ("env_actions", C.c_void_p), ("log_prob", C.c_void_p),
+                ("values", C.c_void_p), ("mean", C.c_void_p)]
+
+
 # ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
 STATE_MAGIC = 0x4554415453544C46
 STATE_ALIGN = 256
@@ -404,6 +417,8 @@ def load_library():
     lib.fleet_policy_load_dev.argtypes = [vp, C.POINTER(vp), C.c_int]
     lib.fleet_policy_forward_dev.argtypes = [vp, f32p, C.c_int, vp, f32p, f32p]
     lib.fleet_policy_describe.argtypes = [vp, C.POINTER(FleetPolicyParams)]
+    lib.fleet_explore_act_dev.argtypes = [vp, f32p, C.c_int, vp, C.POINTER(FleetExploreArgs)]
+    lib.fleet_explore_act_dev.restype = C.c_int
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS)):
         for name in names:
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
@@ -449,6 +464,8 @@ POLICY_SYMBOLS = (
     "fleet_policy_load_dev", "fleet_policy_forward_dev", "fleet_policy_describe",
 )
 
+EXPLORE_SYMBOLS = ("fleet_explore_act_dev",)
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -461,7 +478,7 @@ EXPORTED_SYMBOLS = (
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

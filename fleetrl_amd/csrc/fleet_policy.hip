@@ -14,6 +14,13 @@
 //                   A wavefront works on units of 64 columns x R rows, at most two, which share their LDS reads: R = 16 for layers
 //                   of 4..8 column groups, 8 for 2..3, 4 for one (four wavefronts split the rows of a 64-wide layer).
 //   policy_relay    load_dev: torch's [out, in] tensors -> the padded [in][out] image, one launch for all of them.
+//   policy_forward_sample  fleet_explore_act_dev (include/fleet_hip.h "exploration actions on the device"): the same forward, but
+//                   head 0's last layer leaves its 16 rows of means in the LDS, behind the staged input, instead of storing the
+//                   transformed output; after a barrier the workgroup runs the sampling epilogue as a phase of its own -- one
+//                   thread per (row, 4 columns): one Philox block, two Box-Muller pairs, the action, the env's action and the
+//                   log-probability terms, which a wavefront per 4 rows then sums in an order that depends on A alone.  The
+//                   critic's workgroups (blockIdx.y = 1) are those of policy_forward.
+//   explore_uniform the warm-up's uniform actions: no network.
 // Launch boundaries are the only visibility mechanism.  float32 throughout (the normalisation in float64, as everywhere).
 #include <hip/hip_runtime.h>
 
@@ -24,6 +31,7 @@
 
 #include "fleet_handle.h"
 #include "fleet_norm.h"
+#include "fleet_philox.h"
 #include "fleet_policy.h"
 
 namespace {
@@ -87,10 +95,12 @@ __device__ __forceinline__ float output_of(float y, int output, float lo, float 
   return output == FLEET_POLICY_OUT_TANH ? tanhf(y) : y;
 }
 
-// one layer for the tile: `in` -> `out` (activation buffers in the LDS, row stride S), or the staged input -> ... -> global memory
-template <int R, bool kNorm>
+// one layer for the tile: `in` -> `out` (activation buffers in the LDS, row stride S), or the staged input -> ... -> global memory;
+// kSample: head 0's last layer -> means[16][out64] in the LDS, untransformed (every column and row of the tile: the padding's
+// results are finite-or-NaN numbers nobody reads)
+template <int R, bool kNorm, bool kSample>
 __device__ __forceinline__ void run_layer(const ForwardArgs& a, const PolicyHeadDesc* H, const PolicyLayer& L, bool first, bool last,
-                                          const float* in, float* out, float* xs, int S, int row0, float* gout) {
+                                          const float* in, float* out, float* xs, int S, int row0, float* gout, float* means) {
   constexpr int kSplit = kPolicyRows / R;  // row groups per column group
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -131,6 +141,8 @@ __device__ __forceinline__ void run_layer(const ForwardArgs& a, const PolicyHead
       const int rr = q * R + r;
       if (!last) {
         out[rr * S + j] = hidden_act(y, activation);  // (a padding column gets act(0) = 0: the next layer's padded inputs)
+      } else if (kSample && means) {
+        means[rr * L.out64 + j] = y;
       } else if (j < L.out && row0 + rr < a.E) {
         gout[(size_t)(row0 + rr) * L.out + j] = output_of(y, output, lo, hi);
       }
@@ -138,26 +150,150 @@ __device__ __forceinline__ void run_layer(const ForwardArgs& a, const PolicyHead
   }
 }
 
-template <bool kNorm>
-__global__ __launch_bounds__(kPolicyThreads) void policy_forward(ForwardArgs a) {
-  extern __shared__ float lds[];  // two activation buffers [16][S], then the staged input [16][kPolicyChunk]
+// what the sampling epilogue needs beside the forward's arguments (include/fleet_hip.h FleetExploreArgs)
+struct SampleArgs {
+  const float *scale, *shift;
+  float *noise, *actions, *env_actions, *log_prob, *mean;
+  uint64_t seed, step;
+  uint32_t env0;  // global id of row 0
+  int mode, given;
+  float lo, hi;  // ACTION_NOISE: the clip
+};
+
+// the four standard normals of one Philox block: Box-Muller on (x0, x1) and (x2, x3)
+__device__ __forceinline__ void normals4(const uint32_t* x, float* z) {
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const float u1 = (float)((x[2 * p] >> 8) + 1u) * 0x1p-24f;  // (0, 1], exact
+    const float u2 = (float)(x[2 * p + 1] >> 8) * 0x1p-24f;     // [0, 1), exact
+    const float r = sqrtf(-2.0f * logf(u1));
+    const float t = 6.283185307179586f * u2;
+    z[2 * p] = r * cosf(t);
+    z[2 * p + 1] = r * sinf(t);
+  }
+}
+
+// The epilogue of head 0: means[16][M] (the last layer's output before its transform) -> noise, actions, env_actions, mean; the
+// log-probability terms replace the means in place and are summed per row after a barrier.
+__device__ __forceinline__ void sample_epilogue(const ForwardArgs& a, const SampleArgs& x, const PolicyHeadDesc* H, float* means, int M,
+                                                int A, int row0) {
+  const int nb = (A + 3) / 4;  // Philox blocks per row
+  const int output = H->output;
+  const float hlo = H->lo, hhi = H->hi;
+  const bool gauss = x.mode == FLEET_EXPLORE_GAUSSIAN;
+  for (int item = threadIdx.x; item < kPolicyRows * nb; item += kPolicyThreads) {
+    const int r = item / nb, b = item - r * nb;
+    const int row = row0 + r;
+    if (row >= a.E) continue;
+    const size_t o = (size_t)row * A;
+    float z[4];
+    if (x.given) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) z[c] = 4 * b + c < A ? x.noise[o + 4 * b + c] : 0.0f;
+    } else {
+      uint32_t w[4];
+      philox4x32_10(x.env0 + (uint32_t)row, (uint32_t)b, (uint32_t)x.step, (uint32_t)(x.step >> 32), (uint32_t)x.seed,
+                    (uint32_t)(x.seed >> 32), w);
+      normals4(w, z);
+    }
+    const float4 m4 = *reinterpret_cast<const float4*>(means + r * M + 4 * b);  // (M is a multiple of 64: aligned, inside the row)
+    const float mz[4] = {m4.x, m4.y, m4.z, m4.w};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int j = 4 * b + c;
+      if (j >= A) break;
+      const float eps = z[c], m = mz[c], sc = x.scale[j];
+      if (!x.given && x.noise) x.noise[o + j] = eps;
+      float act, env, mu = m;
+      if (gauss) {
+        const float sd = expf(sc);
+        act = fmaf(sd, eps, m);
+        env = output_of(act, output, hlo, hhi);
+        const float dm = act - m;
+        means[r * M + j] = -(dm * dm) / (2.0f * sd * sd) - sc - 0.9189385332f;  // torch's Normal.log_prob on the stored action
+      } else {
+        mu = output_of(m, output, hlo, hhi);
+        const float n = (x.shift ? x.shift[j] : 0.0f) + sc * eps;
+        const float v = mu + n;
+        act = env = v < x.lo ? x.lo : (v > x.hi ? x.hi : v);
+      }
+      x.actions[o + j] = act;
+      if (x.env_actions) x.env_actions[o + j] = env;
+      if (x.mean) x.mean[o + j] = mu;
+    }
+  }
+  if (!x.log_prob) return;  // (uniform over the launch)
+  __syncthreads();
+  // a wavefront sums 4 rows: every lane its columns lane, lane + 64, ... in ascending order, then a butterfly over the 64 lanes
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int r = w * (kPolicyRows / kPolicyWaves); r < (w + 1) * (kPolicyRows / kPolicyWaves); ++r) {
+    float sum = 0.0f;
+    for (int j = lane; j < A; j += 64) sum += means[r * M + j];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0 && row0 + r < a.E) x.log_prob[row0 + r] = sum;
+  }
+}
+
+template <bool kNorm, bool kSample>
+__device__ __forceinline__ void forward_tile(const ForwardArgs& a, const SampleArgs* x) {
+  extern __shared__ float lds[];  // two activation buffers [16][S], then the staged input [16][kPolicyChunk]; kSample: then [16][M]
   const PolicyDesc* __restrict__ d = a.desc;
   const PolicyHeadDesc* __restrict__ H = &d->head[blockIdx.y];
   const int S = d->stride;
   float *cur = lds, *nxt = lds + kPolicyRows * S, *xs = lds + 2 * kPolicyRows * S;
+  float* means = kSample && blockIdx.y == 0 ? xs + kPolicyRows * kPolicyChunk : nullptr;
   const int row0 = blockIdx.x * kPolicyRows;
   float* gout = blockIdx.y ? a.values : a.actions;
   const int n = H->n_layers;
   for (int l = 0; l < n; ++l) {
     const PolicyLayer L = H->layer[l];
     const int groups = L.out64 / 64;
-    if (groups >= 4) run_layer<16, kNorm>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout);
-    else if (groups >= 2) run_layer<8, kNorm>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout);
-    else run_layer<4, kNorm>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout);
+    if (groups >= 4) run_layer<16, kNorm, kSample>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout, means);
+    else if (groups >= 2) run_layer<8, kNorm, kSample>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout, means);
+    else run_layer<4, kNorm, kSample>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout, means);
     __syncthreads();
     float* t = cur;
     cur = nxt;
     nxt = t;
+  }
+  if (kSample && means) sample_epilogue(a, *x, H, means, H->layer[n - 1].out64, H->layer[n - 1].out, row0);
+}
+
+template <bool kNorm>
+__global__ __launch_bounds__(kPolicyThreads) void policy_forward(ForwardArgs a) {
+  forward_tile<kNorm, false>(a, nullptr);
+}
+
+template <bool kNorm>
+__global__ __launch_bounds__(kPolicyThreads) void policy_forward_sample(ForwardArgs a, SampleArgs x) {
+  forward_tile<kNorm, true>(a, &x);
+}
+
+// ---- explore_uniform -------------------------------------------------------------------------------------------------------------
+// a[e][j] = lo + (hi - lo) * u2 of the column's own word of the row's Philox block, kept below hi; one thread per (row, 4 columns)
+__global__ __launch_bounds__(256) void explore_uniform(SampleArgs x, int E, int A) {
+  const int nb = (A + 3) / 4;
+  const size_t items = (size_t)E * nb;
+  for (size_t item = (size_t)blockIdx.x * 256 + threadIdx.x; item < items; item += (size_t)gridDim.x * 256) {
+    const size_t row = item / nb;
+    const int b = (int)(item - row * nb);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (!x.given)
+      philox4x32_10(x.env0 + (uint32_t)row, (uint32_t)b, (uint32_t)x.step, (uint32_t)(x.step >> 32), (uint32_t)x.seed, (uint32_t)(x.seed >> 32), w);
+    const float top = x.lo < x.hi ? nextafterf(x.hi, x.lo) : x.lo;  // the largest value of [lo, hi)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int j = 4 * b + c;
+      if (j >= A) break;
+      const size_t o = row * A + j;
+      const float u = x.given ? x.noise[o] : (float)(w[c] >> 8) * 0x1p-24f;
+      if (!x.given && x.noise) x.noise[o] = u;
+      float v = x.lo + (x.hi - x.lo) * u;
+      if (v > top) v = top;  // (the sum may round up to hi)
+      x.actions[o] = v;
+      if (x.env_actions) x.env_actions[o] = v;
+    }
   }
 }
 
@@ -249,6 +385,7 @@ struct FleetPolicy : FleetHandleBase {
   PolicyDesc desc{};
   size_t floats = 0;     // of the block
   size_t lds_bytes = 0;  // of one workgroup of policy_forward
+  size_t sample_lds_bytes = 0;  // ... of policy_forward_sample: the means of head 0's last layer behind it
   int n_tensors = 0;
 };
 
@@ -301,6 +438,7 @@ int fleet_policy_create(int device, const FleetPolicyParams* p, const float* hos
   h->p.tile_rows = kPolicyRows;
   h->floats = describe_layout(*p, &h->desc);
   h->lds_bytes = ((size_t)2 * kPolicyRows * h->desc.stride + (size_t)kPolicyRows * kPolicyChunk) * sizeof(float);
+  h->sample_lds_bytes = h->lds_bytes + (size_t)kPolicyRows * h->desc.head[0].layer[p->head[0].n_layers - 1].out64 * sizeof(float);
   for (int hd = 0; hd < p->n_heads; ++hd) h->n_tensors += 2 * p->head[hd].n_layers;
   std::vector<float> image;
   why = build_image(h, host_weights, &image);
@@ -314,10 +452,13 @@ int fleet_policy_create(int device, const FleetPolicyParams* p, const float* hos
     // more than the 64 KiB a launch gets unasked when a hidden layer is wider than 448; the attribute belongs to the kernel, not
     // to the handle, so every policy asks for what the widest one needs
     constexpr int kMaxLds = (2 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk) * (int)sizeof(float);
+    constexpr int kMaxSampleLds = kMaxLds + kPolicyRows * FLEET_POLICY_MAX_WIDTH * (int)sizeof(float);
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward_sample<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSampleLds) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward_sample<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSampleLds) != hipSuccess) {
       (void)hipGetLastError();
-      g_policy_create_error = "hipFuncSetAttribute failed for the policy kernel's " + std::to_string(kMaxLds) + " bytes of LDS";
+      g_policy_create_error = "hipFuncSetAttribute failed for the policy kernel's " + std::to_string(kMaxSampleLds) + " bytes of LDS";
       rc = FLEET_ERR_HIP;
     }
   }
@@ -421,6 +562,64 @@ int fleet_policy_forward_dev(fleet_policy_handle h, const float* obs, int E, fle
 int fleet_policy_describe(fleet_policy_handle h, FleetPolicyParams* out) {
   if (!h || !out) return FLEET_ERR_INVALID;
   *out = h->p;
+  return FLEET_OK;
+}
+
+int fleet_explore_act_dev(fleet_policy_handle h, const float* obs, int E, fleet_norm_handle norm, const FleetExploreArgs* args) {
+  if (!h) return FLEET_ERR_INVALID;
+  const auto refuse = [h](const std::string& why) {
+    h->error = "fleet_explore_act_dev: " + why;
+    return FLEET_ERR_INVALID;
+  };
+  if (!args) return refuse("null FleetExploreArgs");
+  const FleetExploreArgs& x = *args;
+  if (x.struct_bytes != (int32_t)sizeof(FleetExploreArgs)) return refuse("FleetExploreArgs.struct_bytes does not match this library");
+  if (x.mode != FLEET_EXPLORE_GAUSSIAN && x.mode != FLEET_EXPLORE_ACTION_NOISE && x.mode != FLEET_EXPLORE_UNIFORM)
+    return refuse("unknown mode " + std::to_string(x.mode));
+  if (x.noise_mode != FLEET_EXPLORE_NOISE_DRAW && x.noise_mode != FLEET_EXPLORE_NOISE_GIVEN)
+    return refuse("unknown noise_mode " + std::to_string(x.noise_mode));
+  const bool uniform = x.mode == FLEET_EXPLORE_UNIFORM;
+  if (E < 1) return refuse("E must be >= 1, got " + std::to_string(E));
+  if (!x.actions) return refuse("null actions");
+  if (!uniform && !obs) return refuse("null obs");
+  if (!uniform && !x.scale) return refuse("null scale (log_std or sigma)");
+  if (x.log_prob && x.mode != FLEET_EXPLORE_GAUSSIAN) return refuse("log_prob asked outside the GAUSSIAN mode");
+  if (x.values && uniform) return refuse("values asked in the UNIFORM mode: no network runs");
+  if (x.values && h->p.n_heads < 2) return refuse("values asked of a policy without a critic head");
+  if (x.noise_mode == FLEET_EXPLORE_NOISE_GIVEN && !x.noise) return refuse("noise_mode GIVEN with a null noise");
+  // (GAUSSIAN does not read the bounds: the head's own clip is its transform)
+  if (x.mode != FLEET_EXPLORE_GAUSSIAN && !(x.noise_lo <= x.noise_hi)) return refuse("the bounds need noise_lo <= noise_hi");
+  if (x.env_id_offset < 0) return refuse("env_id_offset must be >= 0, got " + std::to_string(x.env_id_offset));
+  SampleArgs s{};
+  s.scale = x.scale, s.shift = x.shift, s.noise = x.noise, s.actions = x.actions, s.env_actions = x.env_actions;
+  s.log_prob = x.log_prob, s.mean = x.mean, s.seed = x.seed, s.step = x.step, s.env0 = (uint32_t)x.env_id_offset;
+  s.mode = x.mode, s.given = x.noise_mode == FLEET_EXPLORE_NOISE_GIVEN, s.lo = x.noise_lo, s.hi = x.noise_hi;
+  const int A = h->p.head[0].width[h->p.head[0].n_layers - 1];
+  FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
+  if (uniform) {
+    hipLaunchKernelGGL(explore_uniform, dim3(grid_for((size_t)E * ((A + 3) / 4), 256, 4096)), dim3(256), 0, h->stream, s, E, A);
+    FLEET_HANDLE_TRY(h, hipGetLastError());
+    return FLEET_OK;
+  }
+  ForwardArgs a{};
+  a.desc = reinterpret_cast<const PolicyDesc*>(h->block);
+  a.base = reinterpret_cast<const float*>(h->block);
+  a.obs = obs, a.actions = nullptr, a.values = x.values, a.E = E;
+  bool norm_obs = false;
+  if (norm) {
+    FleetNormView v{};
+    FLEET_HANDLE_TRY(h, fleet_norm_begin_read(norm, h->stream, &v));
+    if (v.D != h->p.obs_dim || v.device != h->device)
+      return refuse("the normaliser has obs_dim " + std::to_string(v.D) + " on device " + std::to_string(v.device) + ", the policy " +
+                    std::to_string(h->p.obs_dim) + " on device " + std::to_string(h->device));
+    a.mean = v.obs_mean, a.sd = v.obs_sd, a.clip = v.clip_obs;
+    norm_obs = v.norm_obs != 0;
+  }
+  const dim3 grid((unsigned)(((size_t)E + kPolicyRows - 1) / kPolicyRows), x.values ? 2 : 1), block(kPolicyThreads);
+  if (norm_obs) hipLaunchKernelGGL(policy_forward_sample<true>, grid, block, h->sample_lds_bytes, h->stream, a, s);
+  else hipLaunchKernelGGL(policy_forward_sample<false>, grid, block, h->sample_lds_bytes, h->stream, a, s);
+  FLEET_HANDLE_TRY(h, hipGetLastError());
+  if (norm) FLEET_HANDLE_TRY(h, fleet_norm_end_read(norm, h->stream));
   return FLEET_OK;
 }
 

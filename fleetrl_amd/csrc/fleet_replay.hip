@@ -19,6 +19,7 @@
 
 #include "fleet_handle.h"
 #include "fleet_norm.h"
+#include "fleet_philox.h"
 #include "fleet_replay.h"
 
 namespace {
@@ -81,20 +82,6 @@ struct SampleArgs {
   int D, A;
   int norm_obs, norm_reward, obs_vec, act_vec;
 };
-
-// Philox4x32-10 (Salmon et al., SC'11): the block of counter (c0, c1, c2, c3) under key (k0, k1)
-__device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* x) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  x[0] = c0, x[1] = c1, x[2] = c2, x[3] = c3;
-}
 
 // one row of D floats, normalised column by column when kNorm; mean / sd in the LDS or in global memory
 template <bool kNorm>

@@ -4,8 +4,13 @@ SB3's evaluation loop with everything but the episode quotas on the GPU.
 The forward is one launch (fleetrl_amd/csrc/fleet_policy.hip, include/fleet_hip.h `fleet_policy_*`): it takes raw or normalised
 observations, applies a normaliser's frozen statistics where asked, runs the actor and optionally the critic, and writes float32
 actions `FleetVecEnv.step_torch` reads directly.  The weights come from a state dict, from the `policy.pth` of an SB3 archive (read
-with `zipfile` and `torch.load(weights_only=True)`: SB3 itself is not needed) or from plain arrays.  Stochastic actions,
-log-probabilities and training are not here: sampling and the backward pass stay the caller's.
+with `zipfile` and `torch.load(weights_only=True)`: SB3 itself is not needed) or from plain arrays.
+
+Exploration is one launch as well (`fleet_explore_act_dev`): `sample` draws PPO's Gaussian action, its clipped twin for the env,
+the summed log-probability and the value; `explore` adds TD3's action noise to the deterministic action; `sample_uniform` is the
+warm-up's `action_space.sample()`.  The noise is counter-based (Philox4x32-10 keyed by seed, global env id, step and column), so a
+run is reproducible from (seed, step) alone.  `predict` and `evaluate_policy` stay deterministic; training -- the backward pass --
+stays the caller's.
 """
 from __future__ import annotations
 
@@ -138,6 +143,7 @@ class DevicePolicy(_DeviceHandle):
             raise FleetHipError(rc, self.lib.fleet_policy_last_error(None).decode())
         self.h = h
         self._stream = None
+        self._constants = {}  # _per_action's device tensors of float arguments
         self.tile_rows = self.describe()["tile_rows"]
 
     @staticmethod
@@ -207,6 +213,95 @@ class DevicePolicy(_DeviceHandle):
             vp = self._tensor(values_out, (E, max(self.value_dim, 1)), (torch.float32,)).data_ptr()
         self.forward_dev(obs.data_ptr(), E, normalizer, self._tensor(out, (E, self.act_dim), (torch.float32,)).data_ptr(), vp)
         return out
+
+    # ---- exploration ---------------------------------------------------------------------------------------------------------
+    def explore_dev(self, obs_ptr: int | None, num_envs: int, norm, args: "_capi.FleetExploreArgs"):
+        """Raw device addresses in a FleetExploreArgs, on the policy's stream."""
+        args.struct_bytes = C.sizeof(_capi.FleetExploreArgs)
+        self._check(self.lib.fleet_explore_act_dev(self.h, obs_ptr, int(num_envs), _norm_handle(norm), C.byref(args)))
+
+    def _per_action(self, key: str, v):
+        """`v` as a device f32 [act_dim] tensor: a tensor is taken as it is, a float or an array is broadcast into a cached one.
+        A float that CHANGES between calls replaces the cached tensor through a host-to-device copy, which synchronises the host
+        with the stream: a value that varies inside a loop (a decaying sigma, a learned log_std) belongs in a device tensor."""
+        import torch
+
+        if isinstance(v, torch.Tensor):
+            return self._tensor(v.detach(), (self.act_dim,), (torch.float32,))
+        host = np.broadcast_to(np.asarray(v, dtype=np.float32), (self.act_dim,))
+        hit = self._constants.get(key)
+        if hit is None or not np.array_equal(hit[0], host):
+            hit = self._constants[key] = (host.copy(), torch.from_numpy(host.copy()).to(torch.device("cuda", self.device)))
+        return hit[1]
+
+    def _explore(self, mode, obs, E, scale, shift, low, high, seed, step, env_id_offset, normalizer, actions_out, env_actions_out,
+                 log_prob_out, values_out, mean_out, noise, noise_given, want_log_prob):
+        import torch
+
+        self.use_torch_stream()
+        dev, f32, A = torch.device("cuda", self.device), (torch.float32,), self.act_dim
+        a = _capi.FleetExploreArgs()
+        a.mode, a.noise_mode = mode, _capi.EXPLORE_NOISE_GIVEN if noise_given else _capi.EXPLORE_NOISE_DRAW
+        a.seed, a.step, a.env_id_offset = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(env_id_offset)
+        a.noise_lo, a.noise_hi = float(low), float(high)
+        keep = [self._per_action("scale", scale)] if scale is not None else []
+        a.scale = keep[0].data_ptr() if keep else None
+        if shift is not None:
+            keep.append(self._per_action("shift", shift))
+            a.shift = keep[-1].data_ptr()
+        if obs is not None:
+            obs = self._tensor(obs, (E, self.obs_dim), f32)
+
+        def out(t, shape, make=True):
+            if t is None:
+                if not make:
+                    return None
+                t = torch.empty(shape, device=dev, dtype=torch.float32)
+            return self._tensor(t, shape, f32)
+
+        actions, env_actions = out(actions_out, (E, A)), out(env_actions_out, (E, A))
+        log_prob = out(log_prob_out, (E,), want_log_prob)
+        values = out(values_out, (E, max(self.value_dim, 1)), False)
+        mean, noise = out(mean_out, (E, A), False), out(noise, (E, A), False)
+        if noise_given and noise is None:
+            raise ValueError("noise_given needs the noise tensor")
+        a.actions, a.env_actions = actions.data_ptr(), env_actions.data_ptr()
+        for name, t in (("log_prob", log_prob), ("values", values), ("mean", mean), ("noise", noise)):
+            setattr(a, name, None if t is None else t.data_ptr())
+        self.explore_dev(None if obs is None else obs.data_ptr(), E, normalizer, a)
+        return actions, env_actions, log_prob, values
+
+    def sample(self, obs, log_std, *, seed: int, step: int, env_id_offset: int = 0, normalizer=None, actions_out=None,
+               env_actions_out=None, log_prob_out=None, values_out=None, mean_out=None, noise=None, noise_given: bool = False):
+        """PPO's rollout step in one launch: obs f32 [E, obs_dim] -> (actions, env_actions, log_prob, values), SB3's
+        DiagGaussianDistribution with the state-independent `log_std` (a torch parameter f32 [act_dim], read when the launch
+        runs; a float or an array also does).  actions = mean + exp(log_std) * eps is what the buffer keeps, env_actions its
+        output transform (the clip) is what the env steps on, log_prob f32 [E] is torch's Normal.log_prob of the stored action
+        summed over the columns, values (None unless values_out is given) the critic's output.  eps is Philox noise of (seed,
+        env_id_offset + row, step, column).  The *_out tensors may be the rows of `DeviceRolloutBuffer.slot(t)`; `noise` f32
+        [E, act_dim] receives eps, or supplies it with noise_given.  A float `log_std` is cached on the device; one that changes
+        from call to call costs a host synchronisation each time (pass the parameter tensor instead).  env_id_offset >= 0."""
+        E = int(obs.shape[0]) if obs.ndim == 2 else 0
+        return self._explore(_capi.EXPLORE_GAUSSIAN, obs, E, log_std, None, 0.0, 0.0, seed, step, env_id_offset, normalizer,
+                             actions_out, env_actions_out, log_prob_out, values_out, mean_out, noise, noise_given, True)
+
+    def explore(self, obs, sigma, *, shift=None, low: float = -1.0, high: float = 1.0, seed: int, step: int, env_id_offset: int = 0,
+                normalizer=None, actions_out=None, env_actions_out=None, values_out=None, mean_out=None, noise=None,
+                noise_given: bool = False):
+        """TD3 / DDPG's exploration step in one launch (SB3's `_sample_action` with NormalActionNoise): actions = env_actions =
+        clip(act(obs) + shift + sigma * eps, low, high).  sigma, shift: floats, arrays or device tensors f32 [act_dim]; a float
+        is cached on the device, and one that changes from call to call (a decaying sigma) costs a host synchronisation each
+        time: keep such a value in a device tensor."""
+        E = int(obs.shape[0]) if obs.ndim == 2 else 0
+        return self._explore(_capi.EXPLORE_ACTION_NOISE, obs, E, sigma, shift, low, high, seed, step, env_id_offset, normalizer,
+                             actions_out, env_actions_out, None, values_out, mean_out, noise, noise_given, False)
+
+    def sample_uniform(self, num_envs: int, *, low: float = -1.0, high: float = 1.0, seed: int, step: int, env_id_offset: int = 0,
+                       actions_out=None, env_actions_out=None, noise=None, noise_given: bool = False):
+        """The warm-up's `action_space.sample()`: uniform actions low + (high - low) * u in [low, high), no network (where the
+        float32 sum rounds up to `high` the kernel returns the float below it; low == high gives low)."""
+        return self._explore(_capi.EXPLORE_UNIFORM, None, int(num_envs), None, None, low, high, seed, step, env_id_offset, None,
+                             actions_out, env_actions_out, None, None, None, noise, noise_given, False)
 
     def predict(self, observation, state=None, episode_start=None, deterministic: bool = True):
         """SB3's `predict` for host callers: NumPy observations [E, obs_dim] (or one observation [obs_dim]) -> (actions, None)."""

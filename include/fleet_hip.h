@@ -886,6 +886,63 @@ int fleet_policy_forward_dev(fleet_policy_handle h, const float* obs, int E, fle
 /* the parameters the policy was created with, and tile_rows */
 int fleet_policy_describe(fleet_policy_handle h, FleetPolicyParams* out);
 
+/* ---- exploration actions on the device (fleet_policy.hip; DESIGN.md "Exploration on the device") ---------------------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * What a training loop does between reading a step's observations and stepping the env, in ONE launch on a policy handle: the actor
+ * (and the critic when `values` is given) as fleet_policy_forward_dev runs them, the exploration noise drawn on the device, and the
+ * sampled action, the action the env steps on, the summed log-probability and the value written where the caller says -- the rows
+ * of a rollout slot (fleet_rollout_slot) included, which fleet_rollout_add_dev then leaves alone.  float32 throughout.
+ * Noise.  eps[e][j] of env row e and action column j comes from Philox4x32-10 (the generator of fleet_replay_sample_dev) with key
+ * (seed lo, seed hi) and counter (env_id_offset + e, j / 4, step lo, step hi): the block's words x0..x3 give the standard normals of
+ * columns 4(j/4) .. 4(j/4)+3 by Box-Muller on the pairs (x0, x1) and (x2, x3),
+ *   u1 = ((x >> 8) + 1) * 2^-24 in (0, 1],  u2 = (x' >> 8) * 2^-24 in [0, 1),  r = sqrtf(-2 logf(u1)),
+ *   even column r * cosf(2 pi u2), odd column r * sinf(2 pi u2)                                    (|eps| <= sqrt(48 ln 2) = 5.77)
+ * with the device library's functions.  A draw depends on (seed, global env id, step, column) and on nothing else: not on E, on the
+ * row's place in the batch, on the stream, on the critic, or on how the envs are sharded over GPUs.  noise_mode GIVEN reads eps from
+ * noise[e][j] instead; DRAW with a non-null `noise` writes what was drawn there.
+ * GAUSSIAN (PPO / A2C: SB3's DiagGaussianDistribution with a state-independent log_std = scale[A], read from device memory when the
+ * launch runs).  mean = head 0's last layer BEFORE its output transform; std = expf(log_std[j]); a = fmaf(std, eps, mean);
+ * actions = a; env_actions = the head's output transform of a (CLIP for PPO: the env sees the clipped action, the buffer keeps the
+ * sampled one); log_prob[e] = sum over j of -((a - mean)^2) / (2 * std * std) - log_std[j] - 0.9189385332f, torch's expression on
+ * the STORED action, summed in an order that depends on A alone.
+ * ACTION_NOISE (TD3 / DDPG: SB3's NormalActionNoise on the unit action space).  d = head 0's output (tanh for TD3);
+ * a = d + (shift[j] + sigma[j] * eps) with sigma = scale[A] and shift[A] (NULL: 0), clipped to [noise_lo, noise_hi]; actions and
+ * env_actions both get a.
+ * UNIFORM (the learning_starts warm-up, action_space.sample()): a = noise_lo + (noise_hi - noise_lo) * u2 of the column's own word,
+ * kept below noise_hi where the float32 sum rounds up to it (noise_lo == noise_hi gives noise_lo);
+ * no network runs (a small kernel of its own), obs may be NULL, `noise` (when given in DRAW mode) receives u2.
+ * `mean` (optional, f32[E, A]) receives mean (GAUSSIAN) or d (ACTION_NOISE).  Every output of a row is a function of that row. */
+#define FLEET_EXPLORE_GAUSSIAN 0
+#define FLEET_EXPLORE_ACTION_NOISE 1
+#define FLEET_EXPLORE_UNIFORM 2
+#define FLEET_EXPLORE_NOISE_DRAW 0
+#define FLEET_EXPLORE_NOISE_GIVEN 1
+typedef struct FleetExploreArgs {
+  int32_t struct_bytes;    /* sizeof(FleetExploreArgs) */
+  int32_t mode;            /* FLEET_EXPLORE_GAUSSIAN / _ACTION_NOISE / _UNIFORM */
+  int32_t noise_mode;      /* FLEET_EXPLORE_NOISE_DRAW / _GIVEN */
+  int32_t reserved0;       /* 0 */
+  uint64_t seed;           /* Philox key */
+  uint64_t step;           /* Philox counter words 2, 3: the caller's step count */
+  int32_t env_id_offset;   /* global id of row 0 (a shard of a larger batch); >= 0 */
+  int32_t reserved1;       /* 0 */
+  const float* scale;      /* device f32[A]: log_std (GAUSSIAN) or sigma (ACTION_NOISE); unused in UNIFORM */
+  const float* shift;      /* device f32[A] or NULL (0): the action noise's mean */
+  float noise_lo, noise_hi;/* ACTION_NOISE: the clip of a; UNIFORM: the range.  Not read in GAUSSIAN */
+  float* noise;            /* device f32[E, A]: read (GIVEN), written when not NULL (DRAW) */
+  float* actions;          /* device f32[E, A]: the action the buffer keeps */
+  float* env_actions;      /* device f32[E, A] or NULL: the action the env steps on */
+  float* log_prob;         /* device f32[E] or NULL; GAUSSIAN only */
+  float* values;           /* device f32[E, width of head 1] or NULL: the critic's output */
+  float* mean;             /* device f32[E, A] or NULL */
+} FleetExploreArgs;
+/* Enqueues on the policy's stream, no host synchronisation.  norm: as for fleet_policy_forward_dev (ignored in UNIFORM).
+ * FLEET_ERR_INVALID (fleet_policy_last_error(h) says why, nothing is launched) for a wrong struct_bytes, an unknown mode or
+ * noise_mode, E < 1, a null `actions`, a null obs or scale outside UNIFORM, log_prob outside GAUSSIAN, values on a one-head policy
+ * or in UNIFORM, GIVEN with a null noise, a NaN bound or noise_lo > noise_hi (ACTION_NOISE, UNIFORM; GAUSSIAN does not read
+ * the bounds and accepts any), a negative env_id_offset, a normaliser of another width or device. */
+int fleet_explore_act_dev(fleet_policy_handle h, const float* obs, int E, fleet_norm_handle norm, const FleetExploreArgs* args);
+
 #ifdef __cplusplus
 }
 #endif
