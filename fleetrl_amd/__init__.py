@@ -5,6 +5,7 @@
     from fleetrl_amd import plan_linear_optimization, run_linear_optimization
     from fleetrl_amd import DeviceRolloutBuffer, DeviceReplayBuffer
     from fleetrl_amd import DevicePolicy, evaluate_policy
+    from fleetrl_amd import DevicePinkNoise, DeviceOUNoise
 """
 __version__ = "0.1.0"
 
@@ -34,6 +35,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import policy
 
         return getattr(policy, name)
+    if name in ("DevicePinkNoise", "DeviceOUNoise"):
+        from . import noise
+
+        return getattr(noise, name)
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

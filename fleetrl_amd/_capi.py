@@ -174,6 +174,17 @@ class FleetExploreArgs(C.Structure):
                 ("values", C.c_void_p), ("mean", C.c_void_p)]
 
 
+# ---- correlated action noise (include/fleet_hip.h "correlated action noise on the device", fleet_noise_*) ---------------------------
+NOISE_PINK, NOISE_OU = 0, 1
+NOISE_MAX_ACT_DIM, NOISE_MAX_SEQ_LEN = 512, 4096
+
+
+class FleetNoiseParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("kind", C.c_int32), ("num_envs", C.c_int32), ("act_dim", C.c_int32),
+                ("env_id_offset", C.c_int32), ("seq_len", C.c_int32), ("seed", C.c_uint64), ("beta", C.c_double), ("theta", C.c_double),
+                ("dt", C.c_double), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("cache_bytes", C.c_uint64)]
+
+
 # ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
 STATE_MAGIC = 0x4554415453544C46
 STATE_ALIGN = 256
@@ -419,7 +430,19 @@ def load_library():
     lib.fleet_policy_describe.argtypes = [vp, C.POINTER(FleetPolicyParams)]
     lib.fleet_explore_act_dev.argtypes = [vp, f32p, C.c_int, vp, C.POINTER(FleetExploreArgs)]
     lib.fleet_explore_act_dev.restype = C.c_int
-    for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS)):
+    # the correlated noise processes (fleet_noise.hip)
+    lib.fleet_noise_pink_tables.argtypes = [C.c_int, C.c_double, f32p, f32p]
+    lib.fleet_noise_create.argtypes = [C.c_int, C.POINTER(FleetNoiseParams), C.POINTER(vp)]
+    lib.fleet_noise_destroy.argtypes = [vp]
+    lib.fleet_noise_last_error.argtypes = [vp]
+    lib.fleet_noise_set_stream.argtypes = [vp, vp]
+    lib.fleet_noise_next_dev.argtypes = [vp, u8p, f32p]
+    lib.fleet_noise_reset_dev.argtypes = [vp, u8p]
+    lib.fleet_noise_get_state_dev.argtypes = [vp, vp, vp, f32p, C.POINTER(C.c_uint64)]
+    lib.fleet_noise_set_state_dev.argtypes = [vp, vp, vp, f32p, C.c_uint64]
+    lib.fleet_noise_describe.argtypes = [vp, C.POINTER(FleetNoiseParams)]
+    for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
+                          ("noise", NOISE_SYMBOLS)):
         for name in names:
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
@@ -466,6 +489,11 @@ POLICY_SYMBOLS = (
 
 EXPLORE_SYMBOLS = ("fleet_explore_act_dev",)
 
+NOISE_SYMBOLS = (
+    "fleet_noise_pink_tables", "fleet_noise_create", "fleet_noise_destroy", "fleet_noise_last_error", "fleet_noise_set_stream",
+    "fleet_noise_next_dev", "fleet_noise_reset_dev", "fleet_noise_get_state_dev", "fleet_noise_set_state_dev", "fleet_noise_describe",
+)
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -478,7 +506,7 @@ EXPORTED_SYMBOLS = (
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,
@@ -501,6 +529,16 @@ def _layout(prefix: str, params, out):
     if rc != OK:
         raise FleetHipError(rc, getattr(lib, f"fleet_{prefix}_last_error")(None).decode())
     return out
+
+
+def pink_tables(seq_len: int, beta: float = 1.0):
+    """fleet_noise_pink_tables: (gain f32 [seq_len // 2 + 1], twiddle f32 [seq_len, 2]) as the library builds them (no GPU)."""
+    lib = load_library()
+    gain, twiddle = np.zeros(max(int(seq_len), 0) // 2 + 1, np.float32), np.zeros((max(int(seq_len), 0), 2), np.float32)
+    rc = lib.fleet_noise_pink_tables(int(seq_len), float(beta), gain.ctypes.data, twiddle.ctypes.data)
+    if rc != OK:
+        raise FleetHipError(rc, lib.fleet_noise_last_error(None).decode())
+    return gain, twiddle
 
 
 def rollout_layout(num_envs: int, n_steps: int, obs_dim: int, act_dim: int, gamma: float = 0.99,

@@ -1,5 +1,6 @@
-// fleet_philox.h -- Philox4x32-10, the counter-based generator the replay buffer's index draw (fleet_replay.hip) and the exploration
-// noise (fleet_policy.hip) share.  (The env's start-row sampler keeps its own restatement: fleet_wave.h philox_start.)
+// fleet_philox.h -- Philox4x32-10, the counter-based generator the replay buffer's index draw (fleet_replay.hip), the exploration
+// noise (fleet_policy.hip) and the correlated noise processes (fleet_noise.hip) share, and the Box-Muller step of the latter two.
+// (The env's start-row sampler keeps its own restatement: fleet_wave.h philox_start.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,4 +17,17 @@ __device__ inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint
     k1 += 0xBB67AE85u;
   }
   x[0] = c0, x[1] = c1, x[2] = c2, x[3] = c3;
+}
+
+// the four standard normals of one Philox block: Box-Muller on (x0, x1) and (x2, x3)
+__device__ __forceinline__ void normals4(const uint32_t* x, float* z) {
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const float u1 = (float)((x[2 * p] >> 8) + 1u) * 0x1p-24f;  // (0, 1], exact
+    const float u2 = (float)(x[2 * p + 1] >> 8) * 0x1p-24f;     // [0, 1), exact
+    const float r = sqrtf(-2.0f * logf(u1));
+    const float t = 6.283185307179586f * u2;
+    z[2 * p] = r * cosf(t);
+    z[2 * p + 1] = r * sinf(t);
+  }
 }

@@ -160,19 +160,6 @@ struct SampleArgs {
   float lo, hi;  // ACTION_NOISE: the clip
 };
 
-// the four standard normals of one Philox block: Box-Muller on (x0, x1) and (x2, x3)
-__device__ __forceinline__ void normals4(const uint32_t* x, float* z) {
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const float u1 = (float)((x[2 * p] >> 8) + 1u) * 0x1p-24f;  // (0, 1], exact
-    const float u2 = (float)(x[2 * p + 1] >> 8) * 0x1p-24f;     // [0, 1), exact
-    const float r = sqrtf(-2.0f * logf(u1));
-    const float t = 6.283185307179586f * u2;
-    z[2 * p] = r * cosf(t);
-    z[2 * p + 1] = r * sinf(t);
-  }
-}
-
 // The epilogue of head 0: means[16][M] (the last layer's output before its transform) -> noise, actions, env_actions, mean; the
 // log-probability terms replace the means in place and are summed per row after a barrier.
 __device__ __forceinline__ void sample_epilogue(const ForwardArgs& a, const SampleArgs& x, const PolicyHeadDesc* H, float* means, int M,

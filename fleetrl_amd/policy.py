@@ -285,14 +285,24 @@ class DevicePolicy(_DeviceHandle):
         return self._explore(_capi.EXPLORE_GAUSSIAN, obs, E, log_std, None, 0.0, 0.0, seed, step, env_id_offset, normalizer,
                              actions_out, env_actions_out, log_prob_out, values_out, mean_out, noise, noise_given, True)
 
-    def explore(self, obs, sigma, *, shift=None, low: float = -1.0, high: float = 1.0, seed: int, step: int, env_id_offset: int = 0,
-                normalizer=None, actions_out=None, env_actions_out=None, values_out=None, mean_out=None, noise=None,
-                noise_given: bool = False):
+    def explore(self, obs, sigma, *, shift=None, low: float = -1.0, high: float = 1.0, seed: int | None = None, step: int | None = None,
+                env_id_offset: int = 0, normalizer=None, actions_out=None, env_actions_out=None, values_out=None, mean_out=None,
+                noise=None, noise_given: bool = False, action_noise=None, done=None):
         """TD3 / DDPG's exploration step in one launch (SB3's `_sample_action` with NormalActionNoise): actions = env_actions =
         clip(act(obs) + shift + sigma * eps, low, high).  sigma, shift: floats, arrays or device tensors f32 [act_dim]; a float
         is cached on the device, and one that changes from call to call (a decaying sigma) costs a host synchronisation each
-        time: keep such a value in a device tensor."""
+        time: keep such a value in a device tensor.
+        action_noise (a DevicePinkNoise or a DeviceOUNoise of the same E and act_dim): eps is `action_noise.next(done)` -- `done` the
+        env's done flags of the step before, so that an env's process starts afresh with its episode -- read through the given-noise
+        path; seed, step and env_id_offset are then the process's own and not looked at here, `noise` (when given) receives the
+        rows.  Without it, seed and step are required."""
         E = int(obs.shape[0]) if obs.ndim == 2 else 0
+        if action_noise is not None:
+            if noise_given:
+                raise ValueError("action_noise and noise_given exclude each other")
+            noise, noise_given, seed, step = action_noise.next(done, out=noise), True, 0, 0
+        elif seed is None or step is None:
+            raise TypeError("explore() needs seed= and step= unless action_noise= is given")
         return self._explore(_capi.EXPLORE_ACTION_NOISE, obs, E, sigma, shift, low, high, seed, step, env_id_offset, normalizer,
                              actions_out, env_actions_out, None, values_out, mean_out, noise, noise_given, False)
 

@@ -943,6 +943,87 @@ typedef struct FleetExploreArgs {
  * the bounds and accepts any), a negative env_id_offset, a normaliser of another width or device. */
 int fleet_explore_act_dev(fleet_policy_handle h, const float* obs, int E, fleet_norm_handle norm, const FleetExploreArgs* args);
 
+/* ---- correlated action noise on the device (fleet_noise.hip; DESIGN.md "Correlated action noise on the device") -------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * A process that produces the eps rows f32[E, A] fleet_explore_act_dev reads with noise_mode GIVEN, one row per env and call, with
+ * per-env episode resets (SB3's VectorizedActionNoise.reset(indices)).  Two kinds.
+ * PINK: power-law ("colored") noise, the Timmer-Koenig generator as colorednoise.powerlaw_psd_gaussian(beta, n) evaluates it, which
+ * pink.ColoredNoiseProcess / PinkActionNoise wrap (beta = 1): unit scale, the caller's sigma scales it.  Restated from the published
+ * algorithm.  One sequence of n = seq_len samples belongs to (seed, global env id g = env_id_offset + e, column j, sequence number
+ * q) and depends on nothing else: not on E, on the sharding, on the stream, on which other envs regenerate in the same call.  With
+ * K = n/2 + 1, f_k = k/n (f_0 := f_1), s_k = f_k^(-beta/2), w = s[1:] with its last element times (1 + n mod 2)/2 and
+ * sigma = 2 sqrt(sum w^2)/n, the host builds in float64 and rounds to float32 once
+ *   gain[0] = sqrt(2) s_0/(n sigma), gain[k] = 2 s_k/(n sigma) for 0 < 2k < n, gain[n/2] = sqrt(2) s_{n/2}/(n sigma) for even n,
+ *   twiddle[m] = (cos, sin)(2 pi m/n), m < n                                              (fleet_noise_pink_tables returns both)
+ * and the device evaluates the inverse real transform as a direct sum, sample by sample, in float32:
+ *   (a_k, b_k): Philox4x32-10 under key (seed lo, seed hi) at counter (g, 0x80000000 | (j/2), q, k); the Box-Muller of the
+ *   exploration section on (x0, x1) gives (a_k, b_k) of column 2(j/2), on (x2, x3) of column 2(j/2)+1 (cosine: a, sine: b)
+ *   ga = gain[k] * a_k;  gb = gain[k] * b_k, and gb = +0 for k = 0 and for 2k = n
+ *   y[t]: acc = 0; for k = 0 .. K-1 ascending, m = (k t) mod n in integers:
+ *           acc = fmaf(ga, cos[m], acc); acc = fmaf(-gb, sin[m], acc)
+ * -- that chain bit for bit; no sinf / cosf in it, no FFT.  Bit 31 of counter word 1 keeps the draws apart from the exploration
+ * epilogue's white noise (word 1 <= 127 there) and from OU's (bit 30) under one seed.  Var(y[t]) = sum of gain[k]^2 (slightly above
+ * 1: the DC term), corr(y[t], y[t+d]) = sum gain[k]^2 cos(2 pi k d/n) / sum gain[k]^2.
+ * State per env: t (int32, the position, 0..n) and q (uint32, the sequence number); the handle also keeps the current sequences of
+ * every env, E * n * A float32 as [E][n][A] (157 MB at 4096 x 192 x 50).  create generates q = 0 for every env, t = 0.
+ * fleet_noise_next_dev, one launch: an env with done[e] != 0 or t == n (the sequence is used up: the process's own wrap-around)
+ * takes q += 1, t = 0 and regenerates its n x A samples -- only such envs do; then eps_out[e][:] = sequence[t][:] and t += 1.
+ * A call in which many envs regenerate costs n^2/2 x 2 fused multiply-adds per column of each: with phase-locked episodes that is
+ * one slow call per episode.
+ * OU: SB3's OrnsteinUhlenbeckActionNoise per env, x <- x + theta (mu - x) dt + sigma sqrt(dt) eps, the output is x (it carries mu and
+ * sigma: pass sigma = 1 to the exploration step).  Host tables in float64 rounded to float32: th = theta * dt, ss[j] = sigma[j] *
+ * sqrt(dt), mu[j].  eps: the white normal of the exploration section at counter (g, 0x40000000 | (j/4), c lo, c hi), c = the number of
+ * fleet_noise_next_dev calls before this one (uint64, kept by the handle).  Per element, float32:
+ *   x0 = done[e] ? 0 : x;  d = mu[j] - x0;  u = fmaf(th, d, x0);  x = fmaf(ss[j], eps, u)
+ * State: x f32[E, A] and the call count.  Reset zeroes x.
+ * Every *_dev entry takes device pointers and enqueues on the handle's stream (its own, or the one fleet_noise_set_stream borrowed)
+ * without waiting for it, except fleet_noise_set_state_dev of a PINK process, which reads the positions back to look at them.  Calls
+ * on one handle are serialised by the caller.  No atomics. */
+#define FLEET_NOISE_PINK 0
+#define FLEET_NOISE_OU 1
+#define FLEET_NOISE_MAX_ACT_DIM 512
+#define FLEET_NOISE_MAX_SEQ_LEN 4096
+typedef struct FleetNoiseParams {
+  int32_t struct_bytes;   /* sizeof(FleetNoiseParams) */
+  int32_t kind;           /* FLEET_NOISE_PINK / _OU */
+  int32_t num_envs;       /* E >= 1 */
+  int32_t act_dim;        /* A, 1..FLEET_NOISE_MAX_ACT_DIM */
+  int32_t env_id_offset;  /* global id of row 0 (a shard of a larger batch); >= 0 */
+  int32_t seq_len;        /* PINK: n, 2..FLEET_NOISE_MAX_SEQ_LEN (the episode's steps); ignored by OU */
+  uint64_t seed;          /* Philox key */
+  double beta;            /* PINK: the spectrum's exponent, finite and >= 0 (1: pink, 0: white, 2: red) */
+  double theta, dt;       /* OU: finite, dt >= 0 (SB3's defaults: 0.15, 1e-2) */
+  const double* mu;       /* OU: HOST array [A], finite; read by create and not kept (describe returns NULL) */
+  const double* sigma;    /* OU: HOST array [A], finite */
+  uint64_t cache_bytes;   /* out (fleet_noise_describe): bytes of the PINK sequences on the device, 0 for OU; ignored by create */
+} FleetNoiseParams;
+typedef struct FleetNoise* fleet_noise_handle;
+
+/* The host tables of a PINK process, no device: gain f32[seq_len/2 + 1], twiddle f32[seq_len][2] (cos, sin).  FLEET_ERR_INVALID for
+ * seq_len outside 2..4096, a negative or non-finite beta, a null output. */
+int fleet_noise_pink_tables(int seq_len, double beta, float* gain, float* twiddle);
+/* The parameters are validated BEFORE the device is touched: FLEET_ERR_INVALID (fleet_noise_last_error(NULL) says why, starting with
+ * the entry's name) for a wrong struct_bytes, an unknown kind, num_envs < 1, act_dim outside 1..512, seq_len outside 2..4096, a
+ * negative or non-finite beta, a negative env_id_offset, non-finite theta / dt / mu / sigma or dt < 0, null mu / sigma (OU), a cache of
+ * more than 2^40 bytes.  FLEET_ERR_HIP with the byte count when the allocation fails.  The host waits for the first sequences. */
+int fleet_noise_create(int device, const FleetNoiseParams* p, fleet_noise_handle* out);
+int fleet_noise_destroy(fleet_noise_handle h);
+const char* fleet_noise_last_error(fleet_noise_handle h);  /* h may be NULL: error of the last failed fleet_noise_create */
+/* launch on an external hipStream_t (borrowed; NULL = the null stream) from now on; waits for what the previous stream still holds */
+int fleet_noise_set_stream(fleet_noise_handle h, void* hip_stream);
+/* eps_out f32[E, A] <- the next row of every env; done u8[E] or NULL (no env is done).  FLEET_ERR_INVALID for a null eps_out. */
+int fleet_noise_next_dev(fleet_noise_handle h, const uint8_t* done, float* eps_out);
+/* What fleet_noise_next_dev does to the envs with mask[e] != 0 (NULL: all) when they are done, and nothing else: PINK q += 1, t = 0
+ * and new sequences; OU x = 0.  Nothing is emitted, the other envs and OU's call count stay. */
+int fleet_noise_reset_dev(fleet_noise_handle h, const uint8_t* mask);
+/* The state into / from device arrays: PINK t i32[E] and q u32[E] (x is not looked at), OU x f32[E, A] (t, q are not looked at); the
+ * call count through the host (`calls` may be NULL in get).  set of a PINK process regenerates every env's sequences from q, and
+ * refuses (FLEET_ERR_INVALID, nothing changes) a t outside 0..n after reading the positions back: it waits for the stream. */
+int fleet_noise_get_state_dev(fleet_noise_handle h, int32_t* t, uint32_t* q, float* x, uint64_t* calls);
+int fleet_noise_set_state_dev(fleet_noise_handle h, const int32_t* t, const uint32_t* q, const float* x, uint64_t calls);
+/* the parameters the process was created with (mu, sigma NULL), and cache_bytes */
+int fleet_noise_describe(fleet_noise_handle h, FleetNoiseParams* out);
+
 #ifdef __cplusplus
 }
 #endif
