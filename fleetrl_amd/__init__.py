@@ -6,6 +6,7 @@
     from fleetrl_amd import DeviceRolloutBuffer, DeviceReplayBuffer
     from fleetrl_amd import DevicePolicy, evaluate_policy
     from fleetrl_amd import DevicePinkNoise, DeviceOUNoise
+    from fleetrl_amd import DeviceTD3Target
 """
 __version__ = "0.1.0"
 
@@ -39,6 +40,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import noise
 
         return getattr(noise, name)
+    if name == "DeviceTD3Target":
+        from . import qtarget
+
+        return qtarget.DeviceTD3Target
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

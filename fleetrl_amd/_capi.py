@@ -185,6 +185,19 @@ class FleetNoiseParams(C.Structure):
                 ("dt", C.c_double), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("cache_bytes", C.c_uint64)]
 
 
+# ---- TD3 / DDPG learning targets (include/fleet_hip.h "TD3 / DDPG learning targets on the device", fleet_qtarget_*) ----------------
+class FleetQTargetParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("obs_dim", C.c_int32), ("n_critics", C.c_int32), ("tile_rows", C.c_int32),
+                ("actor", FleetPolicyHead), ("critic", FleetPolicyHead * 2)]
+
+
+class FleetQTargetArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("noise_mode", C.c_int32), ("seed", C.c_uint64), ("step", C.c_uint64),
+                ("row_offset", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_float), ("noise_clip", C.c_float),
+                ("act_lo", C.c_float), ("act_hi", C.c_float), ("sigma", C.c_void_p), ("noise", C.c_void_p), ("target_q", C.c_void_p),
+                ("next_actions", C.c_void_p), ("q", C.c_void_p)]
+
+
 # ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
 STATE_MAGIC = 0x4554415453544C46
 STATE_ALIGN = 256
@@ -441,8 +454,19 @@ def load_library():
     lib.fleet_noise_get_state_dev.argtypes = [vp, vp, vp, f32p, C.POINTER(C.c_uint64)]
     lib.fleet_noise_set_state_dev.argtypes = [vp, vp, vp, f32p, C.c_uint64]
     lib.fleet_noise_describe.argtypes = [vp, C.POINTER(FleetNoiseParams)]
+    # the TD3 / DDPG target networks (fleet_qtarget.hip)
+    lib.fleet_qtarget_create.argtypes = [C.c_int, C.POINTER(FleetQTargetParams), f32p, C.POINTER(vp)]
+    lib.fleet_qtarget_destroy.argtypes = [vp]
+    lib.fleet_qtarget_last_error.argtypes = [vp]
+    lib.fleet_qtarget_set_stream.argtypes = [vp, vp]
+    lib.fleet_qtarget_load_host.argtypes = [vp, f32p]
+    lib.fleet_qtarget_load_dev.argtypes = [vp, C.POINTER(vp), C.c_int]
+    lib.fleet_qtarget_polyak_dev.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_double]
+    lib.fleet_qtarget_export_dev.argtypes = [vp, C.POINTER(vp), C.c_int]
+    lib.fleet_qtarget_target_dev.argtypes = [vp, f32p, f32p, f32p, C.c_int, C.POINTER(FleetQTargetArgs)]
+    lib.fleet_qtarget_describe.argtypes = [vp, C.POINTER(FleetQTargetParams)]
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
-                          ("noise", NOISE_SYMBOLS)):
+                          ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS)):
         for name in names:
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
@@ -494,6 +518,11 @@ NOISE_SYMBOLS = (
     "fleet_noise_next_dev", "fleet_noise_reset_dev", "fleet_noise_get_state_dev", "fleet_noise_set_state_dev", "fleet_noise_describe",
 )
 
+QTARGET_SYMBOLS = (
+    "fleet_qtarget_create", "fleet_qtarget_destroy", "fleet_qtarget_last_error", "fleet_qtarget_set_stream", "fleet_qtarget_load_host",
+    "fleet_qtarget_load_dev", "fleet_qtarget_polyak_dev", "fleet_qtarget_export_dev", "fleet_qtarget_target_dev", "fleet_qtarget_describe",
+)
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -506,7 +535,7 @@ EXPORTED_SYMBOLS = (
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

@@ -77,6 +77,21 @@ class _DeviceHandle:
                              f"cuda:{self.device}; got {tuple(t.shape)} {t.dtype} on {t.device}")
         return t
 
+    def _per_action(self, key: str, v):
+        """`v` as a device f32 [act_dim] tensor (handles with an `act_dim` and a `_constants` dict): a tensor is taken as it is, a
+        float or an array is broadcast into a cached one.  A float that CHANGES between calls replaces the cached tensor through a
+        host-to-device copy, which synchronises the host with the stream: a value that varies inside a loop (a decaying sigma, a
+        learned log_std) belongs in a device tensor."""
+        import torch
+
+        if isinstance(v, torch.Tensor):
+            return self._tensor(v.detach(), (self.act_dim,), (torch.float32,))
+        host = np.broadcast_to(np.asarray(v, dtype=np.float32), (self.act_dim,))
+        hit = self._constants.get(key)
+        if hit is None or not np.array_equal(hit[0], host):
+            hit = self._constants[key] = (host.copy(), torch.from_numpy(host.copy()).to(torch.device("cuda", self.device)))
+        return hit[1]
+
     def close(self):
         if getattr(self, "h", None):
             self._tensors = None

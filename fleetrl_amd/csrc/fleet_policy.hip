@@ -22,6 +22,7 @@
 //                   critic's workgroups (blockIdx.y = 1) are those of policy_forward.
 //   explore_uniform the warm-up's uniform actions: no network.
 // Launch boundaries are the only visibility mechanism.  float32 throughout (the normalisation in float64, as everywhere).
+// The layer functions (stage, accumulate, run_layer, run_head) live in fleet_policy_dev.h: fleet_qtarget.hip runs them too.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -33,122 +34,9 @@
 #include "fleet_norm.h"
 #include "fleet_philox.h"
 #include "fleet_policy.h"
+#include "fleet_policy_dev.h"
 
 namespace {
-
-struct ForwardArgs {
-  const PolicyDesc* desc;
-  const float* base;  // the block: offsets of PolicyLayer count from here
-  const float* obs;
-  float *actions, *values;
-  const double *mean, *sd;  // the normaliser's statistics (kNorm)
-  double clip;
-  int E;
-};
-
-// columns [k0, k0 + kPolicyChunk) of the tile's rows -> xs[row][col]; zeros past D and past E
-template <bool kNorm>
-__device__ __forceinline__ void stage(const ForwardArgs& a, float* xs, int row0, int k0, int D) {
-  const int col = threadIdx.x % kPolicyChunk, r0 = threadIdx.x / kPolicyChunk;
-  const int k = k0 + col;
-  double m = 0.0, s = 1.0;
-  if (kNorm && k < D) {
-    m = a.mean[k];
-    s = a.sd[k];
-  }
-#pragma unroll
-  for (int r = r0; r < kPolicyRows; r += kPolicyThreads / kPolicyChunk) {
-    const int row = row0 + r;
-    float v = 0.0f;
-    if (k < D && row < a.E) {
-      v = a.obs[(size_t)row * D + k];
-      if (kNorm) v = fleet_norm_obs1(v, m, s, a.clip);
-    }
-    xs[r * kPolicyChunk + col] = v;
-  }
-}
-
-// acc[r] += sum over k < kn (a multiple of 4) of xs[r][k] * W[k][j], ascending k, for column j0 (and j1 when kTwo)
-template <int R, bool kTwo>
-__device__ __forceinline__ void accumulate(const float* xs, int stride, int kn, const float* __restrict__ W, int O, int j0, int j1,
-                                           float (&acc0)[R], float (&acc1)[R]) {
-  for (int k = 0; k < kn; k += 4) {
-    const float* w = W + (size_t)k * O;
-    const float a0 = w[j0], a1 = w[O + j0], a2 = w[2 * O + j0], a3 = w[3 * O + j0];
-    float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;
-    if (kTwo) b0 = w[j1], b1 = w[O + j1], b2 = w[2 * O + j1], b3 = w[3 * O + j1];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float4 x = *reinterpret_cast<const float4*>(xs + r * stride + k);  // every lane the same address
-      acc0[r] = fmaf(x.w, a3, fmaf(x.z, a2, fmaf(x.y, a1, fmaf(x.x, a0, acc0[r]))));
-      if (kTwo) acc1[r] = fmaf(x.w, b3, fmaf(x.z, b2, fmaf(x.y, b1, fmaf(x.x, b0, acc1[r]))));
-    }
-  }
-}
-
-__device__ __forceinline__ float hidden_act(float y, int activation) {
-  return activation == FLEET_POLICY_ACT_RELU ? (y < 0.0f ? 0.0f : y) : tanhf(y);  // (a NaN stays one)
-}
-
-__device__ __forceinline__ float output_of(float y, int output, float lo, float hi) {
-  if (output == FLEET_POLICY_OUT_CLIP) return y < lo ? lo : (y > hi ? hi : y);
-  return output == FLEET_POLICY_OUT_TANH ? tanhf(y) : y;
-}
-
-// one layer for the tile: `in` -> `out` (activation buffers in the LDS, row stride S), or the staged input -> ... -> global memory;
-// kSample: head 0's last layer -> means[16][out64] in the LDS, untransformed (every column and row of the tile: the padding's
-// results are finite-or-NaN numbers nobody reads)
-template <int R, bool kNorm, bool kSample>
-__device__ __forceinline__ void run_layer(const ForwardArgs& a, const PolicyHeadDesc* H, const PolicyLayer& L, bool first, bool last,
-                                          const float* in, float* out, float* xs, int S, int row0, float* gout, float* means) {
-  constexpr int kSplit = kPolicyRows / R;  // row groups per column group
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int units = (L.out64 / 64) * kSplit;
-  const bool has0 = w < units, has1 = w + kPolicyWaves < units;
-  const int q = w % kSplit;  // (kPolicyWaves % kSplit == 0: both units of a wavefront take the same rows)
-  const int j0 = (w / kSplit) * 64 + lane, j1 = ((w + kPolicyWaves) / kSplit) * 64 + lane;
-  float acc0[R], acc1[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) acc0[r] = acc1[r] = 0.0f;
-  const float* W = a.base + L.w_off;
-  if (first) {
-    for (int k0 = 0; k0 < L.in; k0 += kPolicyChunk) {
-      const int kn = L.in4 - k0 < kPolicyChunk ? L.in4 - k0 : kPolicyChunk;
-      __syncthreads();  // the readers of the chunk before are done
-      stage<kNorm>(a, xs, row0, k0, L.in);
-      __syncthreads();
-      const float* x = xs + q * R * kPolicyChunk;
-      const float* wk = W + (size_t)k0 * L.out64;
-      if (has1) accumulate<R, true>(x, kPolicyChunk, kn, wk, L.out64, j0, j1, acc0, acc1);
-      else if (has0) accumulate<R, false>(x, kPolicyChunk, kn, wk, L.out64, j0, j1, acc0, acc1);
-    }
-  } else if (has1) {
-    accumulate<R, true>(in + q * R * S, S, L.in4, W, L.out64, j0, j1, acc0, acc1);
-  } else if (has0) {
-    accumulate<R, false>(in + q * R * S, S, L.in4, W, L.out64, j0, j1, acc0, acc1);
-  }
-  const int activation = H->activation, output = H->output;
-  const float lo = H->lo, hi = H->hi;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    if (!(u ? has1 : has0)) continue;
-    const int j = u ? j1 : j0;
-    const float b = a.base[L.b_off + j];  // (padded like the columns: zero past `out`)
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float y = (u ? acc1[r] : acc0[r]) + b;
-      const int rr = q * R + r;
-      if (!last) {
-        out[rr * S + j] = hidden_act(y, activation);  // (a padding column gets act(0) = 0: the next layer's padded inputs)
-      } else if (kSample && means) {
-        means[rr * L.out64 + j] = y;
-      } else if (j < L.out && row0 + rr < a.E) {
-        gout[(size_t)(row0 + rr) * L.out + j] = output_of(y, output, lo, hi);
-      }
-    }
-  }
-}
 
 // what the sampling epilogue needs beside the forward's arguments (include/fleet_hip.h FleetExploreArgs)
 struct SampleArgs {
@@ -233,17 +121,7 @@ __device__ __forceinline__ void forward_tile(const ForwardArgs& a, const SampleA
   const int row0 = blockIdx.x * kPolicyRows;
   float* gout = blockIdx.y ? a.values : a.actions;
   const int n = H->n_layers;
-  for (int l = 0; l < n; ++l) {
-    const PolicyLayer L = H->layer[l];
-    const int groups = L.out64 / 64;
-    if (groups >= 4) run_layer<16, kNorm, kSample>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout, means);
-    else if (groups >= 2) run_layer<8, kNorm, kSample>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout, means);
-    else run_layer<4, kNorm, kSample>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gout, means);
-    __syncthreads();
-    float* t = cur;
-    cur = nxt;
-    nxt = t;
-  }
+  run_head<kNorm ? kStageNorm : kStagePlain, kSample>(a, H, cur, nxt, xs, S, row0, gout, means, StageTail{});
   if (kSample && means) sample_epilogue(a, *x, H, means, H->layer[n - 1].out64, H->layer[n - 1].out, row0);
 }
 
@@ -324,29 +202,17 @@ std::string validate(const FleetPolicyParams* p) {
     return "obs_dim must be in 1.." + std::to_string(FLEET_POLICY_MAX_OBS_DIM) + ", got " + std::to_string(p->obs_dim);
   if (p->n_heads < 1 || p->n_heads > FLEET_POLICY_MAX_HEADS) return "n_heads must be 1 or 2, got " + std::to_string(p->n_heads);
   for (int h = 0; h < p->n_heads; ++h) {
-    const FleetPolicyHead& H = p->head[h];
-    const std::string who = "head " + std::to_string(h) + ": ";
-    if (H.n_layers < 1 || H.n_layers > FLEET_POLICY_MAX_LAYERS)
-      return who + "n_layers must be in 1.." + std::to_string(FLEET_POLICY_MAX_LAYERS) + ", got " + std::to_string(H.n_layers);
-    for (int l = 0; l < H.n_layers; ++l)
-      if (H.width[l] < 1 || H.width[l] > FLEET_POLICY_MAX_WIDTH)
-        return who + "width of layer " + std::to_string(l) + " must be in 1.." + std::to_string(FLEET_POLICY_MAX_WIDTH) + ", got " +
-               std::to_string(H.width[l]);
-    if (H.activation != FLEET_POLICY_ACT_TANH && H.activation != FLEET_POLICY_ACT_RELU) return who + "unknown activation";
-    if (H.output != FLEET_POLICY_OUT_NONE && H.output != FLEET_POLICY_OUT_CLIP && H.output != FLEET_POLICY_OUT_TANH)
-      return who + "unknown output transform";
-    if (H.output == FLEET_POLICY_OUT_CLIP && !(H.lo <= H.hi)) return who + "clip bounds need lo <= hi";
+    const std::string why = policy_validate_head(p->head[h], "head " + std::to_string(h) + ": ");
+    if (!why.empty()) return why;
   }
   return "";
 }
-
-int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // the record of the network and the size of the block (floats)
 size_t describe_layout(const FleetPolicyParams& p, PolicyDesc* d) {
   *d = PolicyDesc{};
   d->obs_dim = p.obs_dim, d->n_heads = p.n_heads, d->stride = 64;
-  size_t off = round_up((int)sizeof(PolicyDesc), 256) / 4;
+  size_t off = policy_round_up((int)sizeof(PolicyDesc), 256) / 4;
   for (int h = 0; h < p.n_heads; ++h) {
     const FleetPolicyHead& H = p.head[h];
     PolicyHeadDesc& o = d->head[h];
@@ -354,7 +220,7 @@ size_t describe_layout(const FleetPolicyParams& p, PolicyDesc* d) {
     for (int l = 0; l < H.n_layers; ++l) {
       PolicyLayer& L = o.layer[l];
       L.in = l ? H.width[l - 1] : p.obs_dim, L.out = H.width[l];
-      L.in4 = round_up(L.in, 4), L.out64 = round_up(L.out, 64);
+      L.in4 = policy_round_up(L.in, 4), L.out64 = policy_round_up(L.out, 64);
       L.w_off = (uint32_t)off;
       off += (size_t)L.in4 * L.out64;
       L.b_off = (uint32_t)off;

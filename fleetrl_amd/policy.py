@@ -220,20 +220,6 @@ class DevicePolicy(_DeviceHandle):
         args.struct_bytes = C.sizeof(_capi.FleetExploreArgs)
         self._check(self.lib.fleet_explore_act_dev(self.h, obs_ptr, int(num_envs), _norm_handle(norm), C.byref(args)))
 
-    def _per_action(self, key: str, v):
-        """`v` as a device f32 [act_dim] tensor: a tensor is taken as it is, a float or an array is broadcast into a cached one.
-        A float that CHANGES between calls replaces the cached tensor through a host-to-device copy, which synchronises the host
-        with the stream: a value that varies inside a loop (a decaying sigma, a learned log_std) belongs in a device tensor."""
-        import torch
-
-        if isinstance(v, torch.Tensor):
-            return self._tensor(v.detach(), (self.act_dim,), (torch.float32,))
-        host = np.broadcast_to(np.asarray(v, dtype=np.float32), (self.act_dim,))
-        hit = self._constants.get(key)
-        if hit is None or not np.array_equal(hit[0], host):
-            hit = self._constants[key] = (host.copy(), torch.from_numpy(host.copy()).to(torch.device("cuda", self.device)))
-        return hit[1]
-
     def _explore(self, mode, obs, E, scale, shift, low, high, seed, step, env_id_offset, normalizer, actions_out, env_actions_out,
                  log_prob_out, values_out, mean_out, noise, noise_given, want_log_prob):
         import torch

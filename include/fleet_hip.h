@@ -1024,6 +1024,92 @@ int fleet_noise_set_state_dev(fleet_noise_handle h, const int32_t* t, const uint
 /* the parameters the process was created with (mu, sigma NULL), and cache_bytes */
 int fleet_noise_describe(fleet_noise_handle h, FleetNoiseParams* out);
 
+/* ---- TD3 / DDPG learning targets on the device (fleet_qtarget.hip; DESIGN.md "Learning targets on the device") --------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * The TARGET networks of an off-policy actor-critic agent -- one target actor and n_critics target Q networks (2: TD3; 1: DDPG, with
+ * sigma = 0) -- which torch never differentiates, and the two things a gradient step does with them: the bootstrap target of a
+ * minibatch in ONE launch, and the Polyak update from the online networks' parameters in ONE launch.  float32 throughout.
+ * Networks.  The actor is a FleetPolicyHead over D = obs_dim inputs, its output width is A.  Critic c is a FleetPolicyHead over D + A
+ * inputs -- the observation, then the action: SB3's ContinuousCritic, cat([features, actions], 1) -- with output width 1 and output
+ * transform NONE.  The policy's limits hold: 1..FLEET_POLICY_MAX_LAYERS layers, widths 1..FLEET_POLICY_MAX_WIDTH (so A <= 512),
+ * D + A <= FLEET_POLICY_MAX_OBS_DIM.  The weights are re-laid at upload as the policy's are (Wt[in4][out64], zero padding).
+ * The target, per row b of the minibatch (what fleet_replay_sample_dev wrote: next_obs f32[B,D] already normalised, rewards f32[B],
+ * dones f32[B]), every step in float32 and exactly so:
+ *   d[j]  = the actor head's output, its output transform applied (TANH for TD3)
+ *   n[j]  = sigma[j] * eps[b][j], clipped to [-noise_clip, +noise_clip]               (x < lo ? lo : (x > hi ? hi : x), here and below)
+ *   a'[j] = d[j] + n[j], clipped to [act_lo, act_hi]
+ *   q_c   = critic c over concat(next_obs[b], a'): the policy section's chain, acc = 0; fmaf in ascending k over the D + A inputs; + bias
+ *   qmin  = n_critics == 2 ? (q_1 < q_0 ? q_1 : q_0) : q_0
+ *   t     = (1.0f - dones[b]) * gamma;  y[b] = rewards[b] + t * qmin          (the product and the sum are rounded one by one: no fma)
+ * Every output of a row is a function of that row: not of B, of the row's place in the batch, of the stream, of which optional
+ * outputs are asked for; next_actions and q[:, 0] do not depend on n_critics.  One workgroup takes 16 rows through the actor, then
+ * through critic 0, then through critic 1: no atomics, no ordering between workgroups.
+ * Noise.  eps follows the counter scheme of fleet_explore_act_dev, unchanged: Philox4x32-10 under key (seed lo, seed hi) at counter
+ * (row_offset + b, j / 4, step lo, step hi), Box-Muller as there; noise_mode FLEET_EXPLORE_NOISE_DRAW or _GIVEN as there, and DRAW
+ * with a non-null `noise` records the draw.  A caller who also explores with fleet_explore_act_dev gives the target a SEED OF ITS OWN:
+ * under one seed, row b of a minibatch at gradient step s would repeat the exploration noise of env b at env step s.
+ * The Polyak update.  Every real element t of the padded image, with p the online network's element, becomes
+ *   t' = fmaf(tau32, p, t * omt32),  tau32 = (float)tau,  omt32 = (float)(1.0 - tau)
+ * -- SB3's polyak_update, target.mul_(1 - tau); torch.add(target, param, alpha=tau), with the scaled addition fused into one
+ * rounding.  The padding is not touched and stays zero.  tau = 0 leaves t, tau = 1 gives p bit for bit (but a p of -0 comes out +0
+ * unless t is negative, IEEE's sum of zeros; and a t that is not finite stays NaN: t * 0).
+ * Every *_dev call takes device pointers, only enqueues (no host synchronisation) and runs on the handle's stream: its own, or the one
+ * fleet_qtarget_set_stream borrowed.  Calls on one handle are serialised by the caller. */
+typedef struct FleetQTargetParams {
+  int32_t struct_bytes;       /* sizeof(FleetQTargetParams) */
+  int32_t obs_dim;            /* D >= 1 */
+  int32_t n_critics;          /* 1 or 2 */
+  int32_t tile_rows;          /* out (fleet_qtarget_describe): minibatch rows one workgroup takes through every network; ignored by create */
+  FleetPolicyHead actor;      /* over D inputs; the last width is A */
+  FleetPolicyHead critic[2];  /* over D + A inputs; the last width must be 1, the output FLEET_POLICY_OUT_NONE */
+} FleetQTargetParams;
+typedef struct FleetQTargetArgs {
+  int32_t struct_bytes;   /* sizeof(FleetQTargetArgs) */
+  int32_t noise_mode;     /* FLEET_EXPLORE_NOISE_DRAW / _GIVEN */
+  uint64_t seed;          /* Philox key */
+  uint64_t step;          /* Philox counter words 2, 3: the caller's gradient-step count */
+  int32_t row_offset;     /* global id of row 0 (a shard of a larger minibatch); >= 0 */
+  int32_t reserved;       /* 0 */
+  float gamma;            /* the discount */
+  float noise_clip;       /* >= 0; +inf: no clip */
+  float act_lo, act_hi;   /* the action space: act_lo <= act_hi */
+  const float* sigma;     /* device f32[A]: the target-policy smoothing noise's scale (0: DDPG) */
+  float* noise;           /* device f32[B, A] or NULL: read (GIVEN), written when not NULL (DRAW) */
+  float* target_q;        /* device f32[B]: y */
+  float* next_actions;    /* device f32[B, A] or NULL: a' */
+  float* q;               /* device f32[B, n_critics] or NULL: q_c */
+} FleetQTargetArgs;
+typedef struct FleetQTarget* fleet_qtarget_handle;
+
+/* The parameters and the weights are validated BEFORE the device is touched: FLEET_ERR_INVALID (fleet_qtarget_last_error(NULL) says
+ * why) for a wrong struct_bytes, obs_dim < 1, n_critics outside 1..2, a layer count outside 1..4, a width outside 1..512, D + A above
+ * 8192, a critic whose last width is not 1 or whose output is not NONE, an unknown activation or output transform, lo > hi or a NaN
+ * bound of a CLIP actor, a null pointer, a weight that is not finite.
+ * host_weights: packed float32 -- the actor, then critic 0, then critic 1; for each layer W[out, in] (row-major) then b[out]. */
+int fleet_qtarget_create(int device, const FleetQTargetParams* p, const float* host_weights, fleet_qtarget_handle* out);
+int fleet_qtarget_destroy(fleet_qtarget_handle h);
+const char* fleet_qtarget_last_error(fleet_qtarget_handle h);  /* h may be NULL: error of the last failed call without a handle */
+/* launch on an external hipStream_t (borrowed; NULL = the null stream) from now on; waits for what the previous stream still holds */
+int fleet_qtarget_set_stream(fleet_qtarget_handle h, void* hip_stream);
+/* New weights from HOST memory, packed as for create; FLEET_ERR_INVALID (nothing changes) when one is not finite.  The host waits. */
+int fleet_qtarget_load_host(fleet_qtarget_handle h, const float* weights);
+/* `tensors`: a host array of `count` device pointers, torch's parameter tensors in the order of host_weights (W, b per layer; count
+ * must be twice the number of layers of all networks).  load: one launch copies and re-lays them (a hard update, and how the targets
+ * start as copies of the online networks).  polyak: `tensors` are the ONLINE networks' parameters; one launch, the update above;
+ * FLEET_ERR_INVALID for a tau outside [0, 1] or NaN.  export: the inverse re-lay, the target weights out into torch-layout tensors
+ * (checkpoints; tests that read an update's result).  The values are not inspected. */
+int fleet_qtarget_load_dev(fleet_qtarget_handle h, const float* const* tensors, int count);
+int fleet_qtarget_polyak_dev(fleet_qtarget_handle h, const float* const* tensors, int count, double tau);
+int fleet_qtarget_export_dev(fleet_qtarget_handle h, float* const* tensors, int count);
+/* One launch: the targets of B rows.  FLEET_ERR_INVALID (nothing is launched) for a null or wrongly sized FleetQTargetArgs, an unknown
+ * noise_mode, B < 1, a null next_obs / rewards / dones / sigma / target_q, a NaN bound or act_lo > act_hi, a noise_clip that is
+ * negative or NaN, GIVEN with a null noise, a negative row_offset.  The arguments are looked at before the handle is: with h NULL
+ * the reason (or "null handle") goes to fleet_qtarget_last_error(NULL), so the checks can be exercised without a device. */
+int fleet_qtarget_target_dev(fleet_qtarget_handle h, const float* next_obs, const float* rewards, const float* dones, int B,
+                             const FleetQTargetArgs* args);
+/* the parameters the handle was created with, and tile_rows */
+int fleet_qtarget_describe(fleet_qtarget_handle h, FleetQTargetParams* out);
+
 #ifdef __cplusplus
 }
 #endif
