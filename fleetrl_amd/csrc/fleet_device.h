@@ -277,6 +277,8 @@ struct FleetStepLaunch {
   unsigned packed_n_offset;  // where `p_N` sits: EVs per env | first workgroup of the grid << 16 (a run split over two queues)
   unsigned guard_offset;     // where the eight bytes of the placement record sit (zeros = no check: every launch through HIP)
   unsigned rec_offset;       // where {blocks pointer, rows, rotate} of a run's FIRST launch sit (the launch that writes the record)
+  unsigned dead_offset;      // where the int "this launch's observation row is dead" sits (0 as described: every launch through HIP;
+                             // a run on the library's own queue sets it in all launches but its last, fleet_direct.hip)
   alignas(8) unsigned char args[640];  // (also the distance between two argument blocks of a run: fleet_direct.hip, the step kernel's record)
 };
 // The template arguments of an instance of fleet_step_kernel

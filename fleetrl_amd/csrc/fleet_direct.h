@@ -28,7 +28,9 @@ int fleet_direct_prepare(FleetDirect* q, const FleetStepLaunch& launch, const vo
 int fleet_direct_parts(FleetDirect* q);  // 1 or 2: how the prepared launch is laid out
 // `steps` launches (tape rows 0, 1, ... cyclically) behind the run's placement-record launch, asynchronous.  Fences: every packet acquires
 // at agent scope (the vector / scalar L1s are invalidated; the first at system scope) and releases NOTHING -- except the last, which
-// releases at system scope.
+// releases at system scope.  Outputs: only the run's last launch stores observation rows (the others carry the kernel's
+// `outputs_dead` argument: what they would store is overwritten before the release makes anything visible); a run of one step is
+// its own last launch.
 // `timed`: completion signals with dispatch timestamps on the first and the last packet of the run (fleet_direct_wait reports the span).
 int fleet_direct_submit(FleetDirect* q, int steps, bool timed, std::string* err);
 bool fleet_direct_busy(FleetDirect* q);   // something submitted has not completed

@@ -34,7 +34,9 @@
 //     header, the headers fleet_kernels.hip is made of included).
 //
 // What a caller may rely on: nothing of the run is visible before it has completed (fleet_synchronize / the next call on the handle
-// waits for it), everything after.  What the library relies on beside the placement: the single-step kernels touch an env's state only
+// waits for it), everything after.  "Everything" is the state, and the observations, rewards and done flags of the run's LAST step:
+// the observation rows of the steps before it would be overwritten unseen, so their launches do not compute or store them (the
+// argument blocks of fleet_direct_prepare; fleet_kernels.hip, "Dead outputs").  What the library relies on beside the placement: the single-step kernels touch an env's state only
 // from that env's own workgroup, and bytes of different envs that share a cache line are merged by the L2's byte masks -- as inside
 // any one launch.
 //
@@ -139,13 +141,19 @@ struct FleetDirect {
   unsigned block = 0;
   int parts = 1;              // 1: the whole grid on queue 0; 2: the grid as two ranges of workgroups, one per queue
   unsigned part_grid[2] = {0, 0};
-  char* kargs_dev = nullptr;  // parts x tape_len blocks of kBlockBytes (part-major), then per part the block of the run's FIRST launch
-                              // (tape row 0's with the recording arguments: it writes the placement record into the others)
+  char* kargs_dev = nullptr;  // per part 2 x tape_len blocks of kBlockBytes: one per tape row whose launch's observation row is dead
+                              // (`outputs_dead` set: every launch of a run but its last), then one per tape row for a run's LAST launch
+                              // (clear); then per part the two blocks of a run's FIRST launch (tape row 0's with the recording
+                              // arguments: it writes the placement record into the others) -- dead, and live for a run of one step
   size_t kargs_cap = 0;
   int tape_len = 0;
   std::vector<unsigned char> kargs_host;  // what was uploaded (the fault hook patches a block of it)
   unsigned packed_n_offset = 0, guard_offset = 0, rec_offset = 0;
   static constexpr size_t kBlockBytes = sizeof(FleetStepLaunch::args);
+  // where the blocks sit in kargs_dev / kargs_host (bytes): tape row `row` of a part, for the last launch of a run or any other;
+  // the part's first-launch block, for a run of one step (`live`) or a longer one
+  size_t row_block(int part, int row, bool live) const { return (((size_t)part * 2 + (live ? 1 : 0)) * tape_len + (size_t)row) * kBlockBytes; }
+  size_t first_block(int part, bool live) const { return ((size_t)parts * 2 * tape_len + (size_t)part * 2 + (live ? 1 : 0)) * kBlockBytes; }
   // signals: a pool; the ones handed out since the last wait; per timed run what its span is read from
   std::vector<hsa_signal_t> pool, pending;
   struct Mark { hsa_signal_t first[2], last[2]; int parts; };
@@ -497,14 +505,20 @@ int fleet_direct_prepare(FleetDirect* q, const FleetStepLaunch& L, const void* t
                         std::to_string(part_grid[part]) + ")";
         return FLEET_ERR_UNSUPPORTED;
       }
-  const size_t blocks_bytes = (size_t)parts * tape_len * FleetDirect::kBlockBytes;
-  const size_t need = blocks_bytes + (size_t)parts * FleetDirect::kBlockBytes;
+  // Open loop: nothing a run writes is visible before its last packet has retired, so only the LAST launch's observation rows are
+  // part of the result.  Every tape row has two blocks -- `outputs_dead` set for a launch in the middle of a run, clear for the launch
+  // that ends one -- and fleet_direct_submit picks per packet: no host work per run, whatever row a run ends on.
+  const size_t part_bytes = (size_t)2 * tape_len * FleetDirect::kBlockBytes;
+  const size_t blocks_bytes = (size_t)parts * part_bytes;
+  const size_t need = blocks_bytes + (size_t)parts * 2 * FleetDirect::kBlockBytes;
   std::vector<unsigned char> host(need, 0);
   for (int part = 0; part < parts; ++part)
-    for (int k = 0; k < tape_len; ++k) {
-      unsigned char* b = host.data() + ((size_t)part * tape_len + k) * FleetDirect::kBlockBytes;
+    for (int k = 0; k < 2 * tape_len; ++k) {
+      unsigned char* b = host.data() + (size_t)part * part_bytes + (size_t)k * FleetDirect::kBlockBytes;
       memcpy(b, L.args, L.args_bytes);
-      const void* row = static_cast<const char*>(tape) + (size_t)k * row_bytes;
+      const int32_t dead = k < tape_len ? 1 : 0;
+      memcpy(b + L.dead_offset, &dead, 4);
+      const void* row = static_cast<const char*>(tape) + (size_t)(k % tape_len) * row_bytes;
       memcpy(b + L.actions_offset[0], &row, sizeof row);
       memcpy(b + L.actions_offset[1], &row, sizeof row);
       if (part == 1) {
@@ -524,13 +538,14 @@ int fleet_direct_prepare(FleetDirect* q, const FleetStepLaunch& L, const void* t
       return FLEET_ERR_HIP;
     }
   }
-  for (int part = 0; part < parts; ++part) {  // the first launch of a run: tape row 0's block + where the part's other blocks are
-    unsigned char* f = host.data() + blocks_bytes + (size_t)part * FleetDirect::kBlockBytes;
-    memcpy(f, host.data() + (size_t)part * tape_len * FleetDirect::kBlockBytes, FleetDirect::kBlockBytes);
-    struct { char* blocks; int rows, rotate; } ra = {dev + (size_t)part * tape_len * FleetDirect::kBlockBytes, tape_len, 0};
-    static_assert(sizeof ra == 16, "the recording arguments");
-    memcpy(f + L.rec_offset, &ra, sizeof ra);
-  }
+  for (int part = 0; part < parts; ++part)  // the first launch of a run: tape row 0's block + where the part's other blocks are
+    for (int live = 0; live < 2; ++live) {   // (of both kinds: the record goes into all 2 x tape_len of them)
+      unsigned char* f = host.data() + blocks_bytes + ((size_t)part * 2 + live) * FleetDirect::kBlockBytes;
+      memcpy(f, host.data() + (size_t)part * part_bytes + (size_t)live * tape_len * FleetDirect::kBlockBytes, FleetDirect::kBlockBytes);
+      struct { char* blocks; int rows, rotate; } ra = {dev + (size_t)part * part_bytes, 2 * tape_len, 0};
+      static_assert(sizeof ra == 16, "the recording arguments");
+      memcpy(f + L.rec_offset, &ra, sizeof ra);
+    }
   if (hipMemcpy(dev, host.data(), need, hipMemcpyHostToDevice) != hipSuccess) {
     if (dev != q->kargs_dev) (void)hipFree(dev);
     if (err) *err = "fleet_direct_prepare: argument upload failed";
@@ -565,8 +580,8 @@ int fleet_direct_fault(FleetDirect* q, int kind, int tape_row, std::string* err)
     q->fault_rotate = 1;
     return FLEET_OK;
   }
-  for (int part = 0; part < q->parts; ++part) {  // the grid's first workgroup shifted by one
-    const size_t off = ((size_t)part * q->tape_len + tape_row) * FleetDirect::kBlockBytes;
+  for (int k = 0; k < 2 * q->parts; ++k) {  // the grid's first workgroup shifted by one, wherever in a run the row's launch falls
+    const size_t off = q->row_block(k / 2, tape_row, k % 2 != 0);
     unsigned char* b = q->kargs_host.data() + off;
     uint32_t packed;
     memcpy(&packed, b + q->packed_n_offset, 4);
@@ -603,11 +618,12 @@ int fleet_direct_submit(FleetDirect* q, int steps, bool timed, std::string* err)
     }
   }
   // the run's first launch goes out with the block that has it write the placement record into the others (header comment)
-  const size_t first_blocks = (size_t)q->parts * q->tape_len * FleetDirect::kBlockBytes;
+  // ... and every launch but the run's last with the block that says its observation rows are dead (fleet_direct_prepare)
+  const bool one_step = (steps == 1);
   if (q->fault_rotate) {  // test hook: a record shifted by one workgroup
     const int one = 1;
     for (int part = 0; part < q->parts; ++part)
-      if (hipMemcpy(q->kargs_dev + first_blocks + (size_t)part * FleetDirect::kBlockBytes + q->rec_offset + 12, &one, 4, hipMemcpyHostToDevice) != hipSuccess)
+      if (hipMemcpy(q->kargs_dev + q->first_block(part, one_step) + q->rec_offset + 12, &one, 4, hipMemcpyHostToDevice) != hipSuccess)
         return FLEET_ERR_HIP;
   }
   for (int i = 0; i < steps; ++i)
@@ -618,9 +634,8 @@ int fleet_direct_submit(FleetDirect* q, int steps, bool timed, std::string* err)
       const int acq = (i == 0) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_AGENT;
       const int rel = (i == steps - 1) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_NONE;
       write_packet(q->queue[part], q->kernel, q->block, q->part_grid[part],
-                   i == 0 ? q->kargs_dev + first_blocks + (size_t)part * FleetDirect::kBlockBytes
-                          : q->kargs_dev + ((size_t)part * q->tape_len + (size_t)(i % q->tape_len)) * FleetDirect::kBlockBytes,
-                   acq, rel, sig);
+                   q->kargs_dev + (i == 0 ? q->first_block(part, one_step) : q->row_block(part, i % q->tape_len, i == steps - 1)), acq, rel,
+                   sig);
     }
   if (timed) q->marks.push_back(m);
   for (int part = 0; part < 2; ++part) q->last[part] = part < q->parts ? m.last[part] : hsa_signal_t{};
@@ -631,7 +646,7 @@ int fleet_direct_submit(FleetDirect* q, int steps, bool timed, std::string* err)
     if (rc != FLEET_OK) return rc;
     const int zero = 0;
     for (int part = 0; part < q->parts; ++part)
-      if (hipMemcpy(q->kargs_dev + first_blocks + (size_t)part * FleetDirect::kBlockBytes + q->rec_offset + 12, &zero, 4, hipMemcpyHostToDevice) != hipSuccess)
+      if (hipMemcpy(q->kargs_dev + q->first_block(part, one_step) + q->rec_offset + 12, &zero, 4, hipMemcpyHostToDevice) != hipSuccess)
         return FLEET_ERR_HIP;
     return FLEET_OK;
   }

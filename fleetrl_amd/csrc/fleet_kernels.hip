@@ -234,6 +234,7 @@ struct StepKernargs {
   FleetDev d_arg;
   const void* actions;
   int act_mode, K;
+  int outputs_dead;  // single-step instances: nonzero = nobody can read this launch's observation row (see the kernel, "Dead outputs")
   float* obs;
   double* reward;
   uint8_t* done;
@@ -264,7 +265,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
     // block, so that those loads do not wait for an argument fetch.
     // (no __restrict__ on the state pointers: the same kernel stores to these arrays through the argument block)
     const Hot* p_hot, const SegRec* p_run, const double* p_soh, const void* __restrict__ p_actions, int p_E, int p_N, EnvRec* p_env,
-    FleetDev d_arg, const void* __restrict__ actions, int act_mode, int K,
+    FleetDev d_arg, const void* __restrict__ actions, int act_mode, int K, int outputs_dead,
                                                                float* __restrict__ obs, double* __restrict__ reward,
                                                                uint8_t* __restrict__ done, float* __restrict__ terminal_obs,
                                                                int32_t* __restrict__ done_count, unsigned long long guard_bytes,
@@ -361,6 +362,14 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   float* const obs_row = obs + (size_t)e * d.obs_dim;
   float* const term_row = terminal_obs ? terminal_obs + (size_t)e * d.obs_dim : nullptr;
   const int steps = MULTI ? K : 1;
+  // Dead outputs (single-step launches on the library's own queue, fleet_direct.hip).  Nothing a run on that queue writes is visible
+  // before its last packet has retired, and every launch writes the same observation rows: what any launch but the last stores
+  // there is overwritten before anybody can read it.  Those launches carry `outputs_dead` != 0 -- a kernel argument, the same for
+  // every wavefront, fetched with the arguments the entry reads anyway -- and skip what feeds only the row: write_obs_ev with the
+  // arithmetic of its auxiliary slots, the request for the tail row and its store, the terminal row.  State, reward, done flag,
+  // reset (with the row it writes) and the placement guard are as ever.  Launches through HIP always carry 0; the K-step instances
+  // (the data log among them) decide per step themselves and do not look.
+  const bool obs_live = MULTI || outputs_dead == 0;
   const int vzero = (int)__builtin_amdgcn_mbcnt_lo(0u, 0u);  // 0 in every lane, opaque to the uniformity analysis
   // night-charging policy: the env's "charging since" row travels in a register over the K steps
   int night_st = FLEET_NIGHT_IDLE;
@@ -415,7 +424,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
     // where this step's observation goes: with vec-env auto-reset the terminal observation is reported aside
     float* const step_row = resets ? term_row : obs_row;
     // intermediate steps of a K-step launch only need their observation when the episode ends (terminal observation)
-    const bool write_step_obs = env_ok && (step_row != nullptr) && (!MULTI || rt || resets || k == steps - 1);
+    const bool write_step_obs = obs_live && env_ok && (step_row != nullptr) && (!MULTI || rt || resets || k == steps - 1);
 
     FLEET_STAMP(1);
     // ---- loads that depend on the time row: the row's physics scalars and observation tail -----------------------------

@@ -83,8 +83,8 @@ StepPlan plan_step_g(const FleetDev& d, int act_mode, int K, bool has_done_count
   }
 }
 
-// The argument block of a step launch, as issued on a HIP stream; a run on the library's own queue fills in the placement record's
-// fields itself (fleet_direct_prepare).
+// The argument block of a step launch, as issued on a HIP stream (`outputs_dead` = 0: every launch's outputs can be read); a run on
+// the library's own queue fills in the placement record's fields and `outputs_dead` itself (fleet_direct_prepare).
 StepKernargs step_args(const FleetDev& d, const void* actions, int act_mode, int K, float* obs, double* reward, uint8_t* done,
                        float* terminal_obs, int32_t* done_count) {
   StepKernargs a{};
@@ -135,7 +135,7 @@ hipError_t fleet_launch_step(const FleetDev& d, const void* actions, int act_dty
   const StepPlan p = plan_step(d, act_dtype, K, done_count != nullptr);
   const StepKernargs a = step_args(d, actions, act_dtype, K, obs, reward, done, terminal_obs, done_count);
   hipLaunchKernelGGL(p.fn, dim3(p.grid), dim3(kBlock), 0, s, a.p_hot, a.p_run, a.p_soh, a.p_actions, a.p_E, a.p_N, a.p_env, a.d_arg,
-                     a.actions, a.act_mode, a.K, a.obs, a.reward, a.done, a.terminal_obs, a.done_count, a.guard_bytes, a.rec_blocks,
+                     a.actions, a.act_mode, a.K, a.outputs_dead, a.obs, a.reward, a.done, a.terminal_obs, a.done_count, a.guard_bytes, a.rec_blocks,
                      a.rec_rows, a.rec_rotate);
   return hipGetLastError();
 }
@@ -167,6 +167,7 @@ hipError_t fleet_describe_step(const FleetDev& d, const void* actions, int act_d
   out->packed_n_offset = (unsigned)offsetof(StepKernargs, p_N);
   out->guard_offset = (unsigned)offsetof(StepKernargs, guard_bytes);
   out->rec_offset = (unsigned)offsetof(StepKernargs, rec_blocks);  // (then rec_rows and rec_rotate)
+  out->dead_offset = (unsigned)offsetof(StepKernargs, outputs_dead);
   memcpy(out->args, &a, sizeof a);
   return hipSuccess;
 }

@@ -493,7 +493,12 @@ int fleet_timer_read(fleet_handle h, float* elapsed_ms);
  *                        Semantics: asynchronous like the others, but NOT on the HIP stream -- the run starts after everything
  *                        the stream holds has completed (the call waits for that), nothing of it is visible before it has
  *                        completed, and every later call on the handle (fleet_synchronize, a step, a get ...) waits for it first;
- *                        fleet_stream_query reports it.  Single-step configurations only (no real_time, no data log);
+ *                        fleet_stream_query reports it.  What a run writes: the state after all its steps, and `obs`, `reward`
+ *                        and `done` of its LAST step.  Since nothing is visible before the run has completed, the observation
+ *                        rows of the steps before the last -- which the last one overwrites -- are not stored at all (their
+ *                        launches skip the observation arithmetic and stores; rewards and done flags are still written by
+ *                        every launch).  A caller that needs every step's observation uses fleet_step_dev or another mode.
+ *                        Single-step configurations only (no real_time, no data log);
  *                        needs libfleet_hip.gfx950.hsaco beside the library (fleetrl_amd.build).  */
 #define FLEET_LAUNCH_EAGER 0
 #define FLEET_LAUNCH_GRAPH 1
