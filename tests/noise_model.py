@@ -12,7 +12,11 @@ M32 = rp.M32
 PINK_TAG, OU_TAG = 0x80000000, 0x40000000
 SEED = em.SEED
 NS = (2, 3, 7, 64, 65, 192, 193)
+# the lengths past one block of samples (64 x 4 per lane trip: n > 256) and past one chunk of staged frequencies (K = n / 2 + 1 > 256)
+NS_WIDE = (256, 257, 320, 386, 510, 511, 512, 513, 1030, 4096)
 BETAS = (0.0, 1.0, 2.0)
+NOISE_BOUND = 1e-5  # |eps_dev - eps_model| of one Box-Muller normal, as test_explore_gpu.test_drawn_noise_equals_the_model holds it
+CHUNK = 256  # frequencies the device stages at a time (fleet_noise.hip kChunk)
 
 
 # ---- draws -----------------------------------------------------------------------------------------------------------------------
@@ -129,6 +133,88 @@ def periodogram_expectation(n, beta):
     g2 = n * n * tables(n, beta)[0] ** 2
     edge = real_only(n)
     return np.where(edge, g2, g2 / 2.0), np.where(edge, np.sqrt(2.0) * g2, g2 / 2.0)
+
+
+# ---- the float32 chain and the tolerance it gives -----------------------------------------------------------------------------------
+FAULTS = ("drop_last", "drop_chunk_first", "phase_reset")
+
+
+def chain32(a, b, n, beta, displace=None, fault=None):
+    """y [C, n]: the chain fleet_noise.h states, restated in float32 from the model's coefficients a, b [C, K]: coefficients rounded
+    to float32, the staged products gain x a and gain x b rounded once, +0 for the imaginary part at k = 0 and 2k = n, k ascending,
+    two accumulate steps per k each rounded to float32 once (product and sum formed in float64, then rounded: the device's fmaf
+    rounds the exact sum, this the float64 one), the phase m advanced by t modulo n in integers.
+    displace: a seed; every normal is moved by a uniform draw within +-NOISE_BOUND before it is rounded, which is what the device's
+    Box-Muller may do to it.  fault: one of FAULTS, what the wide lengths exist to catch -- the last frequency dropped, the first
+    frequency of the second chunk (k = CHUNK) dropped, the phase walk restarted at k = CHUNK."""
+    f32, f64 = np.float32, np.float64
+    a, b = np.array(a, dtype=f64), np.array(b, dtype=f64)
+    K = n // 2 + 1
+    assert a.shape == b.shape and a.ndim == 2 and a.shape[1] == K and fault in (None,) + FAULTS
+    if displace is not None:
+        rng = np.random.default_rng(displace)
+        a += rng.uniform(-NOISE_BOUND, NOISE_BOUND, a.shape)
+        b += rng.uniform(-NOISE_BOUND, NOISE_BOUND, b.shape)
+    gain, tw = tables32(n, beta)
+    ga = (gain[None, :] * a.astype(f32)).astype(f64)  # (float32 x float32 rounded to float32, held in float64)
+    gb = (gain[None, :] * b.astype(f32)).astype(f64)
+    gb[:, real_only(n)] = 0.0
+    cos, sin = tw[:, 0].astype(f64), tw[:, 1].astype(f64)
+    t = np.arange(n)
+    m, acc = np.zeros(n, np.int64), np.zeros((len(a), n))
+    for k in range(K):
+        if fault == "phase_reset" and k == CHUNK:
+            m[:] = 0
+        skip = (fault == "drop_last" and k == K - 1) or (fault == "drop_chunk_first" and k == CHUNK)
+        if not skip:
+            acc = (acc + ga[:, k, None] * cos[m]).astype(f32).astype(f64)
+            acc = (acc - gb[:, k, None] * sin[m]).astype(f32).astype(f64)
+        m += t
+        m[m >= n] -= n
+    return acc
+
+
+TOL_COLUMNS = (3, 16)  # E x A = 48 columns under SEED, sequence number 0
+
+
+def chain_errors(n, betas=BETAS, displace=True, fault=None):
+    """{beta: max |chain32 - direct_sum over the float32 tables|} over the 48 columns of TOL_COLUMNS; displaced under the seed n.
+    With displace and without a fault this is R(n, beta): the reference alone decides it."""
+    E, A = TOL_COLUMNS
+    a, b = (c.reshape(E * A, -1) for c in pink_coefficients(SEED, np.arange(E), A, 0, n))
+    out = {}
+    for beta in betas:
+        want = direct_sum(a, b, n, beta, *tables32(n, beta))
+        out[beta] = float(np.abs(chain32(a, b, n, beta, n if displace else None, fault) - want).max())
+    return out
+
+
+def round_up2(x):
+    """x rounded up to two significant digits."""
+    e = int(np.floor(np.log10(x))) - 1
+    return float(f"{int(np.ceil(x / 10.0 ** e - 1e-9))}e{e}")
+
+
+# pink_tol(n, beta) = 2 R(n, beta) rounded up to two digits, R = chain_errors(n)[beta].  The factor 2: R is the maximum under ONE
+# displacement pattern, not the worst one, and the restatement rounds twice where the device's fmaf rounds once.
+# tests/test_noise_cpu.py recomputes every entry, holds it below half the smallest gain, and shows that it sees each of FAULTS.
+PINK_TOL_WIDE = {
+    (256, 0.0): 4.8e-05, (256, 1.0): 4.5e-05, (256, 2.0): 4.1e-05,
+    (257, 0.0): 4.7e-05, (257, 1.0): 4.9e-05, (257, 2.0): 4.8e-05,
+    (320, 0.0): 4.6e-05, (320, 1.0): 4.5e-05, (320, 2.0): 4.2e-05,
+    (386, 0.0): 5.0e-05, (386, 1.0): 4.9e-05, (386, 2.0): 4.4e-05,
+    (510, 0.0): 4.9e-05, (510, 1.0): 5.0e-05, (510, 2.0): 4.4e-05,
+    (511, 0.0): 5.0e-05, (511, 1.0): 4.9e-05, (511, 2.0): 4.4e-05,
+    (512, 0.0): 4.8e-05, (512, 1.0): 5.1e-05, (512, 2.0): 4.9e-05,
+    (513, 0.0): 5.4e-05, (513, 1.0): 5.0e-05, (513, 2.0): 5.3e-05,
+    (1030, 0.0): 5.1e-05, (1030, 1.0): 5.5e-05, (1030, 2.0): 4.8e-05,
+    (4096, 0.0): 5.7e-05, (4096, 1.0): 5.8e-05, (4096, 2.0): 5.9e-05,
+}
+
+
+def pink_tol(n, beta):
+    """|y_dev - y_model| a sample of a wide length is held to."""
+    return PINK_TOL_WIDE[(n, float(beta))]
 
 
 # ---- the processes ---------------------------------------------------------------------------------------------------------------

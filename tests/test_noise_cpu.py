@@ -82,7 +82,7 @@ def test_a_null_handle_and_bad_parameters_are_refused_without_a_device():
 
 
 # ---- the tables --------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", nm.NS + (4096,))
+@pytest.mark.parametrize("n", nm.NS + nm.NS_WIDE)
 def test_the_librarys_host_tables_are_the_models_rounded_to_float32(n):
     from fleetrl_amd import _capi
 
@@ -120,13 +120,87 @@ def test_the_models_array_generator_is_the_scalar_one():
     assert np.array_equal(nm.normals4(em.words(seed, [3], 8, 11))[0].reshape(-1), em.normals(seed, [3], 8, 11)[0])
 
 
-@pytest.mark.parametrize("n", nm.NS)
+@pytest.mark.parametrize("n", nm.NS + nm.NS_WIDE)
 def test_direct_sum_equals_the_irfft_form(n):
     for beta in nm.BETAS:
         a, b = nm.pink_coefficients(nm.SEED, np.arange(3), 5, [0, 1, 7], n)
         direct, fft = nm.direct_sum(a, b, n, beta), nm.irfft_form(a, b, n, beta)
         assert direct.shape == (3, 5, n)
         assert np.abs(direct - fft).max() <= 1e-12, (n, beta, np.abs(direct - fft).max())
+
+
+# ---- the float32 chain and the tolerance of the wide lengths ----------------------------------------------------------------------
+def test_the_wide_lengths_are_the_smallest_cases_of_their_paths():
+    """(G, K) of every wide length: G = ceil(n / 64) groups of samples in blocks of 4, K = n / 2 + 1 frequencies in chunks of 256."""
+    shape = {n: (-(-n // 64), n // 2 + 1) for n in nm.NS_WIDE}
+    assert shape == {256: (4, 129), 257: (5, 129), 320: (5, 161), 386: (7, 194), 510: (8, 256), 511: (8, 256), 512: (8, 257),
+                     513: (9, 257), 1030: (17, 516), 4096: (64, 2049)}
+    assert max(-(-n // 64) for n in nm.NS) <= 4 and max(n // 2 + 1 for n in nm.NS) <= nm.CHUNK  # the old lengths: one block, one chunk
+    assert nm.real_only(512)[256] and not nm.real_only(513)[256]  # the one term of the second chunk: the Nyquist term, a complex term
+
+
+def test_the_float32_chain_is_the_direct_sum_up_to_its_roundings():
+    """Known answers of `chain32` where every step is exact or a single rounding, and the chain against the float64 sum at an old
+    length: undisplaced it stays within the 2K roundings, 2K x 2^-24 x the largest partial sum."""
+    # n = 2: K = 2, both terms real, twiddles (1, 0), (-1, 0): y = (ga0 + ga1, ga0 - ga1), the products and one sum rounded once each
+    f32 = np.float32
+    a, b = np.array([[0.3, -1.7]]), np.array([[0.9, 0.4]])
+    g = nm.tables32(2, 1.0)[0]
+    ga = g * a[0].astype(f32)
+    assert ga.dtype == f32
+    want = np.array([[f32(ga[0] + ga[1]), f32(ga[0] - ga[1])]], dtype=np.float64)
+    assert np.array_equal(nm.chain32(a, b, 2, 1.0), want)
+    # the imaginary part of a real-only frequency is not read: NaN there leaves the sequence as it is
+    for n in (7, 64):
+        a, b = (c.reshape(15, -1) for c in nm.pink_coefficients(nm.SEED, np.arange(3), 5, 0, n))
+        y = nm.chain32(a, b, n, 1.0)
+        bad = np.where(nm.real_only(n), np.nan, b)
+        assert np.array_equal(nm.chain32(a, bad, n, 1.0), y)
+        ref = nm.direct_sum(a, b, n, 1.0, *nm.tables32(n, 1.0))
+        K = n // 2 + 1
+        assert np.abs(y - ref).max() <= 2 * K * 2.0 ** -24 * (np.abs(ref).max() + 1.0)
+        # a displacement moves a sample by at most NOISE_BOUND x 2 sum gain, and does move it
+        moved = nm.chain32(a, b, n, 1.0, displace=n)
+        bound = 2 * nm.NOISE_BOUND * float(nm.tables32(n, 1.0)[0].sum()) + 4 * K * 2.0 ** -24 * (np.abs(ref).max() + 1.0)
+        assert 0.0 < np.abs(moved - y).max() <= bound
+        assert np.array_equal(moved, nm.chain32(a, b, n, 1.0, displace=n))  # seeded
+    # the faults are faults: each changes the sequence, the first two by one frequency's term
+    n = 513
+    a, b = (c.reshape(48, -1) for c in nm.pink_coefficients(nm.SEED, np.arange(3), 16, 0, n))
+    y = nm.chain32(a, b, n, 2.0)
+    g = nm.tables32(n, 2.0)[0].astype(np.float64)
+    for fault, k in (("drop_last", n // 2), ("drop_chunk_first", nm.CHUNK)):
+        d = np.abs(nm.chain32(a, b, n, 2.0, fault=fault) - y).max(axis=1)
+        amp = g[k] * np.hypot(a[:, k], b[:, k])
+        assert np.all(d <= amp * (1 + 1e-3) + 1e-5) and np.all(d >= amp * 0.9 - 1e-5), fault  # (some t is within 26 degrees of the peak)
+    assert np.abs(nm.chain32(a, b, n, 2.0, fault="phase_reset") - y).max() > 1e-4
+
+
+@pytest.mark.parametrize("n", nm.NS_WIDE)
+def test_the_wide_tolerance_table_is_twice_the_recomputed_chain_error(n):
+    """pink_tol(n, beta) = 2 R(n, beta) rounded up to two digits, R recomputed here from the model alone; and the first condition:
+    the tolerance is at most half the smallest gain, so one missing or misplaced frequency is larger than it."""
+    R = nm.chain_errors(n)
+    for beta in nm.BETAS:
+        assert nm.pink_tol(n, beta) == nm.round_up2(2 * R[beta]), (n, beta, R[beta])
+        assert 2 * R[beta] <= nm.pink_tol(n, beta) <= 2 * R[beta] * 1.1
+        smallest = float(nm.tables32(n, beta)[0].min())
+        assert nm.pink_tol(n, beta) <= smallest / 2, (n, beta, smallest)
+    assert set(nm.PINK_TOL_WIDE) == {(m, b) for m in nm.NS_WIDE for b in nm.BETAS}
+    assert nm.round_up2(2.5e-5) == 2.5e-5 and nm.round_up2(2.51e-5) == 2.6e-5 and nm.round_up2(9.91e-6) == 1.0e-5
+
+
+@pytest.mark.parametrize("n", [512, 4096])
+def test_the_wide_tolerance_sees_a_dropped_frequency_and_a_restarted_phase(n):
+    """The second condition, at beta = 2 (the smallest gains): the last frequency dropped, the first frequency of the second chunk
+    (k = 256) dropped, the phase walk restarted at k = 256 -- each, applied to the displaced chain, is off the float64 sum by more
+    than pink_tol over the 48 columns.  At n = 512 the last frequency is the second chunk's only one, the Nyquist term."""
+    tol = nm.pink_tol(n, 2.0)
+    clean = nm.chain_errors(n, (2.0,))[2.0]
+    assert clean <= tol / 2
+    for fault in nm.FAULTS:
+        err = nm.chain_errors(n, (2.0,), fault=fault)[2.0]
+        assert err > tol, (n, fault, err, tol)
 
 
 def test_a_sequence_depends_on_seed_env_column_and_sequence_number_alone():
