@@ -27,12 +27,12 @@ class _DeviceHandle:
     def _entry(self, name: str):
         return getattr(self.lib, f"fleet_{self._prefix}_{name}")
 
-    def _open(self, device: int, params):
-        """fleet_<prefix>_create on `device` with the family's parameter struct."""
+    def _open(self, device: int, params, *more):
+        """fleet_<prefix>_create on `device` with the family's parameter struct, and what the entry takes behind it (`more`)."""
         self.lib = _capi.load_library()
         self.device = int(device)
         h = C.c_void_p()
-        rc = self._entry("create")(self.device, C.byref(params), C.byref(h))
+        rc = self._entry("create")(self.device, C.byref(params), *more, C.byref(h))
         if rc != _capi.OK:
             raise FleetHipError(rc, self._entry("last_error")(None).decode())
         self.h = h

@@ -1,5 +1,6 @@
 // fleet_philox.h -- Philox4x32-10, the counter-based generator the replay buffer's index draw (fleet_replay.hip), the exploration
-// noise (fleet_policy.hip) and the correlated noise processes (fleet_noise.hip) share, and the Box-Muller step of the latter two.
+// noise (fleet_policy.hip), the targets' smoothing noise (fleet_qtarget.hip) and the correlated noise processes (fleet_noise.hip)
+// share, the Box-Muller step of all but the first, and the per-row draw of the second and third.
 // (The env's start-row sampler keeps its own restatement: fleet_wave.h philox_start.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,5 +30,24 @@ __device__ __forceinline__ void normals4(const uint32_t* x, float* z) {
     const float t = 6.283185307179586f * u2;
     z[2 * p] = r * cosf(t);
     z[2 * p + 1] = r * sinf(t);
+  }
+}
+
+// the Philox block of (global row id, block b of the row) at (step, seed): the counter scheme of the exploration and target noise
+__device__ __forceinline__ void philox_row_block(uint32_t id, int b, uint64_t step, uint64_t seed, uint32_t* w) {
+  philox4x32_10(id, (uint32_t)b, (uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), w);
+}
+
+// the four normals of columns 4b .. 4b + 3 of a row of A columns: drawn (philox_row_block of the row's global id), or, `given`, read
+// from noise[o + column], o the row's offset, zeros past A
+__device__ __forceinline__ void row_normals4(int given, const float* noise, size_t o, int b, int A, uint32_t id, uint64_t step,
+                                             uint64_t seed, float* z) {
+  if (given) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) z[c] = 4 * b + c < A ? noise[o + 4 * b + c] : 0.0f;
+  } else {
+    uint32_t w[4];
+    philox_row_block(id, b, step, seed, w);
+    normals4(w, z);
   }
 }

@@ -3,8 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <string>
-
 #include "../../include/fleet_hip.h"
 
 // policy_forward: 256 threads = 4 wavefronts take kPolicyRows env rows through every layer of one head.  A wavefront works on
@@ -37,21 +35,3 @@ struct PolicyDesc {
   int32_t reserved;
   PolicyHeadDesc head[FLEET_POLICY_MAX_HEADS];
 };
-
-// ---- host helpers the handle families built on these records share (fleet_policy.hip, fleet_qtarget.hip) ----------------------------
-inline int policy_round_up(int v, int m) { return (v + m - 1) / m * m; }
-
-// what *_create refuses about one head, before the device is touched; `who` opens the message ("head 0: "); "" when it passes
-inline std::string policy_validate_head(const FleetPolicyHead& H, const std::string& who) {
-  if (H.n_layers < 1 || H.n_layers > FLEET_POLICY_MAX_LAYERS)
-    return who + "n_layers must be in 1.." + std::to_string(FLEET_POLICY_MAX_LAYERS) + ", got " + std::to_string(H.n_layers);
-  for (int l = 0; l < H.n_layers; ++l)
-    if (H.width[l] < 1 || H.width[l] > FLEET_POLICY_MAX_WIDTH)
-      return who + "width of layer " + std::to_string(l) + " must be in 1.." + std::to_string(FLEET_POLICY_MAX_WIDTH) + ", got " +
-             std::to_string(H.width[l]);
-  if (H.activation != FLEET_POLICY_ACT_TANH && H.activation != FLEET_POLICY_ACT_RELU) return who + "unknown activation";
-  if (H.output != FLEET_POLICY_OUT_NONE && H.output != FLEET_POLICY_OUT_CLIP && H.output != FLEET_POLICY_OUT_TANH)
-    return who + "unknown output transform";
-  if (H.output == FLEET_POLICY_OUT_CLIP && !(H.lo <= H.hi)) return who + "clip bounds need lo <= hi";
-  return "";
-}

@@ -3,7 +3,8 @@
 // fleet_step_dev reads directly.
 //
 // One allocation holds the network's record (PolicyDesc, fleet_policy.h) and every layer's weights, re-laid at upload as
-// Wt[in][out] with `out` padded to whole wavefronts: the lanes of a wavefront read consecutive addresses.  Two kernels:
+// Wt[in][out] with `out` padded to whole wavefronts: the lanes of a wavefront read consecutive addresses.  That image -- its layout,
+// the upload, load_dev's re-lay kernel -- is fleet_mlp.hip's, shared with the target networks.  The kernels here:
 //   policy_forward  grid (ceil(E / 16), heads).  A workgroup takes 16 env rows through every layer of one head; the activations
 //                   ping-pong between two buffers in the LDS.  A lane owns ONE output column and keeps one accumulator per row in
 //                   registers; an activation is read from the LDS by all lanes at the same address (a broadcast), four inputs per
@@ -13,7 +14,6 @@
 //                   fleet_norm_obs1 (fleet_norm.h), when a normaliser is given -- so D = 1438 needs no whole row in the LDS.
 //                   A wavefront works on units of 64 columns x R rows, at most two, which share their LDS reads: R = 16 for layers
 //                   of 4..8 column groups, 8 for 2..3, 4 for one (four wavefronts split the rows of a 64-wide layer).
-//   policy_relay    load_dev: torch's [out, in] tensors -> the padded [in][out] image, one launch for all of them.
 //   policy_forward_sample  fleet_explore_act_dev (include/fleet_hip.h "exploration actions on the device"): the same forward, but
 //                   head 0's last layer leaves its 16 rows of means in the LDS, behind the staged input, instead of storing the
 //                   transformed output; after a barrier the workgroup runs the sampling epilogue as a phase of its own -- one
@@ -26,11 +26,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "fleet_handle.h"
+#include "fleet_mlp.h"
 #include "fleet_norm.h"
 #include "fleet_philox.h"
 #include "fleet_policy.h"
@@ -62,15 +60,7 @@ __device__ __forceinline__ void sample_epilogue(const ForwardArgs& a, const Samp
     if (row >= a.E) continue;
     const size_t o = (size_t)row * A;
     float z[4];
-    if (x.given) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) z[c] = 4 * b + c < A ? x.noise[o + 4 * b + c] : 0.0f;
-    } else {
-      uint32_t w[4];
-      philox4x32_10(x.env0 + (uint32_t)row, (uint32_t)b, (uint32_t)x.step, (uint32_t)(x.step >> 32), (uint32_t)x.seed,
-                    (uint32_t)(x.seed >> 32), w);
-      normals4(w, z);
-    }
+    row_normals4(x.given, x.noise, o, b, A, x.env0 + (uint32_t)row, x.step, x.seed, z);
     const float4 m4 = *reinterpret_cast<const float4*>(means + r * M + 4 * b);  // (M is a multiple of 64: aligned, inside the row)
     const float mz[4] = {m4.x, m4.y, m4.z, m4.w};
 #pragma unroll
@@ -144,8 +134,7 @@ __global__ __launch_bounds__(256) void explore_uniform(SampleArgs x, int E, int 
     const size_t row = item / nb;
     const int b = (int)(item - row * nb);
     uint32_t w[4] = {0u, 0u, 0u, 0u};
-    if (!x.given)
-      philox4x32_10(x.env0 + (uint32_t)row, (uint32_t)b, (uint32_t)x.step, (uint32_t)(x.step >> 32), (uint32_t)x.seed, (uint32_t)(x.seed >> 32), w);
+    if (!x.given) philox_row_block(x.env0 + (uint32_t)row, b, x.step, x.seed, w);
     const float top = x.lo < x.hi ? nextafterf(x.hi, x.lo) : x.lo;  // the largest value of [lo, hi)
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -162,36 +151,6 @@ __global__ __launch_bounds__(256) void explore_uniform(SampleArgs x, int E, int 
   }
 }
 
-// ---- policy_relay ----------------------------------------------------------------------------------------------------------------
-constexpr int kPolicyTensors = 2 * FLEET_POLICY_MAX_HEADS * FLEET_POLICY_MAX_LAYERS;
-struct RelayArgs {
-  const float* src[kPolicyTensors];
-  const PolicyDesc* desc;
-  float* base;
-};
-
-// tensor blockIdx.y (W, b per layer, head 0 then head 1): W[out][in] -> Wt[in][out64], b -> b; the padding stays what create made it
-__global__ __launch_bounds__(256) void policy_relay(RelayArgs a) {
-  const PolicyDesc* __restrict__ d = a.desc;
-  int t = blockIdx.y, h = 0;
-  if (t >= 2 * d->head[0].n_layers) {
-    t -= 2 * d->head[0].n_layers;
-    h = 1;
-  }
-  const PolicyLayer L = d->head[h].layer[t >> 1];
-  const float* __restrict__ src = a.src[blockIdx.y];
-  const unsigned stride = gridDim.x * 256, gid = blockIdx.x * 256 + threadIdx.x;
-  if (t & 1) {
-    for (unsigned j = gid; j < (unsigned)L.out; j += stride) a.base[L.b_off + j] = src[j];
-  } else {
-    const unsigned count = (unsigned)L.in * (unsigned)L.out;  // <= 8192 * 512
-    for (unsigned i = gid; i < count; i += stride) {
-      const unsigned k = i / (unsigned)L.out, j = i - k * (unsigned)L.out;
-      a.base[L.w_off + (size_t)k * L.out64 + j] = src[(size_t)j * L.in + k];
-    }
-  }
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 thread_local std::string g_policy_create_error;
 
@@ -202,74 +161,41 @@ std::string validate(const FleetPolicyParams* p) {
     return "obs_dim must be in 1.." + std::to_string(FLEET_POLICY_MAX_OBS_DIM) + ", got " + std::to_string(p->obs_dim);
   if (p->n_heads < 1 || p->n_heads > FLEET_POLICY_MAX_HEADS) return "n_heads must be 1 or 2, got " + std::to_string(p->n_heads);
   for (int h = 0; h < p->n_heads; ++h) {
-    const std::string why = policy_validate_head(p->head[h], "head " + std::to_string(h) + ": ");
+    const std::string why = mlp_validate_head(p->head[h], "head " + std::to_string(h) + ": ");
     if (!why.empty()) return why;
   }
   return "";
 }
 
-// the record of the network and the size of the block (floats)
-size_t describe_layout(const FleetPolicyParams& p, PolicyDesc* d) {
-  *d = PolicyDesc{};
-  d->obs_dim = p.obs_dim, d->n_heads = p.n_heads, d->stride = 64;
-  size_t off = policy_round_up((int)sizeof(PolicyDesc), 256) / 4;
-  for (int h = 0; h < p.n_heads; ++h) {
-    const FleetPolicyHead& H = p.head[h];
-    PolicyHeadDesc& o = d->head[h];
-    o.n_layers = H.n_layers, o.activation = H.activation, o.output = H.output, o.lo = H.lo, o.hi = H.hi;
-    for (int l = 0; l < H.n_layers; ++l) {
-      PolicyLayer& L = o.layer[l];
-      L.in = l ? H.width[l - 1] : p.obs_dim, L.out = H.width[l];
-      L.in4 = policy_round_up(L.in, 4), L.out64 = policy_round_up(L.out, 64);
-      L.w_off = (uint32_t)off;
-      off += (size_t)L.in4 * L.out64;
-      L.b_off = (uint32_t)off;
-      off += (size_t)L.out64;
-      if (l < H.n_layers - 1 && L.out64 > d->stride) d->stride = L.out64;
-    }
-  }
-  return off;  // <= 256 + 2 * 4 * (8192 * 512 + 512) floats: fits the 32-bit offsets
-}
+const char* const kHeadName[FLEET_POLICY_MAX_HEADS] = {"head 0", "head 1"};
+const MlpNames kPolicyNames = {kHeadName, "policy", "policy", ""};
 
 }  // namespace
 
-struct FleetPolicy : FleetHandleBase {
+struct FleetPolicy : FleetMlpHandle {
   FleetPolicyParams p{};
   PolicyDesc desc{};
-  size_t floats = 0;     // of the block
-  size_t lds_bytes = 0;  // of one workgroup of policy_forward
+  size_t lds_bytes = 0;         // of one workgroup of policy_forward
   size_t sample_lds_bytes = 0;  // ... of policy_forward_sample: the means of head 0's last layer behind it
-  int n_tensors = 0;
 };
 
 namespace {
 
-// the packed weights -> the block's image (the record included); "" or why not
-std::string build_image(const FleetPolicy* h, const float* weights, std::vector<float>* image) {
-  image->assign(h->floats, 0.0f);
-  memcpy(image->data(), &h->desc, sizeof(PolicyDesc));
-  const float* src = weights;
-  for (int hd = 0; hd < h->desc.n_heads; ++hd)
-    for (int l = 0; l < h->desc.head[hd].n_layers; ++l) {
-      const PolicyLayer& L = h->desc.head[hd].layer[l];
-      const size_t count = (size_t)L.in * L.out + L.out;
-      for (size_t i = 0; i < count; ++i)
-        if (!std::isfinite(src[i]))
-          return "head " + std::to_string(hd) + ", layer " + std::to_string(l) + ": " + (i < count - L.out ? "weight " : "bias ") +
-                 std::to_string(i < count - L.out ? i : i - (count - L.out)) + " is not finite";
-      for (int j = 0; j < L.out; ++j)
-        for (int k = 0; k < L.in; ++k) (*image)[L.w_off + (size_t)k * L.out64 + j] = src[(size_t)j * L.in + k];
-      src += (size_t)L.in * L.out;
-      for (int j = 0; j < L.out; ++j) (*image)[L.b_off + j] = src[j];
-      src += L.out;
-    }
-  return "";
-}
-
-int upload(FleetPolicy* h, const std::vector<float>& image) {
-  FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
-  FLEET_HANDLE_TRY(h, hipMemcpyAsync(h->block, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  FLEET_HANDLE_TRY(h, hipStreamSynchronize(h->stream));  // (the image is the caller's stack from here on)
+// The normaliser's frozen statistics (when one is given) into the forward's arguments, its read opened on the handle's stream
+// (the caller ends it behind the launch); *norm_obs: whether it normalises observations at all.  A normaliser of another shape or
+// device is refused.
+int bind_norm(FleetPolicy* h, const char* entry, fleet_norm_handle norm, ForwardArgs* a, bool* norm_obs) {
+  *norm_obs = false;
+  if (!norm) return FLEET_OK;
+  FleetNormView v{};
+  FLEET_HANDLE_TRY(h, fleet_norm_begin_read(norm, h->stream, &v));
+  if (v.D != h->p.obs_dim || v.device != h->device) {
+    h->error = std::string(entry) + ": the normaliser has obs_dim " + std::to_string(v.D) + " on device " + std::to_string(v.device) +
+               ", the policy " + std::to_string(h->p.obs_dim) + " on device " + std::to_string(h->device);
+    return FLEET_ERR_INVALID;
+  }
+  a->mean = v.obs_mean, a->sd = v.obs_sd, a->clip = v.clip_obs;
+  *norm_obs = v.norm_obs != 0;
   return FLEET_OK;
 }
 
@@ -289,33 +215,22 @@ int fleet_policy_create(int device, const FleetPolicyParams* p, const float* hos
   FleetPolicy* h = new FleetPolicy();
   h->p = *p;
   h->p.tile_rows = kPolicyRows;
-  h->floats = describe_layout(*p, &h->desc);
+  h->desc.obs_dim = p->obs_dim, h->desc.n_heads = p->n_heads;
+  const FleetPolicyHead* const heads[FLEET_POLICY_MAX_HEADS] = {&p->head[0], &p->head[1]};
+  const int first_in[FLEET_POLICY_MAX_HEADS] = {p->obs_dim, p->obs_dim};
+  h->record = &h->desc, h->record_bytes = sizeof(PolicyDesc), h->nets = h->desc.head, h->n_nets = p->n_heads, h->names = &kPolicyNames;
+  h->floats = mlp_describe_layout(heads, first_in, p->n_heads, sizeof(PolicyDesc), h->desc.head, &h->desc.stride);
   h->lds_bytes = ((size_t)2 * kPolicyRows * h->desc.stride + (size_t)kPolicyRows * kPolicyChunk) * sizeof(float);
   h->sample_lds_bytes = h->lds_bytes + (size_t)kPolicyRows * h->desc.head[0].layer[p->head[0].n_layers - 1].out64 * sizeof(float);
-  for (int hd = 0; hd < p->n_heads; ++hd) h->n_tensors += 2 * p->head[hd].n_layers;
-  std::vector<float> image;
-  why = build_image(h, host_weights, &image);
-  if (!why.empty()) {
-    g_policy_create_error = why;
-    delete h;
-    return FLEET_ERR_INVALID;
-  }
-  int rc = handle_open(h, device, h->floats * sizeof(float), "policy", &g_policy_create_error);
-  if (rc == FLEET_OK) {
-    // more than the 64 KiB a launch gets unasked when a hidden layer is wider than 448; the attribute belongs to the kernel, not
-    // to the handle, so every policy asks for what the widest one needs
-    constexpr int kMaxLds = (2 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk) * (int)sizeof(float);
-    constexpr int kMaxSampleLds = kMaxLds + kPolicyRows * FLEET_POLICY_MAX_WIDTH * (int)sizeof(float);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward_sample<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSampleLds) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_forward_sample<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSampleLds) != hipSuccess) {
-      (void)hipGetLastError();
-      g_policy_create_error = "hipFuncSetAttribute failed for the policy kernel's " + std::to_string(kMaxSampleLds) + " bytes of LDS";
-      rc = FLEET_ERR_HIP;
-    }
-  }
-  if (rc == FLEET_OK && (rc = upload(h, image)) != FLEET_OK) g_policy_create_error = h->error;
+  // (a hidden layer wider than 448 takes the forward past the 64 KiB a launch gets unasked)
+  constexpr int kMaxLds = (2 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk) * (int)sizeof(float);
+  constexpr int kMaxSampleLds = kMaxLds + kPolicyRows * FLEET_POLICY_MAX_WIDTH * (int)sizeof(float);
+  const int rc = mlp_open(h, device, host_weights,
+                          {{reinterpret_cast<const void*>(&policy_forward<false>), kMaxLds},
+                           {reinterpret_cast<const void*>(&policy_forward<true>), kMaxLds},
+                           {reinterpret_cast<const void*>(&policy_forward_sample<false>), kMaxSampleLds},
+                           {reinterpret_cast<const void*>(&policy_forward_sample<true>), kMaxSampleLds}},
+                          &g_policy_create_error);
   if (rc != FLEET_OK) {
     fleet_policy_destroy(h);
     return rc;
@@ -336,41 +251,12 @@ const char* fleet_policy_last_error(fleet_policy_handle h) { return h ? h->error
 int fleet_policy_set_stream(fleet_policy_handle h, void* hip_stream) { return h ? handle_set_stream(h, hip_stream) : FLEET_ERR_INVALID; }
 
 int fleet_policy_load_host(fleet_policy_handle h, const float* weights) {
-  if (!h) return FLEET_ERR_INVALID;
-  if (!weights) {
-    h->error = "fleet_policy_load_host: null weights";
-    return FLEET_ERR_INVALID;
-  }
-  std::vector<float> image;
-  const std::string why = build_image(h, weights, &image);
-  if (!why.empty()) {
-    h->error = "fleet_policy_load_host: " + why;
-    return FLEET_ERR_INVALID;
-  }
-  return upload(h, image);
+  return h ? mlp_load_host(h, "fleet_policy_load_host", weights) : FLEET_ERR_INVALID;
 }
 
 int fleet_policy_load_dev(fleet_policy_handle h, const float* const* tensors, int count) {
   if (!h) return FLEET_ERR_INVALID;
-  if (!tensors || count != h->n_tensors) {
-    h->error = "fleet_policy_load_dev: expected " + std::to_string(h->n_tensors) + " tensors (W, b per layer), got " +
-               (tensors ? std::to_string(count) : std::string("a null array"));
-    return FLEET_ERR_INVALID;
-  }
-  RelayArgs a{};
-  for (int i = 0; i < count; ++i) {
-    if (!tensors[i]) {
-      h->error = "fleet_policy_load_dev: tensor " + std::to_string(i) + " is null";
-      return FLEET_ERR_INVALID;
-    }
-    a.src[i] = tensors[i];
-  }
-  a.desc = reinterpret_cast<const PolicyDesc*>(h->block);
-  a.base = reinterpret_cast<float*>(h->block);
-  FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(policy_relay, dim3(64, count), dim3(256), 0, h->stream, a);
-  FLEET_HANDLE_TRY(h, hipGetLastError());
-  return FLEET_OK;
+  return mlp_launch_relay(h, kMlpLoad, "fleet_policy_load_dev", const_cast<float* const*>(tensors), count, 0.0f, 0.0f);  // (read only)
 }
 
 int fleet_policy_forward_dev(fleet_policy_handle h, const float* obs, int E, fleet_norm_handle norm, float* actions, float* values) {
@@ -392,18 +278,8 @@ int fleet_policy_forward_dev(fleet_policy_handle h, const float* obs, int E, fle
   a.base = reinterpret_cast<const float*>(h->block);
   a.obs = obs, a.actions = actions, a.values = values, a.E = E;
   FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
-  bool norm_obs = false;
-  if (norm) {
-    FleetNormView v{};
-    FLEET_HANDLE_TRY(h, fleet_norm_begin_read(norm, h->stream, &v));
-    if (v.D != h->p.obs_dim || v.device != h->device) {
-      h->error = "fleet_policy_forward_dev: the normaliser has obs_dim " + std::to_string(v.D) + " on device " + std::to_string(v.device) +
-                 ", the policy " + std::to_string(h->p.obs_dim) + " on device " + std::to_string(h->device);
-      return FLEET_ERR_INVALID;
-    }
-    a.mean = v.obs_mean, a.sd = v.obs_sd, a.clip = v.clip_obs;
-    norm_obs = v.norm_obs != 0;
-  }
+  bool norm_obs;
+  if (const int rc = bind_norm(h, "fleet_policy_forward_dev", norm, &a, &norm_obs); rc != FLEET_OK) return rc;
   const dim3 grid((unsigned)(((size_t)E + kPolicyRows - 1) / kPolicyRows), values ? 2 : 1), block(kPolicyThreads);
   if (norm_obs) hipLaunchKernelGGL(policy_forward<true>, grid, block, h->lds_bytes, h->stream, a);
   else hipLaunchKernelGGL(policy_forward<false>, grid, block, h->lds_bytes, h->stream, a);
@@ -458,16 +334,8 @@ int fleet_explore_act_dev(fleet_policy_handle h, const float* obs, int E, fleet_
   a.desc = reinterpret_cast<const PolicyDesc*>(h->block);
   a.base = reinterpret_cast<const float*>(h->block);
   a.obs = obs, a.actions = nullptr, a.values = x.values, a.E = E;
-  bool norm_obs = false;
-  if (norm) {
-    FleetNormView v{};
-    FLEET_HANDLE_TRY(h, fleet_norm_begin_read(norm, h->stream, &v));
-    if (v.D != h->p.obs_dim || v.device != h->device)
-      return refuse("the normaliser has obs_dim " + std::to_string(v.D) + " on device " + std::to_string(v.device) + ", the policy " +
-                    std::to_string(h->p.obs_dim) + " on device " + std::to_string(h->device));
-    a.mean = v.obs_mean, a.sd = v.obs_sd, a.clip = v.clip_obs;
-    norm_obs = v.norm_obs != 0;
-  }
+  bool norm_obs;
+  if (const int rc = bind_norm(h, "fleet_explore_act_dev", norm, &a, &norm_obs); rc != FLEET_OK) return rc;
   const dim3 grid((unsigned)(((size_t)E + kPolicyRows - 1) / kPolicyRows), x.values ? 2 : 1), block(kPolicyThreads);
   if (norm_obs) hipLaunchKernelGGL(policy_forward_sample<true>, grid, block, h->sample_lds_bytes, h->stream, a, s);
   else hipLaunchKernelGGL(policy_forward_sample<false>, grid, block, h->sample_lds_bytes, h->stream, a, s);

@@ -1,8 +1,9 @@
 // fleet_qtarget.hip -- the target networks of a TD3 / DDPG agent on the device (include/fleet_hip.h "TD3 / DDPG learning targets on
 // the device"): the bootstrap target of a minibatch in one launch, the Polyak update in one launch, loads and the export.
 //
-// One allocation holds the record (QTargetDesc) and every layer's weights of the actor, critic 0 and critic 1, laid out as the
-// policy's are (PolicyLayer, fleet_policy.h).  Two kernels:
+// One allocation holds the record (QTargetDesc) and every layer's weights of the actor, critic 0 and critic 1: the image of
+// fleet_mlp.h, which the policy keeps too.  Its layout, the uploads and the kernel behind load_dev, polyak_dev and export_dev (mlp_relay:
+// only real elements are visited, t' = fmaf(tau, p, t * omt)) are fleet_mlp.hip's.  The kernel here:
 //   qtarget_target  grid ceil(B / 16).  A workgroup of 256 threads takes 16 rows through the ACTOR with the layer functions of
 //                   fleet_policy_dev.h; its last layer leaves the rows untransformed in the LDS, act[16][A64], as
 //                   policy_forward_sample's does.  An epilogue phase -- one thread per (row, 4 columns) -- turns them into the
@@ -13,25 +14,19 @@
 //                   is those 16 threads: q, qmin, y.
 //                   LDS: two activation buffers [16][S], S the widest hidden layer of all three networks, the staged chunk
 //                   [16][128], act [16][A64]: 20 KiB .. 104 KiB.
-//   qtarget_relay   grid (64, tensors): load (torch's [out, in] -> the image), polyak (the same walk, t' = fmaf(tau, p, t * omt)) and
-//                   export (the image -> torch's layout).  Only real elements are visited: the padding stays what create made it.
 // Launch boundaries are the only visibility mechanism; no atomics.  float32 throughout.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstring>
 #include <string>
-#include <vector>
 
-#include "fleet_handle.h"
+#include "fleet_mlp.h"
 #include "fleet_philox.h"
 #include "fleet_policy.h"
 #include "fleet_policy_dev.h"
 
 namespace {
 
-constexpr int kQNets = 3;  // actor, critic 0, critic 1
-constexpr int kQTensors = 2 * kQNets * FLEET_POLICY_MAX_LAYERS;
+constexpr int kQNets = kMlpMaxNets;  // actor, critic 0, critic 1
 
 struct QTargetDesc {
   int32_t obs_dim, act_dim, n_critics;
@@ -64,15 +59,7 @@ __device__ __forceinline__ void action_epilogue(const TargetArgs& t, const Polic
     if (row >= t.B) continue;  // (such a row keeps the untransformed numbers: the critics run on them and nobody reads the result)
     const size_t o = (size_t)row * A;
     float z[4];
-    if (t.given) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) z[c] = 4 * b + c < A ? t.noise[o + 4 * b + c] : 0.0f;
-    } else {
-      uint32_t w[4];
-      philox4x32_10(t.row_id0 + (uint32_t)row, (uint32_t)b, (uint32_t)t.step, (uint32_t)(t.step >> 32), (uint32_t)t.seed,
-                    (uint32_t)(t.seed >> 32), w);
-      normals4(w, z);
-    }
+    row_normals4(t.given, t.noise, o, b, A, t.row_id0 + (uint32_t)row, t.step, t.seed, z);
     const float4 m4 = *reinterpret_cast<const float4*>(act + r * M + 4 * b);  // (M is a multiple of 64: aligned, inside the row)
     const float mz[4] = {m4.x, m4.y, m4.z, m4.w};
 #pragma unroll
@@ -131,39 +118,6 @@ __global__ __launch_bounds__(kPolicyThreads) void qtarget_target(TargetArgs t) {
   }
 }
 
-// ---- qtarget_relay ---------------------------------------------------------------------------------------------------------------
-constexpr int kRelayLoad = 0, kRelayPolyak = 1, kRelayExport = 2;
-struct QRelayArgs {
-  float* tensor[kQTensors];  // (read in the load and polyak modes, written in the export mode)
-  const QTargetDesc* desc;
-  float* base;
-  float tau, omt;
-};
-
-// tensor blockIdx.y (W, b per layer; actor, critic 0, critic 1): W[out][in] <-> Wt[in][out64], b <-> b
-template <int kMode>
-__global__ __launch_bounds__(256) void qtarget_relay(QRelayArgs a) {
-  const QTargetDesc* __restrict__ d = a.desc;
-  int t = blockIdx.y, net = 0;
-  while (net < kQNets - 1 && t >= 2 * d->net[net].n_layers) t -= 2 * d->net[net++].n_layers;
-  const PolicyLayer L = d->net[net].layer[t >> 1];
-  float* __restrict__ ext = a.tensor[blockIdx.y];
-  const unsigned stride = gridDim.x * 256, gid = blockIdx.x * 256 + threadIdx.x;
-  const unsigned count = t & 1 ? (unsigned)L.out : (unsigned)L.in * (unsigned)L.out;  // <= 8192 * 512
-  for (unsigned i = gid; i < count; i += stride) {
-    size_t img, e;
-    if (t & 1) {
-      img = L.b_off + i, e = i;
-    } else {
-      const unsigned k = i / (unsigned)L.out, j = i - k * (unsigned)L.out;
-      img = L.w_off + (size_t)k * L.out64 + j, e = (size_t)j * L.in + k;
-    }
-    if (kMode == kRelayLoad) a.base[img] = ext[e];
-    else if (kMode == kRelayExport) ext[e] = a.base[img];
-    else a.base[img] = fmaf(a.tau, ext[e], a.base[img] * a.omt);
-  }
-}
-
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 thread_local std::string g_qtarget_error;  // of the last failed call without a handle
 
@@ -173,7 +127,7 @@ std::string validate(const FleetQTargetParams* p) {
   if (p->obs_dim < 1 || p->obs_dim > FLEET_POLICY_MAX_OBS_DIM)
     return "obs_dim must be in 1.." + std::to_string(FLEET_POLICY_MAX_OBS_DIM) + ", got " + std::to_string(p->obs_dim);
   if (p->n_critics < 1 || p->n_critics > 2) return "n_critics must be 1 or 2, got " + std::to_string(p->n_critics);
-  std::string why = policy_validate_head(p->actor, "actor: ");
+  std::string why = mlp_validate_head(p->actor, "actor: ");
   if (!why.empty()) return why;
   const int A = p->actor.width[p->actor.n_layers - 1];
   if (p->obs_dim + A > FLEET_POLICY_MAX_OBS_DIM)
@@ -181,7 +135,7 @@ std::string validate(const FleetQTargetParams* p) {
            std::to_string(p->obs_dim) + " + " + std::to_string(A);
   for (int c = 0; c < p->n_critics; ++c) {
     const std::string who = "critic " + std::to_string(c) + ": ";
-    why = policy_validate_head(p->critic[c], who);
+    why = mlp_validate_head(p->critic[c], who);
     if (!why.empty()) return why;
     if (p->critic[c].width[p->critic[c].n_layers - 1] != 1)
       return who + "the last width must be 1, got " + std::to_string(p->critic[c].width[p->critic[c].n_layers - 1]);
@@ -190,99 +144,18 @@ std::string validate(const FleetQTargetParams* p) {
   return "";
 }
 
-const FleetPolicyHead& head_of(const FleetQTargetParams& p, int net) { return net ? p.critic[net - 1] : p.actor; }
-
-// the record of the networks and the size of the block (floats)
-size_t describe_layout(const FleetQTargetParams& p, QTargetDesc* d) {
-  *d = QTargetDesc{};
-  const int A = p.actor.width[p.actor.n_layers - 1];
-  d->obs_dim = p.obs_dim, d->act_dim = A, d->n_critics = p.n_critics, d->stride = 64, d->act64 = policy_round_up(A, 64);
-  size_t off = policy_round_up((int)sizeof(QTargetDesc), 256) / 4;
-  for (int net = 0; net < 1 + p.n_critics; ++net) {
-    const FleetPolicyHead& H = head_of(p, net);
-    PolicyHeadDesc& o = d->net[net];
-    o.n_layers = H.n_layers, o.activation = H.activation, o.output = H.output, o.lo = H.lo, o.hi = H.hi;
-    for (int l = 0; l < H.n_layers; ++l) {
-      PolicyLayer& L = o.layer[l];
-      L.in = l ? H.width[l - 1] : (net ? p.obs_dim + A : p.obs_dim), L.out = H.width[l];
-      L.in4 = policy_round_up(L.in, 4), L.out64 = policy_round_up(L.out, 64);
-      L.w_off = (uint32_t)off;
-      off += (size_t)L.in4 * L.out64;
-      L.b_off = (uint32_t)off;
-      off += (size_t)L.out64;
-      if (l < H.n_layers - 1 && L.out64 > d->stride) d->stride = L.out64;
-    }
-  }
-  return off;  // <= 256 + 3 * 4 * (8192 * 512 + 512) floats: fits the 32-bit offsets
-}
+const char* const kNetName[kQNets] = {"actor", "critic 0", "critic 1"};
+const MlpNames kTargetNames = {kNetName, "target networks", "target", "fleet_qtarget_create: "};
 
 }  // namespace
 
-struct FleetQTarget : FleetHandleBase {
+struct FleetQTarget : FleetMlpHandle {
   FleetQTargetParams p{};
   QTargetDesc desc{};
-  size_t floats = 0;     // of the block
   size_t lds_bytes = 0;  // of one workgroup of qtarget_target
-  int n_tensors = 0;
 };
 
 namespace {
-
-const char* const kNetName[kQNets] = {"actor", "critic 0", "critic 1"};
-
-// the packed weights -> the block's image (the record included); "" or why not
-std::string build_image(const FleetQTarget* h, const float* weights, std::vector<float>* image) {
-  image->assign(h->floats, 0.0f);
-  memcpy(image->data(), &h->desc, sizeof(QTargetDesc));
-  const float* src = weights;
-  for (int net = 0; net < 1 + h->desc.n_critics; ++net)
-    for (int l = 0; l < h->desc.net[net].n_layers; ++l) {
-      const PolicyLayer& L = h->desc.net[net].layer[l];
-      const size_t count = (size_t)L.in * L.out + L.out;
-      for (size_t i = 0; i < count; ++i)
-        if (!std::isfinite(src[i]))
-          return std::string(kNetName[net]) + ", layer " + std::to_string(l) + ": " + (i < count - L.out ? "weight " : "bias ") +
-                 std::to_string(i < count - L.out ? i : i - (count - L.out)) + " is not finite";
-      for (int j = 0; j < L.out; ++j)
-        for (int k = 0; k < L.in; ++k) (*image)[L.w_off + (size_t)k * L.out64 + j] = src[(size_t)j * L.in + k];
-      src += (size_t)L.in * L.out;
-      for (int j = 0; j < L.out; ++j) (*image)[L.b_off + j] = src[j];
-      src += L.out;
-    }
-  return "";
-}
-
-int upload(FleetQTarget* h, const std::vector<float>& image) {
-  FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
-  FLEET_HANDLE_TRY(h, hipMemcpyAsync(h->block, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  FLEET_HANDLE_TRY(h, hipStreamSynchronize(h->stream));  // (the image is the caller's stack from here on)
-  return FLEET_OK;
-}
-
-// load_dev, polyak_dev, export_dev: one launch over the tensors
-template <int kMode>
-int relay(FleetQTarget* h, const char* entry, float* const* tensors, int count, float tau, float omt) {
-  if (!tensors || count != h->n_tensors) {
-    h->error = std::string(entry) + ": expected " + std::to_string(h->n_tensors) + " tensors (W, b per layer), got " +
-               (tensors ? std::to_string(count) : std::string("a null array"));
-    return FLEET_ERR_INVALID;
-  }
-  QRelayArgs a{};
-  for (int i = 0; i < count; ++i) {
-    if (!tensors[i]) {
-      h->error = std::string(entry) + ": tensor " + std::to_string(i) + " is null";
-      return FLEET_ERR_INVALID;
-    }
-    a.tensor[i] = tensors[i];
-  }
-  a.desc = reinterpret_cast<const QTargetDesc*>(h->block);
-  a.base = reinterpret_cast<float*>(h->block);
-  a.tau = tau, a.omt = omt;
-  FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
-  hipLaunchKernelGGL(qtarget_relay<kMode>, dim3(64, count), dim3(256), 0, h->stream, a);
-  FLEET_HANDLE_TRY(h, hipGetLastError());
-  return FLEET_OK;
-}
 
 // what fleet_qtarget_target_dev refuses, looked at without the handle; "" when the arguments pass
 std::string check_target_args(const float* next_obs, const float* rewards, const float* dones, int B, const FleetQTargetArgs* args) {
@@ -320,27 +193,15 @@ int fleet_qtarget_create(int device, const FleetQTargetParams* p, const float* h
   FleetQTarget* h = new FleetQTarget();
   h->p = *p;
   h->p.tile_rows = kPolicyRows;
-  h->floats = describe_layout(*p, &h->desc);
+  const int A = p->actor.width[p->actor.n_layers - 1];
+  h->desc.obs_dim = p->obs_dim, h->desc.act_dim = A, h->desc.n_critics = p->n_critics, h->desc.act64 = mlp_round_up(A, 64);
+  const FleetPolicyHead* const heads[kQNets] = {&p->actor, &p->critic[0], &p->critic[1]};
+  const int first_in[kQNets] = {p->obs_dim, p->obs_dim + A, p->obs_dim + A};
+  h->record = &h->desc, h->record_bytes = sizeof(QTargetDesc), h->nets = h->desc.net, h->n_nets = 1 + p->n_critics, h->names = &kTargetNames;
+  h->floats = mlp_describe_layout(heads, first_in, h->n_nets, sizeof(QTargetDesc), h->desc.net, &h->desc.stride);
   h->lds_bytes = ((size_t)2 * kPolicyRows * h->desc.stride + (size_t)kPolicyRows * kPolicyChunk + (size_t)kPolicyRows * h->desc.act64) * sizeof(float);
-  for (int net = 0; net < 1 + p->n_critics; ++net) h->n_tensors += 2 * head_of(*p, net).n_layers;
-  std::vector<float> image;
-  why = build_image(h, host_weights, &image);
-  if (!why.empty()) {
-    g_qtarget_error = "fleet_qtarget_create: " + why;
-    delete h;
-    return FLEET_ERR_INVALID;
-  }
-  int rc = handle_open(h, device, h->floats * sizeof(float), "target networks", &g_qtarget_error);
-  if (rc == FLEET_OK) {
-    // more than the 64 KiB a launch gets unasked; the attribute belongs to the kernel: every handle asks for the widest one's need
-    constexpr int kMaxLds = (3 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk) * (int)sizeof(float);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&qtarget_target), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
-      (void)hipGetLastError();
-      g_qtarget_error = "hipFuncSetAttribute failed for the target kernel's " + std::to_string(kMaxLds) + " bytes of LDS";
-      rc = FLEET_ERR_HIP;
-    }
-  }
-  if (rc == FLEET_OK && (rc = upload(h, image)) != FLEET_OK) g_qtarget_error = h->error;
+  constexpr int kMaxLds = (3 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk) * (int)sizeof(float);
+  const int rc = mlp_open(h, device, host_weights, {{reinterpret_cast<const void*>(&qtarget_target), kMaxLds}}, &g_qtarget_error);
   if (rc != FLEET_OK) {
     fleet_qtarget_destroy(h);
     return rc;
@@ -361,23 +222,12 @@ const char* fleet_qtarget_last_error(fleet_qtarget_handle h) { return h ? h->err
 int fleet_qtarget_set_stream(fleet_qtarget_handle h, void* hip_stream) { return h ? handle_set_stream(h, hip_stream) : FLEET_ERR_INVALID; }
 
 int fleet_qtarget_load_host(fleet_qtarget_handle h, const float* weights) {
-  if (!h) return FLEET_ERR_INVALID;
-  if (!weights) {
-    h->error = "fleet_qtarget_load_host: null weights";
-    return FLEET_ERR_INVALID;
-  }
-  std::vector<float> image;
-  const std::string why = build_image(h, weights, &image);
-  if (!why.empty()) {
-    h->error = "fleet_qtarget_load_host: " + why;
-    return FLEET_ERR_INVALID;
-  }
-  return upload(h, image);
+  return h ? mlp_load_host(h, "fleet_qtarget_load_host", weights) : FLEET_ERR_INVALID;
 }
 
 int fleet_qtarget_load_dev(fleet_qtarget_handle h, const float* const* tensors, int count) {
   if (!h) return FLEET_ERR_INVALID;
-  return relay<kRelayLoad>(h, "fleet_qtarget_load_dev", const_cast<float* const*>(tensors), count, 0.0f, 0.0f);  // (read only)
+  return mlp_launch_relay(h, kMlpLoad, "fleet_qtarget_load_dev", const_cast<float* const*>(tensors), count, 0.0f, 0.0f);  // (read only)
 }
 
 int fleet_qtarget_polyak_dev(fleet_qtarget_handle h, const float* const* tensors, int count, double tau) {
@@ -386,12 +236,12 @@ int fleet_qtarget_polyak_dev(fleet_qtarget_handle h, const float* const* tensors
     h->error = "fleet_qtarget_polyak_dev: tau must be in [0, 1], got " + std::to_string(tau);
     return FLEET_ERR_INVALID;
   }
-  return relay<kRelayPolyak>(h, "fleet_qtarget_polyak_dev", const_cast<float* const*>(tensors), count, (float)tau, (float)(1.0 - tau));
+  return mlp_launch_relay(h, kMlpPolyak, "fleet_qtarget_polyak_dev", const_cast<float* const*>(tensors), count, (float)tau, (float)(1.0 - tau));
 }
 
 int fleet_qtarget_export_dev(fleet_qtarget_handle h, float* const* tensors, int count) {
   if (!h) return FLEET_ERR_INVALID;
-  return relay<kRelayExport>(h, "fleet_qtarget_export_dev", tensors, count, 0.0f, 0.0f);
+  return mlp_launch_relay(h, kMlpExport, "fleet_qtarget_export_dev", tensors, count, 0.0f, 0.0f);
 }
 
 int fleet_qtarget_target_dev(fleet_qtarget_handle h, const float* next_obs, const float* rewards, const float* dones, int B,

@@ -22,22 +22,13 @@ import zipfile
 import numpy as np
 
 from . import _capi
-from ._capi import FleetHipError
-from ._handle import _DeviceHandle
+from ._mlp import _MlpHandle, _arrays
 from .replay import _norm_handle
 
 __all__ = ["DevicePolicy", "evaluate_policy"]
 
-_ACTIVATIONS = {"tanh": _capi.POLICY_ACT_TANH, "relu": _capi.POLICY_ACT_RELU}
-_OUTPUTS = {"none": _capi.POLICY_OUT_NONE, "clip": _capi.POLICY_OUT_CLIP, "tanh": _capi.POLICY_OUT_TANH}
 # keys of an SB3 policy's state dict that carry nothing the deterministic forward needs
 _IGNORED = re.compile(r"^(actor_target|critic|critic_target)\.|^actor\.log_std\.(weight|bias)$")
-
-
-def _array(t) -> np.ndarray:
-    if hasattr(t, "detach"):
-        t = t.detach().cpu().numpy()
-    return np.ascontiguousarray(t, dtype=np.float32)
 
 
 def _chain(sd: dict, prefix: str) -> list:
@@ -96,7 +87,7 @@ def parse_state_dict(sd: dict, activation: str | None = None) -> dict:
     refuse(keys[0] if keys else "<empty>", "no known policy family")
 
 
-class DevicePolicy(_DeviceHandle):
+class DevicePolicy(_MlpHandle):
     """One `fleet_policy_*` handle: an actor and optionally a critic, each a chain of at most 4 linear layers of width <= 512 over
     the same observation of at most 8192 columns.  `layers` / `critic_layers`: [(W [out, in], b [out]), ...] (torch's layout;
     tensors or arrays).  activation: "tanh" | "relu" after every layer but the last; output: "none" | "clip" (to [low, high]) |
@@ -105,51 +96,19 @@ class DevicePolicy(_DeviceHandle):
 
     def __init__(self, layers, critic_layers=None, activation: str = "tanh", output: str = "clip", low: float = -1.0,
                  high: float = 1.0, device: int = 0):
-        if activation not in _ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(_ACTIVATIONS)}, got {activation!r}")
-        if output not in _OUTPUTS:
-            raise ValueError(f"output must be one of {sorted(_OUTPUTS)}, got {output!r}")
-        heads = [[(_array(w), _array(b)) for w, b in layers]]
-        if critic_layers is not None:
-            heads.append([(_array(w), _array(b)) for w, b in critic_layers])
+        self._set_transforms(activation, output)
+        heads = [_arrays(layers)] + ([] if critic_layers is None else [_arrays(critic_layers)])
         if not heads[0]:
             raise ValueError("a policy needs at least one layer")
         self.obs_dim = int(heads[0][0][0].shape[1]) if heads[0][0][0].ndim == 2 else 0
         p = _capi.FleetPolicyParams()
         p.struct_bytes, p.obs_dim, p.n_heads = C.sizeof(_capi.FleetPolicyParams), self.obs_dim, len(heads)
-        for h, head in enumerate(heads):
-            inp = self.obs_dim
-            for l, (w, b) in enumerate(head):
-                if w.ndim != 2 or b.shape != (w.shape[0],) or w.shape[1] != inp:
-                    raise ValueError(f"head {h}, layer {l}: expected W [out, {inp}] and b [out], got {w.shape} and {b.shape}")
-                inp = w.shape[0]
-            P = p.head[h]
-            P.n_layers = len(head)  # (more than the ABI's 4: refused by the library, with its reason)
-            for l, (w, _) in enumerate(head[:_capi.POLICY_MAX_LAYERS]):
-                P.width[l] = w.shape[0]
-            P.activation = _ACTIVATIONS[activation]
-            P.output = _OUTPUTS[output] if h == 0 else _capi.POLICY_OUT_NONE
-            P.lo, P.hi = (float(low), float(high)) if h == 0 else (0.0, 0.0)
+        self._fill_head(p.head[0], "head 0", heads[0], self.obs_dim, output, low, high)
+        for h, head in enumerate(heads[1:], 1):
+            self._fill_head(p.head[h], f"head {h}", head, self.obs_dim)
         self.act_dim = int(heads[0][-1][0].shape[0])
         self.value_dim = int(heads[1][-1][0].shape[0]) if len(heads) > 1 else 0
-        self.activation, self.output = activation, output
-        self._shapes = [(w.shape, b.shape) for head in heads for w, b in head]
-        packed = self._pack(heads)
-        self.lib = _capi.load_library()
-        self.device = int(device)
-        h = C.c_void_p()
-        rc = self.lib.fleet_policy_create(self.device, C.byref(p), packed.ctypes.data, C.byref(h))
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_policy_last_error(None).decode())
-        self.h = h
-        self._stream = None
-        self._constants = {}  # _per_action's device tensors of float arguments
-        self.tile_rows = self.describe()["tile_rows"]
-
-    @staticmethod
-    def _pack(heads) -> np.ndarray:
-        parts = [a.ravel() for head in heads for w, b in head for a in (w, b)]
-        return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+        self._create(device, p, heads)
 
     # ---- constructors from SB3's files ---------------------------------------------------------------------------------------
     @classmethod
@@ -168,7 +127,7 @@ class DevicePolicy(_DeviceHandle):
     # ---- weights -------------------------------------------------------------------------------------------------------------
     def load_host(self, layers, critic_layers=None):
         """New weights of the same shapes from host arrays; FleetHipError (ERR_INVALID) when one is not finite."""
-        heads = [[(_array(w), _array(b)) for w, b in layers]] + ([] if critic_layers is None else [[(_array(w), _array(b)) for w, b in critic_layers]])
+        heads = [_arrays(layers)] + ([] if critic_layers is None else [_arrays(critic_layers)])
         if [(w.shape, b.shape) for head in heads for w, b in head] != self._shapes:
             raise ValueError("load_host: the shapes differ from the policy's")
         packed = self._pack(heads)
@@ -178,19 +137,8 @@ class DevicePolicy(_DeviceHandle):
         """New weights from torch's parameter tensors on the policy's device, in declaration order (W, b per layer, the actor's
         then the critic's): copied and re-laid by one launch on torch's current stream, no host synchronisation -- what a training
         loop calls after an optimiser step."""
-        import torch
-
-        self.use_torch_stream()
-        params = [p.detach() for p in parameters]
-        if len(params) != 2 * len(self._shapes):
-            raise ValueError(f"load_torch: expected {2 * len(self._shapes)} tensors, got {len(params)}")
-        flat = [s for pair in self._shapes for s in pair]
-        tensors = [self._tensor(t, s, (torch.float32,)) for t, s in zip(params, flat)]
-        for t, s in zip(tensors, flat):
-            if tuple(t.shape) != tuple(s):
-                raise ValueError(f"load_torch: expected a tensor of shape {tuple(s)}, got {tuple(t.shape)}")
-        ptrs = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-        self._check(self.lib.fleet_policy_load_dev(self.h, ptrs, len(tensors)))
+        ptrs, keep = self._pointers("load_torch", parameters)
+        self._check(self.lib.fleet_policy_load_dev(self.h, ptrs, len(keep)))
 
     # ---- the forward -----------------------------------------------------------------------------------------------------------
     def forward_dev(self, obs_ptr: int, num_envs: int, norm=None, actions_ptr: int | None = None, values_ptr: int | None = None):
@@ -315,10 +263,8 @@ class DevicePolicy(_DeviceHandle):
         """What fleet_policy_describe reports: the shape of the network and `tile_rows`, the env rows one workgroup takes."""
         p = _capi.FleetPolicyParams()
         self._check(self.lib.fleet_policy_describe(self.h, C.byref(p)))
-        names = {v: k for k, v in _ACTIVATIONS.items()}, {v: k for k, v in _OUTPUTS.items()}
         return {"obs_dim": p.obs_dim, "n_heads": p.n_heads, "tile_rows": p.tile_rows,
-                "heads": [{"widths": list(p.head[h].width[:p.head[h].n_layers]), "activation": names[0][p.head[h].activation],
-                           "output": names[1][p.head[h].output], "low": p.head[h].lo, "high": p.head[h].hi} for h in range(p.n_heads)]}
+                "heads": [self._head_dict(p.head[h]) for h in range(p.n_heads)]}
 
 
 def read_sb3_state_dict(path) -> dict:

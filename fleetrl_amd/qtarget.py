@@ -12,12 +12,9 @@ from __future__ import annotations
 import ctypes as C
 import re
 
-import numpy as np
-
 from . import _capi
-from ._capi import FleetHipError
-from ._handle import _DeviceHandle
-from .policy import _ACTIVATIONS, _OUTPUTS, _array, _chain, read_sb3_state_dict
+from ._mlp import _MlpHandle, _arrays
+from .policy import _chain, read_sb3_state_dict
 
 __all__ = ["DeviceTD3Target", "parse_target_state_dict"]
 
@@ -43,7 +40,7 @@ def parse_target_state_dict(sd: dict) -> dict:
     return {"actor_layers": actor, "critics_layers": critics}
 
 
-class DeviceTD3Target(_DeviceHandle):
+class DeviceTD3Target(_MlpHandle):
     """One `fleet_qtarget_*` handle: a target actor over `obs_dim` columns and one (DDPG) or two (TD3) target critics over
     `obs_dim + act_dim` columns -- the observation, then the action -- each a chain of at most 4 linear layers of width <= 512.
     actor_layers: [(W [out, in], b [out]), ...]; critics_layers: one such list per critic, the last width 1.  activation: "tanh" |
@@ -53,11 +50,8 @@ class DeviceTD3Target(_DeviceHandle):
 
     def __init__(self, actor_layers, critics_layers, activation: str = "relu", output: str = "tanh", low: float = -1.0,
                  high: float = 1.0, device: int = 0):
-        if activation not in _ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(_ACTIVATIONS)}, got {activation!r}")
-        if output not in _OUTPUTS:
-            raise ValueError(f"output must be one of {sorted(_OUTPUTS)}, got {output!r}")
-        nets = [[(_array(w), _array(b)) for w, b in actor_layers]] + [[(_array(w), _array(b)) for w, b in c] for c in critics_layers]
+        self._set_transforms(activation, output)
+        nets = [_arrays(actor_layers)] + [_arrays(c) for c in critics_layers]
         if not nets[0] or len(nets) < 2 or len(nets) > 3 or not all(nets):
             raise ValueError("the targets are an actor and one or two critics, each of at least one layer")
         self.obs_dim = int(nets[0][0][0].shape[1]) if nets[0][0][0].ndim == 2 else 0
@@ -65,37 +59,10 @@ class DeviceTD3Target(_DeviceHandle):
         self.n_critics = len(nets) - 1
         p = _capi.FleetQTargetParams()
         p.struct_bytes, p.obs_dim, p.n_critics = C.sizeof(_capi.FleetQTargetParams), self.obs_dim, self.n_critics
-        for n, net in enumerate(nets):
-            who = "actor" if n == 0 else f"critic {n - 1}"
-            inp = self.obs_dim if n == 0 else self.obs_dim + self.act_dim
-            for l, (w, b) in enumerate(net):
-                if w.ndim != 2 or b.shape != (w.shape[0],) or w.shape[1] != inp:
-                    raise ValueError(f"{who}, layer {l}: expected W [out, {inp}] and b [out], got {w.shape} and {b.shape}")
-                inp = w.shape[0]
-            P = p.actor if n == 0 else p.critic[n - 1]
-            P.n_layers = len(net)  # (more than the ABI's 4: refused by the library, with its reason)
-            for l, (w, _) in enumerate(net[:_capi.POLICY_MAX_LAYERS]):
-                P.width[l] = w.shape[0]
-            P.activation = _ACTIVATIONS[activation]
-            P.output = _OUTPUTS[output] if n == 0 else _capi.POLICY_OUT_NONE
-            P.lo, P.hi = (float(low), float(high)) if n == 0 else (0.0, 0.0)
-        self.activation, self.output = activation, output
-        self._shapes = [(w.shape, b.shape) for net in nets for w, b in net]
-        packed = self._pack(nets)
-        self.lib = _capi.load_library()
-        self.device = int(device)
-        h = C.c_void_p()
-        rc = self.lib.fleet_qtarget_create(self.device, C.byref(p), packed.ctypes.data, C.byref(h))
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_qtarget_last_error(None).decode())
-        self.h = h
-        self._stream = None
-        self._constants = {}  # _per_action's device tensors of float arguments
-        self.tile_rows = self.describe()["tile_rows"]
-
-    @staticmethod
-    def _pack(nets) -> np.ndarray:
-        return np.ascontiguousarray(np.concatenate([a.ravel() for net in nets for w, b in net for a in (w, b)]), dtype=np.float32)
+        self._fill_head(p.actor, "actor", nets[0], self.obs_dim, output, low, high)
+        for c, net in enumerate(nets[1:]):
+            self._fill_head(p.critic[c], f"critic {c}", net, self.obs_dim + self.act_dim)
+        self._create(device, p, nets)
 
     # ---- constructors from SB3's files ---------------------------------------------------------------------------------------
     @classmethod
@@ -111,20 +78,6 @@ class DeviceTD3Target(_DeviceHandle):
         return cls.from_state_dict(read_sb3_state_dict(path), activation, output, low=low, high=high, device=device)
 
     # ---- weights -------------------------------------------------------------------------------------------------------------
-    def _pointers(self, what: str, parameters):
-        import torch
-
-        self.use_torch_stream()
-        params = [p.detach() for p in parameters]
-        flat = [s for pair in self._shapes for s in pair]
-        if len(params) != len(flat):
-            raise ValueError(f"{what}: expected {len(flat)} tensors (W, b per layer: the actor's, then each critic's), got {len(params)}")
-        tensors = [self._tensor(t, s, (torch.float32,)) for t, s in zip(params, flat)]
-        for t, s in zip(tensors, flat):
-            if tuple(t.shape) != tuple(s):
-                raise ValueError(f"{what}: expected a tensor of shape {tuple(s)}, got {tuple(t.shape)}")
-        return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors]), tensors
-
     def load_torch(self, parameters):
         """A hard update: the targets become copies of torch's parameter tensors on the handle's device (W, b per layer: the
         actor's, then each critic's), re-laid by one launch on torch's current stream, no host synchronisation."""
@@ -194,11 +147,5 @@ class DeviceTD3Target(_DeviceHandle):
         """What fleet_qtarget_describe reports: the shapes of the networks and `tile_rows`, the rows one workgroup takes."""
         p = _capi.FleetQTargetParams()
         self._check(self.lib.fleet_qtarget_describe(self.h, C.byref(p)))
-        names = {v: k for k, v in _ACTIVATIONS.items()}, {v: k for k, v in _OUTPUTS.items()}
-
-        def head(H):
-            return {"widths": list(H.width[:H.n_layers]), "activation": names[0][H.activation], "output": names[1][H.output],
-                    "low": H.lo, "high": H.hi}
-
         return {"obs_dim": p.obs_dim, "act_dim": self.act_dim, "n_critics": p.n_critics, "tile_rows": p.tile_rows,
-                "actor": head(p.actor), "critics": [head(p.critic[c]) for c in range(p.n_critics)]}
+                "actor": self._head_dict(p.actor), "critics": [self._head_dict(p.critic[c]) for c in range(p.n_critics)]}

@@ -100,10 +100,11 @@ def _both_heads(pol, x):
     return host(pol.act(x, values_out=values)), host(values)
 
 
-@pytest.mark.parametrize("name", pb.PAIRS[:2])
+@pytest.mark.parametrize("name", pb.PAIRS)
 def test_load_torch_relays_ragged_layers_into_the_padded_image(name):
-    """in4 and out64 padding at their least mild: 389 inputs, widths 50, 400, 300, 1, 3.  Weights B are the case's own (salt 0),
-    the policy is created with others (salt 1) and, for the double load, goes through a third set (salt 2) first."""
+    """in4 and out64 padding at their least mild: 389 inputs, widths 50, 400, 300, 1, 3.  Every pair, because the launch finds a
+    tensor's net by walking the nets' depths: 3 + 3, 3 + 1, a one-layer head in front of a four-layer one, 2 + 2.  Weights B are the
+    case's own (salt 0), the policy is created with others (salt 1) and, for the double load, goes through a third set (salt 2) first."""
     loaded, twice, fresh = make_policy(name, salt=1), make_policy(name, salt=1), make_policy(name)
     loaded.load_torch(_parameters(name, 0))
     twice.load_torch(_parameters(name, 2))

@@ -6,7 +6,8 @@ HIP events on torch's stream, medians of --reps, the arms interleaved in one pro
 Yardsticks: the same network in torch ops on the same device (nn.Linear chain plus the clip / tanh; with normalisation, the
 float64 expression in front of it), eager and replayed from a `torch.cuda.graph` capture, and ONE device-to-device copy of the
 bytes the forward reads and writes (observations in, actions out, the weights once).  The torch result is compared with the
-kernel's first (max abs difference, reported).  No number is gated.
+kernel's first (max abs difference, reported).  For the two 388-column networks one more arm, `load_torch`: the re-lay launch that
+copies torch's parameter tensors into the policy's image (what a training loop pays after every optimiser step).  No number is gated.
 
     python tools/policy_rate.py [--reps 9] [--write]
 """
@@ -22,6 +23,7 @@ sys.path.insert(0, ROOT)
 E = 4096
 NETWORKS = {"388-64-64-50-tanh": ((388, 64, 64, 50), "tanh", "clip"), "388-400-300-50-relu": ((388, 400, 300, 50), "relu", "tanh"),
             "45-64-64-1-tanh": ((45, 64, 64, 1), "tanh", "clip")}
+LOAD_TORCH = ("388-64-64-50-tanh", "388-400-300-50-relu")
 
 
 def event_us(torch, fn, reps, inner):
@@ -106,6 +108,9 @@ def measure(torch, name, reps):
         arms = {"kernel": lambda: pol.forward_dev(optr, E, None, aptr), "kernel_fused_norm": lambda: pol.forward_dev(rptr, E, norm, aptr),
                 "torch_eager": eager, "torch_eager_norm": eager_norm, "torch_graph": graphs["graph"].replay,
                 "torch_graph_norm": graphs["graph_norm"].replay, "copy": lambda: dst.copy_(src)}
+        if name in LOAD_TORCH:
+            params = [torch.from_numpy(a).to(dev) for w, b in layers for a in (w, b)]
+            arms["load_torch"] = lambda: pol.load_torch(params)
         for fn in arms.values():
             for _ in range(10):
                 fn()
