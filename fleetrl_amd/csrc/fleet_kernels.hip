@@ -75,10 +75,14 @@ __device__ __forceinline__ void ev_finish(const FleetDev& d, const EvIx& i, int 
                                           int tail, int sgn, double soc, double soc_deg, double old_deg, float hl, uint32_t there1,
                                           bool t090, bool inplane, bool crosses, const SegRec& nr, double soh0, double a, double en, bool logs,
                                           size_t lrow, const Hot& h_in, uint32_t& err, double& sei_sample, double& sei_soh, int& sei_tail,
-                                          RfTop& sei_top, bool& sei_have_top, RfAccHead& acc_c, RfTop& top_c, bool carry) {
+                                          RfTop& sei_top, bool& sei_have_top, RfAccHead& acc_c, RfTop& top_c, bool carry,
+                                          bool own_b = false) {
   double soh = soh0;
   RfTop top = top_c;
-  if (DEG == FLEET_DEG_RAINFLOW && env_ok) rf_finish(d, i, rq, tail, top, acc_c, err);
+  if (DEG == FLEET_DEG_RAINFLOW && env_ok) {
+    if (own_b) rf_finish_own_b(d, i, rq, tail, top, acc_c, err);  // (one step per launch, one EV per lane: see rf_finish_as)
+    else rf_finish(d, i, rq, tail, top, acc_c, err);
+  }
   const bool pushed = rq.push;
   if (carry && pushed) top_c = top;
   if (DEG == FLEET_DEG_LINEAR && deg_row) soh = soh - linear_degradation(d, old_deg, soc_deg, dt_step);
@@ -366,9 +370,12 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   // before its last packet has retired, and every launch writes the same observation rows: what any launch but the last stores
   // there is overwritten before anybody can read it.  Those launches carry `outputs_dead` != 0 -- a kernel argument, the same for
   // every wavefront, fetched with the arguments the entry reads anyway -- and skip what feeds only the row: write_obs_ev with the
-  // arithmetic of its auxiliary slots, the request for the tail row and its store, the terminal row.  State, reward, done flag,
-  // reset (with the row it writes) and the placement guard are as ever.  Launches through HIP always carry 0; the K-step instances
-  // (the data log among them) decide per step themselves and do not look.
+  // arithmetic of its auxiliary slots, the request for the tail row and its store, the terminal row.  With one EV per lane (`kEarly`)
+  // such a launch does state work only: it stores neither `reward[e]` nor `done[e]` nor EnvRec::cashflow -- every step overwrites all
+  // three, and only the last launch's values can be read --, feeds the cashflow fold a zero, and its auto-reset writes no start row
+  // (the run's last launch writes every env's row).  State -- the EV records, rainflow and SEI, head, ep_return, penalty_record,
+  // ep_len, the episode-end records --, the error bits and the placement guard are as ever.  Launches through HIP always carry 0;
+  // the K-step instances (the data log among them) decide per step themselves and do not look.
   const bool obs_live = MULTI || outputs_dead == 0;
   const int vzero = (int)__builtin_amdgcn_mbcnt_lo(0u, 0u);  // 0 in every lane, opaque to the uniformity analysis
   // night-charging policy: the env's "charging since" row travels in a register over the K steps
@@ -497,6 +504,9 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
     // Several EVs per lane, one step per launch (N > 64): the lane's NEXT EV's records are requested before the current EV is
     // worked on (software pipelining of the lane loop) -- otherwise every turn of the loop starts with a memory round trip
     constexpr bool kPipe = WIDE && !MULTI;
+    // a launch whose outputs nobody can read does state work only ("Dead outputs" above; `if constexpr`, so that the other instances
+    // compile to what they always did)
+    constexpr bool kStateOnly = kEarly;
     Hot hb_n = {0.0, 0.0f, 0u};
     SegRec rr_n = {0.0, 0u, 0u};
     double soh_n = 0.0, act_n = 0.0;
@@ -601,7 +611,11 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       // the env head arrived and has had the charge arithmetic, the state machine and the observation stores to get here
       {
         const double grid_e = fmax(en - ph.pv_share, 0.0);  // :142 (charging only)
-        cash += pos ? -(grid_e * ph.k_cost) : en * ph.k_rev;       // -charging_cost :149 / +discharging_revenue :196-199
+        if constexpr (kStateOnly) {
+          if (obs_live) cash += pos ? -(grid_e * ph.k_cost) : en * ph.k_rev;  // dead: a zero goes into the fold, same shape
+        } else {
+          cash += pos ? -(grid_e * ph.k_cost) : en * ph.k_rev;       // -charging_cost :149 / +discharging_revenue :196-199
+        }
         rew += pos ? ph.k_charge * grid_e : ph.k_discharge * en;   // :154-156 / :204-206
       }
 
@@ -610,7 +624,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       if (!kSplitRf && DEG == FLEET_DEG_RAINFLOW && env_ok && rf_live) rf_begin(d, i, old_deg, soc_deg, tail, sgn, rq, kRfEarly);
       ev_finish<DEG, WIDE>(d, i, c, N, env_ok, deg_row, dt_step, rq, tail, sgn, soc, soc_deg, old_deg, hl, tb1.there, t090, inplane,
                            crosses, nr, soh0, a, en, logs, lrow, hb, err, sei_sample, sei_soh, sei_tail, sei_top, sei_have_top, acc_c,
-                           top_c, kRfCarry);
+                           top_c, kRfCarry, kEarly);
       if (!WIDE) break;  // N <= G: a single pass, and no loop for the compiler to hoist rare-path constants out of
     }
     {  // ---- the rest of the step reads the argument block afresh (see `late_args`) ----
@@ -686,7 +700,13 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       ep_len += 1;
       reward_sum += rew;
       last_rew = rew;
-      if (env_ok) {
+      if constexpr (kStateOnly) {
+        if (env_ok && obs_live) {  // (a dead launch's three values are overwritten unseen)
+          d.env[e].cashflow = cash;
+          reward[e] = rew;
+          done[e] = done_now ? 1 : 0;
+        }
+      } else if (env_ok) {
         d.env[e].cashflow = cash;  // cashflow = -charging_cost + discharging_revenue (ev_charger.py:225)
         if (!MULTI) {
           reward[e] = rew;
@@ -740,7 +760,8 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       if (resets) {
         head_reset = true;
         if (env_ok) {
-          reset_env<G, LOG>(*d.self, e, g, leader, r, obs_row, lp, rf_until);
+          if constexpr (kStateOnly) reset_env<G, LOG>(*d.self, e, g, leader, r, obs_live ? obs_row : nullptr, lp, rf_until);
+          else reset_env<G, LOG>(*d.self, e, g, leader, r, obs_row, lp, rf_until);
           if (kRfCarry) carry_load();  // the reset rewrote the row's head (same lane, same addresses: program order holds)
         } else {  // surplus group: keep its registers moving without touching memory
           r.t = choose_start(d.cold, d.E, e, r.episodes);

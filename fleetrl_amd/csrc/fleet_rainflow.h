@@ -136,7 +136,11 @@ __device__ __forceinline__ void rf_begin(const FleetDev& d, const EvIx& i, doubl
 // of the same push (the new top against what lies below: rare) enters a loop that reads stack words.  The general loop of rounds
 // 2-4 walked every push through its loop control and the first-point test: 8.3 -> 7.9 us per 4096x50 launch for the same
 // algorithm (profiles/r05_experiments/ab7_rf_finish_peeled.log).
-__device__ __forceinline__ void rf_finish(const FleetDev& d, const EvIx& i, const RfReq& q, int& tail, RfTop& top, RfAccHead& acc_out,
+// `OWN_B` (one step per launch, one EV per lane, where the request is issued well before this runs): `b` gets a register of its own
+// -- see where it is used.  Nothing checks the compiled code for this (the scheduling depends on the register coalescer): after a
+// compiler update, look at the block that issues rf_request's loads in `G64.rainflow.single.f32` (EXPERIMENTS.md has the excerpt).
+template <bool OWN_B>
+__device__ __forceinline__ void rf_finish_as(const FleetDev& d, const EvIx& i, const RfReq& q, int& tail, RfTop& top, RfAccHead& acc_out,
                                           uint32_t& err) {
   if (!q.push) return;
   double* row = rf_row_of(d, i);
@@ -161,6 +165,10 @@ __device__ __forceinline__ void rf_finish(const FleetDev& d, const EvIx& i, cons
   double mean_sum = q.acc.mean_sum, dcsum = 0.0;
   bool has_csum = false;
   double a = a0, b = b0;
+  // (a value of its own: otherwise `b`, which the closures below rewrite, shares its register with the requested word `b0`, and the
+  // copy that separates the two is a phi copy: it lands at the end of the block that issued the request, behind a wait for the row
+  // -- in every wavefront, right after the loads)
+  if (OWN_B) asm volatile("" : "+v"(b));
   int t = size;
   if (closes) {
     if (nc >= L - 1) {  // only the closed cycles beyond the last evaluation's count carry stress: none in the steady state
@@ -208,6 +216,16 @@ __device__ __forceinline__ void rf_finish(const FleetDev& d, const EvIx& i, cons
     st_plain(reinterpret_cast<RfAccHead*>(row), out);
     if (has_csum) reinterpret_cast<RfHdr*>(row)->csum += dcsum;
   }
+}
+// (two plain functions in front of the one body: with callers instantiating the template themselves, or with a run-time flag, instances
+// that never push -- other degradation modes, K-step -- came out with another register allocation; EXPERIMENTS.md "What perturbs ...")
+__device__ __forceinline__ void rf_finish(const FleetDev& d, const EvIx& i, const RfReq& q, int& tail, RfTop& top, RfAccHead& acc_out,
+                                          uint32_t& err) {
+  rf_finish_as<false>(d, i, q, tail, top, acc_out, err);
+}
+__device__ __forceinline__ void rf_finish_own_b(const FleetDev& d, const EvIx& i, const RfReq& q, int& tail, RfTop& top, RfAccHead& acc_out,
+                                                uint32_t& err) {
+  rf_finish_as<true>(d, i, q, tail, top, acc_out, err);
 }
 // RainflowSeiDegradation.calculate_degradation for one EV on the daily row (rainflow_sei_degradation.py:91-212).
 // `v` = the sample just logged (forced last reversal), `n` = number of logged samples.  The forced point and the
