@@ -7,6 +7,7 @@
     from fleetrl_amd import DevicePolicy, evaluate_policy
     from fleetrl_amd import DevicePinkNoise, DeviceOUNoise
     from fleetrl_amd import DeviceTD3Target
+    from fleetrl_amd import DevicePPOGrad
 """
 __version__ = "0.1.0"
 
@@ -44,6 +45,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import qtarget
 
         return qtarget.DeviceTD3Target
+    if name == "DevicePPOGrad":
+        from . import ppo
+
+        return ppo.DevicePPOGrad
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

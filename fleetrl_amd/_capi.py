@@ -198,6 +198,18 @@ class FleetQTargetArgs(C.Structure):
                 ("next_actions", C.c_void_p), ("q", C.c_void_p)]
 
 
+# ---- PPO minibatch gradients (include/fleet_hip.h "PPO minibatch gradients on the device", fleet_ppo_*) ------------------------------
+class FleetPpoParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("max_batch", C.c_int32)]
+
+
+class FleetPpoGradArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("B", C.c_int32), ("obs", C.c_void_p), ("actions", C.c_void_p), ("old_log_prob", C.c_void_p),
+                ("advantages", C.c_void_p), ("returns", C.c_void_p), ("log_std", C.c_void_p), ("clip_range", C.c_float),
+                ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("reserved", C.c_int32), ("values", C.c_void_p), ("log_prob", C.c_void_p),
+                ("stats", C.c_void_p)]
+
+
 # ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
 STATE_MAGIC = 0x4554415453544C46
 STATE_ALIGN = 256
@@ -465,8 +477,14 @@ def load_library():
     lib.fleet_qtarget_export_dev.argtypes = [vp, C.POINTER(vp), C.c_int]
     lib.fleet_qtarget_target_dev.argtypes = [vp, f32p, f32p, f32p, C.c_int, C.POINTER(FleetQTargetArgs)]
     lib.fleet_qtarget_describe.argtypes = [vp, C.POINTER(FleetQTargetParams)]
+    # PPO's minibatch gradients (fleet_ppo.hip)
+    lib.fleet_ppo_create.argtypes = [vp, C.POINTER(FleetPpoParams), C.POINTER(vp)]
+    lib.fleet_ppo_destroy.argtypes = [vp]
+    lib.fleet_ppo_last_error.argtypes = [vp]
+    lib.fleet_ppo_describe.argtypes = [vp, C.POINTER(FleetPpoParams), C.POINTER(C.c_uint64), i32p]
+    lib.fleet_ppo_grad_dev.argtypes = [vp, C.POINTER(FleetPpoGradArgs), C.POINTER(vp), C.c_int]
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
-                          ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS)):
+                          ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS), ("ppo", PPO_SYMBOLS)):
         for name in names:
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
@@ -523,6 +541,8 @@ QTARGET_SYMBOLS = (
     "fleet_qtarget_load_dev", "fleet_qtarget_polyak_dev", "fleet_qtarget_export_dev", "fleet_qtarget_target_dev", "fleet_qtarget_describe",
 )
 
+PPO_SYMBOLS = ("fleet_ppo_create", "fleet_ppo_destroy", "fleet_ppo_last_error", "fleet_ppo_describe", "fleet_ppo_grad_dev")
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -535,7 +555,7 @@ EXPORTED_SYMBOLS = (
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

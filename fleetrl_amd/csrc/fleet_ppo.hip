@@ -1,0 +1,529 @@
+// fleet_ppo.hip -- the gradients of PPO's minibatch loss on the device (include/fleet_hip.h "PPO minibatch gradients on the device"):
+// what stable-baselines3's PPO.train computes per minibatch with evaluate_actions, the clipped loss and loss.backward(), in two
+// launches on the policy's stream.  The handle borrows the weight image of a two-head policy (fleet_mlp.h) and owns a scratch.
+//   ppo_rows   grid (ceil(B / 16), 2), 256 threads: the policy's tile.  A workgroup takes 16 rows through one head with the chain of
+//              fleet_policy_dev.h (stage, accumulate, hidden_act as they are); its layer function also stores every hidden
+//              activation to the scratch.  The last layer leaves its rows untransformed in the LDS.  Head 0's epilogue forms the
+//              log-probability terms with sample_epilogue's expression and sums them in its order, then the row's ratio, clip and
+//              d loss / d log-probability; head 1's forms d loss / d value.  The SAME workgroup then walks back through its layers:
+//              a thread owns input column k of all 16 rows, d_prev[r][k] = (fmaf chain over j ascending of Wt[k][j] * d[r][j]) *
+//              act'(h[r][k]); every layer's delta goes to the scratch.  Thread 0 writes the tile's partial sums of the statistics.
+//              LDS: two buffers [16][T], T the widest layer of both heads (out64), the staged chunk [16][128], 64 row scalars.
+//   ppo_weights  one grid over 32 x 32 tiles of every weight gradient, then the log_std gradient's blocks, then one workgroup for the
+//              statistics.  A thread owns 2 x 2 elements of dW; each is ONE chain over the rows in ascending b, acc = fmaf(d[b][j],
+//              x[b][k], acc), with 16 rows at a time staged in the LDS (d and the activations from the scratch, obs for a first
+//              layer); db[j] is the ascending sum of d[b][j], kept by the threads of the first k tile.  Stored with torch's index.
+// The scratch, for a capacity of max_batch rows (floats; every array's row stride is its layer's out64):
+//   per head and layer: act [max_batch][out64] (hidden layers), delta [max_batch][out64] (every layer);
+//   ls [max_batch][A64]: the rows' log_std terms;  part [ceil(max_batch / 16)][8]: the tiles' partial sums.
+// Rows at and past B are never read or written.  No atomics, no ordering between workgroups: launch boundaries only.  float32.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+
+#include "fleet_mlp.h"
+#include "fleet_policy.h"
+#include "fleet_policy_dev.h"
+
+namespace {
+
+constexpr int kGradTile = 32;   // ppo_weights: a workgroup's tile of dW is 32 x 32
+constexpr int kGradRows = 16;   // ... and it stages this many rows at a time
+constexpr int kPartStride = 8;  // floats per tile in part[][]: policy term, squared value error, kl term, clipped rows
+
+struct PpoScratch {  // offsets in floats from the scratch's start
+  uint64_t act[FLEET_POLICY_MAX_HEADS][FLEET_POLICY_MAX_LAYERS];
+  uint64_t delta[FLEET_POLICY_MAX_HEADS][FLEET_POLICY_MAX_LAYERS];
+  uint64_t ls, part, floats;
+};
+
+// the statistics' sums are compensated (Neumaier): s + c is the sum of the terms so far to within a rounding of the result
+struct CompSum {
+  float s = 0.0f, c = 0.0f;
+  __device__ __forceinline__ void add(float x) {
+    const float t = s + x;
+    c += fabsf(s) >= fabsf(x) ? (s - t) + x : (x - t) + s;
+    s = t;
+  }
+  __device__ __forceinline__ float value() const { return s + c; }
+};
+
+struct RowsArgs {
+  const PolicyDesc* desc;
+  const float* base;
+  const float *obs, *actions, *old_lp, *adv, *ret, *log_std;
+  float *values, *log_prob;
+  float* scratch;
+  PpoScratch s;
+  int B, T;
+  float clip, vf_coef, invB;
+};
+
+// run_layer of fleet_policy_dev.h with two changes: a hidden layer's activations also go to gact[row][out64] (rows below B), and a
+// last layer leaves y, untransformed, in out[][] (every row and column of the tile)
+template <int R>
+__device__ __forceinline__ void ppo_layer(const ForwardArgs& a, const PolicyHeadDesc* H, const PolicyLayer& L, bool first, bool last,
+                                          const float* in, float* out, float* xs, int S, int row0, float* gact) {
+  constexpr int kSplit = kPolicyRows / R;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int units = (L.out64 / 64) * kSplit;
+  const bool has0 = w < units, has1 = w + kPolicyWaves < units;
+  const int q = w % kSplit;
+  const int j0 = (w / kSplit) * 64 + lane, j1 = ((w + kPolicyWaves) / kSplit) * 64 + lane;
+  float acc0[R], acc1[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc0[r] = acc1[r] = 0.0f;
+  const float* W = a.base + L.w_off;
+  if (first) {
+    for (int k0 = 0; k0 < L.in; k0 += kPolicyChunk) {
+      const int kn = L.in4 - k0 < kPolicyChunk ? L.in4 - k0 : kPolicyChunk;
+      __syncthreads();
+      stage<kStagePlain>(a, xs, row0, k0, L.in, StageTail{});
+      __syncthreads();
+      const float* x = xs + q * R * kPolicyChunk;
+      const float* wk = W + (size_t)k0 * L.out64;
+      if (has1) accumulate<R, true>(x, kPolicyChunk, kn, wk, L.out64, j0, j1, acc0, acc1);
+      else if (has0) accumulate<R, false>(x, kPolicyChunk, kn, wk, L.out64, j0, j1, acc0, acc1);
+    }
+  } else if (has1) {
+    accumulate<R, true>(in + q * R * S, S, L.in4, W, L.out64, j0, j1, acc0, acc1);
+  } else if (has0) {
+    accumulate<R, false>(in + q * R * S, S, L.in4, W, L.out64, j0, j1, acc0, acc1);
+  }
+  const int activation = H->activation;
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    if (!(u ? has1 : has0)) continue;
+    const int j = u ? j1 : j0;
+    const float b = a.base[L.b_off + j];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const float y = (u ? acc1[r] : acc0[r]) + b;
+      const int rr = q * R + r;
+      if (last) {
+        out[rr * S + j] = y;
+      } else {
+        const float hval = hidden_act(y, activation);
+        out[rr * S + j] = hval;
+        if (row0 + rr < a.E) gact[(size_t)(row0 + rr) * L.out64 + j] = hval;  // (j < out64: inside the row)
+      }
+    }
+  }
+}
+
+// delta of layer l, d[16][S] in the LDS (zero past `out`) -> delta of layer l - 1 into p[16][S] (zero from `in` to the previous
+// layer's out64) and into gdelta[row][out64 of layer l - 1]; hprev: that layer's activations in the scratch
+__device__ __forceinline__ void ppo_back_layer(const float* base, const PolicyLayer& L, int prev64, int activation, const float* d, float* p,
+                                               int S, int row0, int B, const float* hprev, float* gdelta) {
+  const float* W = base + L.w_off;
+  const int out4 = (L.out + 3) & ~3;  // (<= out64; the columns out .. out4 - 1 of Wt and of d are zero: they add +0)
+  for (int k = threadIdx.x; k < prev64; k += kPolicyThreads) {
+    float acc[kPolicyRows];
+#pragma unroll
+    for (int r = 0; r < kPolicyRows; ++r) acc[r] = 0.0f;
+    if (k < L.in) {
+      const float* wk = W + (size_t)k * L.out64;
+      for (int j = 0; j < out4; j += 4) {
+        const float4 w4 = *reinterpret_cast<const float4*>(wk + j);  // (out64 is a multiple of 64: aligned)
+#pragma unroll
+        for (int r = 0; r < kPolicyRows; ++r) {
+          const float4 d4 = *reinterpret_cast<const float4*>(d + r * S + j);
+          acc[r] = fmaf(w4.w, d4.w, fmaf(w4.z, d4.z, fmaf(w4.y, d4.y, fmaf(w4.x, d4.x, acc[r]))));
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kPolicyRows; ++r) {
+      const int row = row0 + r;
+      float v = 0.0f;
+      if (k < L.in && row < B) {
+        const float hv = hprev[(size_t)row * prev64 + k];
+        const float g = activation == FLEET_POLICY_ACT_RELU ? (hv > 0.0f ? 1.0f : 0.0f) : fmaf(-hv, hv, 1.0f);
+        v = acc[r] * g;
+        gdelta[(size_t)row * prev64 + k] = v;
+      }
+      p[r * S + k] = v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kPolicyThreads) void ppo_rows(RowsArgs t) {
+  extern __shared__ float lds[];  // two buffers [16][T], the staged input [16][kPolicyChunk], the rows' scalars [4][16]
+  const PolicyDesc* __restrict__ d = t.desc;
+  const int head = blockIdx.y;
+  const PolicyHeadDesc* __restrict__ H = &d->head[head];
+  const int S = t.T, B = t.B;
+  float *cur = lds, *nxt = lds + kPolicyRows * S, *xs = lds + 2 * kPolicyRows * S;
+  float* rowv = xs + kPolicyRows * kPolicyChunk;  // [0][r]: glp or dv; [1..3][r]: the row's terms of the statistics
+  const int row0 = blockIdx.x * kPolicyRows;
+  const int n = H->n_layers;
+  ForwardArgs a{};
+  a.base = t.base, a.obs = t.obs, a.E = B;
+  // ---- forward ----
+  for (int l = 0; l < n; ++l) {
+    const PolicyLayer L = H->layer[l];
+    const int groups = L.out64 / 64;
+    float* gact = t.scratch + t.s.act[head][l];
+    if (groups >= 4) ppo_layer<16>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gact);
+    else if (groups >= 2) ppo_layer<8>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gact);
+    else ppo_layer<4>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gact);
+    __syncthreads();
+    float* tmp = cur;
+    cur = nxt;
+    nxt = tmp;
+  }
+  // cur: y[16][S] of the last layer; nxt is free
+  const PolicyLayer LL = H->layer[n - 1];
+  float* gdl = t.scratch + t.s.delta[head][n - 1];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (head == 0) {
+    const int A = LL.out, M = LL.out64;
+    // the log-probability terms, sample_epilogue's expression on the stored action -> nxt
+    for (int item = threadIdx.x; item < kPolicyRows * A; item += kPolicyThreads) {
+      const int r = item / A, j = item - r * A;
+      const int row = row0 + r;
+      if (row >= B) continue;
+      const float sc = t.log_std[j], m = cur[r * S + j];
+      const float sd = expf(sc);
+      const float dm = t.actions[(size_t)row * A + j] - m;
+      nxt[r * S + j] = -(dm * dm) / (2.0f * sd * sd) - sc - 0.9189385332f;
+    }
+    __syncthreads();
+    // a wavefront sums 4 rows: every lane its columns lane, lane + 64, ... in ascending order, then a butterfly over the 64 lanes
+    for (int r = w * (kPolicyRows / kPolicyWaves); r < (w + 1) * (kPolicyRows / kPolicyWaves); ++r) {
+      const int row = row0 + r;
+      float sum = 0.0f;
+      if (row < B)  // (uniform over the wavefront)
+        for (int j = lane; j < A; j += 64) sum += nxt[r * S + j];
+#pragma unroll
+      for (int dd = 1; dd < 64; dd <<= 1) sum += __shfl_xor(sum, dd, 64);
+      float glp = 0.0f, pterm = 0.0f, kl = 0.0f, cf = 0.0f;
+      if (lane == 0 && row < B) {
+        const float lp = sum, adv = t.adv[row];
+        if (t.log_prob) t.log_prob[row] = lp;
+        const float lr = lp - t.old_lp[row];
+        const float ratio = expf(lr);
+        const float lo = 1.0f - t.clip, hi = 1.0f + t.clip;
+        const float cl = ratio < lo ? lo : (ratio > hi ? hi : ratio);
+        const float s1 = adv * ratio, s2 = adv * cl;
+        pterm = -(s1 < s2 ? s1 : s2);
+        const bool alive = (ratio >= lo && ratio <= hi) || s1 < s2;
+        glp = alive ? -(adv * ratio) * t.invB : 0.0f;
+        kl = (ratio - 1.0f) - lr;
+        cf = fabsf(ratio - 1.0f) > t.clip ? 1.0f : 0.0f;
+      }
+      if (lane == 0) rowv[r] = glp, rowv[16 + r] = pterm, rowv[32 + r] = kl, rowv[48 + r] = cf;
+    }
+    __syncthreads();
+    // the last layer's delta in place of y (zero past A and in the rows past B), and the rows' log_std terms
+    float* gls = t.scratch + t.s.ls;
+    for (int item = threadIdx.x; item < kPolicyRows * M; item += kPolicyThreads) {
+      const int r = item / M, j = item - r * M;
+      const int row = row0 + r;
+      float dmean = 0.0f;
+      if (row < B && j < A) {
+        const float sc = t.log_std[j], glp = rowv[r];
+        const float sd = expf(sc);
+        const float dm = t.actions[(size_t)row * A + j] - cur[r * S + j];
+        dmean = glp * (dm / (sd * sd));
+        gdl[(size_t)row * M + j] = dmean;
+        gls[(size_t)row * M + j] = glp * ((dm * dm) / (sd * sd) - 1.0f);
+      }
+      cur[r * S + j] = dmean;
+    }
+    if (threadIdx.x == 0) {
+      CompSum p, k, c;
+      for (int r = 0; r < kPolicyRows && row0 + r < B; ++r) p.add(rowv[16 + r]), k.add(rowv[32 + r]), c.add(rowv[48 + r]);
+      float* part = t.scratch + t.s.part + (size_t)blockIdx.x * kPartStride;
+      part[0] = p.value(), part[2] = k.value(), part[3] = c.value();
+    }
+  } else {
+    if (threadIdx.x < kPolicyRows) {
+      const int r = threadIdx.x, row = row0 + r;
+      float dv = 0.0f, sq = 0.0f;
+      if (row < B) {
+        const float v = cur[r * S], ret = t.ret[row];
+        if (t.values) t.values[row] = v;
+        dv = ((2.0f * t.vf_coef) * t.invB) * (v - ret);
+        const float e = ret - v;
+        sq = e * e;
+        gdl[(size_t)row * LL.out64] = dv;
+      }
+      rowv[r] = dv, rowv[16 + r] = sq;
+    }
+    __syncthreads();
+    for (int item = threadIdx.x; item < kPolicyRows * 64; item += kPolicyThreads) {  // (the critic's last out64 is 64)
+      const int r = item >> 6, j = item & 63;
+      cur[r * S + j] = j == 0 ? rowv[r] : 0.0f;
+    }
+    if (threadIdx.x == 0) {
+      CompSum q;
+      for (int r = 0; r < kPolicyRows && row0 + r < B; ++r) q.add(rowv[16 + r]);
+      t.scratch[t.s.part + (size_t)blockIdx.x * kPartStride + 1] = q.value();
+    }
+  }
+  __syncthreads();
+  // ---- backward: layer l's delta in cur -> layer l - 1's in nxt ----
+  for (int l = n - 1; l >= 1; --l) {
+    const PolicyLayer L = H->layer[l];
+    const int prev64 = H->layer[l - 1].out64;
+    ppo_back_layer(t.base, L, prev64, H->activation, cur, nxt, S, row0, B, t.scratch + t.s.act[head][l - 1], t.scratch + t.s.delta[head][l - 1]);
+    __syncthreads();
+    float* tmp = cur;
+    cur = nxt;
+    nxt = tmp;
+  }
+}
+
+// ---- ppo_weights ---------------------------------------------------------------------------------------------------------------------
+struct GradEntry {  // one layer: dW[out][in] and db[out] from delta[B][dstride] and the layer's input x[B][xstride]
+  const float *d, *x;
+  float *dW, *db;
+  int out, in, dstride, xstride, tiles_k, first;  // first: the layer's first workgroup
+};
+constexpr int kMaxEntries = FLEET_POLICY_MAX_HEADS * FLEET_POLICY_MAX_LAYERS;
+
+struct WeightArgs {
+  GradEntry e[kMaxEntries];
+  int n_entries, tile_blocks, ls_blocks, B;
+  const float *ls, *part, *log_std;
+  float *dlog_std, *stats;
+  int A, M, n_tiles;
+  float invB, vf_coef, ent_coef;
+};
+
+__global__ __launch_bounds__(256) void ppo_weights(WeightArgs a) {
+  __shared__ float ds[kGradRows][kGradTile], xs[kGradRows][kGradTile];
+  const int bid = blockIdx.x, B = a.B;
+  if (bid < a.tile_blocks) {
+    int ei = 0;
+    while (ei + 1 < a.n_entries && bid >= a.e[ei + 1].first) ++ei;
+    const GradEntry& E = a.e[ei];
+    const int tile = bid - E.first;
+    const int j0 = (tile / E.tiles_k) * kGradTile, k0 = (tile % E.tiles_k) * kGradTile;
+    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
+    float a00 = 0.0f, a01 = 0.0f, a10 = 0.0f, a11 = 0.0f, bs0 = 0.0f, bs1 = 0.0f;
+    for (int b0 = 0; b0 < B; b0 += kGradRows) {
+      const int nb = B - b0 < kGradRows ? B - b0 : kGradRows;
+      __syncthreads();  // the readers of the rows before are done
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int idx = threadIdx.x + 256 * i;
+        const int r = idx >> 5, c = idx & 31;
+        float dv = 0.0f, xv = 0.0f;
+        if (r < nb) {
+          if (j0 + c < E.out) dv = E.d[(size_t)(b0 + r) * E.dstride + j0 + c];
+          if (k0 + c < E.in) xv = E.x[(size_t)(b0 + r) * E.xstride + k0 + c];
+        }
+        ds[r][c] = dv, xs[r][c] = xv;
+      }
+      __syncthreads();
+      for (int r = 0; r < nb; ++r) {
+        const float d0 = ds[r][ty], d1 = ds[r][ty + 16], x0 = xs[r][tx], x1 = xs[r][tx + 16];
+        a00 = fmaf(d0, x0, a00), a01 = fmaf(d0, x1, a01), a10 = fmaf(d1, x0, a10), a11 = fmaf(d1, x1, a11);
+        bs0 += d0, bs1 += d1;
+      }
+    }
+    const int ja = j0 + ty, jb = j0 + ty + 16, ka = k0 + tx, kb = k0 + tx + 16;
+    if (ja < E.out) {
+      if (ka < E.in) E.dW[(size_t)ja * E.in + ka] = a00;
+      if (kb < E.in) E.dW[(size_t)ja * E.in + kb] = a01;
+      if (k0 == 0 && tx == 0) E.db[ja] = bs0;
+    }
+    if (jb < E.out) {
+      if (ka < E.in) E.dW[(size_t)jb * E.in + ka] = a10;
+      if (kb < E.in) E.dW[(size_t)jb * E.in + kb] = a11;
+      if (k0 == 0 && tx == 0) E.db[jb] = bs1;
+    }
+  } else if (bid < a.tile_blocks + a.ls_blocks) {
+    const int j = (bid - a.tile_blocks) * 256 + (int)threadIdx.x;
+    if (j < a.A) {
+      float sum = 0.0f;
+      for (int b = 0; b < B; ++b) sum += a.ls[(size_t)b * a.M + j];
+      a.dlog_std[j] = sum - a.ent_coef;
+    }
+  } else if (threadIdx.x == 0) {
+    CompSum p, v, k, c;
+    for (int t = 0; t < a.n_tiles; ++t) {
+      const float* q = a.part + (size_t)t * kPartStride;
+      p.add(q[0]), v.add(q[1]), k.add(q[2]), c.add(q[3]);
+    }
+    float ent = 0.0f;
+    for (int j = 0; j < a.A; ++j) ent += 1.4189385332f + a.log_std[j];
+    const float pl = p.value() * a.invB, vl = v.value() * a.invB, el = -ent;
+    a.stats[0] = pl, a.stats[1] = vl, a.stats[2] = el;
+    a.stats[3] = (pl + a.ent_coef * el) + a.vf_coef * vl;
+    a.stats[4] = k.value() * a.invB, a.stats[5] = c.value() * a.invB, a.stats[6] = 0.0f, a.stats[7] = 0.0f;
+  }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+thread_local std::string g_ppo_error;  // of the last failed call without a handle
+
+// FleetPolicy (fleet_policy.hip) derives from FleetMlpHandle and from nothing else: the image's handle is its first base
+FleetMlpHandle* image_of(fleet_policy_handle p) { return reinterpret_cast<FleetMlpHandle*>(p); }
+
+// what fleet_ppo_grad_dev refuses, looked at without the handle; "" when the arguments pass
+std::string check_grad_args(const FleetPpoGradArgs* args, float* const* grads, int count) {
+  if (!args) return "null FleetPpoGradArgs";
+  const FleetPpoGradArgs& x = *args;
+  if (x.struct_bytes != (int32_t)sizeof(FleetPpoGradArgs)) return "FleetPpoGradArgs.struct_bytes does not match this library";
+  if (x.B < 1) return "B must be >= 1, got " + std::to_string(x.B);
+  if (!x.obs) return "null obs";
+  if (!x.actions) return "null actions";
+  if (!x.old_log_prob) return "null old_log_prob";
+  if (!x.advantages) return "null advantages";
+  if (!x.returns) return "null returns";
+  if (!x.log_std) return "null log_std";
+  if (!x.stats) return "null stats";
+  if (!(x.clip_range > 0.0f && x.clip_range < 1.0f)) return "clip_range must be in (0, 1)";
+  if (std::isnan(x.vf_coef)) return "vf_coef is NaN";
+  if (std::isnan(x.ent_coef)) return "ent_coef is NaN";
+  if (!grads) return "null grads";
+  if (count < 1 || count > 2 * kMaxEntries + 1) return "count must be the policy's tensors plus one (log_std), got " + std::to_string(count);
+  for (int i = 0; i < count; ++i)
+    if (!grads[i]) return "gradient tensor " + std::to_string(i) + " is null";
+  return "";
+}
+
+}  // namespace
+
+struct FleetPpo {
+  FleetMlpHandle* pol = nullptr;  // borrowed: the policy outlives this handle
+  std::string error;
+  FleetPpoParams p{};
+  PpoScratch s{};
+  float* scratch = nullptr;
+  int T = 64;  // the widest layer of both heads, out64
+  size_t lds_bytes = 0;
+};
+
+extern "C" {
+
+int fleet_ppo_create(fleet_policy_handle policy, const FleetPpoParams* p, fleet_ppo_handle* out) {
+  if (out) *out = nullptr;
+  const auto refuse = [](const std::string& why, int rc) {
+    g_ppo_error = "fleet_ppo_create: " + why;
+    return rc;
+  };
+  if (!p) return refuse("null FleetPpoParams", FLEET_ERR_INVALID);
+  if (p->struct_bytes != (int32_t)sizeof(FleetPpoParams)) return refuse("FleetPpoParams.struct_bytes does not match this library", FLEET_ERR_INVALID);
+  if (p->max_batch < 1 || p->max_batch > (1 << 24)) return refuse("max_batch must be in 1..16777216, got " + std::to_string(p->max_batch), FLEET_ERR_INVALID);
+  if (!out) return refuse("null output handle", FLEET_ERR_INVALID);
+  if (!policy) return refuse("null policy", FLEET_ERR_INVALID);
+  FleetMlpHandle* pol = image_of(policy);
+  if (pol->n_nets != 2) return refuse("the policy has one head: the loss needs the critic (head 1)", FLEET_ERR_INVALID);
+  const PolicyHeadDesc* nets = pol->nets;
+  if (nets[1].layer[nets[1].n_layers - 1].out != 1)
+    return refuse("the critic's last width must be 1, got " + std::to_string(nets[1].layer[nets[1].n_layers - 1].out), FLEET_ERR_INVALID);
+  if (nets[1].output != FLEET_POLICY_OUT_NONE) return refuse("the critic's output transform must be NONE", FLEET_ERR_INVALID);
+  FleetPpo* h = new FleetPpo();
+  h->pol = pol, h->p = *p;
+  const uint64_t mb = (uint64_t)p->max_batch;
+  uint64_t off = 0;
+  for (int hd = 0; hd < 2; ++hd)
+    for (int l = 0; l < nets[hd].n_layers; ++l) {
+      const uint64_t w = (uint64_t)nets[hd].layer[l].out64;
+      if ((int)w > h->T) h->T = (int)w;
+      if (l < nets[hd].n_layers - 1) h->s.act[hd][l] = off, off += mb * w;
+      h->s.delta[hd][l] = off, off += mb * w;
+    }
+  h->s.ls = off, off += mb * (uint64_t)nets[0].layer[nets[0].n_layers - 1].out64;
+  h->s.part = off, off += (mb + kPolicyRows - 1) / kPolicyRows * kPartStride;
+  h->s.floats = off;
+  h->lds_bytes = ((size_t)2 * kPolicyRows * h->T + (size_t)kPolicyRows * kPolicyChunk + 64) * sizeof(float);
+  constexpr int kMaxLds = (2 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk + 64) * (int)sizeof(float);
+  if (hipSetDevice(pol->device) != hipSuccess) {
+    delete h;
+    return refuse("hipSetDevice failed", FLEET_ERR_HIP);
+  }
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
+    (void)hipGetLastError();
+    delete h;
+    return refuse("hipFuncSetAttribute failed for the rows kernel's " + std::to_string(kMaxLds) + " bytes of LDS", FLEET_ERR_HIP);
+  }
+  void* q = nullptr;
+  if (hipMalloc(&q, off * sizeof(float)) != hipSuccess) {
+    (void)hipGetLastError();
+    delete h;
+    return refuse("hipMalloc of the scratch's " + std::to_string(off * sizeof(float)) + " bytes failed", FLEET_ERR_HIP);
+  }
+  h->scratch = static_cast<float*>(q);
+  *out = h;
+  return FLEET_OK;
+}
+
+int fleet_ppo_destroy(fleet_ppo_handle h) {
+  if (!h) return FLEET_OK;
+  if (h->scratch) (void)hipFree(h->scratch);  // (waits for the device: whatever still reads the scratch is done)
+  delete h;
+  return FLEET_OK;
+}
+
+const char* fleet_ppo_last_error(fleet_ppo_handle h) { return h ? h->error.c_str() : g_ppo_error.c_str(); }
+
+int fleet_ppo_describe(fleet_ppo_handle h, FleetPpoParams* out, uint64_t* scratch_bytes, int32_t* tile_rows) {
+  if (!h || !out || !scratch_bytes || !tile_rows) return FLEET_ERR_INVALID;
+  *out = h->p;
+  *scratch_bytes = h->s.floats * sizeof(float);
+  *tile_rows = kPolicyRows;
+  return FLEET_OK;
+}
+
+int fleet_ppo_grad_dev(fleet_ppo_handle h, const FleetPpoGradArgs* args, float* const* grads, int count) {
+  std::string why = check_grad_args(args, grads, count);
+  if (!h) {
+    g_ppo_error = "fleet_ppo_grad_dev: " + (why.empty() ? std::string("null handle") : why);
+    return FLEET_ERR_INVALID;
+  }
+  FleetMlpHandle* pol = h->pol;
+  if (why.empty() && count != pol->n_tensors + 1)
+    why = "expected " + std::to_string(pol->n_tensors + 1) + " gradient tensors (W, b per layer, then log_std), got " + std::to_string(count);
+  if (why.empty() && args->B > h->p.max_batch)
+    why = "B must be at most max_batch = " + std::to_string(h->p.max_batch) + ", got " + std::to_string(args->B);
+  if (!why.empty()) {
+    h->error = "fleet_ppo_grad_dev: " + why;
+    return FLEET_ERR_INVALID;
+  }
+  const FleetPpoGradArgs& x = *args;
+  const PolicyHeadDesc* nets = pol->nets;
+  const int B = x.B, n_tiles = (B + kPolicyRows - 1) / kPolicyRows;
+  const float invB = 1.0f / (float)B;
+  RowsArgs t{};
+  t.desc = reinterpret_cast<const PolicyDesc*>(pol->block);
+  t.base = reinterpret_cast<const float*>(pol->block);
+  t.obs = x.obs, t.actions = x.actions, t.old_lp = x.old_log_prob, t.adv = x.advantages, t.ret = x.returns, t.log_std = x.log_std;
+  t.values = x.values, t.log_prob = x.log_prob;
+  t.scratch = h->scratch, t.s = h->s, t.B = B, t.T = h->T;
+  t.clip = x.clip_range, t.vf_coef = x.vf_coef, t.invB = invB;
+  WeightArgs g{};
+  int blocks = 0, ti = 0;
+  for (int hd = 0; hd < 2; ++hd)
+    for (int l = 0; l < nets[hd].n_layers; ++l, ti += 2) {
+      const PolicyLayer& L = nets[hd].layer[l];
+      GradEntry& E = g.e[g.n_entries++];
+      E.d = h->scratch + h->s.delta[hd][l], E.dstride = L.out64;
+      if (l == 0) E.x = x.obs, E.xstride = L.in;
+      else E.x = h->scratch + h->s.act[hd][l - 1], E.xstride = nets[hd].layer[l - 1].out64;
+      E.dW = grads[ti], E.db = grads[ti + 1], E.out = L.out, E.in = L.in;
+      E.tiles_k = (L.in + kGradTile - 1) / kGradTile;
+      E.first = blocks;
+      blocks += ((L.out + kGradTile - 1) / kGradTile) * E.tiles_k;
+    }
+  const PolicyLayer& LA = nets[0].layer[nets[0].n_layers - 1];
+  g.tile_blocks = blocks, g.ls_blocks = (LA.out + 255) / 256, g.B = B;
+  g.ls = h->scratch + h->s.ls, g.part = h->scratch + h->s.part, g.log_std = x.log_std;
+  g.dlog_std = grads[count - 1], g.stats = x.stats;
+  g.A = LA.out, g.M = LA.out64, g.n_tiles = n_tiles;
+  g.invB = invB, g.vf_coef = x.vf_coef, g.ent_coef = x.ent_coef;
+  FLEET_HANDLE_TRY(h, hipSetDevice(pol->device));
+  hipLaunchKernelGGL(ppo_rows, dim3((unsigned)n_tiles, 2), dim3(kPolicyThreads), h->lds_bytes, pol->stream, t);
+  FLEET_HANDLE_TRY(h, hipGetLastError());
+  hipLaunchKernelGGL(ppo_weights, dim3((unsigned)(g.tile_blocks + g.ls_blocks + 1)), dim3(256), 0, pol->stream, g);
+  FLEET_HANDLE_TRY(h, hipGetLastError());
+  return FLEET_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,113 @@
+"""`DevicePPOGrad`: the gradients of PPO's minibatch loss on the device (include/fleet_hip.h `fleet_ppo_*`,
+fleetrl_amd/csrc/fleet_ppo.hip).
+
+What SB3's `PPO.train` does with one minibatch before the optimiser -- `evaluate_actions`, the clipped loss (`clip_range_vf=None`) and
+`loss.backward()` -- in two launches on a two-head `DevicePolicy`'s weights: the gradients land in the `.grad` of torch's own
+parameters, so `clip_grad_norm_` and `opt.step()` follow unchanged.  Deterministic by construction: no atomics, every sum in a fixed
+order.  The optimiser, the advantage normalisation and `clip_range_vf` stay the caller's.  The device policy's image is what is
+differentiated: call `policy.load_torch(params)` after every optimiser step.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _capi
+from ._capi import FleetHipError
+from ._handle import _DeviceHandle
+
+__all__ = ["DevicePPOGrad", "STATS"]
+
+STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction")
+
+
+class DevicePPOGrad(_DeviceHandle):
+    """One `fleet_ppo_*` handle on `policy` (a `DevicePolicy` with a critic of width 1, which must outlive it) for minibatches of at
+    most `max_batch` rows.  It launches on the policy's stream."""
+    _prefix = "ppo"
+
+    def __init__(self, policy, max_batch: int):
+        self.lib = _capi.load_library()
+        self.policy, self.device = policy, policy.device
+        self.obs_dim, self.act_dim, self.max_batch = policy.obs_dim, policy.act_dim, int(max_batch)
+        p = _capi.FleetPpoParams(C.sizeof(_capi.FleetPpoParams), self.max_batch)
+        h = C.c_void_p()
+        rc = self.lib.fleet_ppo_create(policy.h, C.byref(p), C.byref(h))
+        if rc != _capi.OK:
+            raise FleetHipError(rc, self.lib.fleet_ppo_last_error(None).decode())
+        self.h = h
+        self._shapes = [tuple(s) for pair in policy._shapes for s in pair] + [(self.act_dim,)]
+        self._into = None  # (the parameters, the pointer array of their .grad) of the last call
+        self.tile_rows = self.describe()["tile_rows"]
+
+    def set_stream(self, hip_stream):
+        """The handle has no stream of its own: the policy's is set."""
+        self.policy.set_stream(hip_stream)
+
+    def use_torch_stream(self, device=None):
+        self.policy.use_torch_stream(device)
+
+    def describe(self) -> dict:
+        """What fleet_ppo_describe reports: max_batch, the bytes of the scratch, the rows one workgroup of the rows launch takes."""
+        p, nbytes, rows = _capi.FleetPpoParams(), C.c_uint64(), C.c_int32()
+        self._check(self.lib.fleet_ppo_describe(self.h, C.byref(p), C.byref(nbytes), C.byref(rows)))
+        return {"max_batch": p.max_batch, "scratch_bytes": int(nbytes.value), "tile_rows": int(rows.value)}
+
+    def grad_dev(self, args: "_capi.FleetPpoGradArgs", grad_ptrs, count: int):
+        """Raw device addresses in a FleetPpoGradArgs and a (c_void_p * count) array, on the policy's stream."""
+        args.struct_bytes = C.sizeof(_capi.FleetPpoGradArgs)
+        self._check(self.lib.fleet_ppo_grad_dev(self.h, C.byref(args), grad_ptrs, int(count)))
+
+    def _grad_pointers(self, into):
+        import torch
+
+        into = list(into)
+        hit = self._into
+        if hit is not None and len(hit[0]) == len(into) and all(a is b for a, b in zip(hit[0], into)) and \
+                all(p.grad is not None and p.grad.data_ptr() == q for p, q in zip(into, hit[2])):
+            return hit[1]
+        if len(into) != len(self._shapes):
+            raise ValueError(f"into: expected {len(self._shapes)} parameters (W, b per layer, the actor's then the critic's, then log_std), "
+                             f"got {len(into)}")
+        ptrs = []
+        for p, s in zip(into, self._shapes):
+            if tuple(p.shape) != s:
+                raise ValueError(f"into: expected a parameter of shape {s}, got {tuple(p.shape)}")
+            if p.grad is None:  # allocated once; the launches overwrite it
+                p.grad = torch.empty_like(p, memory_format=torch.contiguous_format)
+            ptrs.append(self._tensor(p.grad, s, (torch.float32,)).data_ptr())
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        self._into = (into, arr, ptrs)
+        return arr
+
+    def grad(self, batch, log_std, clip_range: float, vf_coef: float, ent_coef: float, *, into, values_out=None, log_prob_out=None,
+             advantages=None, stats_out=None):
+        """The loss of one minibatch and its gradients, two launches on torch's current stream, no host synchronisation.
+        batch: what `DeviceRolloutBuffer.get` yields (observations f32 [B, obs_dim], actions f32 [B, act_dim], old_log_prob,
+        advantages, returns f32 [B]); `advantages` replaces the batch's (the normalised ones).  log_std: the torch parameter f32
+        [act_dim], read when the launch runs.  into: the torch parameters in `DevicePolicy.load_torch`'s order, then log_std; their
+        `.grad` is allocated on the first call and OVERWRITTEN by every call (there is nothing to zero).  values_out, log_prob_out
+        f32 [B]: the critic's values and the new log-probabilities.  Returns stats f32 [8] on the device: `STATS`, then two zeros."""
+        import torch
+
+        self.use_torch_stream()
+        f32 = (torch.float32,)
+        obs = batch.observations
+        B = int(obs.shape[0]) if obs.ndim == 2 else 0
+        adv = batch.advantages if advantages is None else advantages
+        a = _capi.FleetPpoGradArgs()
+        a.B = B
+        keep = [self._tensor(obs, (B, self.obs_dim), f32), self._tensor(batch.actions, (B, self.act_dim), f32),
+                self._tensor(batch.old_log_prob, (B,), f32), self._tensor(adv.detach(), (B,), f32), self._tensor(batch.returns, (B,), f32),
+                self._tensor(log_std.detach(), (self.act_dim,), f32)]
+        a.obs, a.actions, a.old_log_prob, a.advantages, a.returns, a.log_std = (t.data_ptr() for t in keep)
+        a.clip_range, a.vf_coef, a.ent_coef = float(clip_range), float(vf_coef), float(ent_coef)
+        if stats_out is None:
+            stats_out = torch.empty(8, device=obs.device, dtype=torch.float32)
+        a.stats = self._tensor(stats_out, (8,), f32).data_ptr()
+        for name, t in (("values", values_out), ("log_prob", log_prob_out)):
+            if t is not None:
+                keep.append(self._tensor(t, (B,), f32))
+                setattr(a, name, keep[-1].data_ptr())
+        arr = self._grad_pointers(into)
+        self.grad_dev(a, arr, len(self._shapes))
+        return stats_out

@@ -1115,6 +1115,82 @@ int fleet_qtarget_target_dev(fleet_qtarget_handle h, const float* next_obs, cons
 /* the parameters the handle was created with, and tile_rows */
 int fleet_qtarget_describe(fleet_qtarget_handle h, FleetQTargetParams* out);
 
+/* ---- PPO minibatch gradients on the device (fleet_ppo.hip; DESIGN.md "PPO's minibatch gradients on the device") --------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * What stable-baselines3 2.3.2's PPO.train does with one minibatch before the optimiser -- evaluate_actions, the clipped loss
+ * (clip_range_vf = None) and loss.backward() -- in TWO launches on a two-head policy's weight image (actor = head 0 with a
+ * state-independent log_std, critic = head 1 of width 1 and output NONE):
+ *   loss = -mean(min(adv * ratio, adv * clamp(ratio, 1 - c, 1 + c))) + vf_coef * mean((returns - v)^2) - ent_coef * mean(entropy)
+ * and its gradient with respect to every weight and bias of both heads and to log_std.  float32 throughout, no fused contraction but
+ * the fmaf written below, no atomics, no random numbers.  Per row b of the B rows (obs f32[B,D], actions f32[B,A], old_log_prob,
+ * advantages, returns f32[B], as fleet_rollout_gather_dev writes them), exactly:
+ *   mean[j], v = the policy section's forward chain; mean is head 0's last layer BEFORE its output transform
+ *   sd = expf(ls[j]);  dm = a[j] - mean[j];  t[j] = -(dm * dm) / (2.0f * sd * sd) - ls[j] - 0.9189385332f        (ls = log_std)
+ *   lp = the t[j] summed as fleet_explore_act_dev sums them: lane i of 64 adds j = i, i + 64, ... in ascending order to 0, then
+ *        the xor butterfly s += shuffle_xor(s, 1), 2, 4, ..., 32 -- the same bits as the log_prob that launch stored
+ *   lr = lp - old;  ratio = expf(lr);  lo = 1.0f - c;  hi = 1.0f + c;  cl = ratio < lo ? lo : (ratio > hi ? hi : ratio)
+ *   s1 = adv * ratio;  s2 = adv * cl;  the row's policy term is -(s1 < s2 ? s1 : s2)
+ *   alive = (ratio >= lo && ratio <= hi) || s1 < s2          (what torch's min / clamp backward rules, ties included, collapse to)
+ *   invB = 1.0f / (float)B;  glp = alive ? -(adv * ratio) * invB : 0
+ *   dmean[j] = glp * (dm / (sd * sd));  the row's log_std term u[j] = glp * ((dm * dm) / (sd * sd) - 1.0f)
+ *   dv = ((2.0f * vf_coef) * invB) * (v - ret)
+ * Back through layer l into layer l - 1 (h: that layer's activation):
+ *   d_prev[k] = (acc = 0; acc = fmaf(Wt[k][j], d[j], acc) for j ascending over the layer's outputs) * act'(h[k]),
+ *   tanh' = fmaf(-h, h, 1.0f), relu' = h > 0 ? 1 : 0
+ * Gradients, each element one chain over the rows in ascending b:
+ *   dW[j][k]: acc = 0; acc = fmaf(d[b][j], x[b][k], acc)  (x: the layer's input, obs for a first layer);  db[j]: acc = 0; acc += d[b][j]
+ *   dlog_std[j]: acc = 0; acc += u[b][j];  then acc - ent_coef   (the entropy of the Gaussian is sum_j(1.4189385332f + ls[j]))
+ * Statistics, stats f32[8].  A tile is 16 consecutive rows; a tile's partial is the COMPENSATED sum of its rows' terms in ascending
+ * order (Neumaier: s = 0, c = 0; per term x: t = s + x; c += |s| >= |x| ? (s - t) + x : (x - t) + s; s = t; the result is s + c), a
+ * total the compensated sum of the tiles' partials in ascending order:
+ *   [0] policy_loss = total(policy term) * invB        [1] value_loss = total((ret - v) * (ret - v)) * invB
+ *   [2] entropy_loss = -(ascending sum over j of (1.4189385332f + ls[j]))
+ *   [3] loss = (policy_loss + ent_coef * entropy_loss) + vf_coef * value_loss
+ *   [4] approx_kl = total((ratio - 1.0f) - lr) * invB   [5] clip_fraction = total(fabsf(ratio - 1.0f) > c ? 1 : 0) * invB   [6], [7] 0
+ * Every result is a function of the inputs and B only: not of the stream, of max_batch, of what lies behind row B in the buffers,
+ * or of the run.  The gradient tensors and stats are OVERWRITTEN, not accumulated.  values[b] and log_prob[b] depend on row b
+ * alone: an observation that is not finite stays in its row there; it does reach the gradients and the statistics, which sum over
+ * the rows.  The handle owns a scratch sized for max_batch rows (every layer's activations and deltas) and BORROWS the policy's
+ * image: the policy must outlive it.  It launches on the POLICY's stream, whichever that is when the call is made: a call enqueued
+ * behind fleet_policy_load_dev sees the new weights with no host wait.  Calls are serialised by the caller. */
+typedef struct FleetPpoParams {
+  int32_t struct_bytes;  /* sizeof(FleetPpoParams) */
+  int32_t max_batch;     /* rows the scratch holds, 1..2^24 */
+} FleetPpoParams;
+typedef struct FleetPpoGradArgs {
+  int32_t struct_bytes;        /* sizeof(FleetPpoGradArgs) */
+  int32_t B;                   /* rows, 1..max_batch */
+  const float* obs;            /* device f32[B, D] (normalised, as the rollout buffer keeps them) */
+  const float* actions;        /* device f32[B, A]: the stored (unclipped) actions */
+  const float* old_log_prob;   /* device f32[B] */
+  const float* advantages;     /* device f32[B] (already normalised if the caller normalises) */
+  const float* returns;        /* device f32[B] */
+  const float* log_std;        /* device f32[A], read when the launch runs */
+  float clip_range;            /* c, in (0, 1) */
+  float vf_coef, ent_coef;     /* not NaN */
+  int32_t reserved;            /* 0 */
+  float* values;               /* device f32[B] or NULL: v */
+  float* log_prob;             /* device f32[B] or NULL: lp */
+  float* stats;                /* device f32[8] */
+} FleetPpoGradArgs;
+typedef struct FleetPpo* fleet_ppo_handle;
+
+/* FLEET_ERR_INVALID (fleet_ppo_last_error(NULL) says why, starting with the entry's name) for a null or wrongly sized FleetPpoParams,
+ * max_batch outside 1..2^24, a null output or policy, a one-head policy, a critic whose last width is not 1 or whose output is not
+ * NONE.  FLEET_ERR_HIP with the byte count when the scratch cannot be allocated. */
+int fleet_ppo_create(fleet_policy_handle policy, const FleetPpoParams* p, fleet_ppo_handle* out);
+int fleet_ppo_destroy(fleet_ppo_handle h);
+const char* fleet_ppo_last_error(fleet_ppo_handle h);  /* h may be NULL: error of the last failed call without a handle */
+/* the parameters the handle was created with, the bytes of its scratch, and the rows one workgroup of the rows launch takes */
+int fleet_ppo_describe(fleet_ppo_handle h, FleetPpoParams* out, uint64_t* scratch_bytes, int32_t* tile_rows);
+/* Two launches, enqueued only.  grads: a host array of `count` device pointers, the gradient tensors in torch's [out, in] layout and
+ * fleet_policy_load_dev's order (W, b per layer, head 0 then head 1), then log_std's f32[A]: count = the policy's tensors + 1.
+ * FLEET_ERR_INVALID (nothing is launched) for a null or wrongly sized FleetPpoGradArgs, B < 1, a null obs / actions / old_log_prob /
+ * advantages / returns / log_std / stats, a clip_range outside (0, 1) or NaN, a NaN vf_coef or ent_coef, a null grads or a null
+ * pointer in it, and -- these two need the handle -- a count that is not the policy's tensors + 1, B > max_batch.  The arguments are
+ * looked at before the handle is: with h NULL the reason (or "null handle") goes to fleet_ppo_last_error(NULL). */
+int fleet_ppo_grad_dev(fleet_ppo_handle h, const FleetPpoGradArgs* args, float* const* grads, int count);
+
 #ifdef __cplusplus
 }
 #endif
