@@ -389,6 +389,12 @@ def load_library():
         lib.fleet_step_instance.restype = C.c_int
         lib.fleet_max_evs_per_lane_group.argtypes = []
         lib.fleet_max_evs_per_lane_group.restype = C.c_int
+    if hasattr(lib, "fleet_set_direct_state_only"):  # (absent from older libraries the A/B scripts run beside the tree's)
+        lib.fleet_set_direct_state_only.argtypes = [vp, C.c_int]
+        lib.fleet_direct_packet_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        lib.fleet_step_has_state_only.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_int32)]
+        for name in ("fleet_set_direct_state_only", "fleet_direct_packet_counts", "fleet_step_has_state_only"):
+            getattr(lib, name).restype = C.c_int
     if hasattr(lib, "fleet_selftest_stress"):
         lib.fleet_selftest_stress.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]
         lib.fleet_selftest_stress.restype = C.c_int
@@ -555,6 +561,7 @@ EXPORTED_SYMBOLS = (
     "fleet_rccl_comm_destroy", "fleet_gather_episode_stats_rccl", "fleet_selftest_division", "fleet_direct_queues", "fleet_selftest_stress",
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
+    "fleet_set_direct_state_only", "fleet_direct_packet_counts", "fleet_step_has_state_only",
 ) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS
 
 
@@ -569,6 +576,18 @@ def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, 
     if rc != OK:
         raise FleetHipError(rc, "fleet_step_instance: argument out of range")
     return name.value.decode(), int(grid.value)
+
+
+def step_has_state_only(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,
+                        has_done_count: bool = False) -> bool:
+    """Whether a launch of this kind has a state-only twin, which a run on the library's own queue takes for every launch but its
+    last (include/fleet_hip.h fleet_step_has_state_only; needs the library, but no GPU)."""
+    out = C.c_int32()
+    rc = load_library().fleet_step_has_state_only(int(num_envs), int(num_cars), int(deg_mode), int(bool(real_time)), int(bool(log_data)),
+                                                  int(act_mode), int(K), int(bool(has_done_count)), C.byref(out))
+    if rc != OK:
+        raise FleetHipError(rc, "fleet_step_has_state_only: argument out of range")
+    return bool(out.value)
 
 
 def _layout(prefix: str, params, out):

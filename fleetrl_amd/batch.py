@@ -346,6 +346,18 @@ class FleetBatch:
         """How the handle's last direct run (use_graph=_capi.LAUNCH_DIRECT) was laid out: 0 none yet, 1 one queue, 2 two queues."""
         return int(self.lib.fleet_direct_queues(self.h)) if hasattr(self.lib, "fleet_direct_queues") else 0
 
+    def set_direct_state_only(self, on: bool = True):
+        """Whether the launches of a direct run whose outputs nobody can read -- all but the last -- take the step kernel's state-only
+        twin where the configuration has one (the default), or the live instance with its run-time flag (A/B, tests).  Results are
+        the same bit for bit (fleet_set_direct_state_only)."""
+        self._check(self.lib.fleet_set_direct_state_only(self.h, 1 if on else 0))
+
+    def direct_packet_counts(self) -> tuple[int, int]:
+        """(live, state_only): packets the handle's own queue was given so far with the live instance and with its twin."""
+        live, dead = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.fleet_direct_packet_counts(self.h, C.byref(live), C.byref(dead)))
+        return int(live.value), int(dead.value)
+
     def time_steps_dev(self, steps: int, tape_ptr: int, tape_len: int, obs_ptr: int, reward_ptr: int, done_ptr: int,
                        act_dtype: int = _capi.ACT_F32) -> np.ndarray:
         """Per-launch device durations [ms] measured with one HIP event pair per launch on the handle's stream."""

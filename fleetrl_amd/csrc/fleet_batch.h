@@ -91,6 +91,7 @@ struct FleetEnvBatch {
   TapeKey dq_key;
   bool dq_timed = false;  // runs carry dispatch timestamps on their first and last packets: fleet_direct_submit
   std::vector<double> dq_spans_us;
+  bool direct_state_only = true;  // fleet_set_direct_state_only: dead launches of a run take the state-only twin where there is one
   // Every call that changes what a launch's argument block embeds (the handle's streams, its start schedule, its policy parameters:
   // anything a later version may move into FleetDev) bumps the generation: argument blocks prepared before it are never reused.
   uint64_t gen = 1;

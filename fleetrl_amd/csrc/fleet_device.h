@@ -272,6 +272,9 @@ hipError_t fleet_launch_step(const FleetDev& d, const void* actions, int act_dty
 // would issue.  hipErrorNotSupported: not a single-step configuration (real_time, data log).
 struct FleetStepLaunch {
   const void* host_fn;
+  const void* host_fn_dead;  // the instance's state-only twin (same argument block, `outputs_dead` ignored: nobody can read the launch's
+                             // outputs), or nullptr: groups below 64 lanes and the several-EVs-per-lane instance have none.  Only a run
+                             // on the library's own queue launches it, for the packets that otherwise carry `outputs_dead` = 1
   unsigned grid, block, args_bytes;
   unsigned actions_offset[2];
   unsigned packed_n_offset;  // where `p_N` sits: EVs per env | first workgroup of the grid << 16 (a run split over two queues)
@@ -293,6 +296,8 @@ int fleet_describe_step_instance(const FleetDev& d, int act_mode, int K, bool ha
                                  unsigned* grid);
 hipError_t fleet_describe_step(const FleetDev& d, const void* actions, int act_dtype, float* obs, double* reward, uint8_t* done,
                                float* terminal_obs, FleetStepLaunch* out);
+// Whether the instance such a launch takes is a single-step one with a state-only twin (reads what fleet_describe_step_instance reads)
+bool fleet_step_has_twin(const FleetDev& d, int act_mode, int K, bool has_done_count);
 // compact the terminal observations of the envs with done[e] != 0 (env order): idx[k], *count, compact[k, obs_dim]
 hipError_t fleet_launch_term_compact(const FleetDev& d, const uint8_t* done, const float* term, int32_t* idx, int32_t* count,
                                      double* ep_ret, int32_t* ep_len, float* compact, hipStream_t s);

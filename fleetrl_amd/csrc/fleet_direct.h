@@ -22,10 +22,15 @@ int fleet_direct_plan(unsigned grid, bool split, unsigned part_grid[2]);
 // the launch every packet of the next submissions repeats, and the tape its action pointers walk: `tape_len` rows of `row_bytes` from
 // `tape` (argument blocks in device memory, one per tape row; blocks until they are uploaded).  No launch may be in flight.
 // `split`: cover the grid with two ranges of workgroups on two queues (large batches; fleet_direct.hip).
+// `state_only`: where the launch has a state-only twin (launch.host_fn_dead), the packets of a run whose outputs nobody can read --
+// all but its last -- take the twin's kernel object; false, or no twin: every packet takes the live instance and the block's
+// `outputs_dead` flag decides at run time.  Both objects are resolved by name and checked against the argument block's size.
 // Nothing of the handle's prepared state changes unless the call succeeds.
 int fleet_direct_prepare(FleetDirect* q, const FleetStepLaunch& launch, const void* tape, int tape_len, size_t row_bytes, bool split,
-                         std::string* err);
+                         bool state_only, std::string* err);
 int fleet_direct_parts(FleetDirect* q);  // 1 or 2: how the prepared launch is laid out
+// packets written since the queue was opened (probe launches not counted): with the live instance's object, with the twin's
+void fleet_direct_packets(FleetDirect* q, uint64_t* live, uint64_t* state_only);
 // `steps` launches (tape rows 0, 1, ... cyclically) behind the run's placement-record launch, asynchronous.  Fences: every packet acquires
 // at agent scope (the vector / scalar L1s are invalidated; the first at system scope) and releases NOTHING -- except the last, which
 // releases at system scope.  Outputs: only the run's last launch stores observation rows (the others carry the kernel's

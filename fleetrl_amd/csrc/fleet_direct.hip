@@ -136,8 +136,11 @@ struct FleetDirect {
   bool any_grid = false;           // the map also held across grids that are not multiples of 8 workgroups (both queues)
   uint32_t num_xcc = 0;
   int fault_rotate = 0;            // test hook: the next run's placement record is shifted by one workgroup
-  // the prepared launch
-  KernelObject kernel;
+  // the prepared launch: the live instance and, where the configuration has one and the caller wants it, its state-only twin
+  // (fleet_kernels.hip, DEAD) for every packet whose block carries `outputs_dead` = 1
+  KernelObject kernel, kernel_dead;
+  bool have_dead = false;
+  uint64_t packets_live = 0, packets_dead = 0;  // packets written with either object since the queue was opened (fleet_direct_packets)
   unsigned block = 0;
   int parts = 1;              // 1: the whole grid on queue 0; 2: the grid as two ranges of workgroups, one per queue
   unsigned part_grid[2] = {0, 0};
@@ -465,7 +468,7 @@ int fleet_direct_plan(unsigned grid, bool split, unsigned part_grid[2]) {
 }
 
 int fleet_direct_prepare(FleetDirect* q, const FleetStepLaunch& L, const void* tape, int tape_len, size_t row_bytes, bool split,
-                         std::string* err) {
+                         bool state_only, std::string* err) {
   if (!q || !L.host_fn || tape_len < 1 || L.args_bytes > FleetDirect::kBlockBytes) return FLEET_ERR_INVALID;
   if (q->in_flight) {
     if (err) *err = "fleet_direct_prepare: launches are in flight";
@@ -476,14 +479,24 @@ int fleet_direct_prepare(FleetDirect* q, const FleetStepLaunch& L, const void* t
     if (err) *err = "fleet_direct_prepare: the kernel has no name";
     return FLEET_ERR_HIP;
   }
-  KernelObject kernel;
+  KernelObject kernel, kernel_dead;
   int rc = kernel_by_name(q, name, &kernel, err);
   if (rc != FLEET_OK) return rc;
-  if (kernel.kernarg_bytes != L.args_bytes) {  // (cannot happen behind the source-hash check of fleet_direct_open)
-    if (err) *err = "fleet_direct_prepare: the code object's argument segment is " + std::to_string(kernel.kernarg_bytes) +
-                    " bytes, the library's " + std::to_string(L.args_bytes);
-    return FLEET_ERR_STATE;
+  const bool have_dead = state_only && L.host_fn_dead != nullptr;
+  if (have_dead) {  // the twin: resolved and checked like the live instance -- the two share every argument block
+    const char* name_dead = hipKernelNameRefByPtr(L.host_fn_dead, nullptr);
+    if (!name_dead) {
+      if (err) *err = "fleet_direct_prepare: the state-only kernel has no name";
+      return FLEET_ERR_HIP;
+    }
+    if ((rc = kernel_by_name(q, name_dead, &kernel_dead, err)) != FLEET_OK) return rc;
   }
+  for (const KernelObject* k : {&kernel, &kernel_dead})
+    if ((k == &kernel || have_dead) && k->kernarg_bytes != L.args_bytes) {  // (cannot happen behind the source-hash check of fleet_direct_open)
+      if (err) *err = "fleet_direct_prepare: the code object's argument segment is " + std::to_string(k->kernarg_bytes) +
+                      " bytes, the library's " + std::to_string(L.args_bytes);
+      return FLEET_ERR_STATE;
+    }
   // one grid on one queue -- or, for a batch of more wavefronts than are resident at once, two ranges of workgroups on two queues,
   // each an in-order chain of its own: the two halves drift apart and one's loads run under the other's arithmetic and stores
   // (16384 x 50: 24.5 -> 20.9 us per step; no gain at 4096 x 50, profiles/r05_experiments/direct_queue_two_handles.log)
@@ -559,6 +572,8 @@ int fleet_direct_prepare(FleetDirect* q, const FleetStepLaunch& L, const void* t
   }
   q->kargs_host.swap(host);
   q->kernel = kernel;
+  q->kernel_dead = kernel_dead;
+  q->have_dead = have_dead;
   q->block = L.block;
   q->parts = parts;
   q->part_grid[0] = part_grid[0];
@@ -633,9 +648,13 @@ int fleet_direct_submit(FleetDirect* q, int steps, bool timed, std::string* err)
       // at agent scope; a packet releases only when it is the last of a run that asks for it
       const int acq = (i == 0) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_AGENT;
       const int rel = (i == steps - 1) ? HSA_FENCE_SCOPE_SYSTEM : HSA_FENCE_SCOPE_NONE;
-      write_packet(q->queue[part], q->kernel, q->block, q->part_grid[part],
+      // the kernel object goes with the block: a block that says "outputs dead" is the state-only twin's where there is one -- every
+      // packet of a run but its last, the recording first launch of a run of several steps included
+      const bool dead = q->have_dead && i != steps - 1;
+      write_packet(q->queue[part], dead ? q->kernel_dead : q->kernel, q->block, q->part_grid[part],
                    q->kargs_dev + (i == 0 ? q->first_block(part, one_step) : q->row_block(part, i % q->tape_len, i == steps - 1)), acq, rel,
                    sig);
+      (dead ? q->packets_dead : q->packets_live) += 1;
     }
   if (timed) q->marks.push_back(m);
   for (int part = 0; part < 2; ++part) q->last[part] = part < q->parts ? m.last[part] : hsa_signal_t{};
@@ -654,6 +673,11 @@ int fleet_direct_submit(FleetDirect* q, int steps, bool timed, std::string* err)
 }
 
 int fleet_direct_parts(FleetDirect* q) { return q ? q->parts : 0; }
+
+void fleet_direct_packets(FleetDirect* q, uint64_t* live, uint64_t* state_only) {
+  if (live) *live = q ? q->packets_live : 0;
+  if (state_only) *state_only = q ? q->packets_dead : 0;
+}
 
 bool fleet_direct_busy(FleetDirect* q) {
   if (!q || !q->in_flight) return false;

@@ -261,7 +261,10 @@ static_assert(offsetof(StepKernargs, rec_rows) == offsetof(StepKernargs, rec_blo
 // kModeAll = everything behind run-time tests (the data-log instances and the small groups, where instances are not multiplied).
 constexpr int kModeAll = 0, kModeTape = 1, kModePolicy = 2, kModeRt = 3;
 
-template <int G, int DEG, bool MULTI, bool WIDE, bool LOG = false, bool A64 = false, int MODE = kModeAll>
+// DEAD: the state-only twin of a single-step instance ("Dead outputs" in the kernel): the same argument list, `outputs_dead` ignored --
+// that nobody can read this launch's outputs is a compile-time fact.  Only for groups of whole wavefronts with one EV per lane
+// (G = 64 / 128 / 256, the benchmark's shapes); only a run on the library's own queue ever launches it (fleet_direct.hip).
+template <int G, int DEG, bool MULTI, bool WIDE, bool LOG = false, bool A64 = false, int MODE = kModeAll, bool DEAD = false>
 __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWaves) : kSingleWaves) void fleet_step_kernel(
     // The first twelve argument dwords are preloaded into scalar registers at wave launch (-amdgpu-kernarg-preload-count,
     // fleetrl_amd/build.py; twelve is what fits beside the other user registers): what the first loads of a wavefront need --
@@ -283,6 +286,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   // whole step in lanes of a vector register (24 v_writelane + 22 v_readlane on every wavefront's path before; none now).
   // Re-reading in the MIDDLE of the EV's step instead stalls on those loads (+0.3 us at 2048 envs) and re-reading everything at
   // several points costs +0.7 us (profiles/r04_experiments/args_reloaded_*).  `late_args_ok` guards the hard-wired offset.
+  static_assert(!DEAD || (!MULTI && !WIDE && !LOG && G >= 64 && MODE == kModeAll), "the state-only twin: one step, one EV per lane, whole wavefronts");
   const FleetDev& d = d_arg;
   auto late_args = [&]() -> const FleetDev& {
     if constexpr (!MULTI && !WIDE) {
@@ -376,7 +380,10 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   // (the run's last launch writes every env's row).  State -- the EV records, rainflow and SEI, head, ep_return, penalty_record,
   // ep_len, the episode-end records --, the error bits and the placement guard are as ever.  Launches through HIP always carry 0;
   // the K-step instances (the data log among them) decide per step themselves and do not look.
-  const bool obs_live = MULTI || outputs_dead == 0;
+  // The state-only twin (DEAD) is the same launch with the answer compiled in: no observation or terminal row addressing, no tail
+  // request, no cashflow arithmetic (the fold's first sum is a literal zero), no leader store block, no start row from the reset --
+  // and none of the registers, masks and scalar instructions that carry the run-time test through the step.
+  const bool obs_live = DEAD ? false : (MULTI || outputs_dead == 0);
   const int vzero = (int)__builtin_amdgcn_mbcnt_lo(0u, 0u);  // 0 in every lane, opaque to the uniformity analysis
   // night-charging policy: the env's "charging since" row travels in a register over the K steps
   int night_st = FLEET_NIGHT_IDLE;

@@ -2,7 +2,8 @@
 //
 // Provides: StepPlan / step_instance / plan_step_gd / plan_step_g (the ONE place an instance is selected -- for a HIP stream, a
 // captured graph and the library's own queue alike), step_args (the argument block), FLEET_DISPATCH_G, and the functions
-// fleet_device.h declares: fleet_launch_*, fleet_describe_step, fleet_describe_step_instance, fleet_max_evs_per_lane_group.
+// fleet_device.h declares: fleet_launch_*, fleet_describe_step, fleet_describe_step_instance, fleet_step_has_twin,
+// fleet_max_evs_per_lane_group.
 // Restates nothing of the reference.
 // Expects of its includer: it comes last in fleet_kernels.hip, after kBlock / kMaxGroup, kModeAll ... kModeRt, StepKernargs and
 // fleet_step_kernel.  Every instance and grid the selection returns is pinned by tests/test_step_instances_cpu.py.
@@ -30,13 +31,19 @@ struct StepPlan {
   unsigned grid;
   bool single;
   const FleetStepInstance* id;  // the template arguments of `fn` (fleet_step_instance: which kernel a configuration takes)
+  StepKernelFn fn_dead;         // the state-only twin of `fn` (fleet_step_kernel, DEAD), nullptr where there is none
 };
 // The one place that takes an instance's address: the description is formed from the same template arguments as the pointer, so
 // the two cannot disagree.
 template <int G, int DEG, bool MULTI, bool WIDE, bool LOG = false, bool A64 = false, int MODE = kModeAll>
 StepPlan step_instance(unsigned grid, bool single) {
   static constexpr FleetStepInstance id{G, DEG, MULTI, WIDE, LOG, A64, MODE};
-  return {&fleet_step_kernel<G, DEG, MULTI, WIDE, LOG, A64, MODE>, grid, single, &id};
+  // ... and the state-only twin from the same template arguments: single-step, one EV per lane, groups of whole wavefronts.  Smaller
+  // groups and the several-EVs-per-lane instance keep the run-time `outputs_dead` flag (not the benchmark's shapes: 54 more instances
+  // would cost build time for nothing).  Never selected by plan_step: only fleet_describe_step hands it out.
+  StepKernelFn dead = nullptr;
+  if constexpr (!MULTI && !WIDE && !LOG && G >= 64 && MODE == kModeAll) dead = &fleet_step_kernel<G, DEG, false, false, false, A64, kModeAll, true>;
+  return {&fleet_step_kernel<G, DEG, MULTI, WIDE, LOG, A64, MODE>, grid, single, &id, dead};
 }
 
 // Instance selection.  G (EVs per env rounded up to a power of two, at most 64) and DEG come from the switches of plan_step; an env
@@ -157,12 +164,17 @@ int fleet_describe_step_instance(const FleetDev& d, int act_mode, int K, bool ha
                   i.log ? ".log" : "", part, dtype);
 }
 
+bool fleet_step_has_twin(const FleetDev& d, int act_mode, int K, bool has_done_count) {
+  const StepPlan p = plan_step(d, act_mode, K, has_done_count);
+  return p.single && p.fn_dead != nullptr;
+}
+
 hipError_t fleet_describe_step(const FleetDev& d, const void* actions, int act_dtype, float* obs, double* reward, uint8_t* done,
                                float* terminal_obs, FleetStepLaunch* out) {
   const StepPlan p = plan_step(d, act_dtype, 1, false);
   if (!p.single) return hipErrorNotSupported;
   const StepKernargs a = step_args(d, actions, act_dtype, 1, obs, reward, done, terminal_obs, nullptr);
-  out->host_fn = (const void*)p.fn; out->grid = p.grid; out->block = kBlock; out->args_bytes = (unsigned)sizeof a;
+  out->host_fn = (const void*)p.fn; out->host_fn_dead = (const void*)p.fn_dead; out->grid = p.grid; out->block = kBlock; out->args_bytes = (unsigned)sizeof a;
   out->actions_offset[0] = (unsigned)offsetof(StepKernargs, p_actions); out->actions_offset[1] = (unsigned)offsetof(StepKernargs, actions);
   out->packed_n_offset = (unsigned)offsetof(StepKernargs, p_N);
   out->guard_offset = (unsigned)offsetof(StepKernargs, guard_bytes);

@@ -55,7 +55,7 @@ static int direct_ready(fleet_handle h, const void* tape, int tape_len, int act_
     }
     const bool split = mode == FLEET_LAUNCH_DIRECT && h->d.N <= 64 && (size_t)L.grid * (L.block / 64) >= kDirectSplitWaves;
     h->dq_key = TapeKey{};  // whatever happens below, the old key describes nothing any more
-    rc = fleet_direct_prepare(h->direct, L, tape, tape_len, tape_row_bytes(h->d, act_dtype), split, &h->error);
+    rc = fleet_direct_prepare(h->direct, L, tape, tape_len, tape_row_bytes(h->d, act_dtype), split, h->direct_state_only, &h->error);
     if (rc != FLEET_OK) return rc;
     h->dq_key = key;
   }
@@ -152,22 +152,55 @@ int fleet_direct_split_plan(uint32_t grid_workgroups, int split, uint32_t part_g
   return parts;
 }
 
+// What the launch planner reads of a described launch (fleet_step_instance, fleet_step_has_state_only): the arguments checked in ONE
+// place, then a FleetDev with only those fields filled in.  false: an argument out of range.
+static bool described_launch(int num_envs, int num_cars, int deg_mode, int real_time, int log_data, int act_mode, int K, FleetDev* d) {
+  if (num_envs < 1 || num_cars < 1 || num_cars > 65535 || deg_mode < FLEET_DEG_NONE || deg_mode > FLEET_DEG_RAINFLOW ||
+      act_mode < FLEET_ACT_F32 || act_mode > FLEET_ACT_POLICY_NIGHT || K < 1)
+    return false;
+  static int32_t log_on;  // the selection only asks whether the log exists
+  *d = FleetDev{};
+  d->E = num_envs;
+  d->N = num_cars;
+  d->deg_mode = deg_mode;
+  d->real_time = real_time != 0;
+  d->log_pos = log_data ? &log_on : nullptr;
+  return true;
+}
+
 int fleet_step_instance(int num_envs, int num_cars, int deg_mode, int real_time, int log_data, int act_mode, int K,
                         int has_done_count, char* name, size_t name_bytes, uint32_t* grid) {
-  if (num_envs < 1 || num_cars < 1 || num_cars > 65535 || deg_mode < FLEET_DEG_NONE || deg_mode > FLEET_DEG_RAINFLOW ||
-      act_mode < FLEET_ACT_F32 || act_mode > FLEET_ACT_POLICY_NIGHT || K < 1 || !name || name_bytes < 1 || !grid)
+  FleetDev d;
+  if (!name || name_bytes < 1 || !grid || !described_launch(num_envs, num_cars, deg_mode, real_time, log_data, act_mode, K, &d))
     return FLEET_ERR_INVALID;
-  static int32_t log_on;  // the selection only asks whether the log exists
-  FleetDev d{};
-  d.E = num_envs;
-  d.N = num_cars;
-  d.deg_mode = deg_mode;
-  d.real_time = real_time != 0;
-  d.log_pos = log_data ? &log_on : nullptr;
   unsigned g = 0;
   const int n = fleet_describe_step_instance(d, act_mode, K, has_done_count != 0, name, name_bytes, &g);
   *grid = g;
   return (n < 0 || (size_t)n >= name_bytes) ? FLEET_ERR_INVALID : FLEET_OK;
+}
+
+int fleet_set_direct_state_only(fleet_handle h, int on) {
+  if (!h) return FLEET_ERR_INVALID;
+  FLEET_ENTER(h);
+  if (h->direct_state_only != (on != 0)) {
+    h->direct_state_only = (on != 0);
+    h->gen += 1;  // the prepared argument blocks go with a choice of kernel objects: rebuilt at the next run
+  }
+  return FLEET_OK;
+}
+
+int fleet_direct_packet_counts(fleet_handle h, uint64_t* live, uint64_t* state_only) {
+  if (!h) return FLEET_ERR_INVALID;
+  fleet_direct_packets(h->direct, live, state_only);
+  return FLEET_OK;
+}
+
+int fleet_step_has_state_only(int num_envs, int num_cars, int deg_mode, int real_time, int log_data, int act_mode, int K,
+                              int has_done_count, int32_t* has_twin) {
+  FleetDev d;
+  if (!has_twin || !described_launch(num_envs, num_cars, deg_mode, real_time, log_data, act_mode, K, &d)) return FLEET_ERR_INVALID;
+  *has_twin = fleet_step_has_twin(d, act_mode, K, has_done_count != 0) ? 1 : 0;
+  return FLEET_OK;
 }
 
 int fleet_debug_direct_fault(fleet_handle h, int kind, int tape_row) {

@@ -496,8 +496,9 @@ int fleet_timer_read(fleet_handle h, float* elapsed_ms);
  *                        fleet_stream_query reports it.  What a run writes: the state after all its steps, and `obs`, `reward`
  *                        and `done` of its LAST step.  Since nothing is visible before the run has completed, the observation
  *                        rows of the steps before the last -- which the last one overwrites -- are not stored at all (their
- *                        launches skip the observation arithmetic and stores; rewards and done flags are still written by
- *                        every launch).  A caller that needs every step's observation uses fleet_step_dev or another mode.
+ *                        launches skip the observation arithmetic and stores; with one EV per lane also the reward and done
+ *                        stores, see fleet_set_direct_state_only).  A caller that needs every step's observation uses
+ *                        fleet_step_dev or another mode.
  *                        Single-step configurations only (no real_time, no data log);
  *                        needs libfleet_hip.gfx950.hsaco beside the library (fleetrl_amd.build).  */
 #define FLEET_LAUNCH_EAGER 0
@@ -536,6 +537,23 @@ int fleet_step_instance(int num_envs, int num_cars, int deg_mode, int real_time,
 /* Up to this many EVs per env every EV has a lane of its own (groups of up to four wavefronts per env); beyond it the lanes of one
  * wavefront walk several EVs each. */
 int fleet_max_evs_per_lane_group(void);
+/* State-only launches of a run on the library's own queue (fleet_direct.hip; DESIGN.md section 4 "What a run writes").
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * Of a FLEET_LAUNCH_DIRECT run only the last launch's outputs can be read.  Where every EV has a lane of its own and an env is one,
+ * two or four whole wavefronts (33..256 EVs per env: groups of 64, 128 or 256 lanes), the single-step kernel has a state-only
+ * twin, compiled without anything that feeds `obs`, `reward`, `done` or the cashflow, and every packet of a run but its last takes
+ * it.  Results are bit for bit those of the live instance with the run-time flag.
+ * fleet_set_direct_state_only: on != 0 (the default) uses the twin where there is one; 0 keeps the live instance for every packet
+ * (A/B measurements, tests).  Waits for the handle's run in flight; the prepared argument blocks are rebuilt at the next run.
+ * fleet_direct_packet_counts: packets the handle's queue was given so far with the live instance and with the twin (either pointer
+ * may be NULL; zeros before the first direct run).
+ * fleet_step_has_state_only: whether a launch of this kind has a twin -- a pure function of fleet_step_instance's arguments, no
+ * device needed; *has_twin = 1 exactly for single-step launches (K = 1, no done_count, an action buffer, no real_time, no data
+ * log) of groups of 64, 128 or 256 lanes with one EV per lane.  FLEET_ERR_INVALID for the arguments fleet_step_instance refuses. */
+int fleet_set_direct_state_only(fleet_handle h, int on);
+int fleet_direct_packet_counts(fleet_handle h, uint64_t* live, uint64_t* state_only);
+int fleet_step_has_state_only(int num_envs, int num_cars, int deg_mode, int real_time, int log_data, int act_mode, int K,
+                              int has_done_count, int32_t* has_twin);
 /* TEST HOOK for the placement guard (the handle must have run through its own queue before) --
  * kind 1: the handle's NEXT run gets a placement record shifted by one workgroup: what its launches would see if the queue's first
  *         die had moved in the middle of the run;

@@ -11,7 +11,7 @@ for line in sys.stdin:
         if m and cur is not None and ' '+k in line: cur[k]=int(m.group(1))
     if cur and 'LDS Size [bytes/block]' in cur:
         n=cur['name']
-        m=re.search(r'fleet_step_kernelILi(\d+)ELi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELi(\d)E',n)
-        if m: print('step<G=%s,DEG=%s,MULTI=%s,WIDE=%s,LOG=%s,A64=%s,MODE=%s> vgpr=%d agpr=%d sgpr=%d scratch=%d occ=%d'%(*m.groups(),cur.get('VGPRs',-1),cur.get('AGPRs',-1),cur.get('TotalSGPRs',-1),cur.get('ScratchSize [bytes/lane]',-1),cur.get('Occupancy [waves/SIMD]',-1)))
+        m=re.search(r'fleet_step_kernelILi(\d+)ELi(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELi(\d)ELb(\d)E',n)  # (DEAD=1: the state-only twin)
+        if m: print('step<G=%s,DEG=%s,MULTI=%s,WIDE=%s,LOG=%s,A64=%s,MODE=%s,DEAD=%s> vgpr=%d agpr=%d sgpr=%d scratch=%d occ=%d'%(*m.groups(),cur.get('VGPRs',-1),cur.get('AGPRs',-1),cur.get('TotalSGPRs',-1),cur.get('ScratchSize [bytes/lane]',-1),cur.get('Occupancy [waves/SIMD]',-1)))
         cur=None
 "

@@ -7,7 +7,7 @@ python3 - $OUT <<'PY' | tee $R/gpurun_out/r06/launch_by_episode_step.log
 import glob, sys
 import numpy as np, pandas as pd
 c = pd.read_csv(glob.glob(f"{sys.argv[1]}/kt/*/*kernel_trace.csv")[0])
-c = c[c.Kernel_Name.str.contains(r"fleet_step_kernel<\d+, \d+, false,", regex=True)].sort_values("Start_Timestamp")
+c = c[c.Kernel_Name.str.contains(r"fleet_step_kernel<\d+, \d+, false,", regex=True)].sort_values("Start_Timestamp")  # the single-step instances, the state-only twins (<..., 0, true>: a direct run's dead launches) among them
 d = (c.End_Timestamp - c.Start_Timestamp).to_numpy().astype(float)
 gap = np.r_[1e9, (c.Start_Timestamp.to_numpy()[1:] - c.End_Timestamp.to_numpy()[:-1]).astype(float)]
 # runs of launches (a gap above 200 us starts a new one: another phase of the bench); keep those of at least two episodes

@@ -15,6 +15,6 @@ f = glob.glob(f"{sys.argv[1]}/pmc/*/*counter_collection.csv")
 if not f:
     print("no counter output:"); print(open(f"{sys.argv[1]}/bench.log").read()[-1500:]); sys.exit(0)
 c = pd.read_csv(f[0])
-c = c[c.Kernel_Name.str.contains(r"fleet_step_kernel<\d+, \d+, %s," % os.environ.get("FLEET_PROF_MULTI", "false"), regex=True)]
+c = c[c.Kernel_Name.str.contains(r"fleet_step_kernel<\d+, \d+, %s," % os.environ.get("FLEET_PROF_MULTI", "false"), regex=True)]  # (FLEET_PROF_MULTI=false: the single-step instances, the state-only twins <..., 0, true> among them)
 print(c.groupby("Counter_Name").Counter_Value.median().to_string())
 PY

@@ -8,7 +8,7 @@ import glob, sys, pandas as pd
 out = sys.argv[1]
 for p in ("a", "b"):
     c = pd.read_csv(glob.glob(f"{out}/{p}/*/*counter_collection.csv")[0])
-    c = c[c.Kernel_Name.str.contains(r"fleet_step_kernel<\d+, \d+, false,", regex=True)]
+    c = c[c.Kernel_Name.str.contains(r"fleet_step_kernel<\d+, \d+, false,", regex=True)]  # the single-step instances, the state-only twins (<..., 0, true>: a direct run's dead launches) among them
     med = c.groupby("Counter_Name").Counter_Value.median()
     w = med["SQ_WAVES"]
     print((med / w).round(1).to_string())

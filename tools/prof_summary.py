@@ -20,6 +20,6 @@ for f in ("pmc1", "pmc2"):
     if not files:
         continue
     c = pd.read_csv(files[0])
-    c = c[c.Kernel_Name.str.contains(r"fleet_step_kernel<\d+, \d+, false,", regex=True)]  # the single-step instances
+    c = c[c.Kernel_Name.str.contains(r"fleet_step_kernel<\d+, \d+, false,", regex=True)]  # the single-step instances, the state-only twins (<..., 0, true>: a direct run's dead launches) among them
     med = c.groupby("Counter_Name").Counter_Value.median()
     print(med.to_string())
