@@ -1,21 +1,18 @@
 #!/usr/bin/env python3
-"""The TD3 loop of examples/td3_device_loop.py with the two blocks of a gradient step that need no gradient moved into the library:
-the target networks live in a `DeviceTD3Target`, which computes the bootstrap target of the minibatch in ONE launch (smoothing
-noise and its clip, the target actor, the clip of the next action, both target critics, the min, r + (1 - d) * gamma * q) and
-the Polyak update of all three networks in ONE launch.  What torch still does in a gradient step: the two losses, their backward
-passes and the optimiser steps.  Measured: with these 64-64 trunks the target launch takes 79 us against
-303 us of eager torch at a batch of 256; with 400-300 trunks it is 7 % to 25 % SLOWER than eager torch, and the Polyak launch is
-level with the `lerp_` loop below it replaces but 4 to 6 times slower than `torch._foreach_lerp_`.
-examples/td3_device_grad.py moves the two backward passes into the library as well (`DeviceTD3Grad`).
+"""The TD3 loop of examples/td3_device_targets.py with both backward passes of a gradient step moved into the library too: a second
+`DeviceTD3Target` holds the ONLINE actor and critics, and a `DeviceTD3Grad` on it computes the critic loss with its gradients
+(`critic_grad`: two launches) and, on every `policy_delay`-th step, the actor loss with its gradients (`actor_grad`: two launches)
+straight into the `.grad` of torch's own parameters.  What torch still does in a gradient step: the two optimiser steps, each
+followed by one `load_torch` launch that refreshes the online image.  The step is deterministic: no atomics, every sum in a stated
+order.  Measured (profiles/td3_grad_rate.json).
 
 Per env step: the actor reads the normalised observations, Gaussian noise from torch.randn explores, the env and the normaliser
-step on the device, and `add` stores the RAW transition (`FleetVecNormalize.original_torch()`: SB3's off-policy loop keeps the
-original observations and rewards) in one launch.  Per gradient step: `sample` draws the minibatch's indices on the device, gathers
-the rows and normalises them with the statistics of that moment -- one launch.  No tensor crosses to the host inside the loop.
-It shows that the pieces fit -- it is not a tuned trainer.  Needs an MI355X; inputs are synthetic:
+step on the device, and `add` stores the RAW transition in one launch.  Per gradient step: `sample` draws and gathers the minibatch
+in one launch, `target` computes the bootstrap target in one launch.  No tensor crosses to the host inside the loop.  It shows that the
+pieces fit -- it is not a tuned trainer.  Needs an MI355X; inputs are synthetic:
 
-    python examples/td3_device_targets.py [--steps 200] [--envs 256] [--evs 5] [--buffer-size 100000] [--batch-size 256]
-                                          [--learning-starts 20] [--gradient-steps 1] [--log-interval 50]
+    python examples/td3_device_grad.py [--steps 200] [--envs 256] [--evs 5] [--buffer-size 100000] [--batch-size 256]
+                                       [--learning-starts 20] [--gradient-steps 1] [--log-interval 50]
 
 Prints one JSON line per logging interval.
 """
@@ -29,7 +26,7 @@ from torch import nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import bench_config  # noqa: E402  (the reference's config dict with the benchmark's values)
-from fleetrl_amd import DeviceReplayBuffer, DeviceTD3Target, FleetVecEnv, FleetVecNormalize  # noqa: E402
+from fleetrl_amd import DeviceReplayBuffer, DeviceTD3Grad, DeviceTD3Target, FleetVecEnv, FleetVecNormalize  # noqa: E402
 from fleetrl_amd.synth import synth_tables  # noqa: E402
 
 
@@ -77,6 +74,11 @@ def main():
     # the targets start as copies of the online networks; `online` is what polyak() reads: W, b per layer, actor, q1, q2
     targets = DeviceTD3Target(linear_layers(actor), [linear_layers(critics.q1), linear_layers(critics.q2)], activation="relu", output="tanh")
     online = [*actor.parameters(), *critics.q1.parameters(), *critics.q2.parameters()]
+    # the networks that are differentiated: a second image, refreshed from `online` after every optimiser step
+    nets = DeviceTD3Target(linear_layers(actor), [linear_layers(critics.q1), linear_layers(critics.q2)], activation="relu", output="tanh")
+    grad = DeviceTD3Grad(nets, args.batch_size)
+    actor_params, critic_params = list(actor.parameters()), [*critics.q1.parameters(), *critics.q2.parameters()]
+    critic_stats, actor_stats = torch.zeros(8, device=dev), torch.zeros(8, device=dev)
     sigma = torch.full((N,), 0.2, device=dev)  # the target-policy smoothing noise's scale
     opt_a, opt_c = torch.optim.Adam(actor.parameters(), lr=1e-3), torch.optim.Adam(critics.parameters(), lr=1e-3)
     buf = DeviceReplayBuffer(args.buffer_size, E, D, N, seed=args.seed)
@@ -89,7 +91,6 @@ def main():
     env.reset_torch(obs_out=obs)
     last_raw.copy_(env.original_torch().obs)
     updates = 0
-    q_loss = a_loss = torch.zeros((), device=dev)
     reward_sum = torch.zeros((), device=dev, dtype=torch.float64)
 
     for step in range(1, args.steps + 1):
@@ -106,25 +107,26 @@ def main():
                 b = buf.sample(args.batch_size, env=env)  # normalised with the statistics as they are now
                 # one launch; a seed of its own (the exploration above draws from torch's generator), the update count as the step
                 target_q = targets.target(b.next_observations, b.rewards, b.dones, gamma=gamma, sigma=sigma, noise_clip=noise_clip,
-                                          seed=args.seed + 0x7A46E7, step=updates).view_as(b.rewards)
-                q1, q2 = critics(b.observations, b.actions)
-                q_loss = nn.functional.mse_loss(q1, target_q) + nn.functional.mse_loss(q2, target_q)
-                opt_c.zero_grad(set_to_none=True)
-                q_loss.backward()
+                                          seed=args.seed + 0x7A46E7, step=updates)
+                # both MSE losses and their backward: two launches into the critics' .grad (overwritten: nothing to zero)
+                grad.critic_grad(b, target_q, into=critic_params, stats_out=critic_stats)
                 opt_c.step()
+                nets.load_torch(online)  # one launch: the image follows the optimiser
                 updates += 1
                 if updates % policy_delay == 0:
-                    a_loss = -critics.q1(torch.cat([b.observations, actor(b.observations)], dim=1)).mean()
-                    opt_a.zero_grad(set_to_none=True)
-                    a_loss.backward()
+                    # -mean(Q_0(obs, actor(obs))) and its backward into the actor: two launches
+                    grad.actor_grad(b.observations, into=actor_params, stats_out=actor_stats)
                     opt_a.step()
+                    nets.load_torch(online)
                     targets.polyak(online, tau)  # one launch for the actor and both critics
 
         if step % args.log_interval == 0 or step == args.steps:
             buf.check_errors()
             # the only transfers: a few numbers for the log
-            print(json.dumps({"step": step, "transitions": buf.size() * E, "updates": updates, "critic_loss": q_loss.item(),
-                              "actor_loss": a_loss.item(), "mean_raw_reward": (reward_sum / step).item()}), flush=True)
+            print(json.dumps({"step": step, "transitions": buf.size() * E, "updates": updates, "critic_loss": critic_stats[0].item(),
+                              "actor_loss": actor_stats[0].item(), "mean_raw_reward": (reward_sum / step).item()}), flush=True)
+    grad.close()
+    nets.close()
     targets.close()
     buf.close()
     env.close()

@@ -8,6 +8,7 @@
     from fleetrl_amd import DevicePinkNoise, DeviceOUNoise
     from fleetrl_amd import DeviceTD3Target
     from fleetrl_amd import DevicePPOGrad
+    from fleetrl_amd import DeviceTD3Grad
 """
 __version__ = "0.1.0"
 
@@ -49,6 +50,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import ppo
 
         return ppo.DevicePPOGrad
+    if name == "DeviceTD3Grad":
+        from . import td3
+
+        return td3.DeviceTD3Grad
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

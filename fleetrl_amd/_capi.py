@@ -210,6 +210,21 @@ class FleetPpoGradArgs(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+# ---- TD3 / DDPG minibatch gradients (include/fleet_hip.h "TD3 / DDPG minibatch gradients on the device", fleet_td3_*) -------------------
+class FleetTd3Params(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("max_batch", C.c_int32)]
+
+
+class FleetTd3CriticArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("B", C.c_int32), ("obs", C.c_void_p), ("actions", C.c_void_p), ("target_q", C.c_void_p),
+                ("q", C.c_void_p), ("stats", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+class FleetTd3ActorArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("B", C.c_int32), ("obs", C.c_void_p), ("actions_out", C.c_void_p), ("q", C.c_void_p),
+                ("stats", C.c_void_p), ("reserved", C.c_uint64)]
+
+
 # ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
 STATE_MAGIC = 0x4554415453544C46
 STATE_ALIGN = 256
@@ -489,8 +504,16 @@ def load_library():
     lib.fleet_ppo_last_error.argtypes = [vp]
     lib.fleet_ppo_describe.argtypes = [vp, C.POINTER(FleetPpoParams), C.POINTER(C.c_uint64), i32p]
     lib.fleet_ppo_grad_dev.argtypes = [vp, C.POINTER(FleetPpoGradArgs), C.POINTER(vp), C.c_int]
+    # TD3's minibatch gradients (fleet_td3.hip)
+    lib.fleet_td3_create.argtypes = [vp, C.POINTER(FleetTd3Params), C.POINTER(vp)]
+    lib.fleet_td3_destroy.argtypes = [vp]
+    lib.fleet_td3_last_error.argtypes = [vp]
+    lib.fleet_td3_describe.argtypes = [vp, C.POINTER(FleetTd3Params), C.POINTER(C.c_uint64), i32p]
+    lib.fleet_td3_critic_grad_dev.argtypes = [vp, C.POINTER(FleetTd3CriticArgs), C.POINTER(vp), C.c_int]
+    lib.fleet_td3_actor_grad_dev.argtypes = [vp, C.POINTER(FleetTd3ActorArgs), C.POINTER(vp), C.c_int]
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
-                          ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS), ("ppo", PPO_SYMBOLS)):
+                          ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS), ("ppo", PPO_SYMBOLS),
+                          ("td3", TD3_SYMBOLS)):
         for name in names:
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
@@ -549,6 +572,9 @@ QTARGET_SYMBOLS = (
 
 PPO_SYMBOLS = ("fleet_ppo_create", "fleet_ppo_destroy", "fleet_ppo_last_error", "fleet_ppo_describe", "fleet_ppo_grad_dev")
 
+TD3_SYMBOLS = ("fleet_td3_create", "fleet_td3_destroy", "fleet_td3_last_error", "fleet_td3_describe", "fleet_td3_critic_grad_dev",
+               "fleet_td3_actor_grad_dev")
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -562,7 +588,7 @@ EXPORTED_SYMBOLS = (
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
     "fleet_set_direct_state_only", "fleet_direct_packet_counts", "fleet_step_has_state_only",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

@@ -2,7 +2,8 @@
 // what stable-baselines3's PPO.train computes per minibatch with evaluate_actions, the clipped loss and loss.backward(), in two
 // launches on the policy's stream.  The handle borrows the weight image of a two-head policy (fleet_mlp.h) and owns a scratch.
 //   ppo_rows   grid (ceil(B / 16), 2), 256 threads: the policy's tile.  A workgroup takes 16 rows through one head with the chain of
-//              fleet_policy_dev.h (stage, accumulate, hidden_act as they are); its layer function also stores every hidden
+//              fleet_policy_dev.h (stage, accumulate, hidden_act as they are); its layer function (fleet_grad_dev.h, shared with
+//              fleet_td3.hip, as are the backward layer, the compensated sum and the weights launch's tile) also stores every hidden
 //              activation to the scratch.  The last layer leaves its rows untransformed in the LDS.  Head 0's epilogue forms the
 //              log-probability terms with sample_epilogue's expression and sums them in its order, then the row's ratio, clip and
 //              d loss / d log-probability; head 1's forms d loss / d value.  The SAME workgroup then walks back through its layers:
@@ -22,31 +23,19 @@
 #include <cmath>
 #include <string>
 
+#include "fleet_grad_dev.h"
 #include "fleet_mlp.h"
 #include "fleet_policy.h"
 #include "fleet_policy_dev.h"
 
 namespace {
 
-constexpr int kGradTile = 32;   // ppo_weights: a workgroup's tile of dW is 32 x 32
-constexpr int kGradRows = 16;   // ... and it stages this many rows at a time
 constexpr int kPartStride = 8;  // floats per tile in part[][]: policy term, squared value error, kl term, clipped rows
 
 struct PpoScratch {  // offsets in floats from the scratch's start
   uint64_t act[FLEET_POLICY_MAX_HEADS][FLEET_POLICY_MAX_LAYERS];
   uint64_t delta[FLEET_POLICY_MAX_HEADS][FLEET_POLICY_MAX_LAYERS];
   uint64_t ls, part, floats;
-};
-
-// the statistics' sums are compensated (Neumaier): s + c is the sum of the terms so far to within a rounding of the result
-struct CompSum {
-  float s = 0.0f, c = 0.0f;
-  __device__ __forceinline__ void add(float x) {
-    const float t = s + x;
-    c += fabsf(s) >= fabsf(x) ? (s - t) + x : (x - t) + s;
-    s = t;
-  }
-  __device__ __forceinline__ float value() const { return s + c; }
 };
 
 struct RowsArgs {
@@ -59,95 +48,6 @@ struct RowsArgs {
   int B, T;
   float clip, vf_coef, invB;
 };
-
-// run_layer of fleet_policy_dev.h with two changes: a hidden layer's activations also go to gact[row][out64] (rows below B), and a
-// last layer leaves y, untransformed, in out[][] (every row and column of the tile)
-template <int R>
-__device__ __forceinline__ void ppo_layer(const ForwardArgs& a, const PolicyHeadDesc* H, const PolicyLayer& L, bool first, bool last,
-                                          const float* in, float* out, float* xs, int S, int row0, float* gact) {
-  constexpr int kSplit = kPolicyRows / R;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int units = (L.out64 / 64) * kSplit;
-  const bool has0 = w < units, has1 = w + kPolicyWaves < units;
-  const int q = w % kSplit;
-  const int j0 = (w / kSplit) * 64 + lane, j1 = ((w + kPolicyWaves) / kSplit) * 64 + lane;
-  float acc0[R], acc1[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) acc0[r] = acc1[r] = 0.0f;
-  const float* W = a.base + L.w_off;
-  if (first) {
-    for (int k0 = 0; k0 < L.in; k0 += kPolicyChunk) {
-      const int kn = L.in4 - k0 < kPolicyChunk ? L.in4 - k0 : kPolicyChunk;
-      __syncthreads();
-      stage<kStagePlain>(a, xs, row0, k0, L.in, StageTail{});
-      __syncthreads();
-      const float* x = xs + q * R * kPolicyChunk;
-      const float* wk = W + (size_t)k0 * L.out64;
-      if (has1) accumulate<R, true>(x, kPolicyChunk, kn, wk, L.out64, j0, j1, acc0, acc1);
-      else if (has0) accumulate<R, false>(x, kPolicyChunk, kn, wk, L.out64, j0, j1, acc0, acc1);
-    }
-  } else if (has1) {
-    accumulate<R, true>(in + q * R * S, S, L.in4, W, L.out64, j0, j1, acc0, acc1);
-  } else if (has0) {
-    accumulate<R, false>(in + q * R * S, S, L.in4, W, L.out64, j0, j1, acc0, acc1);
-  }
-  const int activation = H->activation;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    if (!(u ? has1 : has0)) continue;
-    const int j = u ? j1 : j0;
-    const float b = a.base[L.b_off + j];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const float y = (u ? acc1[r] : acc0[r]) + b;
-      const int rr = q * R + r;
-      if (last) {
-        out[rr * S + j] = y;
-      } else {
-        const float hval = hidden_act(y, activation);
-        out[rr * S + j] = hval;
-        if (row0 + rr < a.E) gact[(size_t)(row0 + rr) * L.out64 + j] = hval;  // (j < out64: inside the row)
-      }
-    }
-  }
-}
-
-// delta of layer l, d[16][S] in the LDS (zero past `out`) -> delta of layer l - 1 into p[16][S] (zero from `in` to the previous
-// layer's out64) and into gdelta[row][out64 of layer l - 1]; hprev: that layer's activations in the scratch
-__device__ __forceinline__ void ppo_back_layer(const float* base, const PolicyLayer& L, int prev64, int activation, const float* d, float* p,
-                                               int S, int row0, int B, const float* hprev, float* gdelta) {
-  const float* W = base + L.w_off;
-  const int out4 = (L.out + 3) & ~3;  // (<= out64; the columns out .. out4 - 1 of Wt and of d are zero: they add +0)
-  for (int k = threadIdx.x; k < prev64; k += kPolicyThreads) {
-    float acc[kPolicyRows];
-#pragma unroll
-    for (int r = 0; r < kPolicyRows; ++r) acc[r] = 0.0f;
-    if (k < L.in) {
-      const float* wk = W + (size_t)k * L.out64;
-      for (int j = 0; j < out4; j += 4) {
-        const float4 w4 = *reinterpret_cast<const float4*>(wk + j);  // (out64 is a multiple of 64: aligned)
-#pragma unroll
-        for (int r = 0; r < kPolicyRows; ++r) {
-          const float4 d4 = *reinterpret_cast<const float4*>(d + r * S + j);
-          acc[r] = fmaf(w4.w, d4.w, fmaf(w4.z, d4.z, fmaf(w4.y, d4.y, fmaf(w4.x, d4.x, acc[r]))));
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < kPolicyRows; ++r) {
-      const int row = row0 + r;
-      float v = 0.0f;
-      if (k < L.in && row < B) {
-        const float hv = hprev[(size_t)row * prev64 + k];
-        const float g = activation == FLEET_POLICY_ACT_RELU ? (hv > 0.0f ? 1.0f : 0.0f) : fmaf(-hv, hv, 1.0f);
-        v = acc[r] * g;
-        gdelta[(size_t)row * prev64 + k] = v;
-      }
-      p[r * S + k] = v;
-    }
-  }
-}
 
 __global__ __launch_bounds__(kPolicyThreads) void ppo_rows(RowsArgs t) {
   extern __shared__ float lds[];  // two buffers [16][T], the staged input [16][kPolicyChunk], the rows' scalars [4][16]
@@ -162,18 +62,7 @@ __global__ __launch_bounds__(kPolicyThreads) void ppo_rows(RowsArgs t) {
   ForwardArgs a{};
   a.base = t.base, a.obs = t.obs, a.E = B;
   // ---- forward ----
-  for (int l = 0; l < n; ++l) {
-    const PolicyLayer L = H->layer[l];
-    const int groups = L.out64 / 64;
-    float* gact = t.scratch + t.s.act[head][l];
-    if (groups >= 4) ppo_layer<16>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gact);
-    else if (groups >= 2) ppo_layer<8>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gact);
-    else ppo_layer<4>(a, H, L, l == 0, l == n - 1, cur, nxt, xs, S, row0, gact);
-    __syncthreads();
-    float* tmp = cur;
-    cur = nxt;
-    nxt = tmp;
-  }
+  grad_head<kStagePlain>(a, H, cur, nxt, xs, S, row0, t.scratch, t.s.act[head], StageTail{});
   // cur: y[16][S] of the last layer; nxt is free
   const PolicyLayer LL = H->layer[n - 1];
   float* gdl = t.scratch + t.s.delta[head][n - 1];
@@ -265,24 +154,11 @@ __global__ __launch_bounds__(kPolicyThreads) void ppo_rows(RowsArgs t) {
     }
   }
   __syncthreads();
-  // ---- backward: layer l's delta in cur -> layer l - 1's in nxt ----
-  for (int l = n - 1; l >= 1; --l) {
-    const PolicyLayer L = H->layer[l];
-    const int prev64 = H->layer[l - 1].out64;
-    ppo_back_layer(t.base, L, prev64, H->activation, cur, nxt, S, row0, B, t.scratch + t.s.act[head][l - 1], t.scratch + t.s.delta[head][l - 1]);
-    __syncthreads();
-    float* tmp = cur;
-    cur = nxt;
-    nxt = tmp;
-  }
+  // ---- backward: layer l's delta in cur -> layer l - 1's in nxt, and to the scratch ----
+  grad_back_head<true>(t.base, H, cur, nxt, S, row0, B, t.scratch, t.s.act[head], t.s.delta[head]);
 }
 
 // ---- ppo_weights ---------------------------------------------------------------------------------------------------------------------
-struct GradEntry {  // one layer: dW[out][in] and db[out] from delta[B][dstride] and the layer's input x[B][xstride]
-  const float *d, *x;
-  float *dW, *db;
-  int out, in, dstride, xstride, tiles_k, first;  // first: the layer's first workgroup
-};
 constexpr int kMaxEntries = FLEET_POLICY_MAX_HEADS * FLEET_POLICY_MAX_LAYERS;
 
 struct WeightArgs {
@@ -298,45 +174,8 @@ __global__ __launch_bounds__(256) void ppo_weights(WeightArgs a) {
   __shared__ float ds[kGradRows][kGradTile], xs[kGradRows][kGradTile];
   const int bid = blockIdx.x, B = a.B;
   if (bid < a.tile_blocks) {
-    int ei = 0;
-    while (ei + 1 < a.n_entries && bid >= a.e[ei + 1].first) ++ei;
-    const GradEntry& E = a.e[ei];
-    const int tile = bid - E.first;
-    const int j0 = (tile / E.tiles_k) * kGradTile, k0 = (tile % E.tiles_k) * kGradTile;
-    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-    float a00 = 0.0f, a01 = 0.0f, a10 = 0.0f, a11 = 0.0f, bs0 = 0.0f, bs1 = 0.0f;
-    for (int b0 = 0; b0 < B; b0 += kGradRows) {
-      const int nb = B - b0 < kGradRows ? B - b0 : kGradRows;
-      __syncthreads();  // the readers of the rows before are done
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int idx = threadIdx.x + 256 * i;
-        const int r = idx >> 5, c = idx & 31;
-        float dv = 0.0f, xv = 0.0f;
-        if (r < nb) {
-          if (j0 + c < E.out) dv = E.d[(size_t)(b0 + r) * E.dstride + j0 + c];
-          if (k0 + c < E.in) xv = E.x[(size_t)(b0 + r) * E.xstride + k0 + c];
-        }
-        ds[r][c] = dv, xs[r][c] = xv;
-      }
-      __syncthreads();
-      for (int r = 0; r < nb; ++r) {
-        const float d0 = ds[r][ty], d1 = ds[r][ty + 16], x0 = xs[r][tx], x1 = xs[r][tx + 16];
-        a00 = fmaf(d0, x0, a00), a01 = fmaf(d0, x1, a01), a10 = fmaf(d1, x0, a10), a11 = fmaf(d1, x1, a11);
-        bs0 += d0, bs1 += d1;
-      }
-    }
-    const int ja = j0 + ty, jb = j0 + ty + 16, ka = k0 + tx, kb = k0 + tx + 16;
-    if (ja < E.out) {
-      if (ka < E.in) E.dW[(size_t)ja * E.in + ka] = a00;
-      if (kb < E.in) E.dW[(size_t)ja * E.in + kb] = a01;
-      if (k0 == 0 && tx == 0) E.db[ja] = bs0;
-    }
-    if (jb < E.out) {
-      if (ka < E.in) E.dW[(size_t)jb * E.in + ka] = a10;
-      if (kb < E.in) E.dW[(size_t)jb * E.in + kb] = a11;
-      if (k0 == 0 && tx == 0) E.db[jb] = bs1;
-    }
+    const GradEntry& E = a.e[grad_entry_of(a.e, a.n_entries, bid)];
+    grad_tile<false>(E, bid - E.first, B, ds, xs);
   } else if (bid < a.tile_blocks + a.ls_blocks) {
     const int j = (bid - a.tile_blocks) * 256 + (int)threadIdx.x;
     if (j < a.A) {
@@ -505,12 +344,11 @@ int fleet_ppo_grad_dev(fleet_ppo_handle h, const FleetPpoGradArgs* args, float* 
       const PolicyLayer& L = nets[hd].layer[l];
       GradEntry& E = g.e[g.n_entries++];
       E.d = h->scratch + h->s.delta[hd][l], E.dstride = L.out64;
+      E.seam = L.in;  // (one input array)
       if (l == 0) E.x = x.obs, E.xstride = L.in;
       else E.x = h->scratch + h->s.act[hd][l - 1], E.xstride = nets[hd].layer[l - 1].out64;
       E.dW = grads[ti], E.db = grads[ti + 1], E.out = L.out, E.in = L.in;
-      E.tiles_k = (L.in + kGradTile - 1) / kGradTile;
-      E.first = blocks;
-      blocks += ((L.out + kGradTile - 1) / kGradTile) * E.tiles_k;
+      grad_entry_tiles(E, &blocks);
     }
   const PolicyLayer& LA = nets[0].layer[nets[0].n_layers - 1];
   g.tile_blocks = blocks, g.ls_blocks = (LA.out + 255) / 256, g.B = B;

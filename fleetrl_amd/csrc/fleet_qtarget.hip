@@ -23,18 +23,9 @@
 #include "fleet_philox.h"
 #include "fleet_policy.h"
 #include "fleet_policy_dev.h"
+#include "fleet_qtarget.h"
 
 namespace {
-
-constexpr int kQNets = kMlpMaxNets;  // actor, critic 0, critic 1
-
-struct QTargetDesc {
-  int32_t obs_dim, act_dim, n_critics;
-  int32_t stride;  // floats between rows of an activation buffer: the widest hidden layer's out64 over all networks (64 without one)
-  int32_t act64;   // floats between rows of act[][]: the actor's last out64
-  int32_t reserved[3];
-  PolicyHeadDesc net[kQNets];
-};
 
 struct TargetArgs {
   const QTargetDesc* desc;

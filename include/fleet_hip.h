@@ -1133,6 +1133,83 @@ int fleet_qtarget_target_dev(fleet_qtarget_handle h, const float* next_obs, cons
 /* the parameters the handle was created with, and tile_rows */
 int fleet_qtarget_describe(fleet_qtarget_handle h, FleetQTargetParams* out);
 
+/* ---- TD3 / DDPG minibatch gradients on the device (fleet_td3.hip; DESIGN.md "TD3's minibatch gradients on the device") -------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * What stable-baselines3 2.3.2's TD3.train does with one minibatch between the target and the optimisers, in two entries of TWO
+ * launches each: the critic loss sum_c mse_loss(Q_c(obs, actions), y) with its backward, and -- on a delayed step -- the actor loss
+ * -mean(Q_0(obs, pi(obs))) with its backward into the actor.  The networks are the ONLINE ones: the handle BORROWS the weight image of a
+ * fleet_qtarget handle created from the online actor and critics (a second one beside the targets'), which the caller refreshes with
+ * fleet_qtarget_load_dev after every optimiser step and which must outlive this handle.  float32 throughout, no fused contraction but
+ * the fmaf written below, no atomics, no random numbers.  invB = 1.0f / (float)B.
+ * The critic entry, per row b (obs f32[B,D] and actions f32[B,A] as fleet_replay_sample_dev wrote them, y = target_q f32[B] as
+ * fleet_qtarget_target_dev wrote it), for every critic c, exactly:
+ *   q_c  = critic c over concat(obs[b], actions[b]): the learning targets' chain (acc = 0; fmaf in ascending k over D + A; + bias)
+ *   e_c  = q_c - y[b];  dq_c = (2.0f * invB) * e_c        (the delta of the critic's last layer)
+ * The actor entry, per row b (obs f32[B,D]), exactly:
+ *   mean[j] = the actor's last layer BEFORE its output transform;  a[j] = the transform of mean[j] (x < lo ? lo : (x > hi ? hi : x), tanhf)
+ *   q    = critic 0 over concat(obs[b], a);  dq = -invB;  back through critic 0's layers to its first layer's delta d0
+ *   da[j] = (acc = 0; acc = fmaf(Wt0[D + j][i], d0[i], acc) for i ascending over layer 0's outputs)      (no activation factor)
+ *   dmean[j] = da[j] * g:  g = fmaf(-a, a, 1.0f) (TANH);  g = (mean >= lo && mean <= hi) ? 1 : 0 (CLIP: torch's clamp, the bounds
+ *   inclusive);  g = 1 (NONE)                              (the delta of the actor's last layer)
+ * No critic gradient is produced by the actor entry (SB3 discards it there too), and critic 1 is not run.
+ * Back through layer l into layer l - 1 (h: that layer's activation), in both entries:
+ *   d_prev[k] = (acc = 0; acc = fmaf(Wt[k][j], d[j], acc) for j ascending over the layer's outputs) * act'(h[k]),
+ *   tanh' = fmaf(-h, h, 1.0f), relu' = h > 0 ? 1 : 0
+ * Gradients, each element one chain over the rows in ascending b:
+ *   dW[j][k]: acc = 0; acc = fmaf(d[b][j], x[b][k], acc);  db[j]: acc = 0; acc += d[b][j]
+ *   x: the layer's input; for a critic's first layer column k is obs[b][k] for k < D and actions[b][k - D] behind it
+ * Statistics, stats f32[8].  A tile is 16 consecutive rows; a tile's partial is the COMPENSATED sum of its rows' terms in ascending
+ * order (Neumaier: s = 0, c = 0; per term x: t = s + x; c += |s| >= |x| ? (s - t) + x : (x - t) + s; s = t; the result is s + c), a
+ * total the compensated sum of the tiles' partials in ascending order:
+ *   critic entry: [1] = total(e_0 * e_0) * invB;  [2] = total(e_1 * e_1) * invB, 0 with one critic;  [0] = [1] + [2];  [3..7] 0
+ *   actor entry:  [0] = -(total(q) * invB);  [1..7] 0
+ * Every result is a function of the inputs and B only: not of the stream, of max_batch, of what lies behind row B in the buffers, of
+ * which optional outputs are asked for, or of the run.  The gradient tensors and stats are OVERWRITTEN, not accumulated.  The per-row
+ * outputs (q, actions_out) depend on their row alone: an observation that is not finite stays in its row there; it does reach the
+ * gradients and the statistics, which sum over the rows.  The handle owns a scratch sized for max_batch rows (every layer's
+ * activations and deltas).  It launches on the NETWORKS handle's stream, whichever that is when the call is made: a call enqueued behind
+ * fleet_qtarget_load_dev on that handle sees the new weights with no host wait.  Calls are serialised by the caller. */
+typedef struct FleetTd3Params {
+  int32_t struct_bytes;  /* sizeof(FleetTd3Params) */
+  int32_t max_batch;     /* rows the scratch holds, 1..2^24 */
+} FleetTd3Params;
+typedef struct FleetTd3CriticArgs {
+  int32_t struct_bytes;    /* sizeof(FleetTd3CriticArgs) */
+  int32_t B;               /* rows, 1..max_batch */
+  const float* obs;        /* device f32[B, D] (normalised, as the replay buffer samples them) */
+  const float* actions;    /* device f32[B, A] */
+  const float* target_q;   /* device f32[B]: y */
+  float* q;                /* device f32[B, n_critics] or NULL: q_c */
+  float* stats;            /* device f32[8] */
+  uint64_t reserved;       /* 0 */
+} FleetTd3CriticArgs;
+typedef struct FleetTd3ActorArgs {
+  int32_t struct_bytes;    /* sizeof(FleetTd3ActorArgs) */
+  int32_t B;               /* rows, 1..max_batch */
+  const float* obs;        /* device f32[B, D] */
+  float* actions_out;      /* device f32[B, A] or NULL: a */
+  float* q;                /* device f32[B] or NULL: q */
+  float* stats;            /* device f32[8] */
+  uint64_t reserved;       /* 0 */
+} FleetTd3ActorArgs;
+typedef struct FleetTd3* fleet_td3_handle;
+
+/* FLEET_ERR_INVALID (fleet_td3_last_error(NULL) says why, starting with the entry's name) for a null or wrongly sized FleetTd3Params,
+ * max_batch outside 1..2^24, a null output or networks handle.  FLEET_ERR_HIP with the byte count when the scratch cannot be allocated. */
+int fleet_td3_create(fleet_qtarget_handle nets, const FleetTd3Params* p, fleet_td3_handle* out);
+int fleet_td3_destroy(fleet_td3_handle h);
+const char* fleet_td3_last_error(fleet_td3_handle h);  /* h may be NULL: error of the last failed call without a handle */
+/* the parameters the handle was created with, the bytes of its scratch, and the rows one workgroup of a rows launch takes */
+int fleet_td3_describe(fleet_td3_handle h, FleetTd3Params* out, uint64_t* scratch_bytes, int32_t* tile_rows);
+/* Two launches each, enqueued only.  grads: a host array of `count` device pointers, the gradient tensors in torch's [out, in] layout,
+ * W then b per layer: critic 0's then critic 1's for the critic entry (count = the critics' tensors), the actor's for the actor entry.
+ * FLEET_ERR_INVALID (nothing is launched) for a null or wrongly sized argument struct, B < 1, a null obs / actions / target_q / stats
+ * (critic) or obs / stats (actor), a reserved that is not 0, a null grads or a null pointer in it, and -- these two need the handle --
+ * a count that is not the entry's number of tensors, B > max_batch.  The arguments are looked at before the handle is: with h NULL the
+ * reason (or "null handle") goes to fleet_td3_last_error(NULL). */
+int fleet_td3_critic_grad_dev(fleet_td3_handle h, const FleetTd3CriticArgs* a, float* const* grads, int count);
+int fleet_td3_actor_grad_dev(fleet_td3_handle h, const FleetTd3ActorArgs* a, float* const* grads, int count);
+
 /* ---- PPO minibatch gradients on the device (fleet_ppo.hip; DESIGN.md "PPO's minibatch gradients on the device") --------------------
  * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
  * What stable-baselines3 2.3.2's PPO.train does with one minibatch before the optimiser -- evaluate_actions, the clipped loss
