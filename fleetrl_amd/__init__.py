@@ -9,6 +9,7 @@
     from fleetrl_amd import DeviceTD3Target
     from fleetrl_amd import DevicePPOGrad
     from fleetrl_amd import DeviceTD3Grad
+    from fleetrl_amd import DeviceAdam
 """
 __version__ = "0.1.0"
 
@@ -54,6 +55,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import td3
 
         return td3.DeviceTD3Grad
+    if name == "DeviceAdam":
+        from . import adam
+
+        return adam.DeviceAdam
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

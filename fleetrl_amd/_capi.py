@@ -210,6 +210,26 @@ class FleetPpoGradArgs(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+# ---- Adam and clip_grad_norm_ (include/fleet_hip.h "Adam and clip_grad_norm_ on the device", fleet_adam_*) ------------------------------
+ADAM_MAX_EXTRA = 2
+ADAM_STATE_EXPORT, ADAM_STATE_LOAD = 0, 1
+
+
+class FleetAdamParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("first_net", C.c_int32), ("n_nets", C.c_int32), ("n_extra", C.c_int32),
+                ("extra_len", C.c_int32 * ADAM_MAX_EXTRA)]
+
+
+class FleetAdamStepArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("max_grad_norm", C.c_double), ("norm_out", C.c_void_p)]
+
+
+class FleetAdamInfo(C.Structure):
+    _fields_ = [("state_bytes", C.c_uint64), ("n_elements", C.c_uint64), ("step", C.c_int64), ("n_tensors", C.c_int32),
+                ("norm_chunk", C.c_int32), ("step_tile", C.c_int32), ("reserved", C.c_int32)]
+
+
 # ---- TD3 / DDPG minibatch gradients (include/fleet_hip.h "TD3 / DDPG minibatch gradients on the device", fleet_td3_*) -------------------
 class FleetTd3Params(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("max_batch", C.c_int32)]
@@ -511,9 +531,18 @@ def load_library():
     lib.fleet_td3_describe.argtypes = [vp, C.POINTER(FleetTd3Params), C.POINTER(C.c_uint64), i32p]
     lib.fleet_td3_critic_grad_dev.argtypes = [vp, C.POINTER(FleetTd3CriticArgs), C.POINTER(vp), C.c_int]
     lib.fleet_td3_actor_grad_dev.argtypes = [vp, C.POINTER(FleetTd3ActorArgs), C.POINTER(vp), C.c_int]
+    # Adam on a weight image (fleet_adam.hip)
+    lib.fleet_adam_create_policy.argtypes = [vp, C.POINTER(FleetAdamParams), C.POINTER(vp)]
+    lib.fleet_adam_create_qtarget.argtypes = [vp, C.POINTER(FleetAdamParams), C.POINTER(vp)]
+    lib.fleet_adam_destroy.argtypes = [vp]
+    lib.fleet_adam_last_error.argtypes = [vp]
+    lib.fleet_adam_describe.argtypes = [vp, C.POINTER(FleetAdamParams), C.POINTER(FleetAdamInfo)]
+    lib.fleet_adam_step_dev.argtypes = [vp, C.POINTER(FleetAdamStepArgs), C.POINTER(vp), C.POINTER(vp), C.c_int]
+    lib.fleet_adam_state_dev.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(C.c_int64)]
+    lib.fleet_adam_export_image_dev.argtypes = [vp, C.POINTER(vp), C.c_int]
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
                           ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS), ("ppo", PPO_SYMBOLS),
-                          ("td3", TD3_SYMBOLS)):
+                          ("td3", TD3_SYMBOLS), ("adam", ADAM_SYMBOLS)):
         for name in names:
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
@@ -575,6 +604,9 @@ PPO_SYMBOLS = ("fleet_ppo_create", "fleet_ppo_destroy", "fleet_ppo_last_error", 
 TD3_SYMBOLS = ("fleet_td3_create", "fleet_td3_destroy", "fleet_td3_last_error", "fleet_td3_describe", "fleet_td3_critic_grad_dev",
                "fleet_td3_actor_grad_dev")
 
+ADAM_SYMBOLS = ("fleet_adam_create_policy", "fleet_adam_create_qtarget", "fleet_adam_destroy", "fleet_adam_last_error", "fleet_adam_describe",
+                "fleet_adam_step_dev", "fleet_adam_state_dev", "fleet_adam_export_image_dev")
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -588,7 +620,7 @@ EXPORTED_SYMBOLS = (
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
     "fleet_set_direct_state_only", "fleet_direct_packet_counts", "fleet_step_has_state_only",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

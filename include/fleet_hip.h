@@ -1133,6 +1133,97 @@ int fleet_qtarget_target_dev(fleet_qtarget_handle h, const float* next_obs, cons
 /* the parameters the handle was created with, and tile_rows */
 int fleet_qtarget_describe(fleet_qtarget_handle h, FleetQTargetParams* out);
 
+/* ---- Adam and clip_grad_norm_ on the device (fleet_adam.hip; DESIGN.md "The optimiser step on the device") -------------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * What a gradient step does behind the gradients -- torch.nn.utils.clip_grad_norm_(params, max_grad_norm), torch.optim.Adam.step() and
+ * the *_load_dev that copied the new weights into the weight image -- in TWO launches.  The optimiser is created ON a weight image (of a
+ * fleet_policy or a fleet_qtarget handle, which it BORROWS and which must outlive it) and owns nets first_net .. first_net + n_nets - 1
+ * of it, W then b per layer, net after net, and behind them n_extra flat tensors that are in no image (PPO's log_std).  Spans: both
+ * heads of a policy (0, 2); the actor of a TD3 image (0, 1); its critics (1, n_critics); n_nets = 0 with one extra is a plain flat
+ * Adam.  Two optimisers with disjoint spans on one image are allowed.  Every new weight p' goes to torch's own parameter tensor and,
+ * for a tensor of the span, to the image element Wt[k][j] / b[j]: the same bits in both, so no *_load_dev follows a step.  The image's
+ * zero padding is not touched.  The gradients are READ ONLY: the clipped gradient is used and NOT written back.
+ * No weight decay, no amsgrad, no maximize (SB3's defaults use none).  No atomics, no random numbers; every sum in the order below.
+ * The arithmetic, float32 but where stated, no fused contraction but the fmaf written here, sqrtf and / correctly rounded.
+ * The host forms in double, as torch's Python does, with t = the handle's step count + 1, and rounds to float:
+ *   omb1 = 1 - beta1;  omb2 = 1 - beta2;  b2 = beta2;  nstep = -(lr / (1 - beta1^t));  bs = sqrt(1 - beta2^t);  eps;  maxn32 = max_grad_norm
+ * The norm runs iff max_grad_norm > 0 or norm_out is not NULL.  A chunk is 1024 consecutive elements of ONE gradient tensor (a tensor's
+ * last chunk is short; a chunk never straddles two tensors); chunks are numbered tensor after tensor, ascending inside a tensor.
+ *   thread t of 256: acc = 0; acc = fmaf(g, g, acc) over elements 4t .. 4t + 3 of the chunk in ascending order, those past the end skipped
+ *   wavefront w (threads 64w .. 64w + 63): for off = 32, 16, 8, 4, 2, 1: acc = acc + (the acc of lane ^ off)
+ *   part[chunk] = ((wave 0 + wave 1) + wave 2) + wave 3
+ *   norm = (float)sqrt(the float64 sum of (double)part[chunk] in ascending chunk order)
+ * The bits depend on the gradients alone: not on a tensor's alignment, on the grid, on the stream or on which workgroup summed.
+ * The clip, as clip_grad_norm_ does it (error_if_nonfinite = False):
+ *   q = maxn32 / (norm + 1e-6f);  c = q > 1.0f ? 1.0f : q   (torch.clamp(q, max = 1): a NaN stays NaN, and then every g' is NaN)
+ *   g' = g * c   (applied even when c == 1; not applied at all, g' = g, when max_grad_norm <= 0)
+ * The update, per element (m: exp_avg, v: exp_avg_sq):
+ *   m' = fmaf(g' - m, omb1, m)
+ *   v' = fmaf(g' * omb2, g', v * b2)
+ *   den = sqrtf(v') / bs + eps
+ *   p' = fmaf(m' / den, nstep, p)
+ * -- torch's single-tensor Adam (lerp, mul + addcmul, sqrt / bias_correction2_sqrt + eps, addcdiv with value -step_size), each fused
+ * where one torch kernel rounds once.  This is NOT bit-equal to torch's float32 CPU Adam, whose vectorised kernels differ from their
+ * own scalar arithmetic by an ulp here and there; the bits are pinned to the lines above.
+ * The state (m, v per tensor in torch's layout, zero at create; the step count on the host, 0 at create, as torch's non-capturable Adam
+ * keeps it) goes into and out of torch.optim.Adam.state_dict() unchanged through fleet_adam_state_dev.
+ * Every *_dev call takes device pointers, only enqueues, and launches on the IMAGE handle's stream, whichever that is when the call is
+ * made: a forward enqueued behind a step on that handle sees the new weights with no host wait.  Calls are serialised by the caller. */
+#define FLEET_ADAM_MAX_EXTRA 2
+#define FLEET_ADAM_STATE_EXPORT 0
+#define FLEET_ADAM_STATE_LOAD 1
+typedef struct FleetAdamParams {
+  int32_t struct_bytes;                      /* sizeof(FleetAdamParams) */
+  int32_t first_net;                         /* first net of the span in the image (policy: 0 actor head, 1 critic head; TD3: 0 actor, 1.. critics) */
+  int32_t n_nets;                            /* nets in the span, 0 .. the image's */
+  int32_t n_extra;                           /* flat tensors behind the span, 0..FLEET_ADAM_MAX_EXTRA */
+  int32_t extra_len[FLEET_ADAM_MAX_EXTRA];   /* their lengths, 1..2^24 */
+} FleetAdamParams;
+typedef struct FleetAdamStepArgs {
+  int32_t struct_bytes;   /* sizeof(FleetAdamStepArgs) */
+  double lr;              /* finite, >= 0; per call: SB3 sets it anew every iteration */
+  double beta1, beta2;    /* in [0, 1) */
+  double eps;             /* finite, >= 0 */
+  double max_grad_norm;   /* <= 0: no clipping */
+  float* norm_out;        /* device f32[1] or NULL: the norm BEFORE clipping, what clip_grad_norm_ returns */
+} FleetAdamStepArgs;
+typedef struct FleetAdamInfo {
+  uint64_t state_bytes;   /* of exp_avg and exp_avg_sq together */
+  uint64_t n_elements;    /* of all tensors */
+  int64_t step;           /* steps taken (or loaded) */
+  int32_t n_tensors;      /* the span's, then the extras */
+  int32_t norm_chunk;     /* elements per chunk of the norm launch (1024) */
+  int32_t step_tile;      /* edge of a W tile of the step launch (32) */
+  int32_t reserved;
+} FleetAdamInfo;
+typedef struct FleetAdam* fleet_adam_handle;
+
+/* FLEET_ERR_INVALID (fleet_adam_last_error(NULL) says why, starting with the entry's name), before the device is touched, for a null or
+ * wrongly sized FleetAdamParams, a negative first_net or n_nets, n_extra outside 0..2, an extra_len outside 1..2^24, nothing to
+ * optimise, a null output or image handle, a handle of the other family, a span that ends behind the image's last net.  FLEET_ERR_HIP
+ * with the byte count when the state cannot be allocated. */
+int fleet_adam_create_policy(fleet_policy_handle policy, const FleetAdamParams* p, fleet_adam_handle* out);
+int fleet_adam_create_qtarget(fleet_qtarget_handle nets, const FleetAdamParams* p, fleet_adam_handle* out);
+int fleet_adam_destroy(fleet_adam_handle h);
+const char* fleet_adam_last_error(fleet_adam_handle h);  /* h may be NULL: error of the last failed call without a handle */
+/* the parameters the handle was created with, and what FleetAdamInfo lists */
+int fleet_adam_describe(fleet_adam_handle h, FleetAdamParams* out, FleetAdamInfo* info);
+/* One step, two launches (one when the norm does not run), enqueued only; adds one to the step count.  params, grads: host arrays of
+ * `count` device pointers, contiguous float32 tensors in torch's [out, in] layout, the span's (W, b per layer, net after net) then the
+ * extras; params are read and written in place, grads are read.  FLEET_ERR_INVALID (nothing is launched, the step count stays) for a
+ * null or wrongly sized FleetAdamStepArgs, an lr or eps that is negative or not finite, a beta outside [0, 1), a NaN max_grad_norm, a
+ * null array or a null pointer in one, a params[i] that is its own grads[i], and -- this one needs the handle -- a count that is not
+ * the number of the handle's tensors.  The arguments are looked at before the handle is: with h NULL the reason (or "null handle")
+ * goes to fleet_adam_last_error(NULL). */
+int fleet_adam_step_dev(fleet_adam_handle h, const FleetAdamStepArgs* a, float* const* params, float* const* grads, int count);
+/* mode FLEET_ADAM_STATE_EXPORT: the state out into `count` pairs of tensors in torch's layout, and the step count into *step (at once:
+ * it lives on the host).  FLEET_ADAM_STATE_LOAD: the reverse; a negative *step is refused.  Copies on the image handle's stream. */
+int fleet_adam_state_dev(fleet_adam_handle h, int mode, float* const* exp_avg, float* const* exp_avg_sq, int count, int64_t* step);
+/* The WHOLE image the handle was created on (every net of it, not the span alone) out into `count` torch-layout tensors, W then b per
+ * layer, net after net: the inverse re-lay of *_load_dev in one launch on the image handle's stream.  What a test reads a step's
+ * result from, and the only way to read a policy's image back.  FLEET_ERR_INVALID for a null array or pointer, a wrong count. */
+int fleet_adam_export_image_dev(fleet_adam_handle h, float* const* tensors, int count);
+
 /* ---- TD3 / DDPG minibatch gradients on the device (fleet_td3.hip; DESIGN.md "TD3's minibatch gradients on the device") -------------
  * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
  * What stable-baselines3 2.3.2's TD3.train does with one minibatch between the target and the optimisers, in two entries of TWO
