@@ -1,6 +1,7 @@
 """What `DeviceNormalizer`, `DeviceRolloutBuffer` and `DeviceReplayBuffer` share: one handle of the C ABI behind a family of entries
 `fleet_<prefix>_*` (create, destroy, last_error, set_stream), its errors as exceptions, its stream, its end -- the Python side of
-fleetrl_amd/csrc/fleet_handle.h."""
+fleetrl_amd/csrc/fleet_handle.h -- and what `DevicePPOGrad`, `DeviceTD3Grad` and `DeviceAdam` share on top of it: a handle made ON
+another handle's weight image (`_ImageBorrower`; fleetrl_amd/csrc/fleet_mlp.h `FleetMlpUser`)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -103,3 +104,50 @@ class _DeviceHandle:
             self.close()
         except Exception:  # interpreter shutdown
             pass
+
+
+class _ImageBorrower(_DeviceHandle):
+    """A handle that works on the weight image of `owner` (a `DevicePolicy` or a `DeviceTD3Target`) and owns none: it lives on the
+    owner's device, launches on the owner's stream, and the owner must outlive it (the object is kept)."""
+
+    def _open_on(self, owner, create_entry: str, params):
+        """`create_entry` (the C ABI's full name) on `owner`'s handle with the family's parameter struct."""
+        self.lib = _capi.load_library()
+        self._owner, self.device = owner, owner.device
+        h = C.c_void_p()
+        rc = getattr(self.lib, create_entry)(owner.h, C.byref(params), C.byref(h))
+        if rc != _capi.OK:
+            raise FleetHipError(rc, self._entry("last_error")(None).decode())
+        self.h = h
+        self._grad_cache = {}  # slot -> (the parameters, the pointer array of their .grad, the addresses) of the last call
+
+    def set_stream(self, hip_stream):
+        """The handle has no stream of its own: the owner's is set."""
+        self._owner.set_stream(hip_stream)
+
+    def use_torch_stream(self, device=None):
+        self._owner.use_torch_stream(device)
+
+    def _grad_pointers(self, slot, into, shapes, what: str):
+        """The (c_void_p * n) array of the `.grad` addresses of the parameters `into`, which must have `shapes` (`what` names their
+        order in the message); a `.grad` that is missing is allocated.  The array of the last call in `slot` is kept and returned
+        again while the parameters are the same objects and their `.grad` lie where they lay."""
+        import torch
+
+        into = list(into)
+        hit = self._grad_cache.get(slot)
+        if hit is not None and len(hit[0]) == len(into) and all(a is b for a, b in zip(hit[0], into)) and \
+                all(p.grad is not None and p.grad.data_ptr() == q for p, q in zip(into, hit[2])):
+            return hit[1]
+        if len(into) != len(shapes):
+            raise ValueError(f"into: expected {len(shapes)} parameters (W, b per layer, {what}), got {len(into)}")
+        ptrs = []
+        for p, s in zip(into, shapes):
+            if tuple(p.shape) != s:
+                raise ValueError(f"into: expected a parameter of shape {s}, got {tuple(p.shape)}")
+            if p.grad is None:  # allocated once; the launches overwrite it
+                p.grad = torch.empty_like(p, memory_format=torch.contiguous_format)
+            ptrs.append(self._tensor(p.grad, s, (torch.float32,)).data_ptr())
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        self._grad_cache[slot] = (into, arr, ptrs)
+        return arr

@@ -12,8 +12,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _capi
-from ._capi import FleetHipError
-from ._handle import _DeviceHandle
+from ._handle import _ImageBorrower
 
 __all__ = ["DeviceAdam"]
 
@@ -28,7 +27,7 @@ def _net_layers(image) -> list:
     raise TypeError("image must be a DevicePolicy or a DeviceTD3Target")
 
 
-class DeviceAdam(_DeviceHandle):
+class DeviceAdam(_ImageBorrower):
     """One `fleet_adam_*` handle on `image` (a `DevicePolicy` or a `DeviceTD3Target`, which must outlive it).
 
     nets: None (every net of the image), "actor" (net 0), "critic" (the nets behind it), "none" (no net: a flat Adam over the extras).
@@ -38,8 +37,7 @@ class DeviceAdam(_DeviceHandle):
     _prefix = "adam"
 
     def __init__(self, image, params, *, nets=None, lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm=None):
-        self.lib = _capi.load_library()
-        self.image, self.device = image, image.device
+        self.image = image
         per_net = _net_layers(image)
         spans = {None: (0, len(per_net)), "actor": (0, 1), "critic": (1, len(per_net) - 1), "none": (0, 0)}
         if nets not in spans:
@@ -63,21 +61,9 @@ class DeviceAdam(_DeviceHandle):
         p.struct_bytes, p.first_net, p.n_nets, p.n_extra = C.sizeof(p), first, n, n_extra
         for i, t in enumerate(params[len(params) - n_extra:] if n_extra else []):
             p.extra_len[i] = t.numel()
-        h = C.c_void_p()
-        create = self.lib.fleet_adam_create_policy if image._prefix == "policy" else self.lib.fleet_adam_create_qtarget
-        rc = create(image.h, C.byref(p), C.byref(h))
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_adam_last_error(None).decode())
-        self.h = h
+        self._open_on(image, f"fleet_adam_create_{image._prefix}", p)
         self.params = params
         self._ptrs = None  # (the pointer arrays of the parameters and of their .grad, the addresses) of the last step
-
-    def set_stream(self, hip_stream):
-        """The handle has no stream of its own: the image handle's is set."""
-        self.image.set_stream(hip_stream)
-
-    def use_torch_stream(self, device=None):
-        self.image.use_torch_stream(device)
 
     def describe(self) -> dict:
         """What fleet_adam_describe reports."""

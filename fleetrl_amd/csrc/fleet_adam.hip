@@ -146,10 +146,9 @@ __global__ __launch_bounds__(kAdamThreads) void adam_step(StepArgs a) {
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 thread_local std::string g_adam_error;  // of the last failed call without a handle
 
-constexpr int32_t kMaxExtraLen = 1 << 24;
+const std::string kArgsLater;  // fleet_adam_export_image_dev's reason: mlp_launch_relay looks at its arguments
 
-// FleetPolicy and FleetQTarget derive from FleetMlpHandle and from nothing else: the image's handle is their first base
-FleetMlpHandle* image_of(void* p) { return reinterpret_cast<FleetMlpHandle*>(p); }
+constexpr int32_t kMaxExtraLen = 1 << 24;
 
 std::string check_params(const FleetAdamParams* p) {
   if (!p) return "null FleetAdamParams";
@@ -201,41 +200,39 @@ std::string check_state_args(int mode, float* const* exp_avg, float* const* exp_
 
 }  // namespace
 
-struct FleetAdam {
-  FleetMlpHandle* img = nullptr;  // borrowed: the image's handle outlives this one
-  std::string error;
+struct FleetAdam : FleetMlpUser {  // img: either family's; block: the state, the norm's partial sums, the tables
   FleetAdamParams p{};
   std::vector<AdamTensor> tensors;
   uint64_t n_elements = 0;
   int n_chunks = 0, n_items = 0;
   int64_t step = 0;  // on the host, as torch's non-capturable Adam keeps it
-  char* block = nullptr;
   const AdamTensor* d_tensors = nullptr;
   const AdamChunk* d_chunks = nullptr;
   const AdamItem* d_items = nullptr;
   float* d_part = nullptr;
+  ~FleetAdam();  // (out of line, below: the one place that takes the tables down)
 };
+FleetAdam::~FleetAdam() = default;
 
 namespace {
 
+// what the step and the state entries refuse once they have their handle
+void check_count(std::string* why, int count, const FleetAdam* h) {
+  if (count != (int)h->tensors.size())
+    *why = "expected " + std::to_string(h->tensors.size()) + " tensors (W, b per layer, net after net, then the extras), got " + std::to_string(count);
+}
+
 int adam_create(const char* entry, const char* noun, void* image, size_t record_bytes, const FleetAdamParams* p, fleet_adam_handle* out) {
   if (out) *out = nullptr;
-  const auto refuse = [entry](const std::string& why, int rc) {
-    g_adam_error = std::string(entry) + ": " + why;
-    return rc;
-  };
-  const std::string bad = check_params(p);
-  if (!bad.empty()) return refuse(bad, FLEET_ERR_INVALID);
-  if (!out) return refuse("null output handle", FLEET_ERR_INVALID);
-  if (!image) return refuse(std::string("null ") + noun + " handle", FLEET_ERR_INVALID);
-  FleetMlpHandle* img = image_of(image);
-  if (img->record_bytes != record_bytes) return refuse(std::string("the handle is not a ") + noun + " handle", FLEET_ERR_INVALID);
-  if (p->first_net + p->n_nets > img->n_nets)
-    return refuse("the span of nets " + std::to_string(p->first_net) + " .. " + std::to_string(p->first_net + p->n_nets - 1) +
-                      " lies outside the image's " + std::to_string(img->n_nets) + " nets",
-                  FLEET_ERR_INVALID);
+  std::string why = check_params(p);
+  if (why.empty() && !out) why = "null output handle";
+  FleetMlpHandle* img = why.empty() ? mlp_borrow(image, record_bytes, noun, &why) : nullptr;
+  if (img && p->first_net + p->n_nets > img->n_nets)
+    why = "the span of nets " + std::to_string(p->first_net) + " .. " + std::to_string(p->first_net + p->n_nets - 1) +
+          " lies outside the image's " + std::to_string(img->n_nets) + " nets";
+  if (!why.empty()) return handle_refuse(g_adam_error, entry, why, FLEET_ERR_INVALID);
   FleetAdam* h = new FleetAdam();
-  h->img = img, h->p = *p;
+  h->p = *p;
   uint64_t off = 0;
   const auto add = [&](int kind, int out_, int in_, int out64, uint32_t img_off) {
     AdamTensor T{};
@@ -277,25 +274,17 @@ int adam_create(const char* entry, const char* noun, void* image, size_t record_
   memcpy(tables.data(), h->tensors.data(), h->tensors.size() * sizeof(AdamTensor));
   memcpy(tables.data() + (chunks_at - tensors_at), chunks.data(), chunks.size() * sizeof(AdamChunk));
   memcpy(tables.data() + (items_at - tensors_at), items.data(), items.size() * sizeof(AdamItem));
-  if (hipSetDevice(img->device) != hipSuccess) {
-    delete h;
-    return refuse("hipSetDevice failed", FLEET_ERR_HIP);
-  }
-  void* q = nullptr;
-  if (hipMalloc(&q, total) != hipSuccess) {
-    (void)hipGetLastError();
-    delete h;
-    return refuse("hipMalloc of the optimiser's " + std::to_string(total) + " bytes failed", FLEET_ERR_HIP);
-  }
-  h->block = static_cast<char*>(q);
+  int rc = mlp_user_open(h, img, total, "optimiser", {}, "", &why);
   // a zero state and the tables, waited for: the first step may come on any stream
-  if (hipMemset(h->block, 0, tensors_at) != hipSuccess ||
-      hipMemcpy(h->block + tensors_at, tables.data(), tables.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess) {
+  if (rc == FLEET_OK && (hipMemset(h->block, 0, tensors_at) != hipSuccess ||
+                         hipMemcpy(h->block + tensors_at, tables.data(), tables.size(), hipMemcpyHostToDevice) != hipSuccess ||
+                         hipDeviceSynchronize() != hipSuccess)) {
     (void)hipGetLastError();
-    (void)hipFree(h->block);
-    delete h;
-    return refuse("clearing the optimiser's state failed", FLEET_ERR_HIP);
+    why = "clearing the optimiser's state failed", rc = FLEET_ERR_HIP;
+  }
+  if (rc != FLEET_OK) {
+    fleet_adam_destroy(h);
+    return handle_refuse(g_adam_error, entry, why, rc);
   }
   h->d_part = reinterpret_cast<float*>(h->block + part_at);
   h->d_tensors = reinterpret_cast<const AdamTensor*>(h->block + tensors_at);
@@ -319,7 +308,7 @@ int fleet_adam_create_qtarget(fleet_qtarget_handle nets, const FleetAdamParams* 
 
 int fleet_adam_destroy(fleet_adam_handle h) {
   if (!h) return FLEET_OK;
-  if (h->block) (void)hipFree(h->block);  // (waits for the device: whatever still reads the state is done)
+  mlp_user_close(h);
   delete h;
   return FLEET_OK;
 }
@@ -341,16 +330,8 @@ int fleet_adam_describe(fleet_adam_handle h, FleetAdamParams* out, FleetAdamInfo
 
 int fleet_adam_step_dev(fleet_adam_handle h, const FleetAdamStepArgs* x, float* const* params, float* const* grads, int count) {
   std::string why = check_step_args(x, params, grads, count);
-  if (!h) {
-    g_adam_error = "fleet_adam_step_dev: " + (why.empty() ? std::string("null handle") : why);
-    return FLEET_ERR_INVALID;
-  }
-  if (why.empty() && count != (int)h->tensors.size())
-    why = "expected " + std::to_string(h->tensors.size()) + " tensors (W, b per layer, net after net, then the extras), got " + std::to_string(count);
-  if (!why.empty()) {
-    h->error = "fleet_adam_step_dev: " + why;
-    return FLEET_ERR_INVALID;
-  }
+  if (h && why.empty()) check_count(&why, count, h);
+  if (const int rc = handle_enter("fleet_adam_step_dev", why, h, g_adam_error); rc != FLEET_OK) return rc;
   FleetMlpHandle* img = h->img;
   const bool clip = x->max_grad_norm > 0.0, norm = clip || x->norm_out;
   // the scalars in double, as torch's Python forms them, then rounded
@@ -379,16 +360,8 @@ int fleet_adam_step_dev(fleet_adam_handle h, const FleetAdamStepArgs* x, float* 
 
 int fleet_adam_state_dev(fleet_adam_handle h, int mode, float* const* exp_avg, float* const* exp_avg_sq, int count, int64_t* step) {
   std::string why = check_state_args(mode, exp_avg, exp_avg_sq, count, step);
-  if (!h) {
-    g_adam_error = "fleet_adam_state_dev: " + (why.empty() ? std::string("null handle") : why);
-    return FLEET_ERR_INVALID;
-  }
-  if (why.empty() && count != (int)h->tensors.size())
-    why = "expected " + std::to_string(h->tensors.size()) + " tensors (W, b per layer, net after net, then the extras), got " + std::to_string(count);
-  if (!why.empty()) {
-    h->error = "fleet_adam_state_dev: " + why;
-    return FLEET_ERR_INVALID;
-  }
+  if (h && why.empty()) check_count(&why, count, h);
+  if (const int rc = handle_enter("fleet_adam_state_dev", why, h, g_adam_error); rc != FLEET_OK) return rc;
   FleetMlpHandle* img = h->img;
   FLEET_HANDLE_TRY(h, hipSetDevice(img->device));
   float* base = reinterpret_cast<float*>(h->block);
@@ -410,10 +383,7 @@ int fleet_adam_state_dev(fleet_adam_handle h, int mode, float* const* exp_avg, f
 }
 
 int fleet_adam_export_image_dev(fleet_adam_handle h, float* const* tensors, int count) {
-  if (!h) {
-    g_adam_error = "fleet_adam_export_image_dev: null handle";
-    return FLEET_ERR_INVALID;
-  }
+  if (const int rc = handle_enter("fleet_adam_export_image_dev", kArgsLater, h, g_adam_error); rc != FLEET_OK) return rc;
   const int rc = mlp_launch_relay(h->img, kMlpExport, "fleet_adam_export_image_dev", tensors, count, 0.0f, 0.0f);
   if (rc != FLEET_OK) h->error = h->img->error;
   return rc;

@@ -4,8 +4,11 @@
 // including kernel (an unnamed namespace: each translation unit has its own copy).  The arithmetic is the header's
 // (include/fleet_hip.h "PPO minibatch gradients on the device"): forward acc = fmaf(x[k], W[j][k], acc) in ascending k, backward
 // d_prev[k] = (fmaf chain over j ascending of Wt[k][j] * d[j]) * act'(h[k]), dW[j][k] = fmaf(d[b][j], x[b][k], acc) in ascending b.
+// At the end, the host work the two handles share: the scratch's layout, a weights launch's entries, what both refuse about sizes.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <string>
 
 #include "fleet_policy.h"
 #include "fleet_policy_dev.h"
@@ -212,11 +215,59 @@ __device__ __forceinline__ int grad_entry_of(const GradEntry* e, int n_entries, 
   return ei;
 }
 
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+using GradOffsets = uint64_t[FLEET_POLICY_MAX_LAYERS];  // a net's row of a scratch's act[][] or delta[][]
+
 // the host's half of an entry: the tiles of dW[out][in], counted on from *blocks
 inline void grad_entry_tiles(GradEntry& E, int* blocks) {
   E.tiles_k = (E.in + kGradTile - 1) / kGradTile;
   E.first = *blocks;
   *blocks += ((E.out + kGradTile - 1) / kGradTile) * E.tiles_k;
+}
+
+// The scratch of n_nets nets for max_batch rows, in floats from its start: per net and layer act [max_batch][out64] (hidden layers) and
+// delta [max_batch][out64] (every layer).  Raises *widest to the widest out64; returns the offset behind the last array.
+inline uint64_t grad_scratch_layout(const PolicyHeadDesc* nets, int n_nets, uint64_t max_batch, GradOffsets* act, GradOffsets* delta, int* widest) {
+  uint64_t off = 0;
+  for (int nt = 0; nt < n_nets; ++nt)
+    for (int l = 0; l < nets[nt].n_layers; ++l) {
+      const uint64_t w = (uint64_t)nets[nt].layer[l].out64;
+      if ((int)w > *widest) *widest = (int)w;
+      if (l < nets[nt].n_layers - 1) act[nt][l] = off, off += max_batch * w;
+      delta[nt][l] = off, off += max_batch * w;
+    }
+  return off;
+}
+
+// The entries of nets net0 .. net0 + n_nets - 1 behind e[*n_entries], layer after layer, with their gradient tensors (W, b per layer)
+// from grads[] in that order.  A first layer reads x[B][xstride]; with x2, its columns from xstride on are x2[B][x2stride] (a
+// critic: the observation, then the action).
+inline void grad_fill_entries(GradEntry* e, int* n_entries, int* blocks, const PolicyHeadDesc* nets, int net0, int n_nets, float* scratch,
+                              const GradOffsets* act, const GradOffsets* delta, const float* x, int xstride, const float* x2, int x2stride,
+                              float* const* grads) {
+  int ti = 0;
+  for (int nt = net0; nt < net0 + n_nets; ++nt)
+    for (int l = 0; l < nets[nt].n_layers; ++l, ti += 2) {
+      const PolicyLayer& L = nets[nt].layer[l];
+      GradEntry& E = e[(*n_entries)++];
+      E.d = scratch + delta[nt][l], E.dstride = L.out64;
+      E.seam = L.in;  // (one input array, but for a critic's first layer)
+      if (l > 0) {
+        E.x = scratch + act[nt][l - 1], E.xstride = nets[nt].layer[l - 1].out64;
+      } else {
+        E.x = x, E.xstride = xstride;
+        if (x2) E.seam = xstride, E.x2 = x2, E.x2stride = x2stride;
+      }
+      E.dW = grads[ti], E.db = grads[ti + 1], E.out = L.out, E.in = L.in;
+      grad_entry_tiles(E, blocks);
+    }
+}
+
+// what a *_grad_dev entry refuses once it has its handle: another number of gradient tensors than `want` (`order` says which they
+// are), more rows than the scratch holds.  Writes the reason into *why, which the caller hands over empty.
+inline void grad_check_sizes(std::string* why, int count, int want, const char* order, int B, int max_batch) {
+  if (count != want) *why = "expected " + std::to_string(want) + " gradient tensors (" + order + "), got " + std::to_string(count);
+  else if (B > max_batch) *why = "B must be at most max_batch = " + std::to_string(max_batch) + ", got " + std::to_string(B);
 }
 
 }  // namespace

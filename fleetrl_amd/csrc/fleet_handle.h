@@ -1,7 +1,7 @@
 // fleet_handle.h -- the host scaffold the normaliser (fleet_norm.hip), the rollout buffer (fleet_rollout.hip) and the replay buffer
 // (fleet_replay.hip) share: what such a handle holds, how it is opened and closed, how it changes streams, how its HIP errors and
-// its device error word become messages, and how a buffer's arrays are laid out.  Host code only; nothing here launches a kernel,
-// and nothing here builds a string outside an error branch.  (The env's own handle, `fleet_handle`, is not one of these: fleet_batch.h.)
+// its device error word become messages, and how a buffer's arrays are laid out; and what every family's entries share: where a
+// refusal's message goes.  Host code only; nothing here launches a kernel, and nothing here builds a string outside an error branch.  (The env's own handle, `fleet_handle`, is not one of these: fleet_batch.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,6 +37,22 @@ struct FleetBufferBase : FleetHandleBase {
       return FLEET_ERR_HIP;                                               \
     }                                                                     \
   } while (0)
+
+// a refusal without a handle: "<entry>: <why>" into the family's thread-local string (*_last_error(NULL)); returns rc
+inline int handle_refuse(std::string& no_handle, const char* entry, const std::string& why, int rc) {
+  no_handle = std::string(entry) + ": " + why;
+  return rc;
+}
+
+// The opening of an entry that looks at its arguments before its handle: `why` is what the family's check_* function found ("" when
+// the arguments pass).  FLEET_OK to go on.  Otherwise FLEET_ERR_INVALID, with "<entry>: <why>" -- "null handle" when the arguments
+// pass -- in h->error, or in the family's thread-local string when there is no handle.  H: anything with an `error`.
+template <typename H>
+inline int handle_enter(const char* entry, const std::string& why, H* h, std::string& no_handle) {
+  if (h && why.empty()) return FLEET_OK;
+  (h ? h->error : no_handle) = std::string(entry) + ": " + (why.empty() ? "null handle" : why.c_str());
+  return FLEET_ERR_INVALID;
+}
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

@@ -4,9 +4,12 @@
 // itself is here (fleet_mlp.hip): its layout, building it from packed host weights, the upload, the one kernel that walks its real
 // elements (load, polyak, export) and the device half of *_create.  The families keep their records, their validation of their own
 // parameter structs and their forward kernels; the shared code sees a record as its bytes and the span of nets in it.
+// The handles that work ON such an image without owning one (fleet_ppo.hip, fleet_td3.hip, fleet_adam.hip) borrow it here too:
+// FleetMlpUser, mlp_borrow, mlp_user_open, mlp_user_close.
 #pragma once
 #include <initializer_list>
 #include <string>
+#include <type_traits>
 
 #include "fleet_handle.h"
 #include "fleet_policy.h"
@@ -34,6 +37,24 @@ struct FleetMlpHandle : FleetHandleBase {
   const MlpNames* names = nullptr;
 };
 
+// What mlp_borrow relies on, asserted by each family behind its handle's definition: the image's handle is the first base of T.
+template <typename T>
+constexpr bool mlp_image_is_first_base = std::is_base_of<FleetMlpHandle, T>::value && !std::is_polymorphic<T>::value;
+
+// A handle that borrows an image: it launches on the image's device and stream, and the image's owner must outlive it.  It owns
+// one device allocation (a scratch, an optimiser's state).
+struct FleetMlpUser {
+  FleetMlpHandle* img = nullptr;  // borrowed
+  std::string error;              // *_last_error(handle)
+  char* block = nullptr;          // owned
+
+  float* floats() const { return reinterpret_cast<float*>(block); }
+};
+
+// The image behind an opaque fleet_policy_handle or fleet_qtarget_handle, when it is the family's whose record has `record_bytes`
+// bytes; otherwise NULL, with "null <noun> handle" or "the handle is not a <noun> handle" in *why.
+FleetMlpHandle* mlp_borrow(void* owner, size_t record_bytes, const char* noun, std::string* why);
+
 inline int mlp_round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // what *_create refuses about one head, before the device is touched; `who` opens the message ("head 0: "); "" when it passes
@@ -52,6 +73,15 @@ struct MlpKernelLds {
   int bytes;  // hipFuncAttributeMaxDynamicSharedMemorySize
 };
 int mlp_open(FleetMlpHandle* h, int device, const float* weights, std::initializer_list<MlpKernelLds> kernels, std::string* why);
+
+// The device half of a borrower's *_create, after it validated its parameters: the image's device, the kernels' dynamic LDS limits
+// ("the <kernel> kernel's" in the message), `bytes` bytes of device memory (not initialised; "the <noun>'s").  A status other than
+// FLEET_OK comes with the reason in *why, and the handle is then the caller's to destroy.
+int mlp_user_open(FleetMlpUser* u, FleetMlpHandle* img, size_t bytes, const char* noun, std::initializer_list<MlpKernelLds> kernels,
+                  const char* kernel, std::string* why);
+
+// frees the block, which waits for the device: whatever still reads it is done.  The image is not touched.
+void mlp_user_close(FleetMlpUser* u);
 
 // *_load_host: new packed weights of the same shapes
 int mlp_load_host(FleetMlpHandle* h, const char* entry, const float* weights);

@@ -73,7 +73,36 @@ int upload(FleetMlpHandle* h, const std::vector<float>& image) {
   return FLEET_OK;
 }
 
+// more than the 64 KiB a launch gets unasked when the layers are wide; the attribute belongs to the kernel, not to the handle, so
+// every handle asks for what the widest network needs
+int set_lds_limits(std::initializer_list<MlpKernelLds> kernels, const char* noun, std::string* why) {
+  int most = 0;
+  bool set = true;
+  for (const MlpKernelLds& k : kernels) {
+    set = set && hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes) == hipSuccess;
+    most = k.bytes > most ? k.bytes : most;
+  }
+  if (set) return FLEET_OK;
+  (void)hipGetLastError();
+  *why = std::string("hipFuncSetAttribute failed for the ") + noun + " kernel's " + std::to_string(most) + " bytes of LDS";
+  return FLEET_ERR_HIP;
+}
+
 }  // namespace
+
+// FleetPolicy (fleet_policy.hip) and FleetQTarget (fleet_qtarget.hip) derive from FleetMlpHandle and from nothing else, and neither
+// is polymorphic (mlp_image_is_first_base, asserted where each is defined): the image's handle is the first base, at the address
+// the opaque handle holds.  The families are told apart by the size of their records.
+FleetMlpHandle* mlp_borrow(void* owner, size_t record_bytes, const char* noun, std::string* why) {
+  if (!owner) {
+    *why = std::string("null ") + noun + " handle";
+    return nullptr;
+  }
+  FleetMlpHandle* img = reinterpret_cast<FleetMlpHandle*>(owner);
+  if (img->record_bytes == record_bytes) return img;
+  *why = std::string("the handle is not a ") + noun + " handle";
+  return nullptr;
+}
 
 std::string mlp_validate_head(const FleetPolicyHead& H, const std::string& who) {
   if (H.n_layers < 1 || H.n_layers > FLEET_POLICY_MAX_LAYERS)
@@ -126,21 +155,32 @@ int mlp_open(FleetMlpHandle* h, int device, const float* weights, std::initializ
   }
   int rc = handle_open(h, device, h->floats * sizeof(float), h->names->block, why);
   if (rc != FLEET_OK) return rc;
-  // more than the 64 KiB a launch gets unasked when the layers are wide; the attribute belongs to the kernel, not to the handle, so
-  // every handle asks for what the widest network needs
-  int most = 0;
-  bool set = true;
-  for (const MlpKernelLds& k : kernels) {
-    set = set && hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes) == hipSuccess;
-    most = k.bytes > most ? k.bytes : most;
-  }
-  if (!set) {
-    (void)hipGetLastError();
-    *why = std::string("hipFuncSetAttribute failed for the ") + h->names->kernel + " kernel's " + std::to_string(most) + " bytes of LDS";
-    return FLEET_ERR_HIP;
-  }
+  if ((rc = set_lds_limits(kernels, h->names->kernel, why)) != FLEET_OK) return rc;
   if ((rc = upload(h, image)) != FLEET_OK) *why = h->error;
   return rc;
+}
+
+int mlp_user_open(FleetMlpUser* u, FleetMlpHandle* img, size_t bytes, const char* noun, std::initializer_list<MlpKernelLds> kernels,
+                  const char* kernel, std::string* why) {
+  u->img = img;
+  if (hipSetDevice(img->device) != hipSuccess) {
+    *why = "hipSetDevice failed";
+    return FLEET_ERR_HIP;
+  }
+  if (const int rc = set_lds_limits(kernels, kernel, why); rc != FLEET_OK) return rc;
+  void* q = nullptr;
+  if (hipMalloc(&q, bytes) != hipSuccess) {
+    (void)hipGetLastError();  // (the failure is reported here: it must not surface again from the caller's next HIP call)
+    *why = std::string("hipMalloc of the ") + noun + "'s " + std::to_string(bytes) + " bytes failed";
+    return FLEET_ERR_HIP;
+  }
+  u->block = static_cast<char*>(q);
+  return FLEET_OK;
+}
+
+void mlp_user_close(FleetMlpUser* u) {
+  if (u->block) (void)hipFree(u->block);
+  u->block = nullptr;
 }
 
 int mlp_load_host(FleetMlpHandle* h, const char* entry, const float* weights) {

@@ -178,6 +178,7 @@ struct FleetPolicy : FleetMlpHandle {
   size_t lds_bytes = 0;         // of one workgroup of policy_forward
   size_t sample_lds_bytes = 0;  // ... of policy_forward_sample: the means of head 0's last layer behind it
 };
+static_assert(mlp_image_is_first_base<FleetPolicy>, "mlp_borrow (fleet_mlp.hip) reads a fleet_policy_handle as the image's handle");
 
 namespace {
 

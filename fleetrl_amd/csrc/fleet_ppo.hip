@@ -201,8 +201,12 @@ __global__ __launch_bounds__(256) void ppo_weights(WeightArgs a) {
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 thread_local std::string g_ppo_error;  // of the last failed call without a handle
 
-// FleetPolicy (fleet_policy.hip) derives from FleetMlpHandle and from nothing else: the image's handle is its first base
-FleetMlpHandle* image_of(fleet_policy_handle p) { return reinterpret_cast<FleetMlpHandle*>(p); }
+std::string check_params(const FleetPpoParams* p) {
+  if (!p) return "null FleetPpoParams";
+  if (p->struct_bytes != (int32_t)sizeof(FleetPpoParams)) return "FleetPpoParams.struct_bytes does not match this library";
+  if (p->max_batch < 1 || p->max_batch > (1 << 24)) return "max_batch must be in 1..16777216, got " + std::to_string(p->max_batch);
+  return "";
+}
 
 // what fleet_ppo_grad_dev refuses, looked at without the handle; "" when the arguments pass
 std::string check_grad_args(const FleetPpoGradArgs* args, float* const* grads, int count) {
@@ -229,12 +233,9 @@ std::string check_grad_args(const FleetPpoGradArgs* args, float* const* grads, i
 
 }  // namespace
 
-struct FleetPpo {
-  FleetMlpHandle* pol = nullptr;  // borrowed: the policy outlives this handle
-  std::string error;
+struct FleetPpo : FleetMlpUser {  // img: a two-head policy's; block: the scratch
   FleetPpoParams p{};
   PpoScratch s{};
-  float* scratch = nullptr;
   int T = 64;  // the widest layer of both heads, out64
   size_t lds_bytes = 0;
 };
@@ -243,60 +244,39 @@ extern "C" {
 
 int fleet_ppo_create(fleet_policy_handle policy, const FleetPpoParams* p, fleet_ppo_handle* out) {
   if (out) *out = nullptr;
-  const auto refuse = [](const std::string& why, int rc) {
-    g_ppo_error = "fleet_ppo_create: " + why;
-    return rc;
-  };
-  if (!p) return refuse("null FleetPpoParams", FLEET_ERR_INVALID);
-  if (p->struct_bytes != (int32_t)sizeof(FleetPpoParams)) return refuse("FleetPpoParams.struct_bytes does not match this library", FLEET_ERR_INVALID);
-  if (p->max_batch < 1 || p->max_batch > (1 << 24)) return refuse("max_batch must be in 1..16777216, got " + std::to_string(p->max_batch), FLEET_ERR_INVALID);
-  if (!out) return refuse("null output handle", FLEET_ERR_INVALID);
-  if (!policy) return refuse("null policy", FLEET_ERR_INVALID);
-  FleetMlpHandle* pol = image_of(policy);
-  if (pol->n_nets != 2) return refuse("the policy has one head: the loss needs the critic (head 1)", FLEET_ERR_INVALID);
-  const PolicyHeadDesc* nets = pol->nets;
-  if (nets[1].layer[nets[1].n_layers - 1].out != 1)
-    return refuse("the critic's last width must be 1, got " + std::to_string(nets[1].layer[nets[1].n_layers - 1].out), FLEET_ERR_INVALID);
-  if (nets[1].output != FLEET_POLICY_OUT_NONE) return refuse("the critic's output transform must be NONE", FLEET_ERR_INVALID);
+  std::string why = check_params(p);
+  if (why.empty() && !out) why = "null output handle";
+  FleetMlpHandle* pol = why.empty() ? mlp_borrow(policy, sizeof(PolicyDesc), "policy", &why) : nullptr;
+  if (pol && pol->n_nets != 2) why = "the policy has one head: the loss needs the critic (head 1)";
+  if (why.empty()) {
+    const PolicyHeadDesc& critic = pol->nets[1];
+    if (critic.layer[critic.n_layers - 1].out != 1)
+      why = "the critic's last width must be 1, got " + std::to_string(critic.layer[critic.n_layers - 1].out);
+    else if (critic.output != FLEET_POLICY_OUT_NONE) why = "the critic's output transform must be NONE";
+  }
+  if (!why.empty()) return handle_refuse(g_ppo_error, "fleet_ppo_create", why, FLEET_ERR_INVALID);
   FleetPpo* h = new FleetPpo();
-  h->pol = pol, h->p = *p;
+  h->p = *p;
+  const PolicyHeadDesc* nets = pol->nets;
   const uint64_t mb = (uint64_t)p->max_batch;
-  uint64_t off = 0;
-  for (int hd = 0; hd < 2; ++hd)
-    for (int l = 0; l < nets[hd].n_layers; ++l) {
-      const uint64_t w = (uint64_t)nets[hd].layer[l].out64;
-      if ((int)w > h->T) h->T = (int)w;
-      if (l < nets[hd].n_layers - 1) h->s.act[hd][l] = off, off += mb * w;
-      h->s.delta[hd][l] = off, off += mb * w;
-    }
+  uint64_t off = grad_scratch_layout(nets, 2, mb, h->s.act, h->s.delta, &h->T);
   h->s.ls = off, off += mb * (uint64_t)nets[0].layer[nets[0].n_layers - 1].out64;
   h->s.part = off, off += (mb + kPolicyRows - 1) / kPolicyRows * kPartStride;
   h->s.floats = off;
   h->lds_bytes = ((size_t)2 * kPolicyRows * h->T + (size_t)kPolicyRows * kPolicyChunk + 64) * sizeof(float);
   constexpr int kMaxLds = (2 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk + 64) * (int)sizeof(float);
-  if (hipSetDevice(pol->device) != hipSuccess) {
-    delete h;
-    return refuse("hipSetDevice failed", FLEET_ERR_HIP);
+  const int rc = mlp_user_open(h, pol, off * sizeof(float), "scratch", {{reinterpret_cast<const void*>(&ppo_rows), kMaxLds}}, "rows", &why);
+  if (rc != FLEET_OK) {
+    fleet_ppo_destroy(h);
+    return handle_refuse(g_ppo_error, "fleet_ppo_create", why, rc);
   }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_rows), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
-    (void)hipGetLastError();
-    delete h;
-    return refuse("hipFuncSetAttribute failed for the rows kernel's " + std::to_string(kMaxLds) + " bytes of LDS", FLEET_ERR_HIP);
-  }
-  void* q = nullptr;
-  if (hipMalloc(&q, off * sizeof(float)) != hipSuccess) {
-    (void)hipGetLastError();
-    delete h;
-    return refuse("hipMalloc of the scratch's " + std::to_string(off * sizeof(float)) + " bytes failed", FLEET_ERR_HIP);
-  }
-  h->scratch = static_cast<float*>(q);
   *out = h;
   return FLEET_OK;
 }
 
 int fleet_ppo_destroy(fleet_ppo_handle h) {
   if (!h) return FLEET_OK;
-  if (h->scratch) (void)hipFree(h->scratch);  // (waits for the device: whatever still reads the scratch is done)
+  mlp_user_close(h);
   delete h;
   return FLEET_OK;
 }
@@ -313,46 +293,26 @@ int fleet_ppo_describe(fleet_ppo_handle h, FleetPpoParams* out, uint64_t* scratc
 
 int fleet_ppo_grad_dev(fleet_ppo_handle h, const FleetPpoGradArgs* args, float* const* grads, int count) {
   std::string why = check_grad_args(args, grads, count);
-  if (!h) {
-    g_ppo_error = "fleet_ppo_grad_dev: " + (why.empty() ? std::string("null handle") : why);
-    return FLEET_ERR_INVALID;
-  }
-  FleetMlpHandle* pol = h->pol;
-  if (why.empty() && count != pol->n_tensors + 1)
-    why = "expected " + std::to_string(pol->n_tensors + 1) + " gradient tensors (W, b per layer, then log_std), got " + std::to_string(count);
-  if (why.empty() && args->B > h->p.max_batch)
-    why = "B must be at most max_batch = " + std::to_string(h->p.max_batch) + ", got " + std::to_string(args->B);
-  if (!why.empty()) {
-    h->error = "fleet_ppo_grad_dev: " + why;
-    return FLEET_ERR_INVALID;
-  }
+  if (h && why.empty()) grad_check_sizes(&why, count, h->img->n_tensors + 1, "W, b per layer, then log_std", args->B, h->p.max_batch);
+  if (const int rc = handle_enter("fleet_ppo_grad_dev", why, h, g_ppo_error); rc != FLEET_OK) return rc;
+  FleetMlpHandle* pol = h->img;
   const FleetPpoGradArgs& x = *args;
   const PolicyHeadDesc* nets = pol->nets;
   const int B = x.B, n_tiles = (B + kPolicyRows - 1) / kPolicyRows;
   const float invB = 1.0f / (float)B;
+  float* scratch = h->floats();
   RowsArgs t{};
   t.desc = reinterpret_cast<const PolicyDesc*>(pol->block);
   t.base = reinterpret_cast<const float*>(pol->block);
   t.obs = x.obs, t.actions = x.actions, t.old_lp = x.old_log_prob, t.adv = x.advantages, t.ret = x.returns, t.log_std = x.log_std;
   t.values = x.values, t.log_prob = x.log_prob;
-  t.scratch = h->scratch, t.s = h->s, t.B = B, t.T = h->T;
+  t.scratch = scratch, t.s = h->s, t.B = B, t.T = h->T;
   t.clip = x.clip_range, t.vf_coef = x.vf_coef, t.invB = invB;
   WeightArgs g{};
-  int blocks = 0, ti = 0;
-  for (int hd = 0; hd < 2; ++hd)
-    for (int l = 0; l < nets[hd].n_layers; ++l, ti += 2) {
-      const PolicyLayer& L = nets[hd].layer[l];
-      GradEntry& E = g.e[g.n_entries++];
-      E.d = h->scratch + h->s.delta[hd][l], E.dstride = L.out64;
-      E.seam = L.in;  // (one input array)
-      if (l == 0) E.x = x.obs, E.xstride = L.in;
-      else E.x = h->scratch + h->s.act[hd][l - 1], E.xstride = nets[hd].layer[l - 1].out64;
-      E.dW = grads[ti], E.db = grads[ti + 1], E.out = L.out, E.in = L.in;
-      grad_entry_tiles(E, &blocks);
-    }
+  grad_fill_entries(g.e, &g.n_entries, &g.tile_blocks, nets, 0, 2, scratch, h->s.act, h->s.delta, x.obs, nets[0].layer[0].in, nullptr, 0, grads);
   const PolicyLayer& LA = nets[0].layer[nets[0].n_layers - 1];
-  g.tile_blocks = blocks, g.ls_blocks = (LA.out + 255) / 256, g.B = B;
-  g.ls = h->scratch + h->s.ls, g.part = h->scratch + h->s.part, g.log_std = x.log_std;
+  g.ls_blocks = (LA.out + 255) / 256, g.B = B;
+  g.ls = scratch + h->s.ls, g.part = scratch + h->s.part, g.log_std = x.log_std;
   g.dlog_std = grads[count - 1], g.stats = x.stats;
   g.A = LA.out, g.M = LA.out64, g.n_tiles = n_tiles;
   g.invB = invB, g.vf_coef = x.vf_coef, g.ent_coef = x.ent_coef;

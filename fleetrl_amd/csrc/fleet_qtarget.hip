@@ -145,6 +145,7 @@ struct FleetQTarget : FleetMlpHandle {
   QTargetDesc desc{};
   size_t lds_bytes = 0;  // of one workgroup of qtarget_target
 };
+static_assert(mlp_image_is_first_base<FleetQTarget>, "mlp_borrow (fleet_mlp.hip) reads a fleet_qtarget_handle as the image's handle");
 
 namespace {
 
@@ -238,14 +239,7 @@ int fleet_qtarget_export_dev(fleet_qtarget_handle h, float* const* tensors, int 
 int fleet_qtarget_target_dev(fleet_qtarget_handle h, const float* next_obs, const float* rewards, const float* dones, int B,
                              const FleetQTargetArgs* args) {
   const std::string why = check_target_args(next_obs, rewards, dones, B, args);
-  if (!h) {
-    g_qtarget_error = "fleet_qtarget_target_dev: " + (why.empty() ? std::string("null handle") : why);
-    return FLEET_ERR_INVALID;
-  }
-  if (!why.empty()) {
-    h->error = "fleet_qtarget_target_dev: " + why;
-    return FLEET_ERR_INVALID;
-  }
+  if (const int rc = handle_enter("fleet_qtarget_target_dev", why, h, g_qtarget_error); rc != FLEET_OK) return rc;
   const FleetQTargetArgs& x = *args;
   TargetArgs t{};
   t.desc = reinterpret_cast<const QTargetDesc*>(h->block);

@@ -238,8 +238,12 @@ __global__ __launch_bounds__(256) void td3_weights(WeightArgs a) {
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 thread_local std::string g_td3_error;  // of the last failed call without a handle
 
-// FleetQTarget (fleet_qtarget.hip) derives from FleetMlpHandle and from nothing else: the image's handle is its first base
-FleetMlpHandle* image_of(fleet_qtarget_handle p) { return reinterpret_cast<FleetMlpHandle*>(p); }
+std::string check_params(const FleetTd3Params* p) {
+  if (!p) return "null FleetTd3Params";
+  if (p->struct_bytes != (int32_t)sizeof(FleetTd3Params)) return "FleetTd3Params.struct_bytes does not match this library";
+  if (p->max_batch < 1 || p->max_batch > (1 << 24)) return "max_batch must be in 1..16777216, got " + std::to_string(p->max_batch);
+  return "";
+}
 
 // what both entries refuse about their gradient tensors, looked at without the handle
 std::string check_grads(float* const* grads, int count) {
@@ -276,12 +280,9 @@ std::string check_actor_args(const FleetTd3ActorArgs* args, float* const* grads,
 
 }  // namespace
 
-struct FleetTd3 {
-  FleetMlpHandle* nets = nullptr;  // borrowed: the networks' handle outlives this one
-  std::string error;
+struct FleetTd3 : FleetMlpUser {  // img: the ONLINE networks'; block: the scratch
   FleetTd3Params p{};
   Td3Scratch s{};
-  float* scratch = nullptr;
   int S = 64;  // the widest layer of all networks, out64
   size_t lds_bytes = 0;
 };
@@ -290,33 +291,18 @@ namespace {
 
 // the launches of one entry: `rows` over grid (tiles, grid_y), then the weights of networks net0 .. net0 + n_nets - 1
 int launch_entry(FleetTd3* h, void (*rows)(RowsArgs), int grid_y, RowsArgs& t, int entry, int net0, int n_nets, float* const* grads, float* stats) {
-  FleetMlpHandle* img = h->nets;
+  FleetMlpHandle* img = h->img;
   const QTargetDesc* desc = static_cast<const QTargetDesc*>(img->record);
-  const PolicyHeadDesc* nets = img->nets;
   const int B = t.B, n_tiles = (B + kPolicyRows - 1) / kPolicyRows;
   t.desc = reinterpret_cast<const QTargetDesc*>(img->block);
   t.base = reinterpret_cast<const float*>(img->block);
-  t.scratch = h->scratch, t.s = h->s, t.S = h->S;
+  t.scratch = h->floats(), t.s = h->s, t.S = h->S;
   t.invB = 1.0f / (float)B;
   WeightArgs g{};
-  int blocks = 0, ti = 0;
-  for (int nt = net0; nt < net0 + n_nets; ++nt)
-    for (int l = 0; l < nets[nt].n_layers; ++l, ti += 2) {
-      const PolicyLayer& L = nets[nt].layer[l];
-      GradEntry& E = g.e[g.n_entries++];
-      E.d = h->scratch + h->s.delta[nt][l], E.dstride = L.out64;
-      E.seam = L.in;  // (one input array, but for a critic's first layer)
-      if (l > 0) {
-        E.x = h->scratch + h->s.act[nt][l - 1], E.xstride = nets[nt].layer[l - 1].out64;
-      } else {
-        E.x = t.obs, E.xstride = desc->obs_dim;
-        if (nt > 0) E.seam = desc->obs_dim, E.x2 = t.actions, E.x2stride = desc->act_dim;
-      }
-      E.dW = grads[ti], E.db = grads[ti + 1], E.out = L.out, E.in = L.in;
-      grad_entry_tiles(E, &blocks);
-    }
-  g.tile_blocks = blocks, g.B = B, g.n_tiles = n_tiles, g.entry = entry, g.nc = desc->n_critics;
-  g.part = h->scratch + h->s.part, g.stats = stats, g.invB = t.invB;
+  grad_fill_entries(g.e, &g.n_entries, &g.tile_blocks, img->nets, net0, n_nets, t.scratch, h->s.act, h->s.delta, t.obs, desc->obs_dim,
+                    net0 > 0 ? t.actions : nullptr, desc->act_dim, grads);  // (the critics' first layers take the actions behind the seam)
+  g.B = B, g.n_tiles = n_tiles, g.entry = entry, g.nc = desc->n_critics;
+  g.part = t.scratch + h->s.part, g.stats = stats, g.invB = t.invB;
   FLEET_HANDLE_TRY(h, hipSetDevice(img->device));
   hipLaunchKernelGGL(rows, dim3((unsigned)n_tiles, (unsigned)grid_y), dim3(kPolicyThreads), h->lds_bytes, img->stream, t);
   FLEET_HANDLE_TRY(h, hipGetLastError());
@@ -331,59 +317,33 @@ extern "C" {
 
 int fleet_td3_create(fleet_qtarget_handle nets_handle, const FleetTd3Params* p, fleet_td3_handle* out) {
   if (out) *out = nullptr;
-  const auto refuse = [](const std::string& why, int rc) {
-    g_td3_error = "fleet_td3_create: " + why;
-    return rc;
-  };
-  if (!p) return refuse("null FleetTd3Params", FLEET_ERR_INVALID);
-  if (p->struct_bytes != (int32_t)sizeof(FleetTd3Params)) return refuse("FleetTd3Params.struct_bytes does not match this library", FLEET_ERR_INVALID);
-  if (p->max_batch < 1 || p->max_batch > (1 << 24)) return refuse("max_batch must be in 1..16777216, got " + std::to_string(p->max_batch), FLEET_ERR_INVALID);
-  if (!out) return refuse("null output handle", FLEET_ERR_INVALID);
-  if (!nets_handle) return refuse("null networks handle", FLEET_ERR_INVALID);
-  FleetMlpHandle* img = image_of(nets_handle);
-  if (img->record_bytes != sizeof(QTargetDesc) || img->n_nets < 2 || img->n_nets > kQNets)
-    return refuse("the networks handle is not a fleet_qtarget handle", FLEET_ERR_INVALID);
+  std::string why = check_params(p);
+  if (why.empty() && !out) why = "null output handle";
+  FleetMlpHandle* img = why.empty() ? mlp_borrow(nets_handle, sizeof(QTargetDesc), "networks", &why) : nullptr;
+  if (!why.empty()) return handle_refuse(g_td3_error, "fleet_td3_create", why, FLEET_ERR_INVALID);
   const QTargetDesc* desc = static_cast<const QTargetDesc*>(img->record);
-  const PolicyHeadDesc* nets = img->nets;
   FleetTd3* h = new FleetTd3();
-  h->nets = img, h->p = *p;
+  h->p = *p;
   const uint64_t mb = (uint64_t)p->max_batch;
-  uint64_t off = 0;
-  for (int nt = 0; nt < img->n_nets; ++nt)
-    for (int l = 0; l < nets[nt].n_layers; ++l) {
-      const uint64_t w = (uint64_t)nets[nt].layer[l].out64;
-      if ((int)w > h->S) h->S = (int)w;
-      if (l < nets[nt].n_layers - 1) h->s.act[nt][l] = off, off += mb * w;
-      h->s.delta[nt][l] = off, off += mb * w;
-    }
+  uint64_t off = grad_scratch_layout(img->nets, img->n_nets, mb, h->s.act, h->s.delta, &h->S);
   h->s.part = off, off += (mb + kPolicyRows - 1) / kPolicyRows * kPartStride;
   h->s.floats = off;
   h->lds_bytes = ((size_t)2 * kPolicyRows * h->S + (size_t)kPolicyRows * kPolicyChunk + (size_t)kPolicyRows * desc->act64 + kRowScalars) * sizeof(float);
   constexpr int kMaxLds = (3 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk + kRowScalars) * (int)sizeof(float);
-  if (hipSetDevice(img->device) != hipSuccess) {
-    delete h;
-    return refuse("hipSetDevice failed", FLEET_ERR_HIP);
+  const int rc = mlp_user_open(h, img, off * sizeof(float), "scratch",
+                               {{reinterpret_cast<const void*>(&td3_critic_rows), kMaxLds}, {reinterpret_cast<const void*>(&td3_actor_rows), kMaxLds}},
+                               "rows", &why);
+  if (rc != FLEET_OK) {
+    fleet_td3_destroy(h);
+    return handle_refuse(g_td3_error, "fleet_td3_create", why, rc);
   }
-  for (const void* k : {reinterpret_cast<const void*>(&td3_critic_rows), reinterpret_cast<const void*>(&td3_actor_rows)})
-    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
-      (void)hipGetLastError();
-      delete h;
-      return refuse("hipFuncSetAttribute failed for a rows kernel's " + std::to_string(kMaxLds) + " bytes of LDS", FLEET_ERR_HIP);
-    }
-  void* q = nullptr;
-  if (hipMalloc(&q, off * sizeof(float)) != hipSuccess) {
-    (void)hipGetLastError();
-    delete h;
-    return refuse("hipMalloc of the scratch's " + std::to_string(off * sizeof(float)) + " bytes failed", FLEET_ERR_HIP);
-  }
-  h->scratch = static_cast<float*>(q);
   *out = h;
   return FLEET_OK;
 }
 
 int fleet_td3_destroy(fleet_td3_handle h) {
   if (!h) return FLEET_OK;
-  if (h->scratch) (void)hipFree(h->scratch);  // (waits for the device: whatever still reads the scratch is done)
+  mlp_user_close(h);
   delete h;
   return FLEET_OK;
 }
@@ -400,21 +360,10 @@ int fleet_td3_describe(fleet_td3_handle h, FleetTd3Params* out, uint64_t* scratc
 
 int fleet_td3_critic_grad_dev(fleet_td3_handle h, const FleetTd3CriticArgs* args, float* const* grads, int count) {
   std::string why = check_critic_args(args, grads, count);
-  if (!h) {
-    g_td3_error = "fleet_td3_critic_grad_dev: " + (why.empty() ? std::string("null handle") : why);
-    return FLEET_ERR_INVALID;
-  }
-  const PolicyHeadDesc* nets = h->nets->nets;
-  const int nc = h->nets->n_nets - 1;
-  const int want = 2 * (nets[1].n_layers + (nc == 2 ? nets[2].n_layers : 0));
-  if (why.empty() && count != want)
-    why = "expected " + std::to_string(want) + " gradient tensors (W, b per layer, critic after critic), got " + std::to_string(count);
-  if (why.empty() && args->B > h->p.max_batch)
-    why = "B must be at most max_batch = " + std::to_string(h->p.max_batch) + ", got " + std::to_string(args->B);
-  if (!why.empty()) {
-    h->error = "fleet_td3_critic_grad_dev: " + why;
-    return FLEET_ERR_INVALID;
-  }
+  if (h && why.empty())
+    grad_check_sizes(&why, count, h->img->n_tensors - 2 * h->img->nets[0].n_layers, "W, b per layer, critic after critic", args->B, h->p.max_batch);
+  if (const int rc = handle_enter("fleet_td3_critic_grad_dev", why, h, g_td3_error); rc != FLEET_OK) return rc;
+  const int nc = h->img->n_nets - 1;
   RowsArgs t{};
   t.obs = args->obs, t.actions = args->actions, t.target_q = args->target_q, t.q = args->q, t.B = args->B;
   return launch_entry(h, td3_critic_rows, nc, t, kCriticEntry, 1, nc, grads, args->stats);
@@ -422,19 +371,8 @@ int fleet_td3_critic_grad_dev(fleet_td3_handle h, const FleetTd3CriticArgs* args
 
 int fleet_td3_actor_grad_dev(fleet_td3_handle h, const FleetTd3ActorArgs* args, float* const* grads, int count) {
   std::string why = check_actor_args(args, grads, count);
-  if (!h) {
-    g_td3_error = "fleet_td3_actor_grad_dev: " + (why.empty() ? std::string("null handle") : why);
-    return FLEET_ERR_INVALID;
-  }
-  const int want = 2 * h->nets->nets[0].n_layers;
-  if (why.empty() && count != want)
-    why = "expected " + std::to_string(want) + " gradient tensors (W, b per layer of the actor), got " + std::to_string(count);
-  if (why.empty() && args->B > h->p.max_batch)
-    why = "B must be at most max_batch = " + std::to_string(h->p.max_batch) + ", got " + std::to_string(args->B);
-  if (!why.empty()) {
-    h->error = "fleet_td3_actor_grad_dev: " + why;
-    return FLEET_ERR_INVALID;
-  }
+  if (h && why.empty()) grad_check_sizes(&why, count, 2 * h->img->nets[0].n_layers, "W, b per layer of the actor", args->B, h->p.max_batch);
+  if (const int rc = handle_enter("fleet_td3_actor_grad_dev", why, h, g_td3_error); rc != FLEET_OK) return rc;
   RowsArgs t{};
   t.obs = args->obs, t.q = args->q, t.actions_out = args->actions_out, t.B = args->B;
   return launch_entry(h, td3_actor_rows, 1, t, kActorEntry, 0, 1, grads, args->stats);

@@ -12,39 +12,24 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _capi
-from ._capi import FleetHipError
-from ._handle import _DeviceHandle
+from ._handle import _ImageBorrower
 
 __all__ = ["DevicePPOGrad", "STATS"]
 
 STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction")
 
 
-class DevicePPOGrad(_DeviceHandle):
+class DevicePPOGrad(_ImageBorrower):
     """One `fleet_ppo_*` handle on `policy` (a `DevicePolicy` with a critic of width 1, which must outlive it) for minibatches of at
     most `max_batch` rows.  It launches on the policy's stream."""
     _prefix = "ppo"
 
     def __init__(self, policy, max_batch: int):
-        self.lib = _capi.load_library()
-        self.policy, self.device = policy, policy.device
+        self.policy = policy
         self.obs_dim, self.act_dim, self.max_batch = policy.obs_dim, policy.act_dim, int(max_batch)
-        p = _capi.FleetPpoParams(C.sizeof(_capi.FleetPpoParams), self.max_batch)
-        h = C.c_void_p()
-        rc = self.lib.fleet_ppo_create(policy.h, C.byref(p), C.byref(h))
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_ppo_last_error(None).decode())
-        self.h = h
+        self._open_on(policy, "fleet_ppo_create", _capi.FleetPpoParams(C.sizeof(_capi.FleetPpoParams), self.max_batch))
         self._shapes = [tuple(s) for pair in policy._shapes for s in pair] + [(self.act_dim,)]
-        self._into = None  # (the parameters, the pointer array of their .grad) of the last call
         self.tile_rows = self.describe()["tile_rows"]
-
-    def set_stream(self, hip_stream):
-        """The handle has no stream of its own: the policy's is set."""
-        self.policy.set_stream(hip_stream)
-
-    def use_torch_stream(self, device=None):
-        self.policy.use_torch_stream(device)
 
     def describe(self) -> dict:
         """What fleet_ppo_describe reports: max_batch, the bytes of the scratch, the rows one workgroup of the rows launch takes."""
@@ -56,28 +41,6 @@ class DevicePPOGrad(_DeviceHandle):
         """Raw device addresses in a FleetPpoGradArgs and a (c_void_p * count) array, on the policy's stream."""
         args.struct_bytes = C.sizeof(_capi.FleetPpoGradArgs)
         self._check(self.lib.fleet_ppo_grad_dev(self.h, C.byref(args), grad_ptrs, int(count)))
-
-    def _grad_pointers(self, into):
-        import torch
-
-        into = list(into)
-        hit = self._into
-        if hit is not None and len(hit[0]) == len(into) and all(a is b for a, b in zip(hit[0], into)) and \
-                all(p.grad is not None and p.grad.data_ptr() == q for p, q in zip(into, hit[2])):
-            return hit[1]
-        if len(into) != len(self._shapes):
-            raise ValueError(f"into: expected {len(self._shapes)} parameters (W, b per layer, the actor's then the critic's, then log_std), "
-                             f"got {len(into)}")
-        ptrs = []
-        for p, s in zip(into, self._shapes):
-            if tuple(p.shape) != s:
-                raise ValueError(f"into: expected a parameter of shape {s}, got {tuple(p.shape)}")
-            if p.grad is None:  # allocated once; the launches overwrite it
-                p.grad = torch.empty_like(p, memory_format=torch.contiguous_format)
-            ptrs.append(self._tensor(p.grad, s, (torch.float32,)).data_ptr())
-        arr = (C.c_void_p * len(ptrs))(*ptrs)
-        self._into = (into, arr, ptrs)
-        return arr
 
     def grad(self, batch, log_std, clip_range: float, vf_coef: float, ent_coef: float, *, into, values_out=None, log_prob_out=None,
              advantages=None, stats_out=None):
@@ -108,6 +71,6 @@ class DevicePPOGrad(_DeviceHandle):
             if t is not None:
                 keep.append(self._tensor(t, (B,), f32))
                 setattr(a, name, keep[-1].data_ptr())
-        arr = self._grad_pointers(into)
+        arr = self._grad_pointers("grad", into, self._shapes, "the actor's then the critic's, then log_std")
         self.grad_dev(a, arr, len(self._shapes))
         return stats_out

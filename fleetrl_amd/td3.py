@@ -13,8 +13,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _capi
-from ._capi import FleetHipError
-from ._handle import _DeviceHandle
+from ._handle import _ImageBorrower
 
 __all__ = ["DeviceTD3Grad", "CRITIC_STATS", "ACTOR_STATS"]
 
@@ -22,33 +21,19 @@ CRITIC_STATS = ("critic_loss", "critic_0_loss", "critic_1_loss")
 ACTOR_STATS = ("actor_loss",)
 
 
-class DeviceTD3Grad(_DeviceHandle):
+class DeviceTD3Grad(_ImageBorrower):
     """One `fleet_td3_*` handle on `nets` (a `DeviceTD3Target` that holds the online networks, which must outlive it) for minibatches
     of at most `max_batch` rows.  It launches on `nets`' stream."""
     _prefix = "td3"
 
     def __init__(self, nets, max_batch: int):
-        self.lib = _capi.load_library()
-        self.nets, self.device = nets, nets.device
+        self.nets = nets
         self.obs_dim, self.act_dim, self.n_critics, self.max_batch = nets.obs_dim, nets.act_dim, nets.n_critics, int(max_batch)
-        p = _capi.FleetTd3Params(C.sizeof(_capi.FleetTd3Params), self.max_batch)
-        h = C.c_void_p()
-        rc = self.lib.fleet_td3_create(nets.h, C.byref(p), C.byref(h))
-        if rc != _capi.OK:
-            raise FleetHipError(rc, self.lib.fleet_td3_last_error(None).decode())
-        self.h = h
+        self._open_on(nets, "fleet_td3_create", _capi.FleetTd3Params(C.sizeof(_capi.FleetTd3Params), self.max_batch))
         flat = [tuple(s) for pair in nets._shapes for s in pair]
         n_actor = 2 * len(nets.describe()["actor"]["widths"])
         self._shapes = {"actor": flat[:n_actor], "critic": flat[n_actor:]}
-        self._into = {"actor": None, "critic": None}  # (the parameters, the pointer array of their .grad, the addresses) of the last call
         self.tile_rows = self.describe()["tile_rows"]
-
-    def set_stream(self, hip_stream):
-        """The handle has no stream of its own: the networks handle's is set."""
-        self.nets.set_stream(hip_stream)
-
-    def use_torch_stream(self, device=None):
-        self.nets.use_torch_stream(device)
 
     def describe(self) -> dict:
         """What fleet_td3_describe reports: max_batch, the bytes of the scratch, the rows one workgroup of a rows launch takes."""
@@ -64,28 +49,6 @@ class DeviceTD3Grad(_DeviceHandle):
     def actor_grad_dev(self, args: "_capi.FleetTd3ActorArgs", grad_ptrs, count: int):
         args.struct_bytes = C.sizeof(_capi.FleetTd3ActorArgs)
         self._check(self.lib.fleet_td3_actor_grad_dev(self.h, C.byref(args), grad_ptrs, int(count)))
-
-    def _grad_pointers(self, which: str, into):
-        import torch
-
-        into = list(into)
-        hit, shapes = self._into[which], self._shapes[which]
-        if hit is not None and len(hit[0]) == len(into) and all(a is b for a, b in zip(hit[0], into)) and \
-                all(p.grad is not None and p.grad.data_ptr() == q for p, q in zip(into, hit[2])):
-            return hit[1]
-        if len(into) != len(shapes):
-            what = "the actor's" if which == "actor" else "critic 0's, then critic 1's"
-            raise ValueError(f"into: expected {len(shapes)} parameters (W, b per layer, {what}), got {len(into)}")
-        ptrs = []
-        for p, s in zip(into, shapes):
-            if tuple(p.shape) != s:
-                raise ValueError(f"into: expected a parameter of shape {s}, got {tuple(p.shape)}")
-            if p.grad is None:  # allocated once; the launches overwrite it
-                p.grad = torch.empty_like(p, memory_format=torch.contiguous_format)
-            ptrs.append(self._tensor(p.grad, s, (torch.float32,)).data_ptr())
-        arr = (C.c_void_p * len(ptrs))(*ptrs)
-        self._into[which] = (into, arr, ptrs)
-        return arr
 
     def critic_grad(self, batch_or_tensors, target_q, *, into, q_out=None, stats_out=None):
         """The critic loss of one minibatch and its gradients, two launches on torch's current stream, no host synchronisation.
@@ -114,7 +77,7 @@ class DeviceTD3Grad(_DeviceHandle):
         if q_out is not None:
             keep.append(self._tensor(q_out, (B, self.n_critics), f32))
             a.q = keep[-1].data_ptr()
-        arr = self._grad_pointers("critic", into)
+        arr = self._grad_pointers("critic", into, self._shapes["critic"], "critic 0's, then critic 1's")
         self.critic_grad_dev(a, arr, len(self._shapes["critic"]))
         return stats_out
 
@@ -139,6 +102,6 @@ class DeviceTD3Grad(_DeviceHandle):
             if t is not None:
                 keep.append(self._tensor(t, shape, f32))
                 setattr(a, name, keep[-1].data_ptr())
-        arr = self._grad_pointers("actor", into)
+        arr = self._grad_pointers("actor", into, self._shapes["actor"], "the actor's")
         self.actor_grad_dev(a, arr, len(self._shapes["actor"]))
         return stats_out

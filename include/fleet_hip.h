@@ -1363,7 +1363,8 @@ typedef struct FleetPpo* fleet_ppo_handle;
 
 /* FLEET_ERR_INVALID (fleet_ppo_last_error(NULL) says why, starting with the entry's name) for a null or wrongly sized FleetPpoParams,
  * max_batch outside 1..2^24, a null output or policy, a one-head policy, a critic whose last width is not 1 or whose output is not
- * NONE.  FLEET_ERR_HIP with the byte count when the scratch cannot be allocated. */
+ * NONE.  FLEET_ERR_HIP with the byte count when the scratch cannot be allocated.
+ * A handle of another family (a fleet_qtarget handle) is refused as well: "the handle is not a policy handle". */
 int fleet_ppo_create(fleet_policy_handle policy, const FleetPpoParams* p, fleet_ppo_handle* out);
 int fleet_ppo_destroy(fleet_ppo_handle h);
 const char* fleet_ppo_last_error(fleet_ppo_handle h);  /* h may be NULL: error of the last failed call without a handle */

@@ -240,3 +240,32 @@ def test_every_case_meets_the_tables_conditions(name):
     inside = np.abs(m["ratio"] - 1.0) <= ppm.CLIP_RANGE
     print(f"{name}: salt {c['salt']}, {int(inside.sum())} of {ppm.ROWS} rows inside the range, {int((~m['alive']).sum())} dead")
     assert all(np.isfinite(g).all() for g in m["grads"])
+
+
+# ---- the entries that look at their arguments before their handle, across the families ---------------------------------------------
+NULL_HANDLE_REFUSALS = {
+    "fleet_ppo_grad_dev": ("ppo", (None, None, 0), "null FleetPpoGradArgs"),
+    "fleet_td3_critic_grad_dev": ("td3", (None, None, 0), "null FleetTd3CriticArgs"),
+    "fleet_td3_actor_grad_dev": ("td3", (None, None, 0), "null FleetTd3ActorArgs"),
+    "fleet_adam_step_dev": ("adam", (None, None, None, 0), "null FleetAdamStepArgs"),
+    "fleet_adam_state_dev": ("adam", (7, None, None, 0, None), "unknown mode 7"),
+    "fleet_adam_export_image_dev": ("adam", (None, 0), "null handle"),
+    "fleet_qtarget_target_dev": ("qtarget", (None, None, None, 0, None), "null FleetQTargetArgs"),
+}
+
+
+def test_a_null_handles_refusal_lands_in_its_own_familys_string_and_in_no_other():
+    """The seven entries share one opening (fleet_handle.h); the thread-local strings stay one per family."""
+    from fleetrl_amd import _capi
+
+    lib = _capi.load_library()
+    families = sorted({f for f, _, _ in NULL_HANDLE_REFUSALS.values()})
+    last = lambda: {f: getattr(lib, f"fleet_{f}_last_error")(None).decode() for f in families}  # noqa: E731
+    for entry, (family, args, why) in sorted(NULL_HANDLE_REFUSALS.items()):
+        before = last()
+        assert before[family] != f"{entry}: {why}"  # (the entry before this one left another message)
+        assert getattr(lib, entry)(None, *args) == _capi.ERR_INVALID
+        after = last()
+        assert after.pop(family) == f"{entry}: {why}", entry
+        before.pop(family)
+        assert after == before, entry
