@@ -10,6 +10,7 @@
     from fleetrl_amd import DevicePPOGrad
     from fleetrl_amd import DeviceTD3Grad
     from fleetrl_amd import DeviceAdam
+    from fleetrl_amd import DevicePPOTrain
 """
 __version__ = "0.1.0"
 
@@ -59,6 +60,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import adam
 
         return adam.DeviceAdam
+    if name == "DevicePPOTrain":
+        from . import train
+
+        return train.DevicePPOTrain
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

@@ -230,6 +230,23 @@ class FleetAdamInfo(C.Structure):
                 ("norm_chunk", C.c_int32), ("step_tile", C.c_int32), ("reserved", C.c_int32)]
 
 
+# ---- PPO's whole update (include/fleet_hip.h "PPO's whole update on the device", fleet_train_*) ------------------------------------------
+TRAIN_ROUNDS, TRAIN_MIN_HALF_BITS, TRAIN_STATS = 8, 4, 16
+
+
+class FleetTrainPpoArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_epochs", C.c_int32), ("batch_size", C.c_int32), ("normalize_advantage", C.c_int32),
+                ("clip_range", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("reserved", C.c_int32), ("lr", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_grad_norm", C.c_double), ("seed", C.c_uint64),
+                ("first_epoch", C.c_uint64), ("stats", C.c_void_p)]
+
+
+class FleetTrainInfo(C.Structure):
+    _fields_ = [("num_envs", C.c_int32), ("n_steps", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("max_batch", C.c_int32),
+                ("n_tensors", C.c_int32), ("rounds", C.c_int32), ("min_half_bits", C.c_int32), ("tile_rows", C.c_int32),
+                ("cache_rows", C.c_int32), ("staging_bytes", C.c_uint64), ("staging", C.c_void_p)]
+
+
 # ---- TD3 / DDPG minibatch gradients (include/fleet_hip.h "TD3 / DDPG minibatch gradients on the device", fleet_td3_*) -------------------
 class FleetTd3Params(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("max_batch", C.c_int32)]
@@ -540,9 +557,16 @@ def load_library():
     lib.fleet_adam_step_dev.argtypes = [vp, C.POINTER(FleetAdamStepArgs), C.POINTER(vp), C.POINTER(vp), C.c_int]
     lib.fleet_adam_state_dev.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(C.c_int64)]
     lib.fleet_adam_export_image_dev.argtypes = [vp, C.POINTER(vp), C.c_int]
+    # PPO's whole update (fleet_train.hip)
+    lib.fleet_train_create.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    lib.fleet_train_destroy.argtypes = [vp]
+    lib.fleet_train_last_error.argtypes = [vp]
+    lib.fleet_train_describe.argtypes = [vp, C.POINTER(FleetTrainInfo)]
+    lib.fleet_train_ppo_dev.argtypes = [vp, C.POINTER(FleetTrainPpoArgs), C.POINTER(vp), C.POINTER(vp), C.c_int]
+    lib.fleet_train_indices_dev.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, vp]
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
                           ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS), ("ppo", PPO_SYMBOLS),
-                          ("td3", TD3_SYMBOLS), ("adam", ADAM_SYMBOLS)):
+                          ("td3", TD3_SYMBOLS), ("adam", ADAM_SYMBOLS), ("train", TRAIN_SYMBOLS)):
         for name in names:
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
@@ -607,6 +631,9 @@ TD3_SYMBOLS = ("fleet_td3_create", "fleet_td3_destroy", "fleet_td3_last_error", 
 ADAM_SYMBOLS = ("fleet_adam_create_policy", "fleet_adam_create_qtarget", "fleet_adam_destroy", "fleet_adam_last_error", "fleet_adam_describe",
                 "fleet_adam_step_dev", "fleet_adam_state_dev", "fleet_adam_export_image_dev")
 
+TRAIN_SYMBOLS = ("fleet_train_create", "fleet_train_destroy", "fleet_train_last_error", "fleet_train_describe", "fleet_train_ppo_dev",
+                 "fleet_train_indices_dev")
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -620,7 +647,7 @@ EXPORTED_SYMBOLS = (
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
     "fleet_set_direct_state_only", "fleet_direct_packet_counts", "fleet_step_has_state_only",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS + TRAIN_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

@@ -1,0 +1,111 @@
+"""`DevicePPOTrain`: stable-baselines3's `PPO.train()` as one enqueue-only call (include/fleet_hip.h `fleet_train_*`,
+fleetrl_amd/csrc/fleet_train.hip).
+
+`n_epochs` passes over a finished `DeviceRolloutBuffer` in freshly shuffled minibatches (`clip_range_vf=None`, `target_kl=None`): per
+minibatch one launch shuffles, gathers and normalises the advantages, `DevicePPOGrad`'s two launches form the gradients and `DeviceAdam`'s
+two clip, step and refresh the policy's weight image.  The shuffle is a keyed bijection evaluated on the device -- no `torch.randperm`,
+no permutation in memory --, every sum has a stated order, and one block of statistics (`STATS`: what SB3 logs as `train/*`) is
+written at the end.  Deterministic from (buffer, weights, optimiser state, seed, first_epoch) to the weights.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import _capi
+from ._capi import FleetHipError
+from ._handle import _ImageBorrower
+
+__all__ = ["DevicePPOTrain", "STATS"]
+
+# the statistics block f64[16]: the means over all minibatches, the last minibatch's loss, the number of minibatches, the buffer's
+# explained variance, mean(exp(log_std)) after the last step; then zeros
+STATS = ("policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "loss", "n_updates", "explained_variance", "std")
+# SB3's logger keys, in STATS' order
+SB3_NAMES = ("train/policy_gradient_loss", "train/value_loss", "train/entropy_loss", "train/approx_kl", "train/clip_fraction", "train/loss",
+             "train/n_updates", "train/explained_variance", "train/std")
+
+
+class DevicePPOTrain(_ImageBorrower):
+    """One `fleet_train_*` handle on `buffer` (a `DeviceRolloutBuffer`), `grad` (a `DevicePPOGrad`) and `adam` (a `DeviceAdam` over both
+    heads and `log_std`), which lie on one `DevicePolicy` and must outlive it.  Minibatches hold at most `grad.max_batch` rows.  It
+    launches on the policy's stream; the optimiser's betas, eps and max_grad_norm are `adam`'s."""
+    _prefix = "train"
+
+    def __init__(self, buffer, grad, adam):
+        self.buffer, self.grad, self.adam, self.policy = buffer, grad, adam, grad.policy
+        self.lib = _capi.load_library()
+        self._owner, self.device = grad.policy, grad.policy.device
+        h = C.c_void_p()
+        rc = self.lib.fleet_train_create(buffer.h, grad.h, adam.h, C.byref(h))
+        if rc != _capi.OK:
+            raise FleetHipError(rc, self.lib.fleet_train_last_error(None).decode())
+        self.h = h
+        self._grad_cache = {}
+        self._shapes = list(grad._shapes)
+        self._ptrs = None  # (the parameters, their pointer array, their addresses) of the last call
+
+    def describe(self) -> dict:
+        """What fleet_train_describe reports."""
+        i = _capi.FleetTrainInfo()
+        self._check(self.lib.fleet_train_describe(self.h, C.byref(i)))
+        return {n: getattr(i, n) for n, _ in i._fields_}
+
+    def use_torch_stream(self, device=None):
+        """The policy and the buffer both launch on torch's current stream from now on."""
+        self._owner.use_torch_stream(device)
+        self.buffer.use_torch_stream(device)
+
+    def train_dev(self, args: "_capi.FleetTrainPpoArgs", param_ptrs, grad_ptrs, count: int):
+        """Raw device addresses in a FleetTrainPpoArgs and two (c_void_p * count) arrays, on the policy's stream."""
+        args.struct_bytes = C.sizeof(_capi.FleetTrainPpoArgs)
+        self._check(self.lib.fleet_train_ppo_dev(self.h, C.byref(args), param_ptrs, grad_ptrs, int(count)))
+
+    def _param_pointers(self, into):
+        import torch
+
+        into = list(into)
+        hit = self._ptrs
+        if hit is not None and len(hit[0]) == len(into) and all(a is b and a.data_ptr() == q for a, b, q in zip(hit[0], into, hit[2])):
+            return hit[1]
+        ptrs = [self._tensor(p.detach(), s, (torch.float32,)).data_ptr() for p, s in zip(into, self._shapes)]
+        self._ptrs = (into, (C.c_void_p * len(ptrs))(*ptrs), ptrs)
+        return self._ptrs[1]
+
+    def train(self, into, *, n_epochs: int, batch_size: int, clip_range: float, vf_coef: float, ent_coef: float, lr: float,
+              normalize_advantage: bool = True, seed: int, first_epoch: int, stats_out=None):
+        """The whole update on torch's current stream, no host synchronisation.  into: the torch parameters in
+        `DevicePolicy.load_torch`'s order, then log_std; they are stepped in place (and the policy's image with them), their `.grad`
+        holds the last minibatch's gradients.  Epoch e shuffles under (seed, first_epoch + e): pass the number of epochs trained so far.
+        Returns the statistics f64 [16] on the device: `STATS`, then zeros."""
+        import torch
+
+        if not self.buffer.full:
+            raise FleetHipError(_capi.ERR_STATE, "train() needs a full rollout buffer")
+        self.use_torch_stream()
+        a = _capi.FleetTrainPpoArgs()
+        a.n_epochs, a.batch_size, a.normalize_advantage = int(n_epochs), int(batch_size), int(bool(normalize_advantage))
+        a.clip_range, a.vf_coef, a.ent_coef, a.lr = float(clip_range), float(vf_coef), float(ent_coef), float(lr)
+        a.beta1, a.beta2, a.eps, a.max_grad_norm = self.adam.betas[0], self.adam.betas[1], self.adam.eps, self.adam.max_grad_norm
+        a.seed, a.first_epoch = int(seed), int(first_epoch)
+        if stats_out is None:
+            stats_out = torch.empty(_capi.TRAIN_STATS, device=torch.device("cuda", self.device), dtype=torch.float64)
+        a.stats = self._tensor(stats_out, (_capi.TRAIN_STATS,), (torch.float64,)).data_ptr()
+        grads = self._grad_pointers("train", into, self._shapes, "the actor's then the critic's, then log_std")
+        self.train_dev(a, self._param_pointers(into), grads, len(self._shapes))
+        return stats_out
+
+    def indices(self, n: int, seed: int, epoch: int, start: int = 0, count: int | None = None, out=None):
+        """The shuffle on its own: perm(n, seed, epoch, start .. start + count - 1) as int32 [count] on the device, one launch."""
+        import torch
+
+        self._owner.use_torch_stream()
+        count = int(n) - int(start) if count is None else int(count)
+        if count < 0:
+            raise ValueError(f"count must be >= 0, got {count}")
+        if out is None:
+            out = torch.empty(count, device=torch.device("cuda", self.device), dtype=torch.int32)
+        if count == 0:
+            return out
+        ptr = self._tensor(out, (count,), (torch.int32,)).data_ptr()
+        self._check(self.lib.fleet_train_indices_dev(self.h, int(n), int(seed), int(epoch), int(start), count, ptr))
+        return out

@@ -1133,6 +1133,100 @@ int fleet_qtarget_target_dev(fleet_qtarget_handle h, const float* next_obs, cons
 /* the parameters the handle was created with, and tile_rows */
 int fleet_qtarget_describe(fleet_qtarget_handle h, FleetQTargetParams* out);
 
+/* ---- PPO's whole update on the device (fleet_train.hip; DESIGN.md "PPO's whole update on the device") ------------------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * stable-baselines3 2.3.2's PPO.train() with clip_range_vf = None and target_kl = None as ONE enqueue-only call: n_epochs passes over a
+ * finished rollout buffer (fleet_rollout_finish_dev has run) in freshly shuffled minibatches of batch_size rows, the short last one
+ * when n % batch_size != 0 included, as SB3's get() yields them; n = E * K; a batch_size above n means one minibatch of n rows.  Per
+ * minibatch FIVE launches on the policy's stream: the minibatch launch below, fleet_ppo_grad_dev's two, fleet_adam_step_dev's two --
+ * those four through their own entries, as they are (their sections state their arithmetic), on the staged rows, with the call's
+ * clip_range, vf_coef, ent_coef, lr, betas, eps and max_grad_norm; Adam's step count advances once per minibatch.  log_std is the LAST
+ * tensor of params / grads: updated in place, read by the next gradient launch.  One closing launch per call writes the statistics.
+ * The handle BORROWS a rollout buffer, a fleet_ppo handle and a fleet_adam handle, which must outlive it, and owns the staging block.
+ * The shuffle.  perm(n, seed, epoch, p) is a keyed bijection of [0, n), evaluated per position, nothing materialised:
+ *   h = the smallest h >= FLEET_TRAIN_MIN_HALF_BITS with 2^(2h) >= n;  mask = 2^h - 1;  x = p
+ *   repeat:  L = x >> h;  R = x & mask
+ *            for r = 0 .. FLEET_TRAIN_ROUNDS - 1:
+ *              F = word 0 of philox4x32_10(counter (R, r, epoch_lo, epoch_hi); key (seed_lo, seed_hi)) & mask;  (L, R) = (R, L ^ F)
+ *            x = (L << h) | R
+ *   until x < n;  perm = x        (cycle walking: a bijection of [0, 2^(2h)) walked from a point below n returns below n)
+ * Epoch e of a call shuffles with epoch = first_epoch + e: a caller that counts its epochs never repeats a shuffle, and a checkpoint
+ * needs that count only.  Position start + b of the epoch is row b of the minibatch at `start`; i = perm(...) is the flat index
+ * e_env * K + t of fleet_rollout_gather_dev.
+ * The minibatch launch gathers obs, actions, old log-probabilities, advantages and returns of its B rows into the staging block (rows
+ * of obs / actions as 16-byte words when D / A is a multiple of 4; old values are not gathered: nothing reads them) and, when
+ * normalize_advantage != 0 and B > 1, writes a second advantage array, which the gradient launches then read:
+ *   ordered sum S(x) of B values in minibatch order, float64: lane t of 256: s_t = 0.0; s_t = s_t + x[b] for b = t, t + 256, ... ascending;
+ *     then for s = 128, 64, ..., 1: s_t = s_t + s_(t + s) for t < s; the result is s_0
+ *   mean64 = S((double)adv) / (double)B;  std64 = sqrt(S(((double)adv - mean64)^2) / (double)(B - 1))     (the unbiased one)
+ *   mean32 = (float)mean64;  std32 = (float)std64;  advn[b] = (adv[b] - mean32) / (std32 + 1e-8f)           (float32, SB3's expression)
+ * The bits depend on the B values in minibatch order alone: not on the grid, the stream, max_batch or the run.  With B == 1 or
+ * normalize_advantage == 0 the raw advantages are used (SB3 makes the same exception for one row).
+ * The statistics block, stats f64[FLEET_TRAIN_STATS], written by the closing launch:
+ *   [0] policy_loss [1] value_loss [2] entropy_loss [3] approx_kl [4] clip_fraction: the float64 mean over ALL minibatches of all epochs
+ *       of the gradient launches' float32 statistic, in the order they ran: acc = 0.0; acc = acc + (double)stat; acc / (double)count
+ *       -- what SB3 logs as train/policy_gradient_loss, train/value_loss, train/entropy_loss, train/approx_kl, train/clip_fraction
+ *   [5] loss: the LAST minibatch's (train/loss)        [6] count: the number of minibatches
+ *   [7] explained_variance = 1 - vd / vy over the whole buffer, y = (double)returns, d = y - (double)values, time-major order
+ *       (x[t * E + e]), float64 with the ordered sum S over the n values: my = S(y) / n;  md = S(d) / n;
+ *       vy = S((y - my)^2) / n;  vd = S((d - md)^2) / n;  NaN when vy == 0, as SB3's helper returns
+ *   [8] std = S(exp((double)log_std[j])) / A after the last step (train/std)        [9..15] 0
+ * Every *_dev call takes device pointers, only enqueues (it may block on the queue's depth, it never waits for the device) and launches
+ * on the POLICY's stream, whichever that is when the call is made; the rollout buffer must launch on that same stream then (streams
+ * are not ordered with events here).  No atomics, no ordering between workgroups.  Calls are serialised by the caller. */
+#define FLEET_TRAIN_ROUNDS 8
+#define FLEET_TRAIN_MIN_HALF_BITS 4
+#define FLEET_TRAIN_STATS 16
+typedef struct FleetTrainPpoArgs {
+  int32_t struct_bytes;          /* sizeof(FleetTrainPpoArgs) */
+  int32_t n_epochs;              /* >= 1 */
+  int32_t batch_size;            /* >= 1; min(batch_size, n) <= the gradient handle's max_batch */
+  int32_t normalize_advantage;   /* 0: off */
+  float clip_range;              /* in (0, 1) */
+  float vf_coef, ent_coef;       /* not NaN */
+  int32_t reserved;              /* 0 */
+  double lr;                     /* finite, >= 0; constant within the call */
+  double beta1, beta2;           /* in [0, 1) */
+  double eps;                    /* finite, >= 0 */
+  double max_grad_norm;          /* <= 0: no clipping */
+  uint64_t seed;                 /* the shuffle's key */
+  uint64_t first_epoch;          /* epoch e of the call shuffles with first_epoch + e */
+  double* stats;                 /* device f64[FLEET_TRAIN_STATS] */
+} FleetTrainPpoArgs;
+typedef struct FleetTrainInfo {
+  int32_t num_envs, n_steps, obs_dim, act_dim;   /* the rollout buffer's E, K, D, A */
+  int32_t max_batch;             /* the gradient handle's: rows the staging block holds */
+  int32_t n_tensors;             /* the `count` the update takes: the policy's tensors + 1 */
+  int32_t rounds, min_half_bits; /* of the shuffle */
+  int32_t tile_rows;             /* rows per tile of the minibatch launch (4) */
+  int32_t cache_rows;            /* positions of a minibatch whose buffer rows the launch keeps in the LDS (2048) */
+  uint64_t staging_bytes;        /* of the staging arrays */
+  void* staging;                 /* device: obs [max_batch, D], actions [max_batch, A], old_log_prob, advantages, normalised advantages,
+                                    returns [max_batch], each at the next multiple of 256 bytes; the LAST minibatch's rows (tests) */
+} FleetTrainInfo;
+typedef struct FleetTrain* fleet_train_handle;
+
+/* FLEET_ERR_INVALID (fleet_train_last_error(NULL) says why, starting with the entry's name) for a null handle or output, a gradient
+ * handle and an optimiser on different policies, a rollout buffer on another device or whose D or A differs from the policy's, an
+ * optimiser whose span is not both heads plus one extra of length A.  FLEET_ERR_HIP with the byte count when the staging block cannot
+ * be allocated.  (grad: a fleet_ppo_handle, adam: a fleet_adam_handle; their sections follow this one, so the struct tags stand here.) */
+struct FleetPpo;
+struct FleetAdam;
+int fleet_train_create(fleet_rollout_handle buffer, struct FleetPpo* grad, struct FleetAdam* adam, fleet_train_handle* out);
+int fleet_train_destroy(fleet_train_handle h);
+const char* fleet_train_last_error(fleet_train_handle h);  /* h may be NULL: error of the last failed call without a handle */
+int fleet_train_describe(fleet_train_handle h, FleetTrainInfo* out);
+/* The update.  params, grads: host arrays of `count` device pointers as fleet_adam_step_dev takes them (W, b per layer, head 0 then head
+ * 1, then log_std).  FLEET_ERR_INVALID (nothing is launched, the step count stays) for a null or wrongly sized FleetTrainPpoArgs,
+ * n_epochs < 1, batch_size < 1, a reserved that is not 0, a null stats, whatever fleet_ppo_grad_dev and fleet_adam_step_dev refuse (in
+ * their words), and -- these need the handle -- a count that is not the policy's tensors + 1, a minibatch above max_batch, a rollout
+ * buffer that launches on another stream than the policy.  The arguments are looked at before the handle is: with h NULL the reason
+ * (or "null handle") goes to fleet_train_last_error(NULL). */
+int fleet_train_ppo_dev(fleet_train_handle h, const FleetTrainPpoArgs* a, float* const* params, float* const* grads, int count);
+/* The shuffle on its own, one launch: out[k] = perm(n, seed, epoch, start + k) for k < count, int32 in device memory; any n in
+ * 1 .. 2^31 - 1.  FLEET_ERR_INVALID for n < 1, positions outside [0, n), a null out. */
+int fleet_train_indices_dev(fleet_train_handle h, int32_t n, uint64_t seed, uint64_t epoch, int32_t start, int32_t count, int32_t* out);
+
 /* ---- Adam and clip_grad_norm_ on the device (fleet_adam.hip; DESIGN.md "The optimiser step on the device") -------------------------
  * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
  * What a gradient step does behind the gradients -- torch.nn.utils.clip_grad_norm_(params, max_grad_norm), torch.optim.Adam.step() and
