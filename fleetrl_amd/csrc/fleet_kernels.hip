@@ -76,12 +76,16 @@ __device__ __forceinline__ void ev_finish(const FleetDev& d, const EvIx& i, int 
                                           bool t090, bool inplane, bool crosses, const SegRec& nr, double soh0, double a, double en, bool logs,
                                           size_t lrow, const Hot& h_in, uint32_t& err, double& sei_sample, double& sei_soh, int& sei_tail,
                                           RfTop& sei_top, bool& sei_have_top, RfAccHead& acc_c, RfTop& top_c, bool carry,
-                                          bool own_b = false) {
+                                          bool own_b = false, bool deep = false) {
   double soh = soh0;
   RfTop top = top_c;
   if (DEG == FLEET_DEG_RAINFLOW && env_ok) {
-    if (own_b) rf_finish_own_b(d, i, rq, tail, top, acc_c, err);  // (one step per launch, one EV per lane: see rf_finish_as)
-    else rf_finish(d, i, rq, tail, top, acc_c, err);
+    if (own_b) {  // (one step per launch, one EV per lane: see rf_finish_as)
+      if (deep) rf_finish_win(d, i, rq, tail, top, acc_c, err);  // (the state-only twin: the second closure from the request's window)
+      else rf_finish_own_b(d, i, rq, tail, top, acc_c, err);
+    } else {
+      rf_finish(d, i, rq, tail, top, acc_c, err);
+    }
   }
   const bool pushed = rq.push;
   if (carry && pushed) top_c = top;
@@ -605,8 +609,10 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       int tail = HOT_TAIL(hb.bits), sgn = HOT_SGN(hb.bits);
       // (K steps per launch: request and consumption stay together -- the registers the request holds across the observation
       // stores would cost the multi-step kernel a resident wavefront per SIMD)
+      // (the state-only twin with float32 actions: the deep request, for rf_finish_win's second closure)
+      constexpr bool kRfDeep = kEarly && DEAD && !A64;
       constexpr bool kSplitRf = !MULTI;
-      if (kSplitRf && DEG == FLEET_DEG_RAINFLOW && env_ok && rf_live) rf_begin(d, i, old_deg, soc_deg, tail, sgn, rq);
+      if (kSplitRf && DEG == FLEET_DEG_RAINFLOW && env_ok && rf_live) rf_begin(d, i, old_deg, soc_deg, tail, sgn, rq, false, kRfDeep);
 
       FLEET_STAMP(3);
       // ---- observation of the advanced time row (fleet_environment.py:511-518, 645-652) ------------------------
@@ -631,7 +637,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       if (!kSplitRf && DEG == FLEET_DEG_RAINFLOW && env_ok && rf_live) rf_begin(d, i, old_deg, soc_deg, tail, sgn, rq, kRfEarly);
       ev_finish<DEG, WIDE>(d, i, c, N, env_ok, deg_row, dt_step, rq, tail, sgn, soc, soc_deg, old_deg, hl, tb1.there, t090, inplane,
                            crosses, nr, soh0, a, en, logs, lrow, hb, err, sei_sample, sei_soh, sei_tail, sei_top, sei_have_top, acc_c,
-                           top_c, kRfCarry, kEarly);
+                           top_c, kRfCarry, kEarly, kRfDeep);
       if (!WIDE) break;  // N <= G: a single pass, and no loop for the compiler to hoist rare-path constants out of
     }
     {  // ---- the rest of the step reads the argument block afresh (see `late_args`) ----

@@ -1,6 +1,6 @@
 // fleet_rainflow.h -- battery degradation: streaming rainflow + SEI model, the linear model, and the EV's hot record.
 //
-// Provides: exp_small / pow_m0501 / cycle_stress (the stress of one cycle); rf_request / rf_begin / rf_finish (one SOC sample per
+// Provides: exp_small / pow_m0501 / cycle_stress (the stress of one cycle); rf_request / rf_begin / rf_finish / rf_finish_win (one SOC sample per
 // step pushed into the EV's rainflow state); sei_evaluate (the daily evaluation); linear_degradation; hot_encode (struct Hot in
 // fleet_device.h).
 // Restates of the reference: LogDataDeg.log_soc, RainflowSeiDegradation / EmpiricalDegradation.calculate_degradation
@@ -93,20 +93,23 @@ __device__ __forceinline__ double cycle_stress(double rng, double mean, double c
 // the stack words behind the header (struct RfHdr in fleet_device.h).
 // The push is split in two so that its memory round trip hides behind the rest of the step: `rf_begin`, right after the
 // state machine, knows the new sample and therefore whether a reversal point is pushed, and REQUESTS the EV's row (header
-// head, stack top, the two entries below the top two: three 16-byte loads of one cache line); `rf_finish`, after the
+// head, stack top, the two entries below the top two: three 16-byte loads of one cache line; `deep`: see rf_request); `rf_finish`, after the
 // observation stores and the money terms, consumes it.  A step that pushes nothing -- three in four -- never touches the row.
 struct RfReq {
   double p;        // the reversal point to push
   RfAccHead acc;   // requested when a point is pushed
   RfTop top;       // stack[tail-2], stack[tail-1]
   double w0, w1;   // stack[tail-3], [tail-4] (before the push)
+  double w2, w3;   // stack[tail-5], [tail-6]: `deep` requests only
   bool push;
   bool win;        // w0 / w1 were requested (else the pops read the stack words)
 };
 // `early`: the row's header and the entries below the top two were already requested at the start of the EV's step (K steps
 // per launch: the same row lines serve all K steps of the launch from the cache, and a wavefront that advances on its own is
 // bound by its own dependent round trips, which this removes from every step that pushes).
-__device__ __forceinline__ void rf_request(const FleetDev& d, const EvIx& i, int tail, RfReq& q) {
+// `deep` (a constant at every call; for rf_finish_win): the window reaches two entries further down -- one more 16-byte load of
+// the same line, issued with the other three.  The K-step kernel, at its register limit, keeps the shallow request.
+__device__ __forceinline__ void rf_request(const FleetDev& d, const EvIx& i, int tail, RfReq& q, bool deep = false) {
   const double* row = rf_row_of(d, i);
   q.acc = *reinterpret_cast<const RfAccHead*>(row);
   q.top = *reinterpret_cast<const RfTop*>(row + 2);
@@ -115,9 +118,15 @@ __device__ __forceinline__ void rf_request(const FleetDev& d, const EvIx& i, int
   q.w1 = w[0];
   q.w0 = w[1];
   q.win = true;
+  if (deep) {
+    // stack[tail-6], stack[tail-5]: row words tail, tail + 1 -- header words again for a shallow stack, never before the row's first
+    // word (tail >= 1), and never used then: a closure that reads them has found the stack deep enough
+    q.w3 = w[-2];
+    q.w2 = w[-1];
+  }
 }
 __device__ __forceinline__ void rf_begin(const FleetDev& d, const EvIx& i, double old_deg, double soc_deg, int tail, int& sgn, RfReq& q,
-                                         bool early = false) {
+                                         bool early = false, bool deep = false) {
   q.push = false;
   q.p = old_deg;
   // rainflow.reversals, one sample per step: equal samples are skipped, a strict slope sign change makes the previous
@@ -127,7 +136,7 @@ __device__ __forceinline__ void rf_begin(const FleetDev& d, const EvIx& i, doubl
     q.push = (sgn != 0 && sgn != s_next);
     sgn = s_next;
   }
-  if (q.push && !early) rf_request(d, i, tail, q);
+  if (q.push && !early) rf_request(d, i, tail, q, deep);
 }
 // `top`: the stack top after the push (only written when a point was pushed)
 // `acc_out`: the accumulator head after the push (only written when the push closed a cycle)
@@ -226,6 +235,109 @@ __device__ __forceinline__ void rf_finish(const FleetDev& d, const EvIx& i, cons
 __device__ __forceinline__ void rf_finish_own_b(const FleetDev& d, const EvIx& i, const RfReq& q, int& tail, RfTop& top, RfAccHead& acc_out,
                                                 uint32_t& err) {
   rf_finish_as<true>(d, i, q, tail, top, acc_out, err);
+}
+// The same push for the state-only twin of the one-step, one-EV-per-lane kernel with float32 actions -- 1999 of a direct run's 2000
+// launches --, where the request (`deep`) is issued well before this runs and a wavefront pays for its worst lane:
+// a second closure is rare per push (8 %) and common per wavefront (one launch in two has a
+// lane with one), and in the loop above it is a dependent load at the very end of the wavefront's step.  Here the second closure
+// too -- the new top against the two entries below the first cycle, a full cycle or the half cycle at size 3 with its rewrite of
+// slot 0 -- is decided and performed from the request's window, by selects inside the one `closes` region; the loop starts at the
+// third closure and is entered only by a wavefront that has such a lane (0.9 % of pushes).  Every sum is added in the order of
+// the loop above: results are the same bit for bit.  (A window two entries deeper still, and `csum` fetched with the request, were
+// built and measured: EXPERIMENTS.md "The second closure from the request's window".)
+// The live instances and the float64 twins keep rf_finish_own_b: with the deeper window they fall from five resident wavefronts per
+// SIMD to four (99 / 98 VGPRs), which the closed loop pays for at the large shapes (+2.7 % at 16384 x 50, +6.5 % at c5).
+// `b` gets a register of its own as in rf_finish_as<true>; the same care for the closed-cycle count (`k`).
+__device__ __forceinline__ void rf_finish_win(const FleetDev& d, const EvIx& i, const RfReq& q, int& tail, RfTop& top, RfAccHead& acc_out,
+                                                uint32_t& err) {
+  if (!q.push) return;
+  double* row = rf_row_of(d, i);
+  double* stk = row + RF_HDR_WORDS;
+  if (tail >= d.stack_cap) {  // (see rf_finish)
+    err |= FLEET_DEVERR_TABLE_END;
+    return;
+  }
+  const double p = q.p;
+  const double a0 = q.top.s1, b0 = q.top.s2;  // stack[tail-2] (also in the stack words), stack[tail-1] (only in the header)
+  const int size = tail + 1;                  // points on the stack with p pushed
+  const bool closes = (size >= 3) && !(fabs(p - b0) < fabs(b0 - a0));
+  const bool half = closes && (size == 3);    // Y contains the starting point: half cycle, the first point is dropped
+  // ONE store for b0: it joins the stack words when nothing closes (slot tail-1) and is rewritten to slot 0 when the first point
+  // is dropped; a full cycle leaves the stack words as they are
+  if (!closes || half) st_plain(rf_row_of(d, i, (unsigned)(RF_HDR_WORDS + (half ? 0 : tail - 1))), b0);
+  const int L = q.acc.rf_len;
+  // closed cycles of this push, and the first of them that carries stress: only the closed cycles beyond the last evaluation's
+  // count do (index >= L - 1), none in the steady state.  (The requested count itself is only ever read: a count that the closures
+  // rewrite costs what `b` below would.)
+  int k = 0;
+  const int k_stress = L - 1 - q.acc.nc;
+  double mean_sum = q.acc.mean_sum, dcsum = 0.0;
+  bool has_csum = false;
+  double a = a0, b = b0;
+  // (a value of its own: otherwise `b`, which the closures below rewrite, shares its register with the requested word `b0`, and the
+  // copy that separates the two is a phi copy: it lands at the end of the block that issued the request, behind a wait for the row
+  // -- in every wavefront, right after the loads)
+  asm volatile("" : "+v"(b));
+  int t = size;
+  if (closes) {
+    mean_sum += 0.5 * (a0 + b0);
+    // the first cycle was a full one (its two points vanish, p lives in s2): the new top against the two entries below it.  A
+    // window word of a shallow stack is a header word: `t >= 3` keeps it out of the test, and the word that becomes `b` after a
+    // full closure (t >= 4 before it) is always a stack word.
+    const double a1 = q.w1, b1 = q.w0;
+    const int t1 = size - 2;
+    const bool closes2 = !half && (t1 >= 3) && !(fabs(p - b1) < fabs(b1 - a1));
+    const bool half2 = closes2 && (t1 == 3);
+    const bool full2 = closes2 && !half2;
+    mean_sum = closes2 ? mean_sum + 0.5 * (a1 + b1) : mean_sum;
+    k = closes2 ? 2 : 1;
+    t = half ? 2 : (closes2 ? (half2 ? 2 : t1 - 2) : t1);  // half: stack = [b0, p]; half2: [b1, p]
+    b = half ? b : (full2 ? q.w2 : b1);
+    a = full2 ? q.w3 : a1;
+    if (half2) stk[0] = b1;
+    if (k > k_stress) {  // the last closure has the largest index: one test for both
+      if (0 >= k_stress) {
+        dcsum = cycle_stress(fabs(a0 - b0), 0.5 * (a0 + b0), half ? 0.5 : 1.0, d.self->stress_temp);
+        has_csum = true;
+      }
+      if (closes2) {
+        dcsum += cycle_stress(fabs(a1 - b1), 0.5 * (a1 + b1), half2 ? 0.5 : 1.0, d.self->stress_temp);
+        has_csum = true;
+      }
+    }
+    // from the third closure on: the first pair is still the request's, the ones below it come from the stack words
+    if (full2 && (t >= 3) && !(fabs(p - b) < fabs(b - a))) {
+      do {
+        if (k >= k_stress) {
+          dcsum += cycle_stress(fabs(a - b), 0.5 * (a + b), (t == 3) ? 0.5 : 1.0, d.self->stress_temp);
+          has_csum = true;
+        }
+        mean_sum += 0.5 * (a + b);
+        k += 1;
+        if (t == 3) {
+          stk[0] = b;
+          t = 2;
+        } else {
+          t -= 2;
+          b = stk[t - 2];
+          a = (t >= 3) ? stk[t - 3] : 0.0;
+        }
+      } while (t >= 3 && !(fabs(p - b) < fabs(b - a)));
+    }
+  }
+  tail = t;
+  top.s1 = b;  // stack[tail-2]
+  top.s2 = p;  // stack[tail-1]
+  st_plain(reinterpret_cast<RfTop*>(row + 2), top);
+  if (closes) {
+    RfAccHead out;
+    out.mean_sum = mean_sum;
+    out.nc = q.acc.nc + k;
+    out.rf_len = L;
+    acc_out = out;
+    st_plain(reinterpret_cast<RfAccHead*>(row), out);
+    if (has_csum) reinterpret_cast<RfHdr*>(row)->csum += dcsum;
+  }
 }
 // RainflowSeiDegradation.calculate_degradation for one EV on the daily row (rainflow_sei_degradation.py:91-212).
 // `v` = the sample just logged (forced last reversal), `n` = number of logged samples.  The forced point and the
