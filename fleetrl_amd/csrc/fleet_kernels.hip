@@ -265,6 +265,24 @@ static_assert(offsetof(StepKernargs, rec_rows) == offsetof(StepKernargs, rec_blo
 // kModeAll = everything behind run-time tests (the data-log instances and the small groups, where instances are not multiplied).
 constexpr int kModeAll = 0, kModeTape = 1, kModePolicy = 2, kModeRt = 3;
 
+// The tail of the state-only twin (DEAD), three parts that can be compiled one by one for an A/B (-DFLEET_TWIN_TAIL=<bits> through
+// fleetrl_amd.build.build_variant; EXPERIMENTS.md, "The twin's tail: one late argument fetch"); the product has all three (measured one by one and together there):
+//   1  A: the rainflow row request's two scalars (rf_row_stride, stack_cap) are fetched with the entry's argument loads
+//   2  B: ONE late fetch -- everything the rest of the step reads of the kernel-argument segment in one block of scalar loads, one wait
+//   4  C: the env record's final stores through the preloaded `p_env`, the reset's flag re-read inside the reset branch
+// The live instances never look at this.
+#ifndef FLEET_TWIN_TAIL
+#define FLEET_TWIN_TAIL 7
+#endif
+// What part B reads at the first `late_args` point and keeps in scalar registers to the end of the launch.
+struct TwinLateTail { unsigned long long rec; unsigned char* blocks; int rows, rotate; };
+struct TwinLate {
+  int E, T;                                                  // the self-check of the hard-wired offset
+  double evse_power, grid_connection, penalty_overload;      // the leader's overload test
+  int auto_reset;
+  unsigned long long rec; unsigned char* blocks; int rows, rotate;  // the placement guard's 24-byte piece
+};
+
 // DEAD: the state-only twin of a single-step instance ("Dead outputs" in the kernel): the same argument list, `outputs_dead` ignored --
 // that nobody can read this launch's outputs is a compile-time fact.  Only for groups of whole wavefronts with one EV per lane
 // (G = 64 / 128 / 256, the benchmark's shapes); only a run on the library's own queue ever launches it (fleet_direct.hip).
@@ -292,9 +310,15 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   // several points costs +0.7 us (profiles/r04_experiments/args_reloaded_*).  `late_args_ok` guards the hard-wired offset.
   static_assert(!DEAD || (!MULTI && !WIDE && !LOG && G >= 64 && MODE == kModeAll), "the state-only twin: one step, one EV per lane, whole wavefronts");
   const FleetDev& d = d_arg;
+  // (not the rainflow twins with float64 actions: they sit at the scalar register limit, two scalars in lanes, and the late block would
+  // put two more there; they keep the live instance's tail)
+  constexpr bool kTail = DEAD && !(A64 && DEG == FLEET_DEG_RAINFLOW);
+  constexpr bool kTailA = kTail && DEG == FLEET_DEG_RAINFLOW && (FLEET_TWIN_TAIL & 1) != 0;
+  constexpr bool kTailB = kTail && (FLEET_TWIN_TAIL & 2) != 0;
+  constexpr bool kTailC = kTail && (FLEET_TWIN_TAIL & 4) != 0;
+  typedef const __attribute__((address_space(4))) char* karg_ptr;
   auto late_args = [&]() -> const FleetDev& {
     if constexpr (!MULTI && !WIDE) {
-      typedef const __attribute__((address_space(4))) char* karg_ptr;
       karg_ptr kp = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(StepKernargPrefix, d_arg);
       asm volatile("" : "+s"(kp));
       return *(const FleetDev*)(const __attribute__((address_space(4))) FleetDev*)kp;
@@ -302,6 +326,17 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       return d_arg;
     }
   };
+  // (B) the twin launders ONE pointer, at the first late point (`late_args_once`); the second late scope and the placement guard read
+  // through the same one (`late_args_same`)
+  karg_ptr late_kp = nullptr;
+  auto late_args_once = [&]() -> const FleetDev& {
+    late_kp = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(StepKernargPrefix, d_arg);
+    asm volatile("" : "+s"(late_kp));
+    return *(const FleetDev*)(const __attribute__((address_space(4))) FleetDev*)late_kp;
+  };
+  auto late_args_same = [&]() -> const FleetDev& { return *(const FleetDev*)(const __attribute__((address_space(4))) FleetDev*)late_kp; };
+  TwinLate lt = {0, 0, 0.0, 0.0, 0.0, 0, 0ull, nullptr, 0, 0};
+  uint32_t late_bad = 0;  // kTailB: nonzero = the argument block is not where `late_args` assumes it
   constexpr bool kPol = MULTI && (MODE == kModeAll || MODE == kModePolicy);  // the built-in policies are compiled in
   constexpr bool kRt = MULTI && (MODE == kModeAll || MODE == kModeRt);       // the event-skipping loop is compiled in
   // `p_N`: EVs per env in the low half; in the high half the workgroup this launch's grid starts at -- 0 for every launch through HIP;
@@ -364,6 +399,11 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
     ep_len = er->ep_len;
     if (DEG == FLEET_DEG_RAINFLOW && !MULTI) rf_until = er->rf_until;
   }
+  // (A) what rf_begin's row request and rf_finish_win read of the argument block: fetched with the entry's argument loads, under the
+  // wait for the head, so that nothing scalar stands between the push decision and the four row loads.  An input of an opaque asm:
+  // the fetch cannot sink to its use.  Behind the leader's loads: the compiler takes a volatile asm for a store, and a uniform load
+  // behind it is no longer a scalar one.
+  if constexpr (kTailA) asm volatile("" ::"s"(d_arg.rf_row_stride), "s"(d_arg.stack_cap));
   if (DEG == FLEET_DEG_RAINFLOW && MULTI) {
     rf_until = p_env[e].rf_until;
     if (G >= 64) rf_until = __builtin_amdgcn_readfirstlane(rf_until);
@@ -641,8 +681,26 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       if (!WIDE) break;  // N <= G: a single pass, and no loop for the compiler to hoist rare-path constants out of
     }
     {  // ---- the rest of the step reads the argument block afresh (see `late_args`) ----
-    const FleetDev& d = late_args();
-    if (!MULTI && !WIDE && (d.T != d_arg.T || d.E != p_E)) err |= FLEET_DEVERR_INTERNAL;  // the block is not where it is assumed to be
+    const FleetDev& d = kTailB ? late_args_once() : late_args();
+    if constexpr (kTailB) {
+      // (B) everything the rest of the step reads of the kernel-argument segment on its common path, requested here in one block
+      // through the one laundered pointer; the wait is behind the fold (the asm below)
+      typedef const __attribute__((address_space(4))) TwinLateTail* tail_ptr;
+      const TwinLateTail& tl = *(const TwinLateTail*)(tail_ptr)(late_kp + (offsetof(StepKernargs, guard_bytes) - offsetof(StepKernargPrefix, d_arg)));
+      lt.E = d.E;
+      lt.T = d.T;
+      lt.evse_power = d.evse_power;
+      lt.grid_connection = d.grid_connection;
+      lt.penalty_overload = d.penalty_overload;
+      lt.auto_reset = d.auto_reset;
+      lt.rec = tl.rec;
+      lt.blocks = tl.blocks;
+      lt.rows = tl.rows;
+      lt.rotate = tl.rotate;
+      __builtin_amdgcn_sched_barrier(0);  // the block of loads is issued in FRONT of the fold and flies under it
+    } else {
+      if (!MULTI && !WIDE && (d.T != d_arg.T || d.E != p_E)) err |= FLEET_DEVERR_INTERNAL;  // the block is not where it is assumed to be
+    }
     if (write_step_obs) tail_store<G>(d, step_row, t1, g, tail_first);
     if (logs) tail_store<G>(d, log_obs_row, t1, g, tail_first);
     if (DEG != FLEET_DEG_NONE) r.nsamp += 1;
@@ -651,6 +709,12 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
     // ---- per-env reductions; totals land in the leader lane ---------------------------------------------------
     if (G >= 64) {
       wave_sum4_to_last(cash, rew, asum, penrec);  // this wavefront's lanes: totals in its last lane
+      if constexpr (kTailB) {  // the one wait for the late fetch: every field is an input here, so none of the loads sinks to its use
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" ::"s"(lt.E), "s"(lt.T), "s"(lt.evse_power), "s"(lt.grid_connection), "s"(lt.penalty_overload), "s"(lt.auto_reset),
+                     "s"(lt.rec), "s"(lt.blocks), "s"(lt.rows), "s"(lt.rotate));
+        late_bad = (uint32_t)(lt.T ^ d_arg.T) | (uint32_t)(lt.E ^ p_E);  // no branch; OR-ed into `err` where the guard is
+      }
       if (G > 64) {
         // an env of several wavefronts: their partial sums meet in the LDS and the group's last lane adds them in wavefront order
         // (K steps per launch: the env's wavefronts meet here once per step -- every wavefront of the workgroup runs the same K
@@ -693,10 +757,11 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
     if (leader) {
       penalty_record += penrec;
       // LoadCalculation.check_violation (load_calculation.py:93) and the sigmoid penalty (:496-502)
-      const double head_room = d.grid_connection - ph.load - asum * d.evse_power + ph.pv;
+      const double grid_connection = kTailB ? lt.grid_connection : d.grid_connection;
+      const double head_room = grid_connection - ph.load - asum * (kTailB ? lt.evse_power : d.evse_power) + ph.pv;
       const double over = fabs(head_room < 0.0 ? head_room : 0.0);
       if (over > 0.0) {
-        const double pen = overloading_penalty(over / d.grid_connection + 1.0, d.penalty_overload);
+        const double pen = overloading_penalty(over / grid_connection + 1.0, kTailB ? lt.penalty_overload : d.penalty_overload);
         rew += pen;
         penalty_record += pen;
         if (kRt) ev_lane = true;  // :499
@@ -770,7 +835,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
         er->start_done |= (int32_t)0x80000000u;  // episode.done
       }
       r.episodes += 1;
-      if (resets) {
+      if (kTailB ? (lt.auto_reset != 0) : resets) {  // (inside `is_done`)
         head_reset = true;
         if (env_ok) {
           if constexpr (kStateOnly) reset_env<G, LOG>(*d.self, e, g, leader, r, obs_live ? obs_row : nullptr, lp, rf_until);
@@ -784,6 +849,14 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
         ep_return = 0.0;
         ep_len = 0;
         penalty_record = 0.0;
+        if constexpr (kTailC) {
+          // (C) the new start row's flags for the head, read AND waited for here, in the rare branch, so that the common path does
+          // not join behind a pending load of the reset's.  (The drain in front of the env record's stores is still there: the
+          // compiler puts it back for the flags and the time row's leader terms of the FIRST burst, which are pending on the path
+          // around the lane loop's body -- EXPERIMENTS.md has the excerpt and what removing it cost.)
+          head_after = d.tab_phys[r.t].flags_next;
+          asm volatile("" : "+v"(head_after));
+        }
       }
     }
     last_done = done_now;
@@ -799,17 +872,17 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   }
 
   {  // ---- after the steps: again through the freshly read block ----
-  const FleetDev& d = late_args();
+  const FleetDev& d = kTailB ? late_args_same() : late_args();
   // (only where a single-step launch that reads them can follow on the same handle: `carry_run`, i.e. up to kMaxGroup EVs per env)
   if (!kEarly && (!WIDE || d.carry_run) && env_ok) {  // the carried schedule records: the row the NEXT launch advances to
     const int rn = r.t + 1 > d.T - 1 ? d.T - 1 : r.t + 1;
     for (int c = g; c < N; c += G) d.run[(size_t)e * N + c] = d.seg[(size_t)rn * N + c];
   }
   if (leader && env_ok) {
-    EnvRec* er = d.env + e;
+    EnvRec* er = kTailC ? p_env + e : d.env + e;  // (C: the preloaded pointer, no argument fetch in front of the stores)
     // the head carries the row flags the next launch's state machine needs (struct EnvHead)
     uint32_t nflags = head_after;
-    if (!kEarly || head_reset) nflags = d.tab_phys[r.t].flags_next;
+    if (!kEarly || (head_reset && !kTailC)) nflags = d.tab_phys[r.t].flags_next;
     r.nsamp = HEAD_PACK(r.nsamp, nflags, r.t < rf_until);
     er->h = r;
     er->ep_return = ep_return;
@@ -837,12 +910,16 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   // vector load 4 %: profiles/r06_experiments/placement_guard_cost.log).  A mismatch raises FLEET_DEVERR_PLACEMENT (sticky; the
   // run's results are void, fleet_check_errors tells the caller).  Launches through HIP carry a record of zeros: no check.
   if constexpr (!MULTI) {
-    struct Tail { unsigned long long rec; unsigned char* blocks; int rows, rotate; };
+    typedef TwinLateTail Tail;
     static_assert(offsetof(StepKernargs, rec_blocks) == offsetof(StepKernargs, guard_bytes) + 8, "one 24-byte piece of the argument block");
-    typedef const __attribute__((address_space(4))) char* karg_ptr;
-    karg_ptr kp = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(StepKernargs, guard_bytes);
-    asm volatile("" : "+s"(kp));  // (not hoisted to the entry: see late_args)
-    const Tail& tl = *(const Tail*)(const __attribute__((address_space(4))) Tail*)kp;
+    Tail tl_b = {lt.rec, lt.blocks, lt.rows, lt.rotate};  // (B: fetched with the late block, from the same launch's segment)
+    karg_ptr kp = nullptr;
+    if constexpr (!kTailB) {
+      kp = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(StepKernargs, guard_bytes);
+      asm volatile("" : "+s"(kp));  // (not hoisted to the entry: see late_args)
+    }
+    const Tail& tl = kTailB ? tl_b : *(const Tail*)(const __attribute__((address_space(4))) Tail*)kp;
+    if constexpr (kTailB) { if (late_bad) err |= FLEET_DEVERR_INTERNAL; }
     const unsigned w = blockIdx.x + (unsigned)wg_base;
     const unsigned have = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11));  // HW_REG_XCC_ID, bits [3:0]
     const unsigned slot = (unsigned)(tl.rec >> (8u * (w & 7u))) & 0xffu;
