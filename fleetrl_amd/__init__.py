@@ -11,6 +11,7 @@
     from fleetrl_amd import DeviceTD3Grad
     from fleetrl_amd import DeviceAdam
     from fleetrl_amd import DevicePPOTrain
+    from fleetrl_amd import DeviceTD3Train
 """
 __version__ = "0.1.0"
 
@@ -64,6 +65,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import train
 
         return train.DevicePPOTrain
+    if name == "DeviceTD3Train":
+        from . import offpolicy
+
+        return offpolicy.DeviceTD3Train
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

@@ -247,6 +247,28 @@ class FleetTrainInfo(C.Structure):
                 ("cache_rows", C.c_int32), ("staging_bytes", C.c_uint64), ("staging", C.c_void_p)]
 
 
+# ---- TD3 / DDPG's whole update (include/fleet_hip.h "TD3 / DDPG's whole update on the device", fleet_offpolicy_*) ------------------------
+OFFPOLICY_MAX_STEPS, OFFPOLICY_SLOT_FLOATS = 65536, 16
+
+
+class FleetOffpolicyParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("max_steps", C.c_int32)]
+
+
+class FleetOffpolicyArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("gradient_steps", C.c_int32), ("batch_size", C.c_int32), ("policy_delay", C.c_int32),
+                ("reserved", C.c_int32), ("gamma", C.c_float), ("tau", C.c_double), ("noise_clip", C.c_float), ("act_lo", C.c_float),
+                ("act_hi", C.c_float), ("sigma", C.c_void_p), ("lr", C.c_double), ("beta1", C.c_double * 2), ("beta2", C.c_double * 2),
+                ("eps", C.c_double * 2), ("max_grad_norm", C.c_double * 2), ("seed", C.c_uint64), ("first_update", C.c_uint64),
+                ("norm", C.c_void_p), ("stats", C.c_void_p)]
+
+
+class FleetOffpolicyInfo(C.Structure):
+    _fields_ = [("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_critics", C.c_int32), ("max_batch", C.c_int32), ("max_steps", C.c_int32),
+                ("n_actor_tensors", C.c_int32), ("n_critic_tensors", C.c_int32), ("reserved", C.c_int32), ("staging_bytes", C.c_uint64),
+                ("staging", C.c_void_p), ("slots", C.c_void_p)]
+
+
 # ---- TD3 / DDPG minibatch gradients (include/fleet_hip.h "TD3 / DDPG minibatch gradients on the device", fleet_td3_*) -------------------
 class FleetTd3Params(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("max_batch", C.c_int32)]
@@ -564,9 +586,17 @@ def load_library():
     lib.fleet_train_describe.argtypes = [vp, C.POINTER(FleetTrainInfo)]
     lib.fleet_train_ppo_dev.argtypes = [vp, C.POINTER(FleetTrainPpoArgs), C.POINTER(vp), C.POINTER(vp), C.c_int]
     lib.fleet_train_indices_dev.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, vp]
+    # TD3 / DDPG's whole update (fleet_offpolicy.hip)
+    lib.fleet_offpolicy_create.argtypes = [vp, vp, vp, vp, vp, C.POINTER(FleetOffpolicyParams), C.POINTER(vp)]
+    lib.fleet_offpolicy_destroy.argtypes = [vp]
+    lib.fleet_offpolicy_last_error.argtypes = [vp]
+    lib.fleet_offpolicy_describe.argtypes = [vp, C.POINTER(FleetOffpolicyInfo)]
+    lib.fleet_offpolicy_td3_dev.argtypes = [vp, C.POINTER(FleetOffpolicyArgs), C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(vp),
+                                            C.POINTER(vp), C.c_int]
+    lib.fleet_offpolicy_polyak_dev.argtypes = [vp, C.c_double]
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
                           ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS), ("ppo", PPO_SYMBOLS),
-                          ("td3", TD3_SYMBOLS), ("adam", ADAM_SYMBOLS), ("train", TRAIN_SYMBOLS)):
+                          ("td3", TD3_SYMBOLS), ("adam", ADAM_SYMBOLS), ("train", TRAIN_SYMBOLS), ("offpolicy", OFFPOLICY_SYMBOLS)):
         for name in names:
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
@@ -634,6 +664,9 @@ ADAM_SYMBOLS = ("fleet_adam_create_policy", "fleet_adam_create_qtarget", "fleet_
 TRAIN_SYMBOLS = ("fleet_train_create", "fleet_train_destroy", "fleet_train_last_error", "fleet_train_describe", "fleet_train_ppo_dev",
                  "fleet_train_indices_dev")
 
+OFFPOLICY_SYMBOLS = ("fleet_offpolicy_create", "fleet_offpolicy_destroy", "fleet_offpolicy_last_error", "fleet_offpolicy_describe",
+                     "fleet_offpolicy_td3_dev", "fleet_offpolicy_polyak_dev")
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -647,7 +680,7 @@ EXPORTED_SYMBOLS = (
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
     "fleet_set_direct_state_only", "fleet_direct_packet_counts", "fleet_step_has_state_only",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS + TRAIN_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS + TRAIN_SYMBOLS + OFFPOLICY_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

@@ -1133,6 +1133,119 @@ int fleet_qtarget_target_dev(fleet_qtarget_handle h, const float* next_obs, cons
 /* the parameters the handle was created with, and tile_rows */
 int fleet_qtarget_describe(fleet_qtarget_handle h, FleetQTargetParams* out);
 
+/* ---- TD3 / DDPG's whole update on the device (fleet_offpolicy.hip; DESIGN.md "TD3's whole update on the device") -------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * stable-baselines3 2.3.2's TD3.train(gradient_steps, batch_size) -- and DDPG's: n_critics = 1, policy_delay = 1, sigma zeros -- as ONE
+ * enqueue-only call.  The handle BORROWS five handles, which must outlive it: a replay buffer, the TARGET networks' fleet_qtarget handle,
+ * and -- all three on ONE second fleet_qtarget handle that holds the ONLINE networks -- a fleet_td3 gradient handle, a fleet_adam handle
+ * over the actor (span 0, 1, no extras) and one over the critics (span 1, n_critics, no extras).  It owns one block, zeroed at create:
+ * the staging arrays of max_batch rows (the gradient handle's) and max_steps slots of per-step statistics.
+ * Gradient step g = 0 .. gradient_steps - 1 of a call, with u = first_update + g, through the families' own entries, as they are (their
+ * sections state their arithmetic):
+ *   1. fleet_replay_sample_dev(replay, batch_size, norm, the staging arrays): the buffer's own call counter is used, which so advances by
+ *      gradient_steps per call
+ *   2. fleet_qtarget_target_dev on the TARGET networks from the staged next_obs, rewards and dones into the staged target_q; noise_mode
+ *      DRAW (not recorded), key (seed, row_offset 0, step = u)
+ *   3. fleet_td3_critic_grad_dev on the staged obs, actions and target_q; stats -> slot g, floats 0..7
+ *   4. fleet_adam_step_dev(adam_critic, lr, beta1[1], beta2[1], eps[1], max_grad_norm[1])
+ *   5. iff (u + 1) % policy_delay == 0 (SB3 increments _n_updates before it tests):
+ *      fleet_td3_actor_grad_dev on the staged obs; stats -> slot g, floats 8..15
+ *      fleet_adam_step_dev(adam_actor, lr, beta1[0], beta2[0], eps[0], max_grad_norm[0])
+ *      the image-to-image Polyak update below with tau
+ * FIVE launches on a plain step, NINE on a delayed one (SB3's TD3 does not clip: with a max_grad_norm > 0 each optimiser step is two),
+ * and one closing launch per call.  The result is bit-equal to the same entries called one by one.  Every argument is stateless:
+ * first_update is the number of gradient steps taken so far (SB3's _n_updates), the only thing a checkpoint adds to the five handles'.
+ * The fleet_adam handle keeps no hyperparameters, so both optimisers' travel in the arguments.
+ * The image-to-image Polyak update.  Since the optimisers write every new weight to torch's parameter AND to the online image with the
+ * same bits, the targets' image is updated from the online IMAGE: both have one layout, so this is one contiguous stream over the floats
+ * behind the two records, with no pointer array and no transposition,
+ *   t' = fmaf(tau32, p, t * omt32),  tau32 = (float)tau,  omt32 = (float)(1.0 - tau)
+ * -- fleet_qtarget_polyak_dev's expression: the same bits whenever the online image holds torch's parameters.  The launch walks the zero
+ * padding too, which stays +0: fmaf(tau32, +0, +0 * omt32) = +0 for tau in [0, 1].  A caller who changed torch's parameters without
+ * fleet_qtarget_load_dev on the ONLINE handle has let the two diverge: the update follows the image, and the divergence is the caller's.
+ * The statistics block, stats f64[FLEET_TRAIN_STATS], written by the closing launch (one workgroup of 256 threads) with the ordered
+ * float64 sum S of "PPO's whole update on the device" (256 lane sums over positions t, t + 256, ... ascending, then the halving tree
+ * s = 128 .. 1) over the call's slots, G = gradient_steps:
+ *   [0] critic_loss  [1] critic_0_loss  [2] critic_1_loss (0 with one critic): S((double)slot[g][k], g = 0 .. G - 1) / (double)G, k = 0, 1, 2
+ *   [3] actor_loss: S((double)slot[g_j][8], j = 0 .. n - 1) / (double)n over the call's n actor steps g_0 < g_1 < ..., position j of the
+ *       sum being the j-th of them; NaN when n == 0 (SB3 logs train/actor_loss only when there was one)
+ *   [4] the LAST step's critic_loss  [5] the last actor step's actor_loss, or NaN  [6] (double)(first_update + G) (train/n_updates)
+ *   [7] n, the actor steps of the call  [8..15] 0
+ * Which slots hold an actor step follows from (first_update, G, policy_delay) in the launch's arguments, not from a flag in memory:
+ *   g_0 = (policy_delay - (first_update % policy_delay + 1) % policy_delay) % policy_delay;  g_j = g_0 + j * policy_delay
+ * Every *_dev call takes device pointers, only enqueues (it may block on the queue's depth, it never waits for the device) and launches
+ * on the stream the borrowed handles launch on when the call is made: the replay buffer, the target networks and the online networks
+ * must launch on ONE stream then (streams are not ordered with events here).  No atomics, no ordering between workgroups.  Calls are
+ * serialised by the caller. */
+#define FLEET_OFFPOLICY_MAX_STEPS 65536
+#define FLEET_OFFPOLICY_SLOT_FLOATS 16
+typedef struct FleetOffpolicyParams {
+  int32_t struct_bytes;          /* sizeof(FleetOffpolicyParams) */
+  int32_t max_steps;             /* 1..FLEET_OFFPOLICY_MAX_STEPS: gradient steps one call may take */
+} FleetOffpolicyParams;
+typedef struct FleetOffpolicyArgs {
+  int32_t struct_bytes;          /* sizeof(FleetOffpolicyArgs) */
+  int32_t gradient_steps;        /* 1..max_steps */
+  int32_t batch_size;            /* 1..max_batch */
+  int32_t policy_delay;          /* >= 1 */
+  int32_t reserved;              /* 0 */
+  float gamma;                   /* the discount, as fleet_qtarget_target_dev takes it */
+  double tau;                    /* in [0, 1], as fleet_qtarget_polyak_dev takes it */
+  float noise_clip;              /* >= 0; +inf: no clip */
+  float act_lo, act_hi;          /* the action space: act_lo <= act_hi */
+  const float* sigma;            /* device f32[A]: the target-policy smoothing noise's scale (zeros: DDPG) */
+  double lr;                     /* finite, >= 0; both optimisers', constant within the call */
+  double beta1[2], beta2[2];     /* in [0, 1); [0] the actor optimiser's, [1] the critic optimiser's, here and below */
+  double eps[2];                 /* finite, >= 0 */
+  double max_grad_norm[2];       /* <= 0: no clipping (SB3's TD3) */
+  uint64_t seed;                 /* Philox key of the target-policy smoothing noise */
+  uint64_t first_update;         /* gradient steps taken before this call */
+  fleet_norm_handle norm;        /* or NULL: the minibatches are sampled raw */
+  double* stats;                 /* device f64[FLEET_TRAIN_STATS] */
+} FleetOffpolicyArgs;
+typedef struct FleetOffpolicyInfo {
+  int32_t obs_dim, act_dim, n_critics;   /* the networks' D, A and critics */
+  int32_t max_batch;             /* the gradient handle's: rows the staging arrays hold */
+  int32_t max_steps;             /* slots */
+  int32_t n_actor_tensors;       /* the counts the update takes: W, b per layer of the actor ... */
+  int32_t n_critic_tensors;      /* ... and of the critics, critic after critic */
+  int32_t reserved;
+  uint64_t staging_bytes;        /* of the staging arrays */
+  void* staging;                 /* device: obs [max_batch, D], actions [max_batch, A], next_obs [max_batch, D], dones, rewards, target_q
+                                    [max_batch], each at the next multiple of 256 bytes; the LAST step's rows (tests) */
+  void* slots;                   /* device f32[max_steps][FLEET_OFFPOLICY_SLOT_FLOATS] behind them: the last call's per-step stats */
+} FleetOffpolicyInfo;
+typedef struct FleetOffpolicy* fleet_offpolicy_handle;
+
+/* FLEET_ERR_INVALID (fleet_offpolicy_last_error(NULL) says why, starting with the entry's name) for a null or wrongly sized
+ * FleetOffpolicyParams, max_steps out of range, a null output or handle, a target handle that is no fleet_qtarget handle, online and
+ * target networks that are one handle, whose records differ in any byte (shapes, activations, output transform and bounds) or that lie on
+ * different devices, an optimiser on another image than the gradient handle, an actor optimiser whose span is not (0, 1, no extras), a
+ * critic optimiser whose span is not (1, n_critics, no extras), a replay buffer on another device or whose D or A differs from the
+ * networks'.  FLEET_ERR_HIP with the byte count when the block cannot be allocated.  (grad: a fleet_td3_handle, the optimisers:
+ * fleet_adam_handles; their sections follow this one, so the struct tags stand here.) */
+struct FleetTd3;
+struct FleetAdam;
+int fleet_offpolicy_create(fleet_replay_handle replay, fleet_qtarget_handle targets, struct FleetTd3* grad, struct FleetAdam* adam_actor,
+                           struct FleetAdam* adam_critic, const FleetOffpolicyParams* p, fleet_offpolicy_handle* out);
+int fleet_offpolicy_destroy(fleet_offpolicy_handle h);
+const char* fleet_offpolicy_last_error(fleet_offpolicy_handle h);  /* h may be NULL: error of the last failed call without a handle */
+int fleet_offpolicy_describe(fleet_offpolicy_handle h, FleetOffpolicyInfo* out);
+/* The update.  actor_params / actor_grads: host arrays of n_actor device pointers as fleet_adam_step_dev takes them (W, b per layer of
+ * the actor); critic_params / critic_grads: the critics', critic after critic.  The parameters are stepped in place (and the online image
+ * with them); the gradient tensors hold the last step's gradients.  Everything that can be refused is refused before the first launch:
+ * nothing is launched then, and the replay buffer's call counter and both step counts stay.  FLEET_ERR_INVALID for a null or wrongly
+ * sized FleetOffpolicyArgs, gradient_steps < 1, batch_size < 1, policy_delay < 1, a reserved that is not 0, a null stats, whatever
+ * fleet_qtarget_target_dev, fleet_qtarget_polyak_dev, fleet_td3_*_grad_dev and fleet_adam_step_dev refuse (in their words), and -- these
+ * need the handle -- gradient_steps above max_steps, batch_size above max_batch, wrong tensor counts, a norm whose obs_dim is not D, a
+ * replay buffer, target networks and online networks that do not launch on one stream; FLEET_ERR_STATE for an empty buffer.  The
+ * arguments are looked at before the handle is: with h NULL the reason (or "null handle") goes to fleet_offpolicy_last_error(NULL). */
+int fleet_offpolicy_td3_dev(fleet_offpolicy_handle h, const FleetOffpolicyArgs* a, float* const* actor_params, float* const* actor_grads,
+                            int n_actor, float* const* critic_params, float* const* critic_grads, int n_critic);
+/* The image-to-image Polyak update on its own, one launch: the targets' image <- the online image.  FLEET_ERR_INVALID for a tau outside
+ * [0, 1] or NaN, and when the two handles do not launch on one stream. */
+int fleet_offpolicy_polyak_dev(fleet_offpolicy_handle h, double tau);
+
 /* ---- PPO's whole update on the device (fleet_train.hip; DESIGN.md "PPO's whole update on the device") ------------------------------
  * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
  * stable-baselines3 2.3.2's PPO.train() with clip_range_vf = None and target_kl = None as ONE enqueue-only call: n_epochs passes over a
