@@ -12,6 +12,7 @@
     from fleetrl_amd import DeviceAdam
     from fleetrl_amd import DevicePPOTrain
     from fleetrl_amd import DeviceTD3Train
+    from fleetrl_amd import LogSummary, summarize_log, compare, evaluate_strategies
 """
 __version__ = "0.1.0"
 
@@ -73,6 +74,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import lp_benchmark
 
         return getattr(lp_benchmark, name)
+    if name in ("LogSummary", "summarize_log", "compare", "evaluate_strategies"):
+        from . import evaluation
+
+        return getattr(evaluation, name)
     if name in ("FleetBatch", "FleetHipError"):
         from . import batch
 

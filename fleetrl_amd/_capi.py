@@ -284,6 +284,17 @@ class FleetTd3ActorArgs(C.Structure):
                 ("stats", C.c_void_p), ("reserved", C.c_uint64)]
 
 
+# ---- the data log summarised on the device (include/fleet_hip.h fleet_log_summary_dev) ----------------------------------------
+LOG_SUMMARY_SCALARS = ("rows", "reward", "cashflow", "penalty", "overload", "soc_violation", "violations", "deg_rows")
+LOG_SUMMARY_MAX_BINS = 256
+
+
+class FleetLogSummaryArgs(C.Structure):
+    _fields_ = [("drop_last", C.c_int32), ("bins", C.c_int32), ("hist_ev", C.c_int32), ("reserved", C.c_int32),
+                ("lo", C.c_double), ("hi", C.c_double), ("scal", C.c_void_p), ("deg_sum", C.c_void_p), ("soh_last", C.c_void_p),
+                ("prof_sum", C.c_void_p), ("prof_cnt", C.c_void_p), ("hist", C.c_void_p)]
+
+
 # ---- env state (include/fleet_hip.h "env state": FleetStateLayout / FleetStateHeader, FLEET_SEC_*) ---------------------------
 STATE_MAGIC = 0x4554415453544C46
 STATE_ALIGN = 256
@@ -415,6 +426,7 @@ def load_library():
     lib.fleet_log_capacity.argtypes = [vp]
     lib.fleet_log_read.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.fleet_log_clear.argtypes = [vp]
+    lib.fleet_log_summary_dev.argtypes = [vp, C.POINTER(FleetLogSummaryArgs), C.c_size_t]
     lib.fleet_synchronize.argtypes = [vp]
     lib.fleet_set_start_schedule.argtypes = [vp, vp, C.c_int]
     lib.fleet_reset_dev.argtypes = [vp, u8p, f32p]
@@ -601,7 +613,7 @@ def load_library():
             getattr(lib, name).restype = C.c_char_p if name == f"fleet_{prefix}_last_error" else C.c_int
     for name in ("fleet_create", "fleet_destroy", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream", "fleet_log_dropped",
                  "fleet_log_capacity", "fleet_log_read",
-                 "fleet_log_clear", "fleet_synchronize", "fleet_set_start_schedule",
+                 "fleet_log_clear", "fleet_log_summary_dev", "fleet_synchronize", "fleet_set_start_schedule",
                  "fleet_reset_dev", "fleet_step_dev", "fleet_step_many_dev", "fleet_rollout_policy_dev", "fleet_set_night_policy",
                  "fleet_reset_host", "fleet_step_host", "fleet_get", "fleet_get_dev", "fleet_get_dist_factor", "fleet_check_errors", "fleet_timer_start",
                  "fleet_timer_stop", "fleet_timer_mark", "fleet_timer_read", "fleet_run_tape_dev", "fleet_time_steps_dev",
@@ -670,7 +682,7 @@ OFFPOLICY_SYMBOLS = ("fleet_offpolicy_create", "fleet_offpolicy_destroy", "fleet
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
-    "fleet_set_start_schedule", "fleet_reset_dev", "fleet_step_dev", "fleet_step_many_dev", "fleet_rollout_policy_dev",
+    "fleet_log_summary_dev", "fleet_set_start_schedule", "fleet_reset_dev", "fleet_step_dev", "fleet_step_many_dev", "fleet_rollout_policy_dev",
     "fleet_set_night_policy", "fleet_reset_host",
     "fleet_step_host", "fleet_get", "fleet_get_dev", "fleet_get_dist_factor", "fleet_check_errors", "fleet_timer_start",
     "fleet_timer_stop", "fleet_timer_mark", "fleet_timer_read", "fleet_run_tape_dev", "fleet_time_steps_dev",

@@ -208,6 +208,17 @@ class FleetBatch:
     def log_clear(self):
         self._check(self.lib.fleet_log_clear(self.h))
 
+    def log_summary(self, scal_ptr: int, *, deg_sum_ptr: int | None = None, soh_last_ptr: int | None = None,
+                    prof_sum_ptr: int | None = None, prof_cnt_ptr: int | None = None, hist_ptr: int | None = None, drop_last: int = 0,
+                    bins: int = 1, lo: float = -1.0, hi: float = 1.0, hist_ev: int = -1):
+        """The ring reduced on the device (include/fleet_hip.h fleet_log_summary_dev): raw device addresses of scal f64 [E,8],
+        deg_sum / soh_last f64 [E,N], prof_sum f64 / prof_cnt i32 [E,S], hist i32 [E,bins]; two launches on the handle's stream,
+        nothing is read back.  See fleetrl_amd.evaluation.summarize_log for the NumPy-level driver."""
+        a = _capi.FleetLogSummaryArgs()
+        a.drop_last, a.bins, a.hist_ev, a.lo, a.hi = int(drop_last), int(bins), int(hist_ev), float(lo), float(hi)
+        a.scal, a.deg_sum, a.soh_last, a.prof_sum, a.prof_cnt, a.hist = scal_ptr, deg_sum_ptr, soh_last_ptr, prof_sum_ptr, prof_cnt_ptr, hist_ptr
+        self._check(self.lib.fleet_log_summary_dev(self.h, C.byref(a), C.sizeof(a)))
+
     def set_start_schedule(self, starts):
         if starts is None:
             self._check(self.lib.fleet_set_start_schedule(self.h, None, 0))

@@ -98,6 +98,8 @@ struct FleetEnvBatch {
   // fleet_lp_plan_dev: the planner's device scratch, kept for the next call (grows, never shrinks)
   void* lp_scratch = nullptr;
   size_t lp_scratch_bytes = 0;
+  // fleet_log_summary_dev: the block partials of the log reduction (fleet_logsum.h), allocated by the first call
+  void* logsum_scratch = nullptr;
   // env state (fleet_state.hip): the hash of the table contents the handle was created from (half of its fingerprint), pinned
   // staging for a blob header, what a fork keeps between calls (index pairs on the device and their pinned staging, an event)
   uint64_t table_hash = 0;

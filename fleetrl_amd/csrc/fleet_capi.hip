@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "fleet_batch.h"
+#include "fleet_logsum.h"
 #include "fleet_lp.h"
 
 static thread_local std::string g_create_error;
@@ -84,6 +85,7 @@ int fleet_destroy(fleet_handle h) {
     if (e) (void)hipEventDestroy(e);
   if (h->dev_sched) (void)hipFree(h->dev_sched);
   if (h->lp_scratch) (void)hipFree(h->lp_scratch);
+  if (h->logsum_scratch) (void)hipFree(h->logsum_scratch);
   fleet_state_fork_release(&h->fork);
   if (h->pin_state_hdr) (void)hipHostFree(h->pin_state_hdr);
   for (auto& e : h->region_events)
@@ -410,6 +412,51 @@ int fleet_log_clear(fleet_handle h) {
   if (!h || !h->d.log_pos) return FLEET_ERR_INVALID;
   HIP_TRY(h, hipSetDevice(h->device));
   HIP_TRY(h, hipMemsetAsync(h->d.log_pos, 0, (size_t)h->d.E * 4, h->stream));
+  return FLEET_OK;
+}
+
+int fleet_log_summary_dev(fleet_handle h, const FleetLogSummaryArgs* args, size_t args_size) {
+  FLEET_ENTER(h);  // a run on the library's own queue is not on the stream: waited for, as fleet_log_read does
+  if (!h) return FLEET_ERR_INVALID;
+  const FleetDev& d = h->d;
+  const char* why = nullptr;
+  if (!d.log_pos) why = "the data log is off (FleetParams.log_data = 0)";
+  else if (!args || args_size != sizeof(FleetLogSummaryArgs)) why = "null args or args_size is not sizeof(FleetLogSummaryArgs)";
+  else if (!args->scal) why = "null scal";
+  else if (args->drop_last < 0) why = "drop_last < 0";
+  else if (args->hist && (args->bins < 1 || args->bins > kLogsumMaxBins)) why = "bins outside 1..256";
+  else if (!(args->hi > args->lo)) why = "hi <= lo or a NaN bound";
+  else if (args->hist_ev < -1 || args->hist_ev >= d.N) why = "hist_ev outside -1..N-1";
+  const int step_s = h->cold_host.step_s;
+  if (!why && (args->prof_sum || args->prof_cnt)) {
+    if (d.tab_finish) why = "prof_*: an irregular time grid has no time-of-day slots";
+    else if (step_s < 60 || step_s % 60 || 1440 % (step_s / 60)) why = "prof_*: the step is no whole divisor of a day in minutes";
+  }
+  if (!why && (d.log_cap + kLogsumRows - 1) / kLogsumRows > 65535) why = "log_capacity above 64 * 65535 rows";
+  if (why) {
+    h->error = std::string("fleet_log_summary_dev: ") + why;
+    return FLEET_ERR_INVALID;
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (!h->logsum_scratch) HIP_TRY(h, hipMalloc(&h->logsum_scratch, fleet_logsum_scratch_bytes(d.E, d.N, d.log_cap)));
+  FleetLogsumArgs a{};
+  a.drop_last = args->drop_last;
+  a.bins = args->hist ? args->bins : 1;
+  a.hist_ev = args->hist_ev;
+  a.calc_deg = d.deg_mode != FLEET_DEG_NONE;
+  a.minutes_per_step = (args->prof_sum || args->prof_cnt) ? step_s / 60 : 0;
+  a.lo = args->lo;
+  a.hi = args->hi;
+  a.price_multiplier = h->p.price_multiplier;
+  a.tab_hm = h->cold_host.tab_hm;
+  a.scal = args->scal;
+  a.deg_sum = args->deg_sum;
+  a.soh_last = args->soh_last;
+  a.prof_sum = args->prof_sum;
+  a.prof_cnt = args->prof_cnt;
+  a.hist = args->hist;
+  a.scratch = h->logsum_scratch;
+  HIP_TRY(h, fleet_launch_log_summary(d, a, h->stream));
   return FLEET_OK;
 }
 

@@ -352,6 +352,58 @@ int fleet_log_dropped(fleet_handle h, int64_t* rows);
 int fleet_log_read(fleet_handle h, int32_t* pos, int32_t* row, double* env, double* ev, float* obs);
 int fleet_log_clear(fleet_handle h);     /* forget all rows (asynchronous on the handle's stream) */
 
+/* The ring reduced to the numbers of the reference's evaluation (agent_eval/basic_evaluation.py `BasicEvaluation.compare`,
+ * `plot_action_dist`) ON THE DEVICE, so that a few kilobytes per env come back instead of the ring (entry added under
+ * FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays).  DESIGN.md "The data log, summarised on the
+ * device"; tests/logsum_model.py restates it.
+ *
+ * Window of env e: pos = rows written so far, k0 = max(0, pos - capacity), k1 = max(k0, pos - drop_last); the kept rows
+ * k0 <= k < k1, oldest first, row k in slot k % capacity, j = k - k0.  (`drop_last`: the reference drops its last two rows,
+ * `log_RL.iloc[0:-2]`, and a vec env with auto-reset has logged one reset row more than the reference.)
+ * Per row, in float64 without contraction: reset = bit 31 of `row`, t = its low 31 bits;
+ *   reward = env[0], cashflow = env[1], penalty = reset ? 0 : reward - (cashflow * price_multiplier)   (quirk Q13, two roundings)
+ *   overload = fabs(env[2]), socv = fabs(env[3]), viol = socv > 0
+ *   deg[c] = (!reset && deg_mode != FLEET_DEG_NONE && the table row t is 14:45) ? ev[2][c] : 0
+ *   charge[c] = reset ? 0 : (energy of the last EV <= c with action >= 0, else 0) + (energy of the last EV <= c with action < 0,
+ *               else 0)                                                                                 (quirk Q8)
+ *   row_power = (sum of charge[c] over the EVs) / N; the EV sum is, per chunk of 64 EVs, a xor butterfly over 64 lanes (offsets
+ *               1, 2, 4, ..., 32; absent EVs are +0.0), and the chunks are added in ascending order to +0.0
+ *   slot s = (60 * hour + minute) / minutes_per_step of S = 1440 / minutes_per_step time-of-day slots
+ * Order of every sum: the accumulator starts at +0.0 and adds its rows of one 64-row block (j / 64) in ascending j; the block
+ * partials are then added to +0.0 in ascending block order.  No atomics: the result does not depend on the launch geometry.
+ * Outputs, DEVICE pointers, every one but `scal` may be NULL:
+ *   scal     f64 [E,8]     window rows, sum reward, sum cashflow, sum penalty, sum overload, sum socv, sum viol (a count), the
+ *                          number of 14:45 non-reset rows
+ *   deg_sum  f64 [E,N]     sum deg[c]
+ *   soh_last f64 [E,N]     ev[3][c] of row k1 - 1; NaN for an empty window
+ *   prof_sum f64 [E,S]     sum row_power per slot;   prof_cnt i32 [E,S]  rows per slot
+ *   hist     i32 [E,bins]  the logged actions of EV `hist_ev` (-1: of every EV) over all window rows, reset rows included, as
+ *                          np.histogram(a, bins, range=(lo, hi)) counts them: edge[i] = lo + i * ((hi - lo) / bins) for i < bins,
+ *                          edge[bins] = hi; a value falls into the largest i with edge[i] <= a, a == hi into the last bin;
+ *                          a < lo, a > hi and NaN are not counted
+ * Two launches (block partials: one wavefront per env and 64-row block, one EV per lane; then the fold), enqueued on the handle's
+ * stream behind everything the handle has enqueued -- a run on the library's own queue is waited for first, as in
+ * fleet_log_read -- and nothing else: no copy, no synchronisation (fleet_synchronize before reading).  The scratch for the
+ * partials belongs to the handle: allocated by the first call, freed by fleet_destroy.
+ * FLEET_ERR_INVALID, with nothing launched, for: the log being off; a null `args` or args_size != sizeof(FleetLogSummaryArgs); a
+ * null `scal`; drop_last < 0; bins outside 1..256 when `hist` is given; hi <= lo or a NaN bound; hist_ev outside -1..N-1 (the last
+ * two whether `hist` is given or not: a call states a valid histogram or the defaults 1, -1.0, 1.0, -1); a `prof_*` pointer on a handle whose tables are an irregular time grid or whose step is no whole divisor of a day in minutes (the
+ * time-of-day slot is not defined there). */
+typedef struct FleetLogSummaryArgs {
+  int32_t drop_last;  /* newest rows per env left out of the window (>= 0) */
+  int32_t bins;       /* histogram bins, 1..256 */
+  int32_t hist_ev;    /* the EV whose actions are counted, or -1: every EV */
+  int32_t reserved;   /* 0 */
+  double lo, hi;      /* histogram range */
+  double* scal;
+  double* deg_sum;
+  double* soh_last;
+  double* prof_sum;
+  int32_t* prof_cnt;
+  int32_t* hist;
+} FleetLogSummaryArgs;
+int fleet_log_summary_dev(fleet_handle h, const FleetLogSummaryArgs* args, size_t args_size);
+
 /* Device-side errors -- the conditions under which the reference raises inside step(): `TypeError("Observation format not
  * recognized")` fleet_environment.py:610, `TypeError("DoD too large.")` / `TypeError("Life degradation is negative")` /
  * `RuntimeError("Degradation calculation is not correct")` rainflow_sei_degradation.py:164-167,179-180,209-210, and a table
