@@ -12,6 +12,7 @@
     from fleetrl_amd import DeviceAdam
     from fleetrl_amd import DevicePPOTrain
     from fleetrl_amd import DeviceTD3Train
+    from fleetrl_amd import DevicePPOCollect, DeviceTD3Collect
     from fleetrl_amd import LogSummary, summarize_log, compare, evaluate_strategies
 """
 __version__ = "0.1.0"
@@ -70,6 +71,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import offpolicy
 
         return offpolicy.DeviceTD3Train
+    if name in ("DevicePPOCollect", "DeviceTD3Collect"):
+        from . import collect
+
+        return getattr(collect, name)
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

@@ -269,6 +269,34 @@ class FleetOffpolicyInfo(C.Structure):
                 ("staging", C.c_void_p), ("slots", C.c_void_p)]
 
 
+# ---- rollout collection (include/fleet_hip.h "collect_rollouts on the device", fleet_collect_*) ----------------------------------------
+COLLECT_MAX_WINDOW, COLLECT_STATS = 4096, 16
+
+
+class FleetCollectParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("stats_window", C.c_int32)]
+
+
+class FleetCollectPpoArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_steps", C.c_int32), ("env_id_offset", C.c_int32), ("reserved", C.c_int32),
+                ("buffer", C.c_void_p), ("log_std", C.c_void_p), ("seed", C.c_uint64), ("first_step", C.c_uint64), ("stats", C.c_void_p)]
+
+
+class FleetCollectOffpolicyArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_steps", C.c_int32), ("env_id_offset", C.c_int32), ("reserved", C.c_int32),
+                ("learning_starts", C.c_uint64), ("replay", C.c_void_p), ("sigma", C.c_void_p), ("shift", C.c_void_p),
+                ("noise_lo", C.c_float), ("noise_hi", C.c_float), ("noise", C.c_void_p), ("seed", C.c_uint64), ("first_step", C.c_uint64),
+                ("stats", C.c_void_p)]
+
+
+class FleetCollectInfo(C.Structure):
+    _fields_ = [("num_envs", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("stats_window", C.c_int32), ("has_norm", C.c_int32),
+                ("cur", C.c_int32), ("launches", C.c_int32), ("reserved", C.c_int32), ("block_bytes", C.c_uint64),
+                ("carry_obs", C.c_void_p * 2), ("raw_obs", C.c_void_p * 2), ("carry_start", C.c_void_p * 2), ("raw_terminal", C.c_void_p),
+                ("raw_reward", C.c_void_p), ("reward", C.c_void_p), ("env_actions", C.c_void_p), ("last_values", C.c_void_p),
+                ("ring_return", C.c_void_p), ("ring_length", C.c_void_p), ("ring_count", C.c_void_p)]
+
+
 # ---- TD3 / DDPG minibatch gradients (include/fleet_hip.h "TD3 / DDPG minibatch gradients on the device", fleet_td3_*) -------------------
 class FleetTd3Params(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("max_batch", C.c_int32)]
@@ -606,6 +634,19 @@ def load_library():
     lib.fleet_offpolicy_td3_dev.argtypes = [vp, C.POINTER(FleetOffpolicyArgs), C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(vp),
                                             C.POINTER(vp), C.c_int]
     lib.fleet_offpolicy_polyak_dev.argtypes = [vp, C.c_double]
+    # rollout collection (fleet_collect.hip)
+    lib.fleet_collect_create.argtypes = [vp, vp, vp, C.POINTER(FleetCollectParams), C.POINTER(vp)]
+    lib.fleet_collect_destroy.argtypes = [vp]
+    lib.fleet_collect_last_error.argtypes = [vp]
+    lib.fleet_collect_describe.argtypes = [vp, C.POINTER(FleetCollectInfo)]
+    lib.fleet_collect_reset_dev.argtypes = [vp, C.c_int]
+    lib.fleet_collect_ppo_dev.argtypes = [vp, C.POINTER(FleetCollectPpoArgs)]
+    lib.fleet_collect_offpolicy_dev.argtypes = [vp, C.POINTER(FleetCollectOffpolicyArgs)]
+    lib.fleet_collect_episodes_dev.argtypes = [vp, vp, vp, vp, C.c_int]
+    lib.fleet_collect_finish_dev.argtypes = [vp, C.c_uint64, C.c_int32, vp]
+    lib.fleet_collect_episodes_read.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64)]
+    for name in COLLECT_SYMBOLS:
+        getattr(lib, name).restype = C.c_char_p if name == "fleet_collect_last_error" else C.c_int
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
                           ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS), ("ppo", PPO_SYMBOLS),
                           ("td3", TD3_SYMBOLS), ("adam", ADAM_SYMBOLS), ("train", TRAIN_SYMBOLS), ("offpolicy", OFFPOLICY_SYMBOLS)):
@@ -679,6 +720,10 @@ TRAIN_SYMBOLS = ("fleet_train_create", "fleet_train_destroy", "fleet_train_last_
 OFFPOLICY_SYMBOLS = ("fleet_offpolicy_create", "fleet_offpolicy_destroy", "fleet_offpolicy_last_error", "fleet_offpolicy_describe",
                      "fleet_offpolicy_td3_dev", "fleet_offpolicy_polyak_dev")
 
+COLLECT_SYMBOLS = ("fleet_collect_create", "fleet_collect_destroy", "fleet_collect_last_error", "fleet_collect_describe",
+                   "fleet_collect_reset_dev", "fleet_collect_ppo_dev", "fleet_collect_offpolicy_dev", "fleet_collect_episodes_dev",
+                   "fleet_collect_finish_dev", "fleet_collect_episodes_read")
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -692,7 +737,7 @@ EXPORTED_SYMBOLS = (
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
     "fleet_set_direct_state_only", "fleet_direct_packet_counts", "fleet_step_has_state_only",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS + TRAIN_SYMBOLS + OFFPOLICY_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS + TRAIN_SYMBOLS + OFFPOLICY_SYMBOLS + COLLECT_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

@@ -1099,6 +1099,141 @@ int fleet_noise_set_state_dev(fleet_noise_handle h, const int32_t* t, const uint
 /* the parameters the process was created with (mu, sigma NULL), and cache_bytes */
 int fleet_noise_describe(fleet_noise_handle h, FleetNoiseParams* out);
 
+/* ---- collect_rollouts on the device (fleet_collect.hip; DESIGN.md "Rollout collection on the device") -----------------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * stable-baselines3 2.3.2's OnPolicyAlgorithm.collect_rollouts (PPO) and OffPolicyAlgorithm.collect_rollouts (TD3 / DDPG) as ONE
+ * enqueue-only call each: the loop over env steps that calls the families' own entries, as they are, and the one number of SB3's
+ * rollout log that nothing else produces on the device -- rollout/ep_rew_mean and rollout/ep_len_mean over ep_info_buffer, the last
+ * W = stats_window finished episodes in the order Monitor reports them.  The handle BORROWS an env (auto_reset = 1), an optional
+ * normaliser (NULL: none) and a policy, which must outlive it, and owns one block, zeroed at create: two carry observation
+ * buffers f32[E,D] and two raw-observation buffers f32[E,D] (none without a normaliser: the env writes the carry buffers), the raw
+ * terminal rows f32[E,D], the raw and the normalised reward f64[E] each, two carry episode_start / done arrays u8[E], the env actions
+ * f32[E,A], a noise row f32[E,A], last_values f32[E], and the episode ring: ring_return f64[W], ring_length i32[W], a u64 count of the
+ * episodes appended so far and a u64 count of those appended since the last closing launch.  The carry buffers PING-PONG: a call reads
+ * side `cur` and leaves what the next call starts from on the other side, so a rollout of one step copies nothing.
+ * fleet_collect_reset_dev (SB3's _setup_learn): fleet_reset_dev with no mask into raw buffer 0, fleet_norm_reset_dev from it into
+ * carry buffer 0 (without a normaliser the env writes carry buffer 0), cur = 0, episode_start = 1 for every env (one small launch);
+ * the ring and its counts are cleared only when clear_episodes is not 0 (the closing launch then reports NaN means).
+ * fleet_collect_ppo_dev fills all K = n_steps rows of the buffer.  Step t = 0 .. K-1, with cur = the carry for t = 0 and row t's own
+ * obs / episode_start afterwards, next = row t+1's, or the other carry side when t = K-1:
+ *   1. fleet_explore_act_dev GAUSSIAN, DRAW, norm NULL (the buffer holds normalised observations, as under SB3's VecNormalize), key
+ *      (seed, env_id_offset, step = first_step + t); actions, log_prob and values are row t's own, env_actions the handle's
+ *   2. fleet_step_dev into the raw buffer and the raw reward (straight into next.obs without a normaliser), done -> next.episode_start,
+ *      no terminal rows
+ *   3. fleet_norm_step_dev from them into next.obs and the normalised reward                          (not without a normaliser)
+ *   4. fleet_rollout_add_dev(t, cur.obs, row t's actions, the reward as F64, cur.episode_start, row t's value and log_prob, NULL, NULL)
+ *   5. the episode launch below
+ * then fleet_policy_forward_dev on the carry for last_values, fleet_rollout_finish_dev(last_values, the carry's episode_start) and
+ * the closing launch: 5 K + 3 launches with a normaliser, 4 K + 3 without.  SB3's time-limit bootstrap stays off (the reference
+ * never sets TimeLimit.truncated).
+ * fleet_collect_offpolicy_dev takes n_steps env steps.  Global step s = first_step + t:
+ *   1. s < learning_starts: fleet_explore_act_dev UNIFORM DRAW; else with a noise handle fleet_noise_next_dev(noise, the carry's
+ *      done, the noise row) and ACTION_NOISE GIVEN, without one ACTION_NOISE DRAW -- on the carry observation, norm NULL (the actor
+ *      reads normalised observations), key (seed, env_id_offset, step = s), actions = env_actions = the handle's
+ *   2. fleet_step_dev into the other raw buffer, the raw reward and the other done array, with the raw terminal rows
+ *   3. fleet_norm_step_dev from the raw buffer into the other carry buffer (terminal rows are not normalised: nobody reads them)
+ *   4. fleet_replay_add_dev(raw cur, raw next, the actions, the raw reward as F64, done, the raw terminal rows, NULL): the replay
+ *      buffer stores raw observations, as SB3 does
+ *   5. the episode launch; the sides swap
+ * then the closing launch: 4 per step and 1, one more per step with a normaliser, one more per step that asks the noise handle.
+ * The episode launch (collect_episodes: ONE workgroup of 1024 threads, chunks of 1024 envs, a ballot-and-popcount scan in env order;
+ * no atomics).  With count the ring's running total and c the step's number of finished envs, the k-th of them (k = 0 .. c-1,
+ * ascending env id) writes its last episode's return and length -- what info["episode"] carries: FLEET_F_LAST_EP_RETURN and
+ * FLEET_F_LAST_EP_LEN -- to slot (count + k) % W iff c - k <= W: only the last W of a step survive, so no two lanes write one slot.
+ * Then count += c.  This is SB3's _update_info_buffer: a deque(maxlen = W) extended over infos in env order.
+ * The closing launch (collect_finish: one workgroup of 256 threads) writes stats f64[FLEET_COLLECT_STATS]; with n = min(count, W):
+ *   [0] ep_rew_mean = S(ring_return[s], s = 0 .. n-1) / n      [1] ep_len_mean = S((double)ring_length[s], s = 0 .. n-1) / n
+ *   [2] the episodes appended since the previous closing launch (of a run call: those of the call)     [3] count
+ *   [4] (double)(first_step + steps)      [5..15] 0
+ * S is the ordered float64 sum fleet_train_ppo_dev's section states: 256 lane sums over positions t, t + 256, ... ascending, then the
+ * halving tree s = 128 .. 1.  [0] and [1] are NaN when n == 0 (SB3 logs nothing then).
+ * Both run calls only enqueue (they may block on the queue's depth, never on the device) on the stream the borrowed handles launch
+ * on when the call is made: env, normaliser, policy, buffer and noise handle must launch on ONE stream then.  Everything refusable
+ * is refused before the first launch -- nothing is launched then, no counter moves -- in the words of the entry that would refuse.
+ * A result depends on (the handles' state, seed, first_step) and on nothing else.  Out of scope: the time-limit bootstrap, gSDE,
+ * SAC, train_freq in episodes, callbacks.  Calls are serialised by the caller. */
+#define FLEET_COLLECT_MAX_WINDOW 4096
+#define FLEET_COLLECT_STATS 16
+typedef struct FleetCollectParams {
+  int32_t struct_bytes;          /* sizeof(FleetCollectParams) */
+  int32_t stats_window;          /* W, 1..FLEET_COLLECT_MAX_WINDOW (SB3's stats_window_size: 100) */
+} FleetCollectParams;
+typedef struct FleetCollectPpoArgs {
+  int32_t struct_bytes;          /* sizeof(FleetCollectPpoArgs) */
+  int32_t n_steps;               /* K: must be the buffer's */
+  int32_t env_id_offset;         /* the noise's global id of env 0; >= 0 */
+  int32_t reserved;              /* 0 */
+  fleet_rollout_handle buffer;   /* E, D, A as the handle's; launches on the env's stream */
+  const float* log_std;          /* device f32[A] */
+  uint64_t seed;                 /* Philox key of the exploration noise */
+  uint64_t first_step;           /* the noise counter: env steps taken before this call */
+  double* stats;                 /* device f64[FLEET_COLLECT_STATS] */
+} FleetCollectPpoArgs;
+typedef struct FleetCollectOffpolicyArgs {
+  int32_t struct_bytes;          /* sizeof(FleetCollectOffpolicyArgs) */
+  int32_t n_steps;               /* >= 1 */
+  int32_t env_id_offset;         /* >= 0 */
+  int32_t reserved;              /* 0 */
+  uint64_t learning_starts;      /* global steps below it draw uniform actions */
+  fleet_replay_handle replay;    /* E, D, A as the handle's */
+  const float* sigma;            /* device f32[A] */
+  const float* shift;            /* device f32[A] or NULL (0) */
+  float noise_lo, noise_hi;      /* the action space: noise_lo <= noise_hi */
+  fleet_noise_handle noise;      /* or NULL: white noise drawn by the exploration launch */
+  uint64_t seed;
+  uint64_t first_step;           /* env steps taken before this call */
+  double* stats;                 /* device f64[FLEET_COLLECT_STATS] */
+} FleetCollectOffpolicyArgs;
+typedef struct FleetCollectInfo {
+  int32_t num_envs, obs_dim, act_dim;
+  int32_t stats_window;
+  int32_t has_norm;              /* 1: a normaliser was given */
+  int32_t cur;                   /* the side the next call starts from */
+  int32_t launches;              /* kernel launches the last run call (or reset) enqueued */
+  int32_t reserved;
+  uint64_t block_bytes;
+  float* carry_obs[2];           /* device f32[E,D]; [cur]: what the next call's first step reads */
+  float* raw_obs[2];             /* device f32[E,D]; the carry buffers themselves without a normaliser */
+  uint8_t* carry_start[2];       /* device u8[E] */
+  float* raw_terminal;           /* device f32[E,D] */
+  double* raw_reward;            /* device f64[E] */
+  double* reward;                /* device f64[E] */
+  float* env_actions;            /* device f32[E,A] */
+  float* last_values;            /* device f32[E] */
+  double* ring_return;           /* device f64[W] */
+  int32_t* ring_length;          /* device i32[W] */
+  uint64_t* ring_count;          /* device u64[2]: appended so far, appended since the last closing launch */
+} FleetCollectInfo;
+typedef struct FleetCollect* fleet_collect_handle;
+
+/* Everything is refused BEFORE the device is touched: FLEET_ERR_INVALID (fleet_collect_last_error(NULL) says why, starting with the
+ * entry's name) for a null or wrongly sized FleetCollectParams, stats_window outside 1..FLEET_COLLECT_MAX_WINDOW, a null output, env
+ * or policy, a handle that is no policy, an env without auto_reset, a critic head wider than 1, E, D, A or the device of env,
+ * normaliser and policy disagreeing (A: the env's EVs against the actor's output width).  FLEET_ERR_HIP with the byte count when the
+ * block cannot be allocated. */
+int fleet_collect_create(fleet_handle env, fleet_norm_handle norm, fleet_policy_handle policy, const FleetCollectParams* p,
+                         fleet_collect_handle* out);
+int fleet_collect_destroy(fleet_collect_handle h);
+const char* fleet_collect_last_error(fleet_collect_handle h);  /* h may be NULL: error of the last failed call without a handle */
+int fleet_collect_describe(fleet_collect_handle h, FleetCollectInfo* out);
+/* Two launches and the small one with a normaliser, one and the small one without.  FLEET_ERR_INVALID when env and normaliser do not
+ * launch on one stream. */
+int fleet_collect_reset_dev(fleet_collect_handle h, int clear_episodes);
+/* The arguments are looked at before the handle is: with h NULL the reason (or "null handle") goes to fleet_collect_last_error(NULL).
+ * FLEET_ERR_INVALID for a null or wrongly sized args struct, n_steps < 1, a reserved that is not 0, a negative env_id_offset, a null
+ * buffer / replay, log_std / sigma or stats, noise_lo > noise_hi or a NaN bound, and -- these need the handle -- a one-head policy
+ * (PPO), n_steps that is not the buffer's, a buffer or a noise handle whose E, D or A differ from the handle's or that lies on
+ * another device, handles that do not launch on one stream. */
+int fleet_collect_ppo_dev(fleet_collect_handle h, const FleetCollectPpoArgs* a);
+int fleet_collect_offpolicy_dev(fleet_collect_handle h, const FleetCollectOffpolicyArgs* a);
+/* The episode launch on the caller's device arrays done u8[E], ep_return f64[E], ep_len i32[E] (E: any, >= 1) instead of the env's
+ * records: the same kernel body behind another loader.  The closing launch on its own: stats as above with steps = `steps`. */
+int fleet_collect_episodes_dev(fleet_collect_handle h, const uint8_t* done, const double* ep_return, const int32_t* ep_len, int E);
+int fleet_collect_finish_dev(fleet_collect_handle h, uint64_t first_step, int32_t steps, double* stats);
+/* Synchronous: the ring and its count to HOST buffers ring_return f64[W], ring_length i32[W], count u64 (any may be NULL).  The last
+ * n = min(count, W) episodes, oldest first, lie in slots (count - n + i) % W, i = 0 .. n-1. */
+int fleet_collect_episodes_read(fleet_collect_handle h, double* ring_return, int32_t* ring_length, uint64_t* count);
+
 /* ---- TD3 / DDPG learning targets on the device (fleet_qtarget.hip; DESIGN.md "Learning targets on the device") --------------------
  * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
  * The TARGET networks of an off-policy actor-critic agent -- one target actor and n_critics target Q networks (2: TD3; 1: DDPG, with
