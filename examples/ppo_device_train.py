@@ -11,13 +11,17 @@ its seed and a checkpoint needs that count only.  The rollout is the one of exam
 fit -- it is not a tuned trainer.  Needs an MI355X; inputs are synthetic:
 
     python examples/ppo_device_train.py [--iterations 3] [--envs 256] [--evs 5] [--steps 64] [--batch-size 128] [--epochs 4]
+                                        [--clip-range-vf 0.2] [--no-normalize-advantage] [--time]
 
-Prints one JSON line per iteration.
+`--clip-range-vf` is SB3's `clip_range_vf` (off by default, as in SB3): the value loss on the prediction clipped around the rollout's
+values, inside the same launches.  `--no-normalize-advantage` is `normalize_advantage=False`.  Prints one JSON line per iteration;
+with `--time` one more line: the host wall time of further updates on the last rollout, the final synchronisation included.
 """
 import argparse
 import json
 import os
 import sys
+import time
 
 import torch
 from torch import nn
@@ -52,6 +56,10 @@ def main():
     ap.add_argument("--batch-size", type=int, default=128)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--clip-range-vf", type=float, default=None, help="SB3's clip_range_vf; default: no value clipping")
+    ap.add_argument("--no-normalize-advantage", action="store_true", help="SB3's normalize_advantage=False")
+    ap.add_argument("--time", action="store_true", help="after the last iteration, time the update alone on its rollout")
+    ap.add_argument("--reps", type=int, default=7, help="updates timed by --time")
     args = ap.parse_args()
     E, N, K = args.envs, args.evs, args.steps
     dev = torch.device("cuda", 0)
@@ -73,6 +81,9 @@ def main():
     epochs = 0  # the shuffle's epoch counter: never repeats over the run either
     n_updates = 0
     clip_range, vf_coef, ent_coef = 0.2, 0.5, 0.0
+    # (None is the default of train(): the argument is passed only when it is set)
+    extra = {} if args.clip_range_vf is None else {"clip_range_vf": args.clip_range_vf}
+    normalize = not args.no_normalize_advantage
 
     # what the rollout's last step leaves for the next rollout's row 0
     carry_obs, carry_start = torch.empty((E, D), device=dev), torch.ones(E, device=dev, dtype=torch.uint8)
@@ -100,7 +111,7 @@ def main():
 
         # the whole update: one call, enqueued behind the rollout on the same stream
         stats = trainer.train(into, n_epochs=args.epochs, batch_size=args.batch_size, clip_range=clip_range, vf_coef=vf_coef,
-                              ent_coef=ent_coef, lr=3e-4, normalize_advantage=True, seed=args.seed, first_epoch=epochs)
+                              ent_coef=ent_coef, lr=3e-4, normalize_advantage=normalize, seed=args.seed, first_epoch=epochs, **extra)
         epochs += args.epochs
         buf.check_errors()
         # the only transfers of the iteration: the statistics block and two numbers for the log
@@ -109,6 +120,19 @@ def main():
         st["train/n_updates"] = n_updates
         print(json.dumps({"iteration": it, **st, "mean_reward": buf.rewards.mean().item(),
                           "episode_starts": int(buf.episode_starts.sum().item())}), flush=True)
+    if args.time:
+        runs = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            trainer.train(into, n_epochs=args.epochs, batch_size=args.batch_size, clip_range=clip_range, vf_coef=vf_coef, ent_coef=ent_coef,
+                          lr=3e-4, normalize_advantage=normalize, seed=args.seed, first_epoch=epochs, stats_out=stats, **extra)
+            torch.cuda.synchronize()
+            runs.append((time.perf_counter() - t0) * 1e3)
+            epochs += args.epochs
+        print(json.dumps({"time": "one update, host wall time, ms", "rows": E * K, "batch_size": args.batch_size, "epochs": args.epochs,
+                          "clip_range_vf": args.clip_range_vf, "normalize_advantage": normalize, "median_ms": sorted(runs)[len(runs) // 2],
+                          "runs_ms": [round(x, 3) for x in runs]}), flush=True)
     for h in (trainer, opt, grad, pol, buf, env):
         h.close()
 

@@ -210,6 +210,10 @@ class FleetPpoGradArgs(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+class FleetPpoGradVclipArgs(C.Structure):  # fleet_ppo_grad_vclip_dev: the same with SB3's clip_range_vf
+    _fields_ = [("struct_bytes", C.c_int32), ("clip_range_vf", C.c_float), ("old_values", C.c_void_p), ("base", FleetPpoGradArgs)]
+
+
 # ---- Adam and clip_grad_norm_ (include/fleet_hip.h "Adam and clip_grad_norm_ on the device", fleet_adam_*) ------------------------------
 ADAM_MAX_EXTRA = 2
 ADAM_STATE_EXPORT, ADAM_STATE_LOAD = 0, 1
@@ -245,6 +249,10 @@ class FleetTrainInfo(C.Structure):
     _fields_ = [("num_envs", C.c_int32), ("n_steps", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("max_batch", C.c_int32),
                 ("n_tensors", C.c_int32), ("rounds", C.c_int32), ("min_half_bits", C.c_int32), ("tile_rows", C.c_int32),
                 ("cache_rows", C.c_int32), ("staging_bytes", C.c_uint64), ("staging", C.c_void_p)]
+
+
+class FleetTrainPpoVclipArgs(C.Structure):  # fleet_train_ppo_vclip_dev: the same with SB3's clip_range_vf
+    _fields_ = [("struct_bytes", C.c_int32), ("clip_range_vf", C.c_float), ("base", FleetTrainPpoArgs)]
 
 
 # ---- TD3 / DDPG's whole update (include/fleet_hip.h "TD3 / DDPG's whole update on the device", fleet_offpolicy_*) ------------------------
@@ -603,6 +611,7 @@ def load_library():
     lib.fleet_ppo_last_error.argtypes = [vp]
     lib.fleet_ppo_describe.argtypes = [vp, C.POINTER(FleetPpoParams), C.POINTER(C.c_uint64), i32p]
     lib.fleet_ppo_grad_dev.argtypes = [vp, C.POINTER(FleetPpoGradArgs), C.POINTER(vp), C.c_int]
+    lib.fleet_ppo_grad_vclip_dev.argtypes = [vp, C.POINTER(FleetPpoGradVclipArgs), C.POINTER(vp), C.c_int]
     # TD3's minibatch gradients (fleet_td3.hip)
     lib.fleet_td3_create.argtypes = [vp, C.POINTER(FleetTd3Params), C.POINTER(vp)]
     lib.fleet_td3_destroy.argtypes = [vp]
@@ -626,6 +635,10 @@ def load_library():
     lib.fleet_train_describe.argtypes = [vp, C.POINTER(FleetTrainInfo)]
     lib.fleet_train_ppo_dev.argtypes = [vp, C.POINTER(FleetTrainPpoArgs), C.POINTER(vp), C.POINTER(vp), C.c_int]
     lib.fleet_train_indices_dev.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, vp]
+    lib.fleet_train_ppo_vclip_dev.argtypes = [vp, C.POINTER(FleetTrainPpoVclipArgs), C.POINTER(vp), C.POINTER(vp), C.c_int]
+    lib.fleet_train_describe_vclip.argtypes = [vp, C.POINTER(C.c_uint64)]
+    for name in VCLIP_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
     # TD3 / DDPG's whole update (fleet_offpolicy.hip)
     lib.fleet_offpolicy_create.argtypes = [vp, vp, vp, vp, vp, C.POINTER(FleetOffpolicyParams), C.POINTER(vp)]
     lib.fleet_offpolicy_destroy.argtypes = [vp]
@@ -716,6 +729,10 @@ ADAM_SYMBOLS = ("fleet_adam_create_policy", "fleet_adam_create_qtarget", "fleet_
 
 TRAIN_SYMBOLS = ("fleet_train_create", "fleet_train_destroy", "fleet_train_last_error", "fleet_train_describe", "fleet_train_ppo_dev",
                  "fleet_train_indices_dev")
+
+# value-function clipping on the fleet_ppo and fleet_train handles: the header declares these `extern`, behind the two families' own
+# (closed) entry lists, so they stand in a list of their own here as well
+VCLIP_SYMBOLS = ("fleet_ppo_grad_vclip_dev", "fleet_train_ppo_vclip_dev", "fleet_train_describe_vclip")
 
 OFFPOLICY_SYMBOLS = ("fleet_offpolicy_create", "fleet_offpolicy_destroy", "fleet_offpolicy_last_error", "fleet_offpolicy_describe",
                      "fleet_offpolicy_td3_dev", "fleet_offpolicy_polyak_dev")

@@ -6,7 +6,8 @@
 //              fleet_td3.hip, as are the backward layer, the compensated sum and the weights launch's tile) also stores every hidden
 //              activation to the scratch.  The last layer leaves its rows untransformed in the LDS.  Head 0's epilogue forms the
 //              log-probability terms with sample_epilogue's expression and sums them in its order, then the row's ratio, clip and
-//              d loss / d log-probability; head 1's forms d loss / d value.  The SAME workgroup then walks back through its layers:
+//              d loss / d log-probability; head 1's forms d loss / d value (through SB3's value clip in the second instance,
+//              ppo_rows<true>, which fleet_ppo_grad_vclip_dev launches: the same text, the clip compiled in).  The SAME workgroup then walks back through its layers:
 //              a thread owns input column k of all 16 rows, d_prev[r][k] = (fmaf chain over j ascending of Wt[k][j] * d[r][j]) *
 //              act'(h[r][k]); every layer's delta goes to the scratch.  Thread 0 writes the tile's partial sums of the statistics.
 //              LDS: two buffers [16][T], T the widest layer of both heads (out64), the staged chunk [16][128], 64 row scalars.
@@ -22,6 +23,7 @@
 
 #include <cmath>
 #include <string>
+#include <type_traits>
 
 #include "fleet_grad_dev.h"
 #include "fleet_mlp.h"
@@ -49,7 +51,14 @@ struct RowsArgs {
   float clip, vf_coef, invB;
 };
 
-__global__ __launch_bounds__(kPolicyThreads) void ppo_rows(RowsArgs t) {
+struct RowsArgsVclip : RowsArgs {
+  const float* old_v;  // the value clip's old values
+  float cv;            // clip_range_vf
+};
+
+// kVclip: the instance with the value clip (a second instance, so that the first one stays the code it was)
+template <bool kVclip>
+__global__ __launch_bounds__(kPolicyThreads) void ppo_rows(std::conditional_t<kVclip, RowsArgsVclip, RowsArgs> t) {
   extern __shared__ float lds[];  // two buffers [16][T], the staged input [16][kPolicyChunk], the rows' scalars [4][16]
   const PolicyDesc* __restrict__ d = t.desc;
   const int head = blockIdx.y;
@@ -135,8 +144,17 @@ __global__ __launch_bounds__(kPolicyThreads) void ppo_rows(RowsArgs t) {
       if (row < B) {
         const float v = cur[r * S], ret = t.ret[row];
         if (t.values) t.values[row] = v;
-        dv = ((2.0f * t.vf_coef) * t.invB) * (v - ret);
-        const float e = ret - v;
+        float vp = v;
+        bool inside = true;
+        if constexpr (kVclip) {
+          const float ov = t.old_v[row], cv = t.cv;
+          const float dl = v - ov;
+          const float cd = dl < -cv ? -cv : (dl > cv ? cv : dl);
+          vp = ov + cd;
+          inside = dl >= -cv && dl <= cv;  // torch's clamp backward: ties pass, NaN does not
+        }
+        dv = inside ? ((2.0f * t.vf_coef) * t.invB) * (vp - ret) : 0.0f;
+        const float e = ret - vp;
         sq = e * e;
         gdl[(size_t)row * LL.out64] = dv;
       }
@@ -231,6 +249,17 @@ std::string check_grad_args(const FleetPpoGradArgs* args, float* const* grads, i
   return "";
 }
 
+// what fleet_ppo_grad_vclip_dev refuses on top of that
+std::string check_vclip_args(const FleetPpoGradVclipArgs* args, float* const* grads, int count) {
+  if (!args) return "null FleetPpoGradVclipArgs";
+  if (args->struct_bytes != (int32_t)sizeof(FleetPpoGradVclipArgs)) return "FleetPpoGradVclipArgs.struct_bytes does not match this library";
+  std::string why = check_grad_args(&args->base, grads, count);
+  if (!why.empty()) return why;
+  if (!args->old_values) return "null old_values";
+  if (!(std::isfinite(args->clip_range_vf) && args->clip_range_vf > 0.0f)) return "clip_range_vf must be finite and > 0";
+  return "";
+}
+
 }  // namespace
 
 struct FleetPpo : FleetMlpUser {  // img: a two-head policy's; block: the scratch
@@ -265,7 +294,7 @@ int fleet_ppo_create(fleet_policy_handle policy, const FleetPpoParams* p, fleet_
   h->s.floats = off;
   h->lds_bytes = ((size_t)2 * kPolicyRows * h->T + (size_t)kPolicyRows * kPolicyChunk + 64) * sizeof(float);
   constexpr int kMaxLds = (2 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk + 64) * (int)sizeof(float);
-  const int rc = mlp_user_open(h, pol, off * sizeof(float), "scratch", {{reinterpret_cast<const void*>(&ppo_rows), kMaxLds}}, "rows", &why);
+  const int rc = mlp_user_open(h, pol, off * sizeof(float), "scratch", {{reinterpret_cast<const void*>(&ppo_rows<false>), kMaxLds}, {reinterpret_cast<const void*>(&ppo_rows<true>), kMaxLds}}, "rows", &why);
   if (rc != FLEET_OK) {
     fleet_ppo_destroy(h);
     return handle_refuse(g_ppo_error, "fleet_ppo_create", why, rc);
@@ -291,23 +320,25 @@ int fleet_ppo_describe(fleet_ppo_handle h, FleetPpoParams* out, uint64_t* scratc
   return FLEET_OK;
 }
 
-int fleet_ppo_grad_dev(fleet_ppo_handle h, const FleetPpoGradArgs* args, float* const* grads, int count) {
-  std::string why = check_grad_args(args, grads, count);
-  if (h && why.empty()) grad_check_sizes(&why, count, h->img->n_tensors + 1, "W, b per layer, then log_std", args->B, h->p.max_batch);
-  if (const int rc = handle_enter("fleet_ppo_grad_dev", why, h, g_ppo_error); rc != FLEET_OK) return rc;
+}  // extern "C"
+
+namespace {
+
+// the two launches of both entries; old_values null: no value clip
+int ppo_grad_launch(fleet_ppo_handle h, const FleetPpoGradArgs& x, const float* old_values, float clip_range_vf, float* const* grads, int count) {
   FleetMlpHandle* pol = h->img;
-  const FleetPpoGradArgs& x = *args;
   const PolicyHeadDesc* nets = pol->nets;
   const int B = x.B, n_tiles = (B + kPolicyRows - 1) / kPolicyRows;
   const float invB = 1.0f / (float)B;
   float* scratch = h->floats();
-  RowsArgs t{};
+  RowsArgsVclip t{};
   t.desc = reinterpret_cast<const PolicyDesc*>(pol->block);
   t.base = reinterpret_cast<const float*>(pol->block);
   t.obs = x.obs, t.actions = x.actions, t.old_lp = x.old_log_prob, t.adv = x.advantages, t.ret = x.returns, t.log_std = x.log_std;
   t.values = x.values, t.log_prob = x.log_prob;
   t.scratch = scratch, t.s = h->s, t.B = B, t.T = h->T;
   t.clip = x.clip_range, t.vf_coef = x.vf_coef, t.invB = invB;
+  t.old_v = old_values, t.cv = clip_range_vf;
   WeightArgs g{};
   grad_fill_entries(g.e, &g.n_entries, &g.tile_blocks, nets, 0, 2, scratch, h->s.act, h->s.delta, x.obs, nets[0].layer[0].in, nullptr, 0, grads);
   const PolicyLayer& LA = nets[0].layer[nets[0].n_layers - 1];
@@ -317,11 +348,30 @@ int fleet_ppo_grad_dev(fleet_ppo_handle h, const FleetPpoGradArgs* args, float* 
   g.A = LA.out, g.M = LA.out64, g.n_tiles = n_tiles;
   g.invB = invB, g.vf_coef = x.vf_coef, g.ent_coef = x.ent_coef;
   FLEET_HANDLE_TRY(h, hipSetDevice(pol->device));
-  hipLaunchKernelGGL(ppo_rows, dim3((unsigned)n_tiles, 2), dim3(kPolicyThreads), h->lds_bytes, pol->stream, t);
+  if (old_values) hipLaunchKernelGGL(ppo_rows<true>, dim3((unsigned)n_tiles, 2), dim3(kPolicyThreads), h->lds_bytes, pol->stream, t);
+  else hipLaunchKernelGGL(ppo_rows<false>, dim3((unsigned)n_tiles, 2), dim3(kPolicyThreads), h->lds_bytes, pol->stream, static_cast<const RowsArgs&>(t));
   FLEET_HANDLE_TRY(h, hipGetLastError());
   hipLaunchKernelGGL(ppo_weights, dim3((unsigned)(g.tile_blocks + g.ls_blocks + 1)), dim3(256), 0, pol->stream, g);
   FLEET_HANDLE_TRY(h, hipGetLastError());
   return FLEET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fleet_ppo_grad_dev(fleet_ppo_handle h, const FleetPpoGradArgs* args, float* const* grads, int count) {
+  std::string why = check_grad_args(args, grads, count);
+  if (h && why.empty()) grad_check_sizes(&why, count, h->img->n_tensors + 1, "W, b per layer, then log_std", args->B, h->p.max_batch);
+  if (const int rc = handle_enter("fleet_ppo_grad_dev", why, h, g_ppo_error); rc != FLEET_OK) return rc;
+  return ppo_grad_launch(h, *args, nullptr, 0.0f, grads, count);
+}
+
+int fleet_ppo_grad_vclip_dev(fleet_ppo_handle h, const FleetPpoGradVclipArgs* args, float* const* grads, int count) {
+  std::string why = check_vclip_args(args, grads, count);
+  if (h && why.empty()) grad_check_sizes(&why, count, h->img->n_tensors + 1, "W, b per layer, then log_std", args->base.B, h->p.max_batch);
+  if (const int rc = handle_enter("fleet_ppo_grad_vclip_dev", why, h, g_ppo_error); rc != FLEET_OK) return rc;
+  return ppo_grad_launch(h, args->base, args->old_values, args->clip_range_vf, grads, count);
 }
 
 }  // extern "C"

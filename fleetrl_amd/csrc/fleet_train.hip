@@ -8,7 +8,8 @@
 //              deviation itself: float64, lane t adds positions t, t + 256, ... in ascending order, then a halving tree over the 256
 //              lane sums -- every workgroup holds the same bits with no ordering between them.  Then it strides over tiles of 4
 //              rows: a wavefront moves one row, lanes along the row (16-byte words when D or A is a multiple of 4), lane 0
-//              the row's scalars and its normalised advantage.  Thread 0 of workgroup 0 first folds the PREVIOUS minibatch's
+//              the row's scalars (the buffer's value too in the second instance, train_minibatch<true>, which
+//              fleet_train_ppo_vclip_dev launches) and its normalised advantage.  Thread 0 of workgroup 0 first folds the PREVIOUS minibatch's
 //              statistics into the running float64 sums (or clears them: the call's first launch).
 //   train_finish     one workgroup of 256 threads per call: the last minibatch's statistics into the sums, the means,
 //              explained_variance over the whole buffer and mean(exp(log_std)) with the same ordered sum, the statistics block.
@@ -18,6 +19,7 @@
 
 #include <cmath>
 #include <string>
+#include <type_traits>
 
 #include "fleet_handle.h"
 #include "fleet_mlp.h"
@@ -82,6 +84,11 @@ struct MiniArgs {
   int obs_vec, act_vec, normalise, fold;
 };
 
+struct MiniArgsVclip : MiniArgs {
+  const float* val;  // the buffer's values, [K, E]
+  float* o_val;      // their staging array, [max_batch]
+};
+
 // the buffer row t * E + e of position start + b of the epoch: the shuffle gives i = e * K + t
 __device__ inline uint32_t buffer_row(const MiniArgs& a, uint32_t b) {
   const uint32_t i = train_perm(a.key, a.start + b);
@@ -106,7 +113,9 @@ __device__ inline void move_row(const float* src, float* dst, size_t from, size_
   }
 }
 
-__global__ __launch_bounds__(kTrainThreads) void train_minibatch(MiniArgs a) {
+// kVclip: the instance that stages the old values too (a second instance, so that the first one stays the code it was)
+template <bool kVclip>
+__global__ __launch_bounds__(kTrainThreads) void train_minibatch(std::conditional_t<kVclip, MiniArgsVclip, MiniArgs> a) {
   __shared__ double red[kTrainThreads];
   __shared__ uint32_t rows[kTrainCache];
   const uint32_t tid = threadIdx.x, B = a.B;
@@ -145,8 +154,11 @@ __global__ __launch_bounds__(kTrainThreads) void train_minibatch(MiniArgs a) {
       const uint32_t b = tile * kTrainRows + r;  // (uniform over the wavefront)
       if (b >= B) break;
       const uint32_t row = __builtin_amdgcn_readfirstlane(row_of(b));
-      float x = 0.0f, lp = 0.0f, rt = 0.0f;
-      if (lane == 0) x = a.adv[row], lp = a.logp[row], rt = a.ret[row];  // (issued ahead of the row's words)
+      float x = 0.0f, lp = 0.0f, rt = 0.0f, ov = 0.0f;
+      if (lane == 0) {  // (issued ahead of the row's words)
+        x = a.adv[row], lp = a.logp[row], rt = a.ret[row];
+        if constexpr (kVclip) ov = a.val[row];
+      }
       if (a.obs_vec) move_row<float4>(a.obs, a.o_obs, row, b, a.obs_words, lane);
       else move_row<float>(a.obs, a.o_obs, row, b, a.obs_words, lane);
       if (a.act_vec) move_row<float4>(a.act, a.o_act, row, b, a.act_words, lane);
@@ -156,6 +168,7 @@ __global__ __launch_bounds__(kTrainThreads) void train_minibatch(MiniArgs a) {
         a.o_ret[b] = rt;
         a.o_adv[b] = x;
         if (normalise) a.o_advn[b] = (x - mean) / den;
+        if constexpr (kVclip) a.o_val[b] = ov;
       }
     }
   }
@@ -274,6 +287,7 @@ struct FleetTrain : FleetMlpUser {  // img: the policy's; block: the staging arr
   FleetRolloutArrays arr{};
   int E = 0, K = 0, D = 0, A = 0, max_batch = 0, n_tensors = 0;
   uint64_t stage[kStageArrays] = {}, stats_at = 0, acc_at = 0, staging_bytes = 0;
+  uint64_t val_at = 0;  // the staged old values, behind everything else
 
   float* staged(int which) const { return reinterpret_cast<float*>(block + stage[which]); }
 };
@@ -324,6 +338,7 @@ int fleet_train_create(fleet_rollout_handle buffer, struct FleetPpo* grad, struc
   h->staging_bytes = off;
   h->stats_at = off, off += 256;
   h->acc_at = off, off += 256;
+  h->val_at = off, off += (mb * 4 + 255) / 256 * 256;
   int rc = mlp_user_open(h, img, off, "staging block", {}, "", &why);
   if (rc == FLEET_OK && (hipMemset(h->block, 0, off) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
     (void)hipGetLastError();
@@ -368,8 +383,13 @@ int fleet_train_indices_dev(fleet_train_handle h, int32_t n, uint64_t seed, uint
   return FLEET_OK;
 }
 
-int fleet_train_ppo_dev(fleet_train_handle h, const FleetTrainPpoArgs* x, float* const* params, float* const* grads, int count) {
-  std::string why = check_ppo_args(x, params, grads, count);
+}  // extern "C"
+
+namespace {
+
+// both updates; clip_range_vf 0: no value clip (`why`: what the entry's own checks found)
+int train_ppo(const char* entry, fleet_train_handle h, std::string why, const FleetTrainPpoArgs* x, float clip_range_vf, float* const* params,
+              float* const* grads, int count) {
   const uint32_t n = h ? (uint32_t)h->E * (uint32_t)h->K : 0;
   const uint32_t bs = h && why.empty() ? ((uint32_t)x->batch_size < n ? (uint32_t)x->batch_size : n) : 0;
   if (h && why.empty()) {
@@ -381,21 +401,25 @@ int fleet_train_ppo_dev(fleet_train_handle h, const FleetTrainPpoArgs* x, float*
     else if (rollout_base(h->buffer)->stream != h->img->stream)
       why = "the rollout buffer launches on another stream than the policy: fleet_rollout_set_stream it to the policy's first";
   }
-  if (const int rc = handle_enter("fleet_train_ppo_dev", why, h, g_train_error); rc != FLEET_OK) return rc;
+  if (const int rc = handle_enter(entry, why, h, g_train_error); rc != FLEET_OK) return rc;
+  const bool vclip = clip_range_vf > 0.0f;
   FleetMlpHandle* pol = h->img;
   float* gstats = reinterpret_cast<float*>(h->block + h->stats_at);
   double* acc = reinterpret_cast<double*>(h->block + h->acc_at);
-  MiniArgs m{};
+  MiniArgsVclip m{};
   m.obs = h->arr.obs, m.act = h->arr.actions, m.logp = h->arr.log_probs, m.adv = h->arr.advantages, m.ret = h->arr.returns;
   m.o_obs = h->staged(kStageObs), m.o_act = h->staged(kStageAct), m.o_logp = h->staged(kStageLogp), m.o_adv = h->staged(kStageAdv);
   m.o_advn = h->staged(kStageAdvn), m.o_ret = h->staged(kStageRet);
+  m.val = h->arr.values, m.o_val = vclip ? reinterpret_cast<float*>(h->block + h->val_at) : nullptr;
   m.prev_stats = gstats, m.acc = acc;
   m.E = (uint32_t)h->E, m.K = (uint32_t)h->K;
   // (the buffer's arrays and the staging arrays start at multiples of 256 bytes: a row of 4k floats starts at a multiple of 16)
   m.obs_vec = h->D % 4 == 0, m.act_vec = h->A % 4 == 0;
   m.obs_words = (uint32_t)(m.obs_vec ? h->D / 4 : h->D), m.act_words = (uint32_t)(m.act_vec ? h->A / 4 : h->A);
   m.normalise = x->normalize_advantage != 0;
-  FleetPpoGradArgs g{};
+  FleetPpoGradVclipArgs gv{};
+  gv.struct_bytes = (int32_t)sizeof gv, gv.clip_range_vf = clip_range_vf, gv.old_values = m.o_val;
+  FleetPpoGradArgs& g = gv.base;
   g.struct_bytes = (int32_t)sizeof g;
   g.obs = m.o_obs, g.actions = m.o_act, g.old_log_prob = m.o_logp, g.returns = m.o_ret, g.log_std = params[count - 1];
   g.clip_range = x->clip_range, g.vf_coef = x->vf_coef, g.ent_coef = x->ent_coef, g.stats = gstats;
@@ -410,17 +434,19 @@ int fleet_train_ppo_dev(fleet_train_handle h, const FleetTrainPpoArgs* x, float*
       const uint32_t B = n - start < bs ? n - start : bs;
       m.start = start, m.B = B, m.fold = done != 0;
       const unsigned tiles = (B + kTrainRows - 1) / kTrainRows;
-      hipLaunchKernelGGL(train_minibatch, dim3(tiles < (unsigned)kTrainMaxBlocks ? tiles : (unsigned)kTrainMaxBlocks), dim3(kTrainThreads), 0,
-                         pol->stream, m);
+      const dim3 grid(tiles < (unsigned)kTrainMaxBlocks ? tiles : (unsigned)kTrainMaxBlocks);
+      if (vclip) hipLaunchKernelGGL(train_minibatch<true>, grid, dim3(kTrainThreads), 0, pol->stream, m);
+      else hipLaunchKernelGGL(train_minibatch<false>, grid, dim3(kTrainThreads), 0, pol->stream, static_cast<const MiniArgs&>(m));
       FLEET_HANDLE_TRY(h, hipGetLastError());
       g.B = (int32_t)B;
       g.advantages = m.normalise && B > 1 ? m.o_advn : m.o_adv;
-      if (const int rc = fleet_ppo_grad_dev(h->grad, &g, grads, count); rc != FLEET_OK) {
-        h->error = std::string("fleet_train_ppo_dev: ") + fleet_ppo_last_error(h->grad);
+      if (const int rc = vclip ? fleet_ppo_grad_vclip_dev(h->grad, &gv, grads, count) : fleet_ppo_grad_dev(h->grad, &g, grads, count);
+          rc != FLEET_OK) {
+        h->error = std::string(entry) + ": " + fleet_ppo_last_error(h->grad);
         return rc;
       }
       if (const int rc = fleet_adam_step_dev(h->adam, &s, params, grads, count); rc != FLEET_OK) {
-        h->error = std::string("fleet_train_ppo_dev: ") + fleet_adam_last_error(h->adam);
+        h->error = std::string(entry) + ": " + fleet_adam_last_error(h->adam);
         return rc;
       }
     }
@@ -430,6 +456,29 @@ int fleet_train_ppo_dev(fleet_train_handle h, const FleetTrainPpoArgs* x, float*
   f.n = n, f.A = h->A, f.count = (double)done;
   hipLaunchKernelGGL(train_finish, dim3(1), dim3(kTrainThreads), 0, pol->stream, f);
   FLEET_HANDLE_TRY(h, hipGetLastError());
+  return FLEET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fleet_train_ppo_dev(fleet_train_handle h, const FleetTrainPpoArgs* x, float* const* params, float* const* grads, int count) {
+  return train_ppo("fleet_train_ppo_dev", h, check_ppo_args(x, params, grads, count), x, 0.0f, params, grads, count);
+}
+
+int fleet_train_ppo_vclip_dev(fleet_train_handle h, const FleetTrainPpoVclipArgs* a, float* const* params, float* const* grads, int count) {
+  std::string why;
+  if (!a) why = "null FleetTrainPpoVclipArgs";
+  else if (a->struct_bytes != (int32_t)sizeof(FleetTrainPpoVclipArgs)) why = "FleetTrainPpoVclipArgs.struct_bytes does not match this library";
+  else why = check_ppo_args(&a->base, params, grads, count);
+  if (why.empty() && !(std::isfinite(a->clip_range_vf) && a->clip_range_vf > 0.0f)) why = "clip_range_vf must be finite and > 0";
+  return train_ppo("fleet_train_ppo_vclip_dev", h, why, a ? &a->base : nullptr, a ? a->clip_range_vf : 0.0f, params, grads, count);
+}
+
+int fleet_train_describe_vclip(fleet_train_handle h, uint64_t* old_values_offset) {
+  if (!h || !old_values_offset) return FLEET_ERR_INVALID;
+  *old_values_offset = h->val_at;
   return FLEET_OK;
 }
 

@@ -1,11 +1,12 @@
 """`DevicePPOGrad`: the gradients of PPO's minibatch loss on the device (include/fleet_hip.h `fleet_ppo_*`,
 fleetrl_amd/csrc/fleet_ppo.hip).
 
-What SB3's `PPO.train` does with one minibatch before the optimiser -- `evaluate_actions`, the clipped loss (`clip_range_vf=None`) and
-`loss.backward()` -- in two launches on a two-head `DevicePolicy`'s weights: the gradients land in the `.grad` of torch's own
+What SB3's `PPO.train` does with one minibatch before the optimiser -- `evaluate_actions`, the clipped loss and `loss.backward()`
+-- in two launches on a two-head `DevicePolicy`'s weights: the gradients land in the `.grad` of torch's own
 parameters, so `clip_grad_norm_` and `opt.step()` follow unchanged.  Deterministic by construction: no atomics, every sum in a fixed
-order.  The optimiser, the advantage normalisation and `clip_range_vf` stay the caller's.  The device policy's image is what is
-differentiated: call `policy.load_torch(params)` after every optimiser step.
+order.  `clip_range_vf` is SB3's: `None` for the plain squared error, a positive float to clip the value prediction around the batch's
+`old_values` inside the same two launches (`fleet_ppo_grad_vclip_dev`).  The optimiser and the advantage normalisation stay the
+caller's.  The device policy's image is what is differentiated: call `policy.load_torch(params)` after every optimiser step.
 """
 from __future__ import annotations
 
@@ -14,9 +15,19 @@ import ctypes as C
 from . import _capi
 from ._handle import _ImageBorrower
 
-__all__ = ["DevicePPOGrad", "STATS"]
+__all__ = ["DevicePPOGrad", "STATS", "check_clip_range_vf"]
 
 STATS = ("policy_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction")
+
+
+def check_clip_range_vf(clip_range_vf):
+    """None, or the positive finite float: SB3 refuses the rest in the same words."""
+    if clip_range_vf is None:
+        return None
+    cv = float(clip_range_vf)
+    if not (cv > 0.0 and cv != float("inf")):
+        raise ValueError(f"`clip_range_vf` must be positive, pass `None` to deactivate vf clipping (got {clip_range_vf!r})")
+    return cv
 
 
 class DevicePPOGrad(_ImageBorrower):
@@ -42,22 +53,31 @@ class DevicePPOGrad(_ImageBorrower):
         args.struct_bytes = C.sizeof(_capi.FleetPpoGradArgs)
         self._check(self.lib.fleet_ppo_grad_dev(self.h, C.byref(args), grad_ptrs, int(count)))
 
+    def grad_vclip_dev(self, args: "_capi.FleetPpoGradVclipArgs", grad_ptrs, count: int):
+        """The same through fleet_ppo_grad_vclip_dev: a FleetPpoGradVclipArgs, whose `base` is a FleetPpoGradArgs."""
+        args.struct_bytes, args.base.struct_bytes = C.sizeof(_capi.FleetPpoGradVclipArgs), C.sizeof(_capi.FleetPpoGradArgs)
+        self._check(self.lib.fleet_ppo_grad_vclip_dev(self.h, C.byref(args), grad_ptrs, int(count)))
+
     def grad(self, batch, log_std, clip_range: float, vf_coef: float, ent_coef: float, *, into, values_out=None, log_prob_out=None,
-             advantages=None, stats_out=None):
+             advantages=None, stats_out=None, clip_range_vf=None):
         """The loss of one minibatch and its gradients, two launches on torch's current stream, no host synchronisation.
         batch: what `DeviceRolloutBuffer.get` yields (observations f32 [B, obs_dim], actions f32 [B, act_dim], old_log_prob,
         advantages, returns f32 [B]); `advantages` replaces the batch's (the normalised ones).  log_std: the torch parameter f32
         [act_dim], read when the launch runs.  into: the torch parameters in `DevicePolicy.load_torch`'s order, then log_std; their
         `.grad` is allocated on the first call and OVERWRITTEN by every call (there is nothing to zero).  values_out, log_prob_out
-        f32 [B]: the critic's values and the new log-probabilities.  Returns stats f32 [8] on the device: `STATS`, then two zeros."""
+        f32 [B]: the critic's (unclipped) values and the new log-probabilities.  clip_range_vf: None, or SB3's positive float: the value
+        loss is then taken on `old_values + clamp(values - old_values, -clip_range_vf, clip_range_vf)` with the batch's `old_values`
+        f32 [B].  Returns stats f32 [8] on the device: `STATS`, then two zeros."""
         import torch
 
+        cv = check_clip_range_vf(clip_range_vf)
         self.use_torch_stream()
         f32 = (torch.float32,)
         obs = batch.observations
         B = int(obs.shape[0]) if obs.ndim == 2 else 0
         adv = batch.advantages if advantages is None else advantages
-        a = _capi.FleetPpoGradArgs()
+        v = None if cv is None else _capi.FleetPpoGradVclipArgs()
+        a = _capi.FleetPpoGradArgs() if v is None else v.base
         a.B = B
         keep = [self._tensor(obs, (B, self.obs_dim), f32), self._tensor(batch.actions, (B, self.act_dim), f32),
                 self._tensor(batch.old_log_prob, (B,), f32), self._tensor(adv.detach(), (B,), f32), self._tensor(batch.returns, (B,), f32),
@@ -72,5 +92,10 @@ class DevicePPOGrad(_ImageBorrower):
                 keep.append(self._tensor(t, (B,), f32))
                 setattr(a, name, keep[-1].data_ptr())
         arr = self._grad_pointers("grad", into, self._shapes, "the actor's then the critic's, then log_std")
-        self.grad_dev(a, arr, len(self._shapes))
+        if v is None:
+            self.grad_dev(a, arr, len(self._shapes))
+        else:
+            keep.append(self._tensor(batch.old_values, (B,), f32))
+            v.old_values, v.clip_range_vf = keep[-1].data_ptr(), cv
+            self.grad_vclip_dev(v, arr, len(self._shapes))
         return stats_out

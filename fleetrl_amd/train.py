@@ -1,9 +1,10 @@
 """`DevicePPOTrain`: stable-baselines3's `PPO.train()` as one enqueue-only call (include/fleet_hip.h `fleet_train_*`,
 fleetrl_amd/csrc/fleet_train.hip).
 
-`n_epochs` passes over a finished `DeviceRolloutBuffer` in freshly shuffled minibatches (`clip_range_vf=None`, `target_kl=None`): per
-minibatch one launch shuffles, gathers and normalises the advantages, `DevicePPOGrad`'s two launches form the gradients and `DeviceAdam`'s
-two clip, step and refresh the policy's weight image.  The shuffle is a keyed bijection evaluated on the device -- no `torch.randperm`,
+`n_epochs` passes over a finished `DeviceRolloutBuffer` in freshly shuffled minibatches (`target_kl=None`): per minibatch one launch
+shuffles, gathers and normalises the advantages, `DevicePPOGrad`'s two launches form the gradients and `DeviceAdam`'s two clip, step
+and refresh the policy's weight image.  With SB3's `clip_range_vf` set, the gather also stages the buffer's values and the gradient
+launches clip the value prediction around them (`fleet_train_ppo_vclip_dev`): still five launches per minibatch.  The shuffle is a keyed bijection evaluated on the device -- no `torch.randperm`,
 no permutation in memory --, every sum has a stated order, and one block of statistics (`STATS`: what SB3 logs as `train/*`) is
 written at the end.  Deterministic from (buffer, weights, optimiser state, seed, first_epoch) to the weights.
 """
@@ -14,6 +15,7 @@ import ctypes as C
 from . import _capi
 from ._capi import FleetHipError
 from ._handle import _ImageBorrower
+from .ppo import check_clip_range_vf
 
 __all__ = ["DevicePPOTrain", "STATS"]
 
@@ -45,10 +47,13 @@ class DevicePPOTrain(_ImageBorrower):
         self._ptrs = None  # (the parameters, their pointer array, their addresses) of the last call
 
     def describe(self) -> dict:
-        """What fleet_train_describe reports."""
+        """What fleet_train_describe reports, and `old_values_offset` (fleet_train_describe_vclip): the bytes from `staging` to the
+        old values f32 [max_batch] that the last value-clipped minibatch staged."""
         i = _capi.FleetTrainInfo()
         self._check(self.lib.fleet_train_describe(self.h, C.byref(i)))
-        return {n: getattr(i, n) for n, _ in i._fields_}
+        off = C.c_uint64()
+        self._check(self.lib.fleet_train_describe_vclip(self.h, C.byref(off)))
+        return {**{n: getattr(i, n) for n, _ in i._fields_}, "old_values_offset": int(off.value)}
 
     def use_torch_stream(self, device=None):
         """The policy and the buffer both launch on torch's current stream from now on."""
@@ -59,6 +64,11 @@ class DevicePPOTrain(_ImageBorrower):
         """Raw device addresses in a FleetTrainPpoArgs and two (c_void_p * count) arrays, on the policy's stream."""
         args.struct_bytes = C.sizeof(_capi.FleetTrainPpoArgs)
         self._check(self.lib.fleet_train_ppo_dev(self.h, C.byref(args), param_ptrs, grad_ptrs, int(count)))
+
+    def train_vclip_dev(self, args: "_capi.FleetTrainPpoVclipArgs", param_ptrs, grad_ptrs, count: int):
+        """The same through fleet_train_ppo_vclip_dev: a FleetTrainPpoVclipArgs, whose `base` is a FleetTrainPpoArgs."""
+        args.struct_bytes, args.base.struct_bytes = C.sizeof(_capi.FleetTrainPpoVclipArgs), C.sizeof(_capi.FleetTrainPpoArgs)
+        self._check(self.lib.fleet_train_ppo_vclip_dev(self.h, C.byref(args), param_ptrs, grad_ptrs, int(count)))
 
     def _param_pointers(self, into):
         import torch
@@ -72,17 +82,20 @@ class DevicePPOTrain(_ImageBorrower):
         return self._ptrs[1]
 
     def train(self, into, *, n_epochs: int, batch_size: int, clip_range: float, vf_coef: float, ent_coef: float, lr: float,
-              normalize_advantage: bool = True, seed: int, first_epoch: int, stats_out=None):
+              normalize_advantage: bool = True, seed: int, first_epoch: int, stats_out=None, clip_range_vf=None):
         """The whole update on torch's current stream, no host synchronisation.  into: the torch parameters in
         `DevicePolicy.load_torch`'s order, then log_std; they are stepped in place (and the policy's image with them), their `.grad`
         holds the last minibatch's gradients.  Epoch e shuffles under (seed, first_epoch + e): pass the number of epochs trained so far.
+        clip_range_vf: None, or SB3's positive float (the value loss on the prediction clipped around the buffer's values).
         Returns the statistics f64 [16] on the device: `STATS`, then zeros."""
         import torch
 
+        cv = check_clip_range_vf(clip_range_vf)
         if not self.buffer.full:
             raise FleetHipError(_capi.ERR_STATE, "train() needs a full rollout buffer")
         self.use_torch_stream()
-        a = _capi.FleetTrainPpoArgs()
+        v = None if cv is None else _capi.FleetTrainPpoVclipArgs()
+        a = _capi.FleetTrainPpoArgs() if v is None else v.base
         a.n_epochs, a.batch_size, a.normalize_advantage = int(n_epochs), int(batch_size), int(bool(normalize_advantage))
         a.clip_range, a.vf_coef, a.ent_coef, a.lr = float(clip_range), float(vf_coef), float(ent_coef), float(lr)
         a.beta1, a.beta2, a.eps, a.max_grad_norm = self.adam.betas[0], self.adam.betas[1], self.adam.eps, self.adam.max_grad_norm
@@ -91,7 +104,11 @@ class DevicePPOTrain(_ImageBorrower):
             stats_out = torch.empty(_capi.TRAIN_STATS, device=torch.device("cuda", self.device), dtype=torch.float64)
         a.stats = self._tensor(stats_out, (_capi.TRAIN_STATS,), (torch.float64,)).data_ptr()
         grads = self._grad_pointers("train", into, self._shapes, "the actor's then the critic's, then log_std")
-        self.train_dev(a, self._param_pointers(into), grads, len(self._shapes))
+        if v is None:
+            self.train_dev(a, self._param_pointers(into), grads, len(self._shapes))
+        else:
+            v.clip_range_vf = cv
+            self.train_vclip_dev(v, self._param_pointers(into), grads, len(self._shapes))
         return stats_out
 
     def indices(self, n: int, seed: int, epoch: int, start: int = 0, count: int | None = None, out=None):

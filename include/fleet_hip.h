@@ -1454,7 +1454,7 @@ int fleet_offpolicy_polyak_dev(fleet_offpolicy_handle h, double tau);
  * needs that count only.  Position start + b of the epoch is row b of the minibatch at `start`; i = perm(...) is the flat index
  * e_env * K + t of fleet_rollout_gather_dev.
  * The minibatch launch gathers obs, actions, old log-probabilities, advantages and returns of its B rows into the staging block (rows
- * of obs / actions as 16-byte words when D / A is a multiple of 4; old values are not gathered: nothing reads them) and, when
+ * of obs / actions as 16-byte words when D / A is a multiple of 4; old values are gathered by fleet_train_ppo_vclip_dev alone, below) and, when
  * normalize_advantage != 0 and B > 1, writes a second advantage array, which the gradient launches then read:
  *   ordered sum S(x) of B values in minibatch order, float64: lane t of 256: s_t = 0.0; s_t = s_t + x[b] for b = t, t + 256, ... ascending;
  *     then for s = 128, 64, ..., 1: s_t = s_t + s_(t + s) for t < s; the result is s_0
@@ -1526,6 +1526,24 @@ int fleet_train_ppo_dev(fleet_train_handle h, const FleetTrainPpoArgs* a, float*
 /* The shuffle on its own, one launch: out[k] = perm(n, seed, epoch, start + k) for k < count, int32 in device memory; any n in
  * 1 .. 2^31 - 1.  FLEET_ERR_INVALID for n < 1, positions outside [0, n), a null out. */
 int fleet_train_indices_dev(fleet_train_handle h, int32_t n, uint64_t seed, uint64_t epoch, int32_t start, int32_t count, int32_t* out);
+/* -- the update with value-function clipping (clip_range_vf; DESIGN.md "PPO's value clipping on the device") --
+ * (entries added under FLEET_ABI_VERSION 11 on the existing handle: fleet_train_ppo_dev, FleetTrainPpoArgs and FleetTrainInfo are as
+ * they were)  fleet_train_ppo_dev with SB3's clip_range_vf = cv > 0: still five launches per minibatch.  The minibatch launch also
+ * gathers the buffer's values of its rows (lane 0, with the row's other scalars) into one more staging array, f32[max_batch], which
+ * lies BEHIND the existing parts of the block -- staging_bytes, the stats and the running sums keep their places --, and the gradient
+ * step goes through fleet_ppo_grad_vclip_dev (the PPO gradients' section states the arithmetic).  The statistics block keeps its
+ * layout; [1] and [5] carry the clipped value loss.  FLEET_ERR_INVALID for a null or wrongly sized FleetTrainPpoVclipArgs, whatever
+ * fleet_train_ppo_dev refuses of `base` (in its words), a clip_range_vf that is not finite and > 0. */
+typedef struct FleetTrainPpoVclipArgs {
+  int32_t struct_bytes;          /* sizeof(FleetTrainPpoVclipArgs) */
+  float clip_range_vf;           /* cv: finite, > 0 */
+  FleetTrainPpoArgs base;        /* everything fleet_train_ppo_dev takes; base.struct_bytes = sizeof(FleetTrainPpoArgs) */
+} FleetTrainPpoVclipArgs;
+extern int fleet_train_ppo_vclip_dev(fleet_train_handle h, const FleetTrainPpoVclipArgs* a, float* const* params, float* const* grads,
+                                     int count);
+/* *old_values_offset: the bytes from FleetTrainInfo.staging to the staged old values f32[max_batch] (the LAST value-clipped
+ * minibatch's rows; tests).  FLEET_ERR_INVALID for a null handle or output. */
+extern int fleet_train_describe_vclip(fleet_train_handle h, uint64_t* old_values_offset);
 
 /* ---- Adam and clip_grad_norm_ on the device (fleet_adam.hip; DESIGN.md "The optimiser step on the device") -------------------------
  * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
@@ -1771,6 +1789,30 @@ int fleet_ppo_describe(fleet_ppo_handle h, FleetPpoParams* out, uint64_t* scratc
  * pointer in it, and -- these two need the handle -- a count that is not the policy's tensors + 1, B > max_batch.  The arguments are
  * looked at before the handle is: with h NULL the reason (or "null handle") goes to fleet_ppo_last_error(NULL). */
 int fleet_ppo_grad_dev(fleet_ppo_handle h, const FleetPpoGradArgs* args, float* const* grads, int count);
+
+/* -- the same with value-function clipping (clip_range_vf; DESIGN.md "PPO's value clipping on the device") --
+ * (an entry added under FLEET_ABI_VERSION 11 on the existing handle: fleet_ppo_grad_dev and FleetPpoGradArgs are as they were)
+ * SB3 2.3.2 with clip_range_vf = cv > 0:  values_pred = old_values + clamp(values - old_values, -cv, cv);  value_loss =
+ * mse_loss(returns, values_pred).  Per row b, with ov = old_values[b], the critic head's tail becomes, float32, no contraction:
+ *   dl  = v - ov
+ *   cd  = dl < -cv ? -cv : (dl > cv ? cv : dl)
+ *   vp  = ov + cd
+ *   e   = ret - vp;  the row's value term is e * e             (stats[1] = total(e * e) * invB, the same compensated sums)
+ *   inside = (dl >= -cv && dl <= cv)                           (torch's clamp backward: ties pass, NaN does not)
+ *   dv  = inside ? ((2.0f * vf_coef) * invB) * (vp - ret) : 0.0f
+ * values[b] stays the unclipped v.  The critic's tensors, stats[1] and with it stats[3] follow from dv and e; the actor's tensors, the
+ * log_std gradient, stats[0], [2], [4], [5], values and log_prob are fleet_ppo_grad_dev's bits on the same batch.  The same two
+ * launches (the rows launch is a second instance of its kernel with the clip compiled in, so that the first stays the code it was),
+ * the same scratch, the same rules.
+ * FLEET_ERR_INVALID for a null or wrongly sized FleetPpoGradVclipArgs, whatever fleet_ppo_grad_dev refuses of `base` (in its words), a
+ * null old_values, a clip_range_vf that is not finite and > 0; the arguments are looked at before the handle is. */
+typedef struct FleetPpoGradVclipArgs {
+  int32_t struct_bytes;        /* sizeof(FleetPpoGradVclipArgs) */
+  float clip_range_vf;         /* cv: finite, > 0 */
+  const float* old_values;     /* device f32[B]: the values the rollout stored */
+  FleetPpoGradArgs base;       /* everything fleet_ppo_grad_dev takes; base.struct_bytes = sizeof(FleetPpoGradArgs) */
+} FleetPpoGradVclipArgs;
+extern int fleet_ppo_grad_vclip_dev(fleet_ppo_handle h, const FleetPpoGradVclipArgs* args, float* const* grads, int count);
 
 #ifdef __cplusplus
 }
