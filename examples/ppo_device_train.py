@@ -11,10 +11,13 @@ its seed and a checkpoint needs that count only.  The rollout is the one of exam
 fit -- it is not a tuned trainer.  Needs an MI355X; inputs are synthetic:
 
     python examples/ppo_device_train.py [--iterations 3] [--envs 256] [--evs 5] [--steps 64] [--batch-size 128] [--epochs 4]
-                                        [--clip-range-vf 0.2] [--no-normalize-advantage] [--time]
+                                        [--clip-range-vf 0.2] [--no-normalize-advantage] [--target-kl 0.01] [--time]
 
 `--clip-range-vf` is SB3's `clip_range_vf` (off by default, as in SB3): the value loss on the prediction clipped around the rollout's
-values, inside the same launches.  `--no-normalize-advantage` is `normalize_advantage=False`.  Prints one JSON line per iteration;
+values, inside the same launches.  `--no-normalize-advantage` is `normalize_advantage=False`.  `--target-kl` is SB3's `target_kl` (off
+by default): the device stops the update at the first minibatch whose approx_kl exceeds 1.5 times it, and the line also carries the
+optimiser steps taken, the epochs entered, whether the update stopped, the approx_kl compared last and its mean over the last epoch
+(what SB3 logs as train/approx_kl); `train/n_updates` then counts epochs entered, as SB3 does.  Prints one JSON line per iteration;
 with `--time` one more line: the host wall time of further updates on the last rollout, the final synchronisation included.
 """
 import argparse
@@ -30,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import bench_config  # noqa: E402  (the reference's config dict with the benchmark's values)
 from fleetrl_amd import DeviceAdam, DevicePolicy, DevicePPOGrad, DevicePPOTrain, DeviceRolloutBuffer, FleetVecEnv, FleetVecNormalize  # noqa: E402
 from fleetrl_amd.synth import synth_tables  # noqa: E402
-from fleetrl_amd.train import SB3_NAMES  # noqa: E402
+from fleetrl_amd.train import KL_SB3_NAMES, SB3_NAMES  # noqa: E402
 
 
 class ActorCritic(nn.Module):
@@ -58,6 +61,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--clip-range-vf", type=float, default=None, help="SB3's clip_range_vf; default: no value clipping")
     ap.add_argument("--no-normalize-advantage", action="store_true", help="SB3's normalize_advantage=False")
+    ap.add_argument("--target-kl", type=float, default=None, help="SB3's target_kl; default: no early stopping")
     ap.add_argument("--time", action="store_true", help="after the last iteration, time the update alone on its rollout")
     ap.add_argument("--reps", type=int, default=7, help="updates timed by --time")
     args = ap.parse_args()
@@ -83,6 +87,9 @@ def main():
     clip_range, vf_coef, ent_coef = 0.2, 0.5, 0.0
     # (None is the default of train(): the argument is passed only when it is set)
     extra = {} if args.clip_range_vf is None else {"clip_range_vf": args.clip_range_vf}
+    if args.target_kl is not None:
+        extra["target_kl"] = args.target_kl
+    names = SB3_NAMES if args.target_kl is None else SB3_NAMES + KL_SB3_NAMES
     normalize = not args.no_normalize_advantage
 
     # what the rollout's last step leaves for the next rollout's row 0
@@ -115,8 +122,8 @@ def main():
         epochs += args.epochs
         buf.check_errors()
         # the only transfers of the iteration: the statistics block and two numbers for the log
-        st = dict(zip(SB3_NAMES, stats.tolist()))
-        n_updates += int(st["train/n_updates"])
+        st = dict(zip(names, stats.tolist()))
+        n_updates += int(st["train/n_updates"] if args.target_kl is None else st["train/epochs"])
         st["train/n_updates"] = n_updates
         print(json.dumps({"iteration": it, **st, "mean_reward": buf.rewards.mean().item(),
                           "episode_starts": int(buf.episode_starts.sum().item())}), flush=True)
@@ -131,7 +138,7 @@ def main():
             runs.append((time.perf_counter() - t0) * 1e3)
             epochs += args.epochs
         print(json.dumps({"time": "one update, host wall time, ms", "rows": E * K, "batch_size": args.batch_size, "epochs": args.epochs,
-                          "clip_range_vf": args.clip_range_vf, "normalize_advantage": normalize, "median_ms": sorted(runs)[len(runs) // 2],
+                          "clip_range_vf": args.clip_range_vf, "target_kl": args.target_kl, "normalize_advantage": normalize, "median_ms": sorted(runs)[len(runs) // 2],
                           "runs_ms": [round(x, 3) for x in runs]}), flush=True)
     for h in (trainer, opt, grad, pol, buf, env):
         h.close()

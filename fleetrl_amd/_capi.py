@@ -214,6 +214,15 @@ class FleetPpoGradVclipArgs(C.Structure):  # fleet_ppo_grad_vclip_dev: the same 
     _fields_ = [("struct_bytes", C.c_int32), ("clip_range_vf", C.c_float), ("old_values", C.c_void_p), ("base", FleetPpoGradArgs)]
 
 
+class FleetPpoGate(C.Structure):  # two device words and the threshold of early stopping on approx_kl
+    _fields_ = [("skip", C.c_void_p), ("decided", C.c_void_p), ("threshold", C.c_double)]
+
+
+class FleetPpoGradGatedArgs(C.Structure):  # fleet_ppo_grad_gated_dev: either of the above behind a gate (clip_range_vf 0: no value clip)
+    _fields_ = [("struct_bytes", C.c_int32), ("clip_range_vf", C.c_float), ("old_values", C.c_void_p), ("gate", FleetPpoGate),
+                ("base", FleetPpoGradArgs)]
+
+
 # ---- Adam and clip_grad_norm_ (include/fleet_hip.h "Adam and clip_grad_norm_ on the device", fleet_adam_*) ------------------------------
 ADAM_MAX_EXTRA = 2
 ADAM_STATE_EXPORT, ADAM_STATE_LOAD = 0, 1
@@ -253,6 +262,10 @@ class FleetTrainInfo(C.Structure):
 
 class FleetTrainPpoVclipArgs(C.Structure):  # fleet_train_ppo_vclip_dev: the same with SB3's clip_range_vf
     _fields_ = [("struct_bytes", C.c_int32), ("clip_range_vf", C.c_float), ("base", FleetTrainPpoArgs)]
+
+
+class FleetTrainPpoKlArgs(C.Structure):  # fleet_train_ppo_kl_dev: the same with SB3's target_kl (clip_range_vf 0: no value clip)
+    _fields_ = [("struct_bytes", C.c_int32), ("clip_range_vf", C.c_float), ("target_kl", C.c_double), ("base", FleetTrainPpoArgs)]
 
 
 # ---- TD3 / DDPG's whole update (include/fleet_hip.h "TD3 / DDPG's whole update on the device", fleet_offpolicy_*) ------------------------
@@ -639,6 +652,13 @@ def load_library():
     lib.fleet_train_describe_vclip.argtypes = [vp, C.POINTER(C.c_uint64)]
     for name in VCLIP_SYMBOLS:
         getattr(lib, name).restype = C.c_int
+    # early stopping on approx_kl (fleet_ppo.hip, fleet_adam.hip, fleet_train.hip)
+    lib.fleet_ppo_grad_gated_dev.argtypes = [vp, C.POINTER(FleetPpoGradGatedArgs), C.POINTER(vp), C.c_int]
+    lib.fleet_adam_step_gated_dev.argtypes = [vp, C.POINTER(FleetAdamStepArgs), C.POINTER(vp), C.POINTER(vp), C.c_int, vp]
+    lib.fleet_adam_settle_dev.argtypes = [vp, C.c_int64, vp]
+    lib.fleet_train_ppo_kl_dev.argtypes = [vp, C.POINTER(FleetTrainPpoKlArgs), C.POINTER(vp), C.POINTER(vp), C.c_int]
+    for name in KL_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
     # TD3 / DDPG's whole update (fleet_offpolicy.hip)
     lib.fleet_offpolicy_create.argtypes = [vp, vp, vp, vp, vp, C.POINTER(FleetOffpolicyParams), C.POINTER(vp)]
     lib.fleet_offpolicy_destroy.argtypes = [vp]
@@ -733,6 +753,10 @@ TRAIN_SYMBOLS = ("fleet_train_create", "fleet_train_destroy", "fleet_train_last_
 # value-function clipping on the fleet_ppo and fleet_train handles: the header declares these `extern`, behind the two families' own
 # (closed) entry lists, so they stand in a list of their own here as well
 VCLIP_SYMBOLS = ("fleet_ppo_grad_vclip_dev", "fleet_train_ppo_vclip_dev", "fleet_train_describe_vclip")
+
+# early stopping on approx_kl (target_kl) on the fleet_ppo, fleet_adam and fleet_train handles: the header declares these `FLEET_API int`,
+# behind the three families' own (closed) entry lists
+KL_SYMBOLS = ("fleet_ppo_grad_gated_dev", "fleet_adam_step_gated_dev", "fleet_adam_settle_dev", "fleet_train_ppo_kl_dev")
 
 OFFPOLICY_SYMBOLS = ("fleet_offpolicy_create", "fleet_offpolicy_destroy", "fleet_offpolicy_last_error", "fleet_offpolicy_describe",
                      "fleet_offpolicy_td3_dev", "fleet_offpolicy_polyak_dev")

@@ -96,10 +96,26 @@ class DeviceAdam(_ImageBorrower):
         self._ptrs = ((C.c_void_p * n)(*pa), (C.c_void_p * n)(*ga), pa, ga)
         return self._ptrs[0], self._ptrs[1]
 
-    def step(self, lr=None, norm_out=None):
+    def step_gated_dev(self, args: "_capi.FleetAdamStepArgs", param_ptrs, grad_ptrs, count: int, skip_ptr: int):
+        """The same through fleet_adam_step_gated_dev: `skip_ptr` is the address of a device u32."""
+        args.struct_bytes = C.sizeof(_capi.FleetAdamStepArgs)
+        self._check(self.lib.fleet_adam_step_gated_dev(self.h, C.byref(args), param_ptrs, grad_ptrs, int(count), skip_ptr))
+
+    def settle(self, base_step: int, steps_taken):
+        """The step count becomes `base_step` + the one-element int32 / uint32 device tensor `steps_taken`, read behind everything
+        enqueued so far (fleet_adam_settle_dev): enqueue-only; whoever asks for the count next waits for it."""
+        import torch
+
+        self.use_torch_stream()
+        words = (torch.int32, torch.uint32) if hasattr(torch, "uint32") else (torch.int32,)
+        self._check(self.lib.fleet_adam_settle_dev(self.h, int(base_step), self._tensor(steps_taken, (1,), words).data_ptr()))
+
+    def step(self, lr=None, norm_out=None, skip=None):
         """One optimiser step on torch's current stream, no host synchronisation: the parameters and the image move together.
         lr: this step's learning rate (default: the constructor's; SB3 sets it every iteration).  norm_out f32 [1] on the device:
-        the gradients' norm before clipping, what `clip_grad_norm_` returns."""
+        the gradients' norm before clipping, what `clip_grad_norm_` returns.  skip: None, or a one-element int32 / uint32 device
+        tensor written by something enqueued earlier (fleet_adam_step_gated_dev): nonzero when the launches run means that they
+        return at once and write nothing; the step count on the host advances all the same (`settle` says afterwards how many ran)."""
         import torch
 
         self.use_torch_stream()
@@ -109,7 +125,11 @@ class DeviceAdam(_ImageBorrower):
         if norm_out is not None:
             a.norm_out = self._tensor(norm_out, (1,), (torch.float32,)).data_ptr()
         pa, ga = self._pointers()
-        self.step_dev(a, pa, ga, len(self.params))
+        if skip is None:
+            self.step_dev(a, pa, ga, len(self.params))
+        else:
+            words = (torch.int32, torch.uint32) if hasattr(torch, "uint32") else (torch.int32,)
+            self.step_gated_dev(a, pa, ga, len(self.params), self._tensor(skip, (1,), words).data_ptr())
 
     def export_image(self, out_tensors=None) -> list:
         """The WHOLE weight image (every net of it) in torch's layout, into `out_tensors` (ordered and shaped as for the image's

@@ -15,11 +15,19 @@
 //              or 1024 elements of a bias (p' to b[j] of the image too) or of an extra.  Only real elements are visited: the image's
 //              zero padding stays what create made it.
 // No atomics, no ordering between workgroups: the launch boundary between the two is the only one.  float32 but for the sum above.
+// The gated instances (kGated; fleet_adam_step_gated_dev launches them, the others keep their text and their code): every workgroup
+// of both launches reads the word `skip` once at its top, one uniform load and a scalar branch, and returns when it is set, having
+// written nothing -- no parameter, no moment, no image word, no part[], no norm_out.  An EARLIER launch wrote that word: no launch
+// reads a word that a workgroup of the same launch may write.
+// The step count lives on the host.  After a gated train call only the device knows how many steps ran: fleet_adam_settle_dev copies
+// that word to a pinned host word behind everything enqueued and records an event; every entry that reads or writes the count waits
+// for that event first (adam_settle, below).  No kernel writes host memory.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "fleet_adam.h"
@@ -35,7 +43,15 @@ struct NormArgs {
   float* part;
 };
 
-__global__ __launch_bounds__(kAdamThreads) void adam_norm(NormArgs a) {
+struct NormArgsGated : NormArgs {
+  const uint32_t* skip;  // nonzero: the launch returns at once
+};
+
+template <bool kGated>
+__global__ __launch_bounds__(kAdamThreads) void adam_norm(std::conditional_t<kGated, NormArgsGated, NormArgs> a) {
+  if constexpr (kGated) {
+    if (__builtin_amdgcn_readfirstlane(*a.skip)) return;
+  }
   __shared__ float ws[kAdamThreads / 64];
   const AdamChunk ch = a.chunks[blockIdx.x];
   const int t = __builtin_amdgcn_readfirstlane(ch.tensor);
@@ -87,7 +103,15 @@ __device__ __forceinline__ float adam_element(float g, float* __restrict__ m, fl
   return fmaf(m1 / den, k.nstep, p);
 }
 
-__global__ __launch_bounds__(kAdamThreads) void adam_step(StepArgs a) {
+struct StepArgsGated : StepArgs {
+  const uint32_t* skip;  // nonzero: the launch returns at once
+};
+
+template <bool kGated>
+__global__ __launch_bounds__(kAdamThreads) void adam_step(std::conditional_t<kGated, StepArgsGated, StepArgs> a) {
+  if constexpr (kGated) {
+    if (__builtin_amdgcn_readfirstlane(*a.skip)) return;
+  }
   __shared__ float tile[kAdamTile][kAdamTile + 1];
   AdamCoef k{1.0f, a.omb1, a.omb2, a.b2, a.nstep, a.bs, a.eps, a.clip};
   if (a.n_chunks > 0) {
@@ -210,6 +234,11 @@ struct FleetAdam : FleetMlpUser {  // img: either family's; block: the state, th
   const AdamChunk* d_chunks = nullptr;
   const AdamItem* d_items = nullptr;
   float* d_part = nullptr;
+  // a settlement (fleet_adam_settle_dev): once `settle_event` has completed, step = settle_base + *settle_word
+  uint32_t* settle_word = nullptr;  // pinned host memory, owned
+  hipEvent_t settle_event = nullptr;
+  int64_t settle_base = 0;
+  bool settle_pending = false;
   ~FleetAdam();  // (out of line, below: the one place that takes the tables down)
 };
 FleetAdam::~FleetAdam() = default;
@@ -220,6 +249,25 @@ namespace {
 void check_count(std::string* why, int count, const FleetAdam* h) {
   if (count != (int)h->tensors.size())
     *why = "expected " + std::to_string(h->tensors.size()) + " tensors (W, b per layer, net after net, then the extras), got " + std::to_string(count);
+}
+
+// Settling on use: what every entry that reads or writes h->step calls first.  A pending settlement is waited for (in a training
+// loop a whole rollout lies between two updates: the event completed long ago) and fixes the count.
+int adam_settle(FleetAdam* h) {
+  if (!h->settle_pending) return FLEET_OK;
+  FLEET_HANDLE_TRY(h, hipEventSynchronize(h->settle_event));
+  h->step = h->settle_base + (int64_t)*h->settle_word;
+  h->settle_pending = false;
+  return FLEET_OK;
+}
+
+// a stream that is being captured cannot take the settlement's event wait: the gated entries refuse it
+int adam_refuse_capture(const char* entry, FleetAdam* h) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  FLEET_HANDLE_TRY(h, hipStreamIsCapturing(h->img->stream, &st));
+  if (st == hipStreamCaptureStatusNone) return FLEET_OK;
+  h->error = std::string(entry) + ": the image handle's stream is capturing a graph; a step count that the device decides cannot be captured";
+  return FLEET_ERR_STATE;
 }
 
 int adam_create(const char* entry, const char* noun, void* image, size_t record_bytes, const FleetAdamParams* p, fleet_adam_handle* out) {
@@ -308,7 +356,9 @@ int fleet_adam_create_qtarget(fleet_qtarget_handle nets, const FleetAdamParams* 
 
 int fleet_adam_destroy(fleet_adam_handle h) {
   if (!h) return FLEET_OK;
-  mlp_user_close(h);
+  mlp_user_close(h);  // (waits for the device: a settlement's copy has landed)
+  if (h->settle_event) (void)hipEventDestroy(h->settle_event);
+  if (h->settle_word) (void)hipHostFree(h->settle_word);
   delete h;
   return FLEET_OK;
 }
@@ -317,6 +367,7 @@ const char* fleet_adam_last_error(fleet_adam_handle h) { return h ? h->error.c_s
 
 int fleet_adam_describe(fleet_adam_handle h, FleetAdamParams* out, FleetAdamInfo* info) {
   if (!h || !out || !info) return FLEET_ERR_INVALID;
+  if (const int rc = adam_settle(h); rc != FLEET_OK) return rc;
   *out = h->p;
   info->state_bytes = 2 * h->n_elements * sizeof(float);
   info->n_elements = h->n_elements;
@@ -328,16 +379,23 @@ int fleet_adam_describe(fleet_adam_handle h, FleetAdamParams* out, FleetAdamInfo
   return FLEET_OK;
 }
 
-int fleet_adam_step_dev(fleet_adam_handle h, const FleetAdamStepArgs* x, float* const* params, float* const* grads, int count) {
-  std::string why = check_step_args(x, params, grads, count);
+}  // extern "C"
+
+namespace {
+
+// both step entries; skip null: the ungated instances
+int adam_step_launch(const char* entry, fleet_adam_handle h, std::string why, const FleetAdamStepArgs* x, float* const* params,
+                     float* const* grads, int count, const uint32_t* skip) {
   if (h && why.empty()) check_count(&why, count, h);
-  if (const int rc = handle_enter("fleet_adam_step_dev", why, h, g_adam_error); rc != FLEET_OK) return rc;
+  if (const int rc = handle_enter(entry, why, h, g_adam_error); rc != FLEET_OK) return rc;
+  if (const int rc = adam_settle(h); rc != FLEET_OK) return rc;
   FleetMlpHandle* img = h->img;
   const bool clip = x->max_grad_norm > 0.0, norm = clip || x->norm_out;
   // the scalars in double, as torch's Python forms them, then rounded
   const double t = (double)(h->step + 1);
   const double bc1 = 1.0 - std::pow(x->beta1, t), bc2 = 1.0 - std::pow(x->beta2, t);
-  StepArgs s{};
+  StepArgsGated s{};
+  s.skip = skip;
   for (int i = 0; i < count; ++i) s.p[i] = params[i], s.g[i] = grads[i];
   s.tensors = h->d_tensors, s.items = h->d_items, s.part = h->d_part;
   s.block = reinterpret_cast<float*>(h->block), s.image = reinterpret_cast<float*>(img->block), s.norm_out = x->norm_out;
@@ -346,15 +404,49 @@ int fleet_adam_step_dev(fleet_adam_handle h, const FleetAdamStepArgs* x, float* 
   s.nstep = (float)-(x->lr / bc1), s.bs = (float)std::sqrt(bc2), s.eps = (float)x->eps;
   FLEET_HANDLE_TRY(h, hipSetDevice(img->device));
   if (norm) {
-    NormArgs n{};
+    NormArgsGated n{};
+    n.skip = skip;
     for (int i = 0; i < count; ++i) n.g[i] = grads[i];
     n.tensors = h->d_tensors, n.chunks = h->d_chunks, n.part = h->d_part;
-    hipLaunchKernelGGL(adam_norm, dim3((unsigned)h->n_chunks), dim3(kAdamThreads), 0, img->stream, n);
+    if (skip) hipLaunchKernelGGL(adam_norm<true>, dim3((unsigned)h->n_chunks), dim3(kAdamThreads), 0, img->stream, n);
+    else hipLaunchKernelGGL(adam_norm<false>, dim3((unsigned)h->n_chunks), dim3(kAdamThreads), 0, img->stream, static_cast<const NormArgs&>(n));
     FLEET_HANDLE_TRY(h, hipGetLastError());
   }
-  hipLaunchKernelGGL(adam_step, dim3((unsigned)h->n_items), dim3(kAdamThreads), 0, img->stream, s);
+  if (skip) hipLaunchKernelGGL(adam_step<true>, dim3((unsigned)h->n_items), dim3(kAdamThreads), 0, img->stream, s);
+  else hipLaunchKernelGGL(adam_step<false>, dim3((unsigned)h->n_items), dim3(kAdamThreads), 0, img->stream, static_cast<const StepArgs&>(s));
   FLEET_HANDLE_TRY(h, hipGetLastError());
   h->step += 1;
+  return FLEET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fleet_adam_step_dev(fleet_adam_handle h, const FleetAdamStepArgs* x, float* const* params, float* const* grads, int count) {
+  return adam_step_launch("fleet_adam_step_dev", h, check_step_args(x, params, grads, count), x, params, grads, count, nullptr);
+}
+
+int fleet_adam_step_gated_dev(fleet_adam_handle h, const FleetAdamStepArgs* x, float* const* params, float* const* grads, int count,
+                              const uint32_t* skip) {
+  std::string why = check_step_args(x, params, grads, count);
+  if (why.empty() && !skip) why = "null skip";
+  return adam_step_launch("fleet_adam_step_gated_dev", h, why, x, params, grads, count, skip);
+}
+
+int fleet_adam_settle_dev(fleet_adam_handle h, int64_t base_step, const uint32_t* steps_taken) {
+  std::string why;
+  if (base_step < 0) why = "base_step must be >= 0, got " + std::to_string(base_step);
+  else if (!steps_taken) why = "null steps_taken";
+  if (const int rc = handle_enter("fleet_adam_settle_dev", why, h, g_adam_error); rc != FLEET_OK) return rc;
+  if (const int rc = adam_settle(h); rc != FLEET_OK) return rc;
+  FLEET_HANDLE_TRY(h, hipSetDevice(h->img->device));
+  if (const int rc = adam_refuse_capture("fleet_adam_settle_dev", h); rc != FLEET_OK) return rc;
+  if (!h->settle_word) FLEET_HANDLE_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->settle_word), sizeof(uint32_t), hipHostMallocDefault));
+  if (!h->settle_event) FLEET_HANDLE_TRY(h, hipEventCreateWithFlags(&h->settle_event, hipEventDisableTiming));
+  FLEET_HANDLE_TRY(h, hipMemcpyAsync(h->settle_word, steps_taken, sizeof(uint32_t), hipMemcpyDeviceToHost, h->img->stream));
+  FLEET_HANDLE_TRY(h, hipEventRecord(h->settle_event, h->img->stream));
+  h->settle_base = base_step, h->settle_pending = true;
   return FLEET_OK;
 }
 
@@ -362,6 +454,7 @@ int fleet_adam_state_dev(fleet_adam_handle h, int mode, float* const* exp_avg, f
   std::string why = check_state_args(mode, exp_avg, exp_avg_sq, count, step);
   if (h && why.empty()) check_count(&why, count, h);
   if (const int rc = handle_enter("fleet_adam_state_dev", why, h, g_adam_error); rc != FLEET_OK) return rc;
+  if (const int rc = adam_settle(h); rc != FLEET_OK) return rc;
   FleetMlpHandle* img = h->img;
   FLEET_HANDLE_TRY(h, hipSetDevice(img->device));
   float* base = reinterpret_cast<float*>(h->block);

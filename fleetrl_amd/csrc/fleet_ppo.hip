@@ -19,6 +19,11 @@
 //   per head and layer: act [max_batch][out64] (hidden layers), delta [max_batch][out64] (every layer);
 //   ls [max_batch][A64]: the rows' log_std terms;  part [ceil(max_batch / 16)][8]: the tiles' partial sums.
 // Rows at and past B are never read or written.  No atomics, no ordering between workgroups: launch boundaries only.  float32.
+// The gated instances (kGated; fleet_ppo_grad_gated_dev launches them, the others keep their text and their code): every workgroup
+// of both launches reads the word `skip` once at its top, one uniform load and a scalar branch, and returns when it is set; the
+// statistics workgroup of ppo_weights then writes `decided` = ((double)approx_kl > threshold) behind the statistics.  The property
+// that makes this safe without atomics: NO launch reads a word that a workgroup of the SAME launch may write -- `skip` was written
+// by an earlier launch, and `decided` is read by later launches only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -56,9 +61,18 @@ struct RowsArgsVclip : RowsArgs {
   float cv;            // clip_range_vf
 };
 
+struct RowsArgsGated : RowsArgsVclip {  // (old_v and cv are not read without the value clip)
+  const uint32_t* skip;  // nonzero: the launch returns at once
+};
+
 // kVclip: the instance with the value clip (a second instance, so that the first one stays the code it was)
-template <bool kVclip>
-__global__ __launch_bounds__(kPolicyThreads) void ppo_rows(std::conditional_t<kVclip, RowsArgsVclip, RowsArgs> t) {
+// kGated: the instances that return at their top when *skip is set (further instances, for the same reason)
+template <bool kVclip, bool kGated = false>
+__global__ __launch_bounds__(kPolicyThreads) void ppo_rows(
+    std::conditional_t<kGated, RowsArgsGated, std::conditional_t<kVclip, RowsArgsVclip, RowsArgs>> t) {
+  if constexpr (kGated) {
+    if (__builtin_amdgcn_readfirstlane(*t.skip)) return;
+  }
   extern __shared__ float lds[];  // two buffers [16][T], the staged input [16][kPolicyChunk], the rows' scalars [4][16]
   const PolicyDesc* __restrict__ d = t.desc;
   const int head = blockIdx.y;
@@ -188,7 +202,17 @@ struct WeightArgs {
   float invB, vf_coef, ent_coef;
 };
 
-__global__ __launch_bounds__(256) void ppo_weights(WeightArgs a) {
+struct WeightArgsGated : WeightArgs {
+  const uint32_t* skip;  // nonzero: the launch returns at once
+  uint32_t* decided;     // written by the statistics workgroup: (double)approx_kl > thr
+  double thr;
+};
+
+template <bool kGated>
+__global__ __launch_bounds__(256) void ppo_weights(std::conditional_t<kGated, WeightArgsGated, WeightArgs> a) {
+  if constexpr (kGated) {
+    if (__builtin_amdgcn_readfirstlane(*a.skip)) return;
+  }
   __shared__ float ds[kGradRows][kGradTile], xs[kGradRows][kGradTile];
   const int bid = blockIdx.x, B = a.B;
   if (bid < a.tile_blocks) {
@@ -213,6 +237,10 @@ __global__ __launch_bounds__(256) void ppo_weights(WeightArgs a) {
     a.stats[0] = pl, a.stats[1] = vl, a.stats[2] = el;
     a.stats[3] = (pl + a.ent_coef * el) + a.vf_coef * vl;
     a.stats[4] = k.value() * a.invB, a.stats[5] = c.value() * a.invB, a.stats[6] = 0.0f, a.stats[7] = 0.0f;
+    if constexpr (kGated) {
+      const float kl = k.value() * a.invB;                 // (stats[4]'s bits)
+      *a.decided = (double)kl > a.thr ? 1u : 0u;  // (a NaN does not stop the update, as in SB3)
+    }
   }
 }
 
@@ -246,6 +274,21 @@ std::string check_grad_args(const FleetPpoGradArgs* args, float* const* grads, i
   if (count < 1 || count > 2 * kMaxEntries + 1) return "count must be the policy's tensors plus one (log_std), got " + std::to_string(count);
   for (int i = 0; i < count; ++i)
     if (!grads[i]) return "gradient tensor " + std::to_string(i) + " is null";
+  return "";
+}
+
+// what fleet_ppo_grad_gated_dev refuses on top of fleet_ppo_grad_dev
+std::string check_gated_args(const FleetPpoGradGatedArgs* args, float* const* grads, int count) {
+  if (!args) return "null FleetPpoGradGatedArgs";
+  if (args->struct_bytes != (int32_t)sizeof(FleetPpoGradGatedArgs)) return "FleetPpoGradGatedArgs.struct_bytes does not match this library";
+  std::string why = check_grad_args(&args->base, grads, count);
+  if (!why.empty()) return why;
+  if (!(std::isfinite(args->clip_range_vf) && args->clip_range_vf >= 0.0f)) return "clip_range_vf must be finite and >= 0 (0: no value clip)";
+  if (args->clip_range_vf > 0.0f && !args->old_values) return "null old_values";
+  if (!args->gate.skip) return "null gate.skip";
+  if (!args->gate.decided) return "null gate.decided";
+  if (args->gate.skip == args->gate.decided) return "gate.skip and gate.decided are the same word";
+  if (std::isnan(args->gate.threshold)) return "gate.threshold is NaN";
   return "";
 }
 
@@ -294,7 +337,8 @@ int fleet_ppo_create(fleet_policy_handle policy, const FleetPpoParams* p, fleet_
   h->s.floats = off;
   h->lds_bytes = ((size_t)2 * kPolicyRows * h->T + (size_t)kPolicyRows * kPolicyChunk + 64) * sizeof(float);
   constexpr int kMaxLds = (2 * kPolicyRows * FLEET_POLICY_MAX_WIDTH + kPolicyRows * kPolicyChunk + 64) * (int)sizeof(float);
-  const int rc = mlp_user_open(h, pol, off * sizeof(float), "scratch", {{reinterpret_cast<const void*>(&ppo_rows<false>), kMaxLds}, {reinterpret_cast<const void*>(&ppo_rows<true>), kMaxLds}}, "rows", &why);
+  const int rc = mlp_user_open(h, pol, off * sizeof(float), "scratch", {{reinterpret_cast<const void*>(&ppo_rows<false>), kMaxLds}, {reinterpret_cast<const void*>(&ppo_rows<true>), kMaxLds},
+                                 {reinterpret_cast<const void*>(&ppo_rows<false, true>), kMaxLds}, {reinterpret_cast<const void*>(&ppo_rows<true, true>), kMaxLds}}, "rows", &why);
   if (rc != FLEET_OK) {
     fleet_ppo_destroy(h);
     return handle_refuse(g_ppo_error, "fleet_ppo_create", why, rc);
@@ -324,14 +368,15 @@ int fleet_ppo_describe(fleet_ppo_handle h, FleetPpoParams* out, uint64_t* scratc
 
 namespace {
 
-// the two launches of both entries; old_values null: no value clip
-int ppo_grad_launch(fleet_ppo_handle h, const FleetPpoGradArgs& x, const float* old_values, float clip_range_vf, float* const* grads, int count) {
+// the two launches of every entry; old_values null: no value clip; gate null: the ungated instances
+int ppo_grad_launch(fleet_ppo_handle h, const FleetPpoGradArgs& x, const float* old_values, float clip_range_vf, float* const* grads, int count,
+                    const FleetPpoGate* gate = nullptr) {
   FleetMlpHandle* pol = h->img;
   const PolicyHeadDesc* nets = pol->nets;
   const int B = x.B, n_tiles = (B + kPolicyRows - 1) / kPolicyRows;
   const float invB = 1.0f / (float)B;
   float* scratch = h->floats();
-  RowsArgsVclip t{};
+  RowsArgsGated t{};
   t.desc = reinterpret_cast<const PolicyDesc*>(pol->block);
   t.base = reinterpret_cast<const float*>(pol->block);
   t.obs = x.obs, t.actions = x.actions, t.old_lp = x.old_log_prob, t.adv = x.advantages, t.ret = x.returns, t.log_std = x.log_std;
@@ -339,7 +384,7 @@ int ppo_grad_launch(fleet_ppo_handle h, const FleetPpoGradArgs& x, const float* 
   t.scratch = scratch, t.s = h->s, t.B = B, t.T = h->T;
   t.clip = x.clip_range, t.vf_coef = x.vf_coef, t.invB = invB;
   t.old_v = old_values, t.cv = clip_range_vf;
-  WeightArgs g{};
+  WeightArgsGated g{};
   grad_fill_entries(g.e, &g.n_entries, &g.tile_blocks, nets, 0, 2, scratch, h->s.act, h->s.delta, x.obs, nets[0].layer[0].in, nullptr, 0, grads);
   const PolicyLayer& LA = nets[0].layer[nets[0].n_layers - 1];
   g.ls_blocks = (LA.out + 255) / 256, g.B = B;
@@ -348,10 +393,20 @@ int ppo_grad_launch(fleet_ppo_handle h, const FleetPpoGradArgs& x, const float* 
   g.A = LA.out, g.M = LA.out64, g.n_tiles = n_tiles;
   g.invB = invB, g.vf_coef = x.vf_coef, g.ent_coef = x.ent_coef;
   FLEET_HANDLE_TRY(h, hipSetDevice(pol->device));
-  if (old_values) hipLaunchKernelGGL(ppo_rows<true>, dim3((unsigned)n_tiles, 2), dim3(kPolicyThreads), h->lds_bytes, pol->stream, t);
-  else hipLaunchKernelGGL(ppo_rows<false>, dim3((unsigned)n_tiles, 2), dim3(kPolicyThreads), h->lds_bytes, pol->stream, static_cast<const RowsArgs&>(t));
+  const dim3 rows_grid((unsigned)n_tiles, 2), weights_grid((unsigned)(g.tile_blocks + g.ls_blocks + 1));
+  if (gate) {
+    t.skip = g.skip = gate->skip, g.decided = gate->decided, g.thr = gate->threshold;
+    if (old_values) hipLaunchKernelGGL((ppo_rows<true, true>), rows_grid, dim3(kPolicyThreads), h->lds_bytes, pol->stream, t);
+    else hipLaunchKernelGGL((ppo_rows<false, true>), rows_grid, dim3(kPolicyThreads), h->lds_bytes, pol->stream, t);
+    FLEET_HANDLE_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(ppo_weights<true>, weights_grid, dim3(256), 0, pol->stream, g);
+    FLEET_HANDLE_TRY(h, hipGetLastError());
+    return FLEET_OK;
+  }
+  if (old_values) hipLaunchKernelGGL(ppo_rows<true>, rows_grid, dim3(kPolicyThreads), h->lds_bytes, pol->stream, static_cast<const RowsArgsVclip&>(t));
+  else hipLaunchKernelGGL(ppo_rows<false>, rows_grid, dim3(kPolicyThreads), h->lds_bytes, pol->stream, static_cast<const RowsArgs&>(t));
   FLEET_HANDLE_TRY(h, hipGetLastError());
-  hipLaunchKernelGGL(ppo_weights, dim3((unsigned)(g.tile_blocks + g.ls_blocks + 1)), dim3(256), 0, pol->stream, g);
+  hipLaunchKernelGGL(ppo_weights<false>, weights_grid, dim3(256), 0, pol->stream, static_cast<const WeightArgs&>(g));
   FLEET_HANDLE_TRY(h, hipGetLastError());
   return FLEET_OK;
 }
@@ -372,6 +427,14 @@ int fleet_ppo_grad_vclip_dev(fleet_ppo_handle h, const FleetPpoGradVclipArgs* ar
   if (h && why.empty()) grad_check_sizes(&why, count, h->img->n_tensors + 1, "W, b per layer, then log_std", args->base.B, h->p.max_batch);
   if (const int rc = handle_enter("fleet_ppo_grad_vclip_dev", why, h, g_ppo_error); rc != FLEET_OK) return rc;
   return ppo_grad_launch(h, args->base, args->old_values, args->clip_range_vf, grads, count);
+}
+
+int fleet_ppo_grad_gated_dev(fleet_ppo_handle h, const FleetPpoGradGatedArgs* args, float* const* grads, int count) {
+  std::string why = check_gated_args(args, grads, count);
+  if (h && why.empty()) grad_check_sizes(&why, count, h->img->n_tensors + 1, "W, b per layer, then log_std", args->base.B, h->p.max_batch);
+  if (const int rc = handle_enter("fleet_ppo_grad_gated_dev", why, h, g_ppo_error); rc != FLEET_OK) return rc;
+  const bool vclip = args->clip_range_vf > 0.0f;
+  return ppo_grad_launch(h, args->base, vclip ? args->old_values : nullptr, args->clip_range_vf, grads, count, &args->gate);
 }
 
 }  // extern "C"

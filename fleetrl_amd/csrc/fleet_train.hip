@@ -15,6 +15,20 @@
 //              explained_variance over the whole buffer and mean(exp(log_std)) with the same ordered sum, the statistics block.
 //   train_indices    the shuffle on its own: one position per thread.
 // No atomics, no ordering between workgroups: launch boundaries only.
+// Early stopping on approx_kl (target_kl; fleet_train_ppo_kl_dev) runs GATED instances of train_minibatch and train_finish, of
+// fleet_ppo.hip's ppo_rows and ppo_weights and of fleet_adam.hip's adam_norm and adam_step; the ungated ones keep their text and their
+// code.  The handle's block carries a control record (TrainCtl) behind everything else.  The property that makes the device's own
+// decision safe without atomics: NO launch reads a word that a workgroup of the SAME launch may write.
+//   `decided`  written by the statistics workgroup of minibatch i's ppo_weights: (double)approx_kl > 1.5 * target_kl.  Read by LATER
+//              launches only: minibatch i's two Adam launches (set: they return at their top, nothing is written) and every
+//              workgroup of minibatch i + 1's train_minibatch (set: no gather).
+//   `stopped`  read and written by thread 0 of workgroup 0 of train_minibatch alone: clear -> it folds minibatch i's statistics into
+//              the running sums and bumps the counters (minibatches run; optimiser steps taken, only when `decided` is clear; epochs
+//              entered; the last epoch's approx_kl sum), then stopped = decided.  Read by LATER launches: ppo_rows and ppo_weights
+//              return at their top when it is set.
+//   The call's first train_minibatch clears the record and does not read `decided`.  train_finish<true> (one workgroup) folds the
+//   last minibatch that ran unless `stopped` says it was folded already, divides by the DEVICE's count and writes slots [9..13].
+// After a stop every remaining launch of the call loads one word and returns.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -89,6 +103,32 @@ struct MiniArgsVclip : MiniArgs {
   float* o_val;      // their staging array, [max_batch]
 };
 
+// the control record of a gated call (the head comment states who reads and who writes which word)
+struct TrainCtl {
+  uint32_t decided, stopped;
+  uint32_t minibatches, steps, epochs;  // run; optimiser steps taken; epochs entered
+  uint32_t epoch_n;                     // minibatches of the last epoch entered
+  double epoch_kl;                      // their approx_kl, the ordered float64 sum
+};
+static_assert(sizeof(TrainCtl) <= 256, "the record's place in the block");
+
+struct MiniArgsGated : MiniArgsVclip {  // (val and o_val are not read without the value clip; fold is not read)
+  TrainCtl* ctl;
+  int first;             // the call's first launch: clears the record and the sums
+  int prev_epoch_start;  // the previous minibatch was the first of its epoch
+};
+
+// minibatch statistics `st` (the gradient launches' f32[8]) into the running sums and the counters
+__device__ inline void ctl_fold(TrainCtl* c, double* acc, const float* st, uint32_t decided, int epoch_start) {
+#pragma unroll
+  for (int k = 0; k < 5; ++k) acc[k] = acc[k] + (double)st[k < 3 ? k : k + 1];
+  c->minibatches = c->minibatches + 1u;
+  if (!decided) c->steps = c->steps + 1u;
+  if (epoch_start) c->epochs = c->epochs + 1u, c->epoch_n = 0u, c->epoch_kl = 0.0;
+  c->epoch_n = c->epoch_n + 1u;
+  c->epoch_kl = c->epoch_kl + (double)st[4];
+}
+
 // the buffer row t * E + e of position start + b of the epoch: the shuffle gives i = e * K + t
 __device__ inline uint32_t buffer_row(const MiniArgs& a, uint32_t b) {
   const uint32_t i = train_perm(a.key, a.start + b);
@@ -114,12 +154,30 @@ __device__ inline void move_row(const float* src, float* dst, size_t from, size_
 }
 
 // kVclip: the instance that stages the old values too (a second instance, so that the first one stays the code it was)
-template <bool kVclip>
-__global__ __launch_bounds__(kTrainThreads) void train_minibatch(std::conditional_t<kVclip, MiniArgsVclip, MiniArgs> a) {
+// kGated: the instances of a call that may stop itself (further instances, for the same reason)
+template <bool kVclip, bool kGated = false>
+__global__ __launch_bounds__(kTrainThreads) void train_minibatch(
+    std::conditional_t<kGated, MiniArgsGated, std::conditional_t<kVclip, MiniArgsVclip, MiniArgs>> a) {
   __shared__ double red[kTrainThreads];
   __shared__ uint32_t rows[kTrainCache];
   const uint32_t tid = threadIdx.x, B = a.B;
-  if (blockIdx.x == 0 && tid == 0) {
+  if constexpr (kGated) {
+    // (the previous minibatch's ppo_weights wrote `decided`; the first launch clears it and does not read it)
+    const uint32_t decided = a.first ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane(a.ctl->decided);
+    if (blockIdx.x == 0 && tid == 0) {
+      TrainCtl* c = a.ctl;
+      if (a.first) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) a.acc[k] = 0.0;
+        c->decided = 0u, c->stopped = 0u, c->minibatches = 0u, c->steps = 0u, c->epochs = 0u, c->epoch_n = 0u, c->epoch_kl = 0.0;
+      } else {
+        const uint32_t stopped = c->stopped;
+        if (!stopped) ctl_fold(c, a.acc, a.prev_stats, decided, a.prev_epoch_start);
+        c->stopped = stopped | decided;
+      }
+    }
+    if (decided) return;  // (uniform over the launch)
+  } else if (blockIdx.x == 0 && tid == 0) {
     // [0] policy_loss [1] value_loss [2] entropy_loss [3] approx_kl [4] clip_fraction <- stats[0], [1], [2], [4], [5]
     if (!a.fold) {
 #pragma unroll
@@ -186,7 +244,13 @@ struct FinishArgs {
   double count;             // minibatches of the call
 };
 
-__global__ __launch_bounds__(kTrainThreads) void train_finish(FinishArgs a) {
+struct FinishArgsGated : FinishArgs {  // (count is not read: the device counted)
+  TrainCtl* ctl;
+  int last_epoch_start;  // the call's last scheduled minibatch is the first of its epoch
+};
+
+template <bool kGated>
+__global__ __launch_bounds__(kTrainThreads) void train_finish(std::conditional_t<kGated, FinishArgsGated, FinishArgs> a) {
   __shared__ double red[kTrainThreads];
   const uint32_t tid = threadIdx.x, n = a.n;
   const float* __restrict__ ret = a.ret;
@@ -211,7 +275,27 @@ __global__ __launch_bounds__(kTrainThreads) void train_finish(FinishArgs a) {
   double se = 0.0;
   for (int j = (int)tid; j < a.A; j += kTrainThreads) se = se + exp((double)a.log_std[j]);
   const double sdev = tree_total(se, red) / (double)a.A;
-  if (tid == 0) {
+  if constexpr (kGated) {
+    if (tid == 0) {
+      TrainCtl* c = a.ctl;
+      const uint32_t decided = c->decided;
+      // stopped clear: the last scheduled minibatch ran and no train_minibatch came behind it to fold it
+      if (!c->stopped) ctl_fold(c, a.acc, a.last_stats, decided, a.last_epoch_start);
+      const double count = (double)c->minibatches;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) a.out[k] = a.acc[k] / count;
+      a.out[5] = (double)a.last_stats[3];  // (the gradient launches after a stop wrote nothing: the last minibatch that ran)
+      a.out[6] = count;
+      a.out[7] = vy == 0.0 ? (double)NAN : 1.0 - vd / vy;
+      a.out[8] = sdev;
+      a.out[9] = (double)c->steps;
+      a.out[10] = (double)c->epochs;
+      a.out[11] = decided ? 1.0 : 0.0;
+      a.out[12] = (double)a.last_stats[4];
+      a.out[13] = c->epoch_kl / (double)c->epoch_n;
+      for (int k = 14; k < FLEET_TRAIN_STATS; ++k) a.out[k] = 0.0;
+    }
+  } else if (tid == 0) {
 #pragma unroll
     for (int k = 0; k < 5; ++k) a.out[k] = (a.acc[k] + (double)a.last_stats[k < 3 ? k : k + 1]) / a.count;
     a.out[5] = (double)a.last_stats[3];
@@ -287,7 +371,8 @@ struct FleetTrain : FleetMlpUser {  // img: the policy's; block: the staging arr
   FleetRolloutArrays arr{};
   int E = 0, K = 0, D = 0, A = 0, max_batch = 0, n_tensors = 0;
   uint64_t stage[kStageArrays] = {}, stats_at = 0, acc_at = 0, staging_bytes = 0;
-  uint64_t val_at = 0;  // the staged old values, behind everything else
+  uint64_t val_at = 0;  // the staged old values, behind everything that was there before them
+  uint64_t ctl_at = 0;  // a gated call's control record (TrainCtl), behind those
 
   float* staged(int which) const { return reinterpret_cast<float*>(block + stage[which]); }
 };
@@ -339,6 +424,7 @@ int fleet_train_create(fleet_rollout_handle buffer, struct FleetPpo* grad, struc
   h->stats_at = off, off += 256;
   h->acc_at = off, off += 256;
   h->val_at = off, off += (mb * 4 + 255) / 256 * 256;
+  h->ctl_at = off, off += 256;
   int rc = mlp_user_open(h, img, off, "staging block", {}, "", &why);
   if (rc == FLEET_OK && (hipMemset(h->block, 0, off) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
     (void)hipGetLastError();
@@ -387,9 +473,10 @@ int fleet_train_indices_dev(fleet_train_handle h, int32_t n, uint64_t seed, uint
 
 namespace {
 
-// both updates; clip_range_vf 0: no value clip (`why`: what the entry's own checks found)
+// every update; clip_range_vf 0: no value clip; target_kl 0: no early stop, the ungated launches (`why`: what the entry's own checks
+// found)
 int train_ppo(const char* entry, fleet_train_handle h, std::string why, const FleetTrainPpoArgs* x, float clip_range_vf, float* const* params,
-              float* const* grads, int count) {
+              float* const* grads, int count, double target_kl = 0.0) {
   const uint32_t n = h ? (uint32_t)h->E * (uint32_t)h->K : 0;
   const uint32_t bs = h && why.empty() ? ((uint32_t)x->batch_size < n ? (uint32_t)x->batch_size : n) : 0;
   if (h && why.empty()) {
@@ -402,15 +489,38 @@ int train_ppo(const char* entry, fleet_train_handle h, std::string why, const Fl
       why = "the rollout buffer launches on another stream than the policy: fleet_rollout_set_stream it to the policy's first";
   }
   if (const int rc = handle_enter(entry, why, h, g_train_error); rc != FLEET_OK) return rc;
-  const bool vclip = clip_range_vf > 0.0f;
+  const bool vclip = clip_range_vf > 0.0f, gated = target_kl > 0.0;
   FleetMlpHandle* pol = h->img;
+  TrainCtl* ctl = reinterpret_cast<TrainCtl*>(h->block + h->ctl_at);
+  int64_t base_step = 0;
+  if (gated) {
+    FLEET_HANDLE_TRY(h, hipSetDevice(pol->device));
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    FLEET_HANDLE_TRY(h, hipStreamIsCapturing(pol->stream, &capture));
+    if (capture != hipStreamCaptureStatusNone) {
+      h->error = std::string(entry) + ": the policy's stream is capturing a graph; an update that may stop itself settles the optimiser's "
+                 "step count through an event and cannot be captured";
+      return FLEET_ERR_STATE;
+    }
+    FleetAdamParams ap{};
+    FleetAdamInfo ai{};
+    if (const int rc = fleet_adam_describe(h->adam, &ap, &ai); rc != FLEET_OK) {  // (settles what an earlier call left pending)
+      h->error = std::string(entry) + ": " + fleet_adam_last_error(h->adam);
+      return rc;
+    }
+    base_step = ai.step;
+  }
   float* gstats = reinterpret_cast<float*>(h->block + h->stats_at);
   double* acc = reinterpret_cast<double*>(h->block + h->acc_at);
-  MiniArgsVclip m{};
+  MiniArgsGated m{};
+  m.ctl = ctl;
   m.obs = h->arr.obs, m.act = h->arr.actions, m.logp = h->arr.log_probs, m.adv = h->arr.advantages, m.ret = h->arr.returns;
   m.o_obs = h->staged(kStageObs), m.o_act = h->staged(kStageAct), m.o_logp = h->staged(kStageLogp), m.o_adv = h->staged(kStageAdv);
   m.o_advn = h->staged(kStageAdvn), m.o_ret = h->staged(kStageRet);
   m.val = h->arr.values, m.o_val = vclip ? reinterpret_cast<float*>(h->block + h->val_at) : nullptr;
+  FleetPpoGradGatedArgs gg{};  // (the gated call's; its base is filled from `g` per minibatch)
+  gg.struct_bytes = (int32_t)sizeof gg, gg.clip_range_vf = vclip ? clip_range_vf : 0.0f, gg.old_values = m.o_val;
+  gg.gate.skip = &ctl->stopped, gg.gate.decided = &ctl->decided, gg.gate.threshold = 1.5 * target_kl;
   m.prev_stats = gstats, m.acc = acc;
   m.E = (uint32_t)h->E, m.K = (uint32_t)h->K;
   // (the buffer's arrays and the staging arrays start at multiples of 256 bytes: a row of 4k floats starts at a multiple of 16)
@@ -428,6 +538,7 @@ int train_ppo(const char* entry, fleet_train_handle h, std::string why, const Fl
   s.lr = x->lr, s.beta1 = x->beta1, s.beta2 = x->beta2, s.eps = x->eps, s.max_grad_norm = x->max_grad_norm;
   FLEET_HANDLE_TRY(h, hipSetDevice(pol->device));
   uint64_t done = 0;
+  bool prev_epoch_start = false;
   for (int e = 0; e < x->n_epochs; ++e) {
     m.key = perm_key(n, x->seed, x->first_epoch + (uint64_t)e);
     for (uint32_t start = 0; start < n; start += bs, ++done) {
@@ -435,11 +546,26 @@ int train_ppo(const char* entry, fleet_train_handle h, std::string why, const Fl
       m.start = start, m.B = B, m.fold = done != 0;
       const unsigned tiles = (B + kTrainRows - 1) / kTrainRows;
       const dim3 grid(tiles < (unsigned)kTrainMaxBlocks ? tiles : (unsigned)kTrainMaxBlocks);
-      if (vclip) hipLaunchKernelGGL(train_minibatch<true>, grid, dim3(kTrainThreads), 0, pol->stream, m);
+      m.first = done == 0, m.prev_epoch_start = prev_epoch_start, prev_epoch_start = start == 0;
+      if (gated && vclip) hipLaunchKernelGGL((train_minibatch<true, true>), grid, dim3(kTrainThreads), 0, pol->stream, m);
+      else if (gated) hipLaunchKernelGGL((train_minibatch<false, true>), grid, dim3(kTrainThreads), 0, pol->stream, m);
+      else if (vclip) hipLaunchKernelGGL(train_minibatch<true>, grid, dim3(kTrainThreads), 0, pol->stream, static_cast<const MiniArgsVclip&>(m));
       else hipLaunchKernelGGL(train_minibatch<false>, grid, dim3(kTrainThreads), 0, pol->stream, static_cast<const MiniArgs&>(m));
       FLEET_HANDLE_TRY(h, hipGetLastError());
       g.B = (int32_t)B;
       g.advantages = m.normalise && B > 1 ? m.o_advn : m.o_adv;
+      if (gated) {
+        gg.base = g;
+        if (const int rc = fleet_ppo_grad_gated_dev(h->grad, &gg, grads, count); rc != FLEET_OK) {
+          h->error = std::string(entry) + ": " + fleet_ppo_last_error(h->grad);
+          return rc;
+        }
+        if (const int rc = fleet_adam_step_gated_dev(h->adam, &s, params, grads, count, &ctl->decided); rc != FLEET_OK) {
+          h->error = std::string(entry) + ": " + fleet_adam_last_error(h->adam);
+          return rc;
+        }
+        continue;
+      }
       if (const int rc = vclip ? fleet_ppo_grad_vclip_dev(h->grad, &gv, grads, count) : fleet_ppo_grad_dev(h->grad, &g, grads, count);
           rc != FLEET_OK) {
         h->error = std::string(entry) + ": " + fleet_ppo_last_error(h->grad);
@@ -451,11 +577,20 @@ int train_ppo(const char* entry, fleet_train_handle h, std::string why, const Fl
       }
     }
   }
-  FinishArgs f{};
+  FinishArgsGated f{};
+  f.ctl = ctl, f.last_epoch_start = prev_epoch_start;
   f.ret = h->arr.returns, f.val = h->arr.values, f.log_std = params[count - 1], f.last_stats = gstats, f.acc = acc, f.out = x->stats;
   f.n = n, f.A = h->A, f.count = (double)done;
-  hipLaunchKernelGGL(train_finish, dim3(1), dim3(kTrainThreads), 0, pol->stream, f);
+  if (gated) hipLaunchKernelGGL(train_finish<true>, dim3(1), dim3(kTrainThreads), 0, pol->stream, f);
+  else hipLaunchKernelGGL(train_finish<false>, dim3(1), dim3(kTrainThreads), 0, pol->stream, static_cast<const FinishArgs&>(f));
   FLEET_HANDLE_TRY(h, hipGetLastError());
+  if (gated) {
+    // the steps that ran are the device's to say: base_step + ctl->steps, once everything enqueued here has run
+    if (const int rc = fleet_adam_settle_dev(h->adam, base_step, &ctl->steps); rc != FLEET_OK) {
+      h->error = std::string(entry) + ": " + fleet_adam_last_error(h->adam);
+      return rc;
+    }
+  }
   return FLEET_OK;
 }
 
@@ -474,6 +609,17 @@ int fleet_train_ppo_vclip_dev(fleet_train_handle h, const FleetTrainPpoVclipArgs
   else why = check_ppo_args(&a->base, params, grads, count);
   if (why.empty() && !(std::isfinite(a->clip_range_vf) && a->clip_range_vf > 0.0f)) why = "clip_range_vf must be finite and > 0";
   return train_ppo("fleet_train_ppo_vclip_dev", h, why, a ? &a->base : nullptr, a ? a->clip_range_vf : 0.0f, params, grads, count);
+}
+
+int fleet_train_ppo_kl_dev(fleet_train_handle h, const FleetTrainPpoKlArgs* a, float* const* params, float* const* grads, int count) {
+  std::string why;
+  if (!a) why = "null FleetTrainPpoKlArgs";
+  else if (a->struct_bytes != (int32_t)sizeof(FleetTrainPpoKlArgs)) why = "FleetTrainPpoKlArgs.struct_bytes does not match this library";
+  else why = check_ppo_args(&a->base, params, grads, count);
+  if (why.empty() && !(std::isfinite(a->target_kl) && a->target_kl > 0.0)) why = "target_kl must be finite and > 0";
+  if (why.empty() && !(std::isfinite(a->clip_range_vf) && a->clip_range_vf >= 0.0f)) why = "clip_range_vf must be finite and >= 0 (0: no value clip)";
+  return train_ppo("fleet_train_ppo_kl_dev", h, why, a ? &a->base : nullptr, a ? a->clip_range_vf : 0.0f, params, grads, count,
+                   a ? a->target_kl : 0.0);
 }
 
 int fleet_train_describe_vclip(fleet_train_handle h, uint64_t* old_values_offset) {

@@ -58,8 +58,13 @@ class DevicePPOGrad(_ImageBorrower):
         args.struct_bytes, args.base.struct_bytes = C.sizeof(_capi.FleetPpoGradVclipArgs), C.sizeof(_capi.FleetPpoGradArgs)
         self._check(self.lib.fleet_ppo_grad_vclip_dev(self.h, C.byref(args), grad_ptrs, int(count)))
 
+    def grad_gated_dev(self, args: "_capi.FleetPpoGradGatedArgs", grad_ptrs, count: int):
+        """The same through fleet_ppo_grad_gated_dev: a FleetPpoGradGatedArgs, whose `base` is a FleetPpoGradArgs."""
+        args.struct_bytes, args.base.struct_bytes = C.sizeof(_capi.FleetPpoGradGatedArgs), C.sizeof(_capi.FleetPpoGradArgs)
+        self._check(self.lib.fleet_ppo_grad_gated_dev(self.h, C.byref(args), grad_ptrs, int(count)))
+
     def grad(self, batch, log_std, clip_range: float, vf_coef: float, ent_coef: float, *, into, values_out=None, log_prob_out=None,
-             advantages=None, stats_out=None, clip_range_vf=None):
+             advantages=None, stats_out=None, clip_range_vf=None, gate=None):
         """The loss of one minibatch and its gradients, two launches on torch's current stream, no host synchronisation.
         batch: what `DeviceRolloutBuffer.get` yields (observations f32 [B, obs_dim], actions f32 [B, act_dim], old_log_prob,
         advantages, returns f32 [B]); `advantages` replaces the batch's (the normalised ones).  log_std: the torch parameter f32
@@ -67,10 +72,18 @@ class DevicePPOGrad(_ImageBorrower):
         `.grad` is allocated on the first call and OVERWRITTEN by every call (there is nothing to zero).  values_out, log_prob_out
         f32 [B]: the critic's (unclipped) values and the new log-probabilities.  clip_range_vf: None, or SB3's positive float: the value
         loss is then taken on `old_values + clamp(values - old_values, -clip_range_vf, clip_range_vf)` with the batch's `old_values`
-        f32 [B].  Returns stats f32 [8] on the device: `STATS`, then two zeros."""
+        f32 [B].  gate: None, or (skip, decided, threshold) for early stopping on approx_kl (`fleet_ppo_grad_gated_dev`): two
+        DIFFERENT one-element int32 / uint32 device tensors and a float.  When `skip` (written by something enqueued earlier) is
+        nonzero, both launches return at once and write nothing; otherwise they run as without a gate and also write
+        `decided = float64(stats[4]) > threshold`.  Returns stats f32 [8] on the device: `STATS`, then two zeros."""
         import torch
 
         cv = check_clip_range_vf(clip_range_vf)
+        if gate is not None:
+            skip, decided, threshold = gate
+            threshold = float(threshold)
+            if threshold != threshold:
+                raise ValueError("gate: the threshold is NaN")
         self.use_torch_stream()
         f32 = (torch.float32,)
         obs = batch.observations
@@ -92,6 +105,17 @@ class DevicePPOGrad(_ImageBorrower):
                 keep.append(self._tensor(t, (B,), f32))
                 setattr(a, name, keep[-1].data_ptr())
         arr = self._grad_pointers("grad", into, self._shapes, "the actor's then the critic's, then log_std")
+        if gate is not None:
+            words = (torch.int32, torch.uint32) if hasattr(torch, "uint32") else (torch.int32,)
+            g = _capi.FleetPpoGradGatedArgs()
+            g.base = a  # (a copy: `a` is complete by now)
+            keep += [self._tensor(skip, (1,), words), self._tensor(decided, (1,), words)]
+            g.gate.skip, g.gate.decided, g.gate.threshold = keep[-2].data_ptr(), keep[-1].data_ptr(), threshold
+            if cv is not None:
+                keep.append(self._tensor(batch.old_values, (B,), f32))
+                g.old_values, g.clip_range_vf = keep[-1].data_ptr(), cv
+            self.grad_gated_dev(g, arr, len(self._shapes))
+            return stats_out
         if v is None:
             self.grad_dev(a, arr, len(self._shapes))
         else:

@@ -30,6 +30,8 @@ extern "C" {
 #endif
 
 #define FLEET_ABI_VERSION 11
+/* marks an exported entry (the entries added with PPO's early stopping are declared with it) */
+#define FLEET_API __attribute__((visibility("default")))
 
 /* status codes */
 #define FLEET_OK 0
@@ -1466,6 +1468,8 @@ int fleet_offpolicy_polyak_dev(fleet_offpolicy_handle h, double tau);
  *   [0] policy_loss [1] value_loss [2] entropy_loss [3] approx_kl [4] clip_fraction: the float64 mean over ALL minibatches of all epochs
  *       of the gradient launches' float32 statistic, in the order they ran: acc = 0.0; acc = acc + (double)stat; acc / (double)count
  *       -- what SB3 logs as train/policy_gradient_loss, train/value_loss, train/entropy_loss, train/approx_kl, train/clip_fraction
+ *       ([3] averages over ALL epochs; SB3 clears its approx_kl list at the start of every epoch, so what it logs as train/approx_kl
+ *       is the LAST epoch's mean: slot [13] of fleet_train_ppo_kl_dev, below, carries that one)
  *   [5] loss: the LAST minibatch's (train/loss)        [6] count: the number of minibatches
  *   [7] explained_variance = 1 - vd / vy over the whole buffer, y = (double)returns, d = y - (double)values, time-major order
  *       (x[t * E + e]), float64 with the ordered sum S over the n values: my = S(y) / n;  md = S(d) / n;
@@ -1544,6 +1548,50 @@ extern int fleet_train_ppo_vclip_dev(fleet_train_handle h, const FleetTrainPpoVc
 /* *old_values_offset: the bytes from FleetTrainInfo.staging to the staged old values f32[max_batch] (the LAST value-clipped
  * minibatch's rows; tests).  FLEET_ERR_INVALID for a null handle or output. */
 extern int fleet_train_describe_vclip(fleet_train_handle h, uint64_t* old_values_offset);
+/* -- the update with early stopping on approx_kl (target_kl; DESIGN.md "PPO's early stopping on the device") --
+ * (an entry added under FLEET_ABI_VERSION 11 on the existing handle: everything above is as it was)  SB3 2.3.2's PPO.train() with
+ * target_kl set, still ONE enqueue-only call and still five launches per scheduled minibatch.  thr = 1.5 * target_kl, formed once in
+ * double on the host.  Per minibatch, in the order fleet_train_ppo_dev runs them: the minibatch launch, the two gradient launches (they
+ * write the minibatch's statistics), then:  if (double)approx_kl > thr -- approx_kl the float32 stats[4] of the gradient launches; a NaN
+ * does NOT stop, as in SB3 -- the update STOPS: this minibatch's optimiser step is not taken and no later launch of the call does any
+ * work; otherwise the two Adam launches run.  The arithmetic of every minibatch that runs is fleet_train_ppo_dev's (clip_range_vf 0) or
+ * fleet_train_ppo_vclip_dev's, bit for bit; a target_kl that never triggers gives their weights, moments, step count and stats [0..8].
+ * The stopping minibatch's statistics DO count in the means (SB3 appends them before its break).
+ * One difference from SB3: after a stop the gradient tensors (`.grad`) hold the STOPPING minibatch's gradients -- the gradient launches
+ * had run when the decision fell; they were never applied.  SB3 does not call backward() for that minibatch.
+ * The device decides, with launch boundaries only and no atomics: gated instances of the six kernels (the ungated ones are the code
+ * they were) and a control record in the handle's block, behind the staged old values (every earlier offset stays).  NO launch reads
+ * a word that a workgroup of the SAME launch may write:
+ *   decided  written by the statistics workgroup of a minibatch's second gradient launch: (double)approx_kl > thr.  Read only by
+ *            LATER launches: that minibatch's two Adam launches (set: they return at their top and write nothing -- no parameter, no
+ *            moment, no image word, no norm) and every workgroup of the NEXT minibatch launch (set: no gather).
+ *   stopped  read and written by thread 0 of workgroup 0 of the minibatch launch alone: when it is clear, the previous minibatch's
+ *            statistics go into the running float64 sums, as in fleet_train_ppo_dev, and the device's counters are bumped (minibatches
+ *            run; optimiser steps taken: only when decided is clear; epochs entered; the last epoch's approx_kl sum); then stopped =
+ *            decided.  Read by LATER launches: both gradient launches return at their top when it is set.
+ *   The call's first launch clears the record.  The closing launch folds the last minibatch that ran, unless that was done, and divides
+ *   by the DEVICE's count.  After a stop every remaining launch of the call reads one word (a uniform load, a scalar branch) and returns.
+ * The optimiser's step count.  The host's scheduled t = (count before the call) + 1 + k is right for every step that runs, since nothing
+ * runs after a skip: the bias corrections stay host-formed in double.  The count AFTER the call is the device's to say: the call ends
+ * with fleet_adam_settle_dev (the optimiser's section), a 4-byte copy to pinned host memory and an event.  The call is therefore
+ * enqueue-only but NOT capturable into a graph: FLEET_ERR_STATE, nothing launched, when the policy's stream is capturing.
+ * The statistics block keeps its 16 doubles; this entry defines:
+ *   [0..4] the means over the minibatches that RAN, the stopping one included, in the order they ran (the same ordered float64 sum)
+ *   [5] loss of the last minibatch that ran     [6] minibatches that ran     [7], [8] as above ([8]: after the last step TAKEN)
+ *   [9] optimiser steps taken     [10] epochs entered (what SB3 adds to _n_updates)     [11] 1.0 if the update stopped early, else 0.0
+ *   [12] approx_kl of the last minibatch that ran: the value that was compared
+ *   [13] the mean of approx_kl over the minibatches of the LAST epoch entered (acc = 0.0; acc = acc + (double)stat in order; acc / their
+ *        number): what SB3 logs as train/approx_kl          [14], [15] 0
+ * FLEET_ERR_INVALID for a null or wrongly sized FleetTrainPpoKlArgs, whatever fleet_train_ppo_dev refuses of `base` (in its words), a
+ * target_kl that is not finite and > 0, a clip_range_vf that is negative or not finite. */
+typedef struct FleetTrainPpoKlArgs {
+  int32_t struct_bytes;          /* sizeof(FleetTrainPpoKlArgs) */
+  float clip_range_vf;           /* 0: no value clipping; otherwise cv of fleet_train_ppo_vclip_dev: finite, > 0 */
+  double target_kl;              /* finite, > 0 */
+  FleetTrainPpoArgs base;        /* everything fleet_train_ppo_dev takes; base.struct_bytes = sizeof(FleetTrainPpoArgs) */
+} FleetTrainPpoKlArgs;
+FLEET_API int fleet_train_ppo_kl_dev(fleet_train_handle h, const FleetTrainPpoKlArgs* a, float* const* params, float* const* grads,
+                                     int count);
 
 /* ---- Adam and clip_grad_norm_ on the device (fleet_adam.hip; DESIGN.md "The optimiser step on the device") -------------------------
  * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
@@ -1635,6 +1683,24 @@ int fleet_adam_state_dev(fleet_adam_handle h, int mode, float* const* exp_avg, f
  * layer, net after net: the inverse re-lay of *_load_dev in one launch on the image handle's stream.  What a test reads a step's
  * result from, and the only way to read a policy's image back.  FLEET_ERR_INVALID for a null array or pointer, a wrong count. */
 int fleet_adam_export_image_dev(fleet_adam_handle h, float* const* tensors, int count);
+/* -- a step the device may skip, and a step count settled after the fact (DESIGN.md "PPO's early stopping on the device") --
+ * (entries added under FLEET_ABI_VERSION 11 on the existing handle: the entries above are as they were)
+ * fleet_adam_step_gated_dev is fleet_adam_step_dev plus a device word, skip u32[1], read when the launches run: nonzero means that both
+ * launches return at their top -- a gated instance of each kernel, one uniform load and a scalar branch; the ungated ones are the code
+ * they were -- and write NOTHING: no parameter, no moment, no image word, no partial sum, no norm_out.  An EARLIER launch must have
+ * written the word.  With the word clear the step is fleet_adam_step_dev's, bit for bit.  The host's step count advances by one either
+ * way, as scheduled: a caller that lets the device skip steps says afterwards how many ran, with fleet_adam_settle_dev.
+ * FLEET_ERR_INVALID for whatever fleet_adam_step_dev refuses (in its words) and a null skip.
+ * fleet_adam_settle_dev(h, base_step, steps_taken): the step count becomes base_step + *steps_taken, steps_taken a device u32[1] read
+ * BEHIND everything enqueued on the image handle's stream so far: the entry enqueues a 4-byte copy into pinned host memory that the
+ * handle owns and records an event; it does not wait, and no kernel writes host memory.  Settling on use: every entry that reads or
+ * writes the step count -- fleet_adam_step_dev, fleet_adam_step_gated_dev, fleet_adam_state_dev, fleet_adam_describe, this one --
+ * first waits for a pending settlement's event and fixes the count.  In a training loop a whole rollout lies between two updates and
+ * the wait costs nothing; a caller that asks for the count right away gets the right one at the price of that wait.  An event wait
+ * cannot be captured: FLEET_ERR_STATE when the stream is capturing a graph.  FLEET_ERR_INVALID for a negative base_step, a null word. */
+FLEET_API int fleet_adam_step_gated_dev(fleet_adam_handle h, const FleetAdamStepArgs* a, float* const* params, float* const* grads,
+                                        int count, const uint32_t* skip);
+FLEET_API int fleet_adam_settle_dev(fleet_adam_handle h, int64_t base_step, const uint32_t* steps_taken);
 
 /* ---- TD3 / DDPG minibatch gradients on the device (fleet_td3.hip; DESIGN.md "TD3's minibatch gradients on the device") -------------
  * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
@@ -1813,6 +1879,33 @@ typedef struct FleetPpoGradVclipArgs {
   FleetPpoGradArgs base;       /* everything fleet_ppo_grad_dev takes; base.struct_bytes = sizeof(FleetPpoGradArgs) */
 } FleetPpoGradVclipArgs;
 extern int fleet_ppo_grad_vclip_dev(fleet_ppo_handle h, const FleetPpoGradVclipArgs* args, float* const* grads, int count);
+
+/* -- the same behind a gate, for early stopping on approx_kl (target_kl; DESIGN.md "PPO's early stopping on the device") --
+ * (an entry added under FLEET_ABI_VERSION 11 on the existing handle: the entries above are as they were)
+ * fleet_ppo_grad_dev (clip_range_vf == 0) or fleet_ppo_grad_vclip_dev (clip_range_vf > 0, with old_values) behind two device words:
+ *   skip     u32[1], written by an EARLIER launch, read when the launches run: nonzero means that every workgroup of both launches
+ *            returns at its top (one uniform load, a scalar branch) and NOTHING is written: no gradient, no stats, no decided
+ *   decided  u32[1], written by the statistics workgroup behind stats:  decided = ((double)stats[4] > threshold) ? 1 : 0
+ *            (stats[4] = approx_kl, the float32 that was stored; a NaN gives 0).  No workgroup of these two launches reads it.
+ * With skip clear the gradients, stats, values and log_prob are the ungated entry's, bit for bit; the launches are gated instances of
+ * the same kernels (the ungated ones stay the code they were).  skip and decided must be two words: no launch reads a word that a
+ * workgroup of the same launch may write.
+ * FLEET_ERR_INVALID for a null or wrongly sized FleetPpoGradGatedArgs, whatever fleet_ppo_grad_dev refuses of `base` (in its words), a
+ * clip_range_vf that is negative or not finite, a null old_values with clip_range_vf > 0, a null gate.skip or gate.decided, the same
+ * word for both, a NaN gate.threshold; the arguments are looked at before the handle is. */
+typedef struct FleetPpoGate {
+  const uint32_t* skip;        /* device u32[1] */
+  uint32_t* decided;           /* device u32[1] */
+  double threshold;            /* not NaN; fleet_train_ppo_kl_dev passes 1.5 * target_kl */
+} FleetPpoGate;
+typedef struct FleetPpoGradGatedArgs {
+  int32_t struct_bytes;        /* sizeof(FleetPpoGradGatedArgs) */
+  float clip_range_vf;         /* 0: no value clipping; otherwise cv: finite, > 0 */
+  const float* old_values;     /* device f32[B]; read only when clip_range_vf > 0 */
+  FleetPpoGate gate;
+  FleetPpoGradArgs base;       /* everything fleet_ppo_grad_dev takes; base.struct_bytes = sizeof(FleetPpoGradArgs) */
+} FleetPpoGradGatedArgs;
+FLEET_API int fleet_ppo_grad_gated_dev(fleet_ppo_handle h, const FleetPpoGradGatedArgs* args, float* const* grads, int count);
 
 #ifdef __cplusplus
 }
