@@ -13,6 +13,7 @@
     from fleetrl_amd import DevicePPOTrain
     from fleetrl_amd import DeviceTD3Train
     from fleetrl_amd import DevicePPOCollect, DeviceTD3Collect
+    from fleetrl_amd import DeviceEvalCallback
     from fleetrl_amd import LogSummary, summarize_log, compare, evaluate_strategies
 """
 __version__ = "0.1.0"
@@ -75,6 +76,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import collect
 
         return getattr(collect, name)
+    if name == "DeviceEvalCallback":
+        from . import eval_callback
+
+        return eval_callback.DeviceEvalCallback
     if name in ("plan_linear_optimization", "run_linear_optimization"):
         from . import lp_benchmark
 

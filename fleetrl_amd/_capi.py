@@ -318,6 +318,26 @@ class FleetCollectInfo(C.Structure):
                 ("ring_return", C.c_void_p), ("ring_length", C.c_void_p), ("ring_count", C.c_void_p)]
 
 
+# ---- evaluation of the agent (include/fleet_hip.h "evaluation of the agent on the device", fleet_eval_*) -------------------------------
+EVAL_MAX_EPISODES, EVAL_STATS = 65536, 16
+
+
+class FleetEvalParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("max_episodes", C.c_int32)]
+
+
+class FleetEvalArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_eval_episodes", C.c_int32), ("n_steps", C.c_int32), ("reward_source", C.c_int32),
+                ("sync_from", C.c_void_p), ("reserved", C.c_uint64), ("num_timesteps", C.c_uint64), ("stats", C.c_void_p)]
+
+
+class FleetEvalInfo(C.Structure):
+    _fields_ = [("num_envs", C.c_int32), ("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("max_episodes", C.c_int32), ("has_norm", C.c_int32),
+                ("launches", C.c_int32), ("block_bytes", C.c_uint64), ("snapshot_floats", C.c_uint64)] + \
+               [(n, C.c_void_p) for n in ("obs", "raw_obs", "actions", "raw_reward", "reward", "done", "sums", "lengths", "counts", "ep_reward",
+                                          "ep_length", "listed", "best_mean_reward", "evaluations", "gate", "snapshot")]
+
+
 # ---- TD3 / DDPG minibatch gradients (include/fleet_hip.h "TD3 / DDPG minibatch gradients on the device", fleet_td3_*) -------------------
 class FleetTd3Params(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("max_batch", C.c_int32)]
@@ -680,6 +700,20 @@ def load_library():
     lib.fleet_collect_episodes_read.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64)]
     for name in COLLECT_SYMBOLS:
         getattr(lib, name).restype = C.c_char_p if name == "fleet_collect_last_error" else C.c_int
+    # evaluation of the agent (fleet_eval.hip)
+    lib.fleet_eval_create.argtypes = [vp, vp, vp, C.POINTER(FleetEvalParams), C.POINTER(vp)]
+    lib.fleet_eval_destroy.argtypes = [vp]
+    lib.fleet_eval_last_error.argtypes = [vp]
+    lib.fleet_eval_describe.argtypes = [vp, C.POINTER(FleetEvalInfo)]
+    lib.fleet_eval_sync_norm_dev.argtypes = [vp, vp]
+    lib.fleet_eval_run_dev.argtypes = [vp, C.POINTER(FleetEvalArgs)]
+    lib.fleet_eval_episodes_dev.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int]
+    lib.fleet_eval_clear_dev.argtypes = [vp]
+    lib.fleet_eval_best_load_dev.argtypes = [vp, vp]
+    lib.fleet_eval_best_export_dev.argtypes = [vp, C.POINTER(vp), C.c_int]
+    lib.fleet_eval_episodes_read.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64)]
+    for name in EVAL_SYMBOLS:
+        getattr(lib, name).restype = C.c_char_p if name == "fleet_eval_last_error" else C.c_int
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
                           ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS), ("ppo", PPO_SYMBOLS),
                           ("td3", TD3_SYMBOLS), ("adam", ADAM_SYMBOLS), ("train", TRAIN_SYMBOLS), ("offpolicy", OFFPOLICY_SYMBOLS)):
@@ -765,6 +799,10 @@ COLLECT_SYMBOLS = ("fleet_collect_create", "fleet_collect_destroy", "fleet_colle
                    "fleet_collect_reset_dev", "fleet_collect_ppo_dev", "fleet_collect_offpolicy_dev", "fleet_collect_episodes_dev",
                    "fleet_collect_finish_dev", "fleet_collect_episodes_read")
 
+EVAL_SYMBOLS = ("fleet_eval_create", "fleet_eval_destroy", "fleet_eval_last_error", "fleet_eval_describe", "fleet_eval_sync_norm_dev",
+                "fleet_eval_run_dev", "fleet_eval_episodes_dev", "fleet_eval_clear_dev", "fleet_eval_best_load_dev", "fleet_eval_best_export_dev",
+                "fleet_eval_episodes_read")
+
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",
     "fleet_synchronize", "fleet_stream_query", "fleet_log_capacity", "fleet_log_dropped", "fleet_log_read", "fleet_log_clear",
@@ -778,7 +816,7 @@ EXPORTED_SYMBOLS = (
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
     "fleet_set_direct_state_only", "fleet_direct_packet_counts", "fleet_step_has_state_only",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS + TRAIN_SYMBOLS + OFFPOLICY_SYMBOLS + COLLECT_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS + TRAIN_SYMBOLS + OFFPOLICY_SYMBOLS + COLLECT_SYMBOLS + EVAL_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

@@ -89,3 +89,5 @@ int mlp_load_host(FleetMlpHandle* h, const char* entry, const float* weights);
 // *_load_dev, *_polyak_dev, *_export_dev: one launch over `count` tensors in torch's layout (read; written by kMlpExport)
 constexpr int kMlpLoad = 0, kMlpPolyak = 1, kMlpExport = 2;
 int mlp_launch_relay(FleetMlpHandle* h, int mode, const char* entry, float* const* tensors, int count, float tau, float omt);
+// ... the same launch over a COPY of the image at `base` (h's layout, h's stream): the evaluation's snapshot (fleet_eval.hip)
+int mlp_launch_relay_at(FleetMlpHandle* h, float* base, int mode, const char* entry, float* const* tensors, int count, float tau, float omt);

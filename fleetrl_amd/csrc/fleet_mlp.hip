@@ -198,6 +198,10 @@ int mlp_load_host(FleetMlpHandle* h, const char* entry, const float* weights) {
 }
 
 int mlp_launch_relay(FleetMlpHandle* h, int mode, const char* entry, float* const* tensors, int count, float tau, float omt) {
+  return mlp_launch_relay_at(h, reinterpret_cast<float*>(h->block), mode, entry, tensors, count, tau, omt);
+}
+
+int mlp_launch_relay_at(FleetMlpHandle* h, float* base, int mode, const char* entry, float* const* tensors, int count, float tau, float omt) {
   if (!tensors || count != h->n_tensors) {
     h->error = std::string(entry) + ": expected " + std::to_string(h->n_tensors) + " tensors (W, b per layer), got " +
                (tensors ? std::to_string(count) : std::string("a null array"));
@@ -213,7 +217,7 @@ int mlp_launch_relay(FleetMlpHandle* h, int mode, const char* entry, float* cons
   }
   a.nets = reinterpret_cast<const PolicyHeadDesc*>(h->block + (reinterpret_cast<const char*>(h->nets) - static_cast<const char*>(h->record)));
   a.n_nets = h->n_nets;
-  a.base = reinterpret_cast<float*>(h->block);
+  a.base = base;
   a.tau = tau, a.omt = omt;
   FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
   const dim3 grid(64, count), block(256);

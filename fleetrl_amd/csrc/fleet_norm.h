@@ -17,6 +17,10 @@ float* fleet_norm_out_buffer(fleet_norm_handle n);
 hipError_t fleet_norm_enqueue_reset(fleet_norm_handle n, const float* raw_obs, float* obs, hipStream_t s);
 hipError_t fleet_norm_enqueue_step(fleet_norm_handle n, const float* raw_obs, const double* raw_reward, const uint8_t* done,
                                    const float* raw_terminal, float* obs, double* reward, float* terminal, hipStream_t s);
+// fleet_eval_sync_norm_dev (fleet_eval.hip): FLEET_OK, or FLEET_ERR_INVALID with the reason in *why, when src's statistics cannot go
+// into dst (a null handle, another D, another device); and the copy itself, one launch on dst's stream behind src's last launch
+int fleet_norm_check_sync(fleet_norm_handle dst, fleet_norm_handle src, std::string* why);
+hipError_t fleet_norm_enqueue_sync(fleet_norm_handle dst, fleet_norm_handle src);
 
 // ---- what a reader of the statistics needs (fleet_replay.hip: the sample-time normalisation of the replay buffer) -----------------
 // The arithmetic of norm_apply, shared instead of restated: obs' = (float)clip(((double)x - mean) / sd, +-clip_obs) and

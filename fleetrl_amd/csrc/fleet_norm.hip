@@ -161,6 +161,25 @@ __global__ __launch_bounds__(kThreads) void norm_derive(int D, double eps, const
   if (i == 0) ret_stat[2] = sqrt(ret_stat[1] + eps);
 }
 
+// another normaliser's running statistics into this one (fleet_eval_sync_norm_dev), and sd from them as norm_derive forms it
+__global__ __launch_bounds__(kThreads) void norm_sync(int D, double eps, const double* src_mean, const double* src_var,
+                                                      const double* src_ret, double* obs_mean, double* obs_var, double* obs_sd,
+                                                      double* ret_stat) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i < D) {
+    const double m = src_mean[i], v = src_var[i];
+    obs_mean[i] = m;
+    obs_var[i] = v;
+    obs_sd[i] = sqrt(v + eps);
+  }
+  if (i == 0) {
+    const double m = src_ret[0], v = src_ret[1];
+    ret_stat[0] = m;
+    ret_stat[1] = v;
+    ret_stat[2] = sqrt(v + eps);
+  }
+}
+
 struct ApplyArgs {
   const float* raw;
   float* out;
@@ -431,6 +450,37 @@ hipError_t fleet_norm_enqueue_step(fleet_norm_handle n, const float* raw_obs, co
   n->last_raw_obs = obs == raw_obs ? nullptr : raw_obs;
   n->have_reward = true;
   return launch_apply(n, a, s);
+}
+
+int fleet_norm_check_sync(fleet_norm_handle dst, fleet_norm_handle src, std::string* why) {
+  if (!dst || !src) *why = dst ? "null source normaliser" : "null destination normaliser";
+  else if (dst->D != src->D || dst->device != src->device)
+    *why = "the source normaliser has obs_dim " + std::to_string(src->D) + " on device " + std::to_string(src->device) + ", the destination " +
+           std::to_string(dst->D) + " on device " + std::to_string(dst->device);
+  else return FLEET_OK;
+  return FLEET_ERR_INVALID;
+}
+
+hipError_t fleet_norm_enqueue_sync(fleet_norm_handle dst, fleet_norm_handle src) {
+  const hipStream_t s = dst->stream;
+  if (dst->last_stream != s) {  // (as the step: dst's last call on another stream uses the same state)
+    const hipError_t e = hipStreamSynchronize(dst->last_stream);
+    if (e != hipSuccess) return e;
+  }
+  dst->last_stream = s;
+  if (dst->reader_pending) {
+    const hipError_t e = wait_reader(dst, s);
+    if (e != hipSuccess) return e;
+  }
+  FleetNormView v{};
+  hipError_t e = dst == src ? hipSuccess : fleet_norm_begin_read(src, s, &v);  // (s waits for src's last launch elsewhere)
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(norm_sync, dim3((dst->D + kThreads - 1) / kThreads), dim3(kThreads), 0, s, dst->D, dst->p.epsilon, src->obs_mean,
+                     src->obs_var, src->ret_stat, dst->obs_mean, dst->obs_var, dst->obs_sd, dst->ret_stat);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  dst->obs_count = src->obs_count;
+  dst->ret_count = src->ret_count;
+  return dst == src ? hipSuccess : fleet_norm_end_read(src, s);
 }
 
 extern "C" {

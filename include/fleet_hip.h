@@ -1020,6 +1020,130 @@ typedef struct FleetExploreArgs {
  * the bounds and accepts any), a negative env_id_offset, a normaliser of another width or device. */
 int fleet_explore_act_dev(fleet_policy_handle h, const float* obs, int E, fleet_norm_handle norm, const FleetExploreArgs* args);
 
+/* ---- evaluation of the agent on the device (fleet_eval.hip; DESIGN.md "Evaluating the agent on the device") -----------------------
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
+ * stable-baselines3 2.3.2's EvalCallback as ONE enqueue-only call: sync_envs_normalization, evaluate_policy for n_eval_episodes
+ * deterministic episodes, and "keep the best model" decided and carried out on the device.  The handle BORROWS the evaluation env
+ * (auto_reset = 1), an optional evaluation normaliser (NULL: none) and a policy, which must outlive it, and owns one block, zeroed at
+ * create: the observation buffer f32[E,D] and the raw-observation buffer f32[E,D] (one buffer without a normaliser), the actions
+ * f32[E,A], the raw and the normalised reward f64[E] each, done u8[E], the running sums f64[E], the running lengths i32[E] and the
+ * episode counts i32[E], the episode lists ep_reward f64[max_episodes] and ep_length i32[max_episodes], a u64 count of the episodes
+ * listed, best_mean_reward f64 (which starts at -inf), a u64 count of the evaluations run, a u32 gate, and the snapshot: room for the
+ * policy image's floats.
+ * fleet_eval_sync_norm_dev(dst, src), ONE launch on dst's stream: obs_rms {mean, var, count} and ret_rms {mean, var, count} of src
+ * into dst -- what sync_envs_normalization copies -- and what the steps derive from them, sd = sqrt(var + dst's epsilon), in the
+ * arithmetic fleet_norm_set_state leaves behind.  dst's returns and settings stay.  The counts are the host's (functions of the
+ * number of updates enqueued so far) and are copied there.  When src's last launch went to another stream, dst's stream is made to
+ * wait for it by an event; src's next update on another stream waits for the copy.  FLEET_ERR_INVALID for a null handle, another D
+ * or another device.
+ * fleet_eval_run_dev only enqueues, in this order:
+ *   1. with sync_from: the sync launch into the handle's normaliser
+ *   2. the reset: fleet_reset_dev with no mask into the raw buffer, fleet_norm_reset_dev from it into the observation buffer (not
+ *      without a normaliser), then one small launch that clears the sums, the lengths, the counts and the list's count
+ *   3. for t = 0 .. n_steps-1: fleet_policy_forward_dev on the observation buffer (norm NULL: it holds normalised observations; no
+ *      values), fleet_step_dev into the raw buffer, the raw reward and done (no terminal rows), fleet_norm_step_dev from them into the
+ *      observation buffer and the normalised reward (not without a normaliser), the bookkeeping launch below
+ *   4. the closing launch          5. the snapshot launch
+ * 4 n_steps + 5 launches with a normaliser, 3 n_steps + 4 without, one more with sync_from (an entry of another family counts as one).
+ * n_steps is the caller's: the device cannot end a host loop.  Outside real_time every episode of an env handle has episode_steps
+ * steps, so SB3's loop ends after exactly ceil(n_eval_episodes / E) * episode_steps steps; steps after every quota is met change
+ * nothing in the lists.
+ * The bookkeeping launch (eval_episodes: ONE workgroup of 1024 threads, chunks of 1024 envs in env order, a ballot and a popcount per
+ * wavefront, a prefix over the sixteen wavefront counts; no atomics) is evaluate_policy's inner loop.  Env i owes
+ * target_i = (n_eval_episodes + i) / E episodes (integer division).  With r the reward the stack hands SB3 -- the normaliser's float64
+ * output with a normaliser, (double)(float)raw reward without one:
+ *   sums[i] += r;  lengths[i] += 1
+ *   if counts[i] < target_i and done[i]:  list slot (listed + k) takes the episode;  counts[i] += 1;  sums[i] = 0;  lengths[i] = 0
+ * k: the env's rank among this step's envs that satisfy the predicate, ascending env id; then listed += c, their number.  A slot at
+ * or beyond max_episodes is not written (the run call cannot get there: the targets sum to n_eval_episodes <= max_episodes).
+ * reward_source 0: the episode is (sums[i], lengths[i]) as they stand before they are zeroed -- what evaluate_policy sums on an env
+ * without Monitor.  reward_source 1: the env is Monitor-wrapped (what make_vec_env gives), the episode is the env's
+ * FLEET_F_LAST_EP_RETURN and FLEET_F_LAST_EP_LEN (raw rewards; Monitor's round(.., 6) is not applied).
+ * The closing launch (eval_finish: one workgroup of 256 threads) writes stats f64[FLEET_EVAL_STATS]; with n = listed and S the
+ * ordered float64 sum fleet_train_ppo_dev's section states (256 lane sums over positions t, t + 256, ... ascending, then the halving
+ * tree s = 128 .. 1):
+ *   [0] mean_reward = S(ep_reward) / n        [1] std_reward = sqrt(S((x - mean_reward)^2) / n), the population std (np.std)
+ *   [2] mean_ep_length = S((double)ep_length) / n                [3] the lengths' std, the same way        [4] n
+ *   [5] best_mean_reward after this call      [6] 1.0 if mean_reward > best_mean_reward held (SB3's test: false for NaN), else 0.0
+ *   [7] (double)num_timesteps                 [8] evaluations run on this handle so far, this one included        [9..15] 0
+ * [0] .. [3] are NaN when n == 0.  The launch writes the gate ([6] as a u32) and, when it is set, best_mean_reward = mean_reward.
+ * The snapshot launch (eval_snapshot: a grid over the policy image's weights) copies them into the handle's snapshot iff the gate is
+ * set: a call that does not improve leaves the snapshot's bits alone.  The gate is read on the device; the host does not look.
+ * Everything refusable is refused before the first launch -- nothing is launched then -- in the words of the entry that would refuse.
+ * A result depends on the handles' state and the arguments and on nothing else: not on the stream, not on max_episodes.  Env,
+ * normaliser and policy must launch on ONE stream when a call is made; sync_from may launch elsewhere.  Calls are serialised by the
+ * caller.  Out of scope: stochastic evaluation, real_time envs, callback_on_new_best, success rates. */
+#define FLEET_EVAL_MAX_EPISODES 65536
+#define FLEET_EVAL_STATS 16
+typedef struct FleetEvalParams {
+  int32_t struct_bytes;          /* sizeof(FleetEvalParams) */
+  int32_t max_episodes;          /* 1..FLEET_EVAL_MAX_EPISODES: the lists' length, the largest n_eval_episodes */
+} FleetEvalParams;
+typedef struct FleetEvalArgs {
+  int32_t struct_bytes;          /* sizeof(FleetEvalArgs) */
+  int32_t n_eval_episodes;       /* 1..max_episodes */
+  int32_t n_steps;               /* >= 1: env steps to take */
+  int32_t reward_source;         /* 0: the sums of the step rewards; 1: the env's own episode records (Monitor) */
+  fleet_norm_handle sync_from;   /* or NULL: the training normaliser whose statistics the evaluation normaliser takes first */
+  uint64_t reserved;             /* 0 */
+  uint64_t num_timesteps;        /* passed through to stats[7] */
+  double* stats;                 /* device f64[FLEET_EVAL_STATS] */
+} FleetEvalArgs;
+typedef struct FleetEvalInfo {
+  int32_t num_envs, obs_dim, act_dim;
+  int32_t max_episodes;
+  int32_t has_norm;              /* 1: a normaliser was given */
+  int32_t launches;              /* launches the last fleet_eval_run_dev enqueued */
+  uint64_t block_bytes;
+  uint64_t snapshot_floats;      /* the policy image's size */
+  float* obs;                    /* device f32[E,D] */
+  float* raw_obs;                /* device f32[E,D]; obs itself without a normaliser */
+  float* actions;                /* device f32[E,A] */
+  double* raw_reward;            /* device f64[E] */
+  double* reward;                /* device f64[E] */
+  uint8_t* done;                 /* device u8[E] */
+  double* sums;                  /* device f64[E] */
+  int32_t* lengths;              /* device i32[E] */
+  int32_t* counts;               /* device i32[E] */
+  double* ep_reward;             /* device f64[max_episodes] */
+  int32_t* ep_length;            /* device i32[max_episodes] */
+  uint64_t* listed;              /* device u64 */
+  double* best_mean_reward;      /* device f64 */
+  uint64_t* evaluations;         /* device u64 */
+  uint32_t* gate;                /* device u32 */
+  float* snapshot;               /* device f32[snapshot_floats]: the image's layout; its record's bytes stay zero */
+} FleetEvalInfo;
+typedef struct FleetEval* fleet_eval_handle;
+
+/* Everything is refused BEFORE the device is touched: FLEET_ERR_INVALID (fleet_eval_last_error(NULL) says why, starting with the
+ * entry's name) for a null or wrongly sized FleetEvalParams, max_episodes outside 1..FLEET_EVAL_MAX_EPISODES, a null output, env or
+ * policy, a handle that is no policy, an env without auto_reset, E, D, A or the device of env, normaliser and policy disagreeing.
+ * FLEET_ERR_HIP with the byte count when the block cannot be allocated. */
+int fleet_eval_create(fleet_handle env, fleet_norm_handle norm, fleet_policy_handle policy, const FleetEvalParams* p, fleet_eval_handle* out);
+int fleet_eval_destroy(fleet_eval_handle h);
+const char* fleet_eval_last_error(fleet_eval_handle h);  /* h may be NULL: error of the last failed call without a handle */
+int fleet_eval_describe(fleet_eval_handle h, FleetEvalInfo* out);
+int fleet_eval_sync_norm_dev(fleet_norm_handle dst, fleet_norm_handle src);
+/* The arguments are looked at before the handle is: with h NULL the reason (or "null handle") goes to fleet_eval_last_error(NULL).
+ * FLEET_ERR_INVALID for a null or wrongly sized args struct, n_eval_episodes < 1, n_steps < 1, a reward_source outside {0, 1}, a
+ * reserved that is not 0, null stats, and -- these need the handle -- n_eval_episodes > max_episodes, handles that do not launch on
+ * one stream, sync_from without a normaliser on the handle, a sync_from of another D or device. */
+int fleet_eval_run_dev(fleet_eval_handle h, const FleetEvalArgs* a);
+/* The bookkeeping launch on the caller's device arrays done u8[E], reward f64[E] (taken as it is), and for reward_source 1 ep_return
+ * f64[E] and ep_len i32[E] (else they may be NULL), 1 <= E <= the handle's num_envs: the same kernel body behind another loader.  The
+ * clearing launch on its own. */
+int fleet_eval_episodes_dev(fleet_eval_handle h, const uint8_t* done, const double* reward, const double* ep_return, const int32_t* ep_len,
+                            int E, int n_eval_episodes, int reward_source);
+int fleet_eval_clear_dev(fleet_eval_handle h);
+/* The snapshot into a policy of identical layout (dst may be the evaluated policy; it must launch on the env's stream), one launch;
+ * and into `count` device tensors in torch's layout and order, the ones fleet_policy_load_dev reads, one launch.  FLEET_ERR_STATE
+ * before the first fleet_eval_run_dev. */
+int fleet_eval_best_load_dev(fleet_eval_handle h, fleet_policy_handle dst);
+int fleet_eval_best_export_dev(fleet_eval_handle h, float* const* tensors, int count);
+/* Synchronous: the lists and their count to HOST buffers ep_reward f64[max_episodes], ep_length i32[max_episodes], count u64 (any may
+ * be NULL). */
+int fleet_eval_episodes_read(fleet_eval_handle h, double* ep_reward, int32_t* ep_length, uint64_t* count);
+
 /* ---- correlated action noise on the device (fleet_noise.hip; DESIGN.md "Correlated action noise on the device") -------------------
  * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays)
  * A process that produces the eps rows f32[E, A] fleet_explore_act_dev reads with noise_mode GIVEN, one row per env and call, with
