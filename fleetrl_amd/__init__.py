@@ -7,6 +7,7 @@
     from fleetrl_amd import DevicePolicy, evaluate_policy
     from fleetrl_amd import DevicePinkNoise, DeviceOUNoise
     from fleetrl_amd import DeviceTD3Target
+    from fleetrl_amd import DeviceSACNetworks
     from fleetrl_amd import DevicePPOGrad
     from fleetrl_amd import DeviceTD3Grad
     from fleetrl_amd import DeviceAdam
@@ -52,6 +53,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import qtarget
 
         return qtarget.DeviceTD3Target
+    if name == "DeviceSACNetworks":
+        from . import sac
+
+        return sac.DeviceSACNetworks
     if name == "DevicePPOGrad":
         from . import ppo
 

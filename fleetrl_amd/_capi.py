@@ -198,6 +198,24 @@ class FleetQTargetArgs(C.Structure):
                 ("next_actions", C.c_void_p), ("q", C.c_void_p)]
 
 
+# ---- SAC's actor and soft targets (include/fleet_hip.h "SAC on the device", fleet_sac_*) ----------------------------------------------
+class FleetSacParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("obs_dim", C.c_int32), ("n_critics", C.c_int32), ("reserved", C.c_int32),
+                ("actor", FleetPolicyHead), ("critic", FleetPolicyHead * 2)]
+
+
+class FleetSacActArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("noise_mode", C.c_int32), ("deterministic", C.c_int32), ("env_id_offset", C.c_int32),
+                ("seed", C.c_uint64), ("step", C.c_uint64), ("noise", C.c_void_p), ("actions", C.c_void_p),
+                ("gaussian_actions", C.c_void_p), ("log_prob", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p)]
+
+
+class FleetSacTargetArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("noise_mode", C.c_int32), ("seed", C.c_uint64), ("step", C.c_uint64),
+                ("row_offset", C.c_int32), ("gamma", C.c_float), ("ent_coef", C.c_void_p), ("noise", C.c_void_p),
+                ("target_q", C.c_void_p), ("next_actions", C.c_void_p), ("next_log_prob", C.c_void_p), ("q", C.c_void_p)]
+
+
 # ---- PPO minibatch gradients (include/fleet_hip.h "PPO minibatch gradients on the device", fleet_ppo_*) ------------------------------
 class FleetPpoParams(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("max_batch", C.c_int32)]
@@ -687,6 +705,13 @@ def load_library():
     lib.fleet_offpolicy_td3_dev.argtypes = [vp, C.POINTER(FleetOffpolicyArgs), C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(vp),
                                             C.POINTER(vp), C.c_int]
     lib.fleet_offpolicy_polyak_dev.argtypes = [vp, C.c_double]
+    # SAC's actor and soft targets (fleet_sac.hip), on a fleet_qtarget handle
+    lib.fleet_sac_create.argtypes = [C.c_int, C.POINTER(FleetSacParams), f32p, C.POINTER(vp)]
+    lib.fleet_sac_last_error.argtypes = [vp]
+    lib.fleet_sac_act_dev.argtypes = [vp, f32p, C.c_int, vp, C.POINTER(FleetSacActArgs)]
+    lib.fleet_sac_target_dev.argtypes = [vp, vp, f32p, f32p, f32p, C.c_int, C.POINTER(FleetSacTargetArgs)]
+    for name in SAC_SYMBOLS:
+        getattr(lib, name).restype = C.c_char_p if name == "fleet_sac_last_error" else C.c_int
     # rollout collection (fleet_collect.hip)
     lib.fleet_collect_create.argtypes = [vp, vp, vp, C.POINTER(FleetCollectParams), C.POINTER(vp)]
     lib.fleet_collect_destroy.argtypes = [vp]
@@ -795,6 +820,8 @@ KL_SYMBOLS = ("fleet_ppo_grad_gated_dev", "fleet_adam_step_gated_dev", "fleet_ad
 OFFPOLICY_SYMBOLS = ("fleet_offpolicy_create", "fleet_offpolicy_destroy", "fleet_offpolicy_last_error", "fleet_offpolicy_describe",
                      "fleet_offpolicy_td3_dev", "fleet_offpolicy_polyak_dev")
 
+SAC_SYMBOLS = ("fleet_sac_create", "fleet_sac_last_error", "fleet_sac_act_dev", "fleet_sac_target_dev")
+
 COLLECT_SYMBOLS = ("fleet_collect_create", "fleet_collect_destroy", "fleet_collect_last_error", "fleet_collect_describe",
                    "fleet_collect_reset_dev", "fleet_collect_ppo_dev", "fleet_collect_offpolicy_dev", "fleet_collect_episodes_dev",
                    "fleet_collect_finish_dev", "fleet_collect_episodes_read")
@@ -816,7 +843,7 @@ EXPORTED_SYMBOLS = (
     "fleet_direct_placement", "fleet_direct_split_plan", "fleet_debug_direct_fault", "fleet_set_rainflow_count_all",
     "fleet_lp_plan_dev", "fleet_step_instance", "fleet_max_evs_per_lane_group",
     "fleet_set_direct_state_only", "fleet_direct_packet_counts", "fleet_step_has_state_only",
-) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS + TRAIN_SYMBOLS + OFFPOLICY_SYMBOLS + COLLECT_SYMBOLS + EVAL_SYMBOLS
+) + NORM_SYMBOLS + STATE_SYMBOLS + ROLLOUT_SYMBOLS + REPLAY_SYMBOLS + POLICY_SYMBOLS + EXPLORE_SYMBOLS + NOISE_SYMBOLS + QTARGET_SYMBOLS + PPO_SYMBOLS + TD3_SYMBOLS + ADAM_SYMBOLS + TRAIN_SYMBOLS + OFFPOLICY_SYMBOLS + SAC_SYMBOLS + COLLECT_SYMBOLS + EVAL_SYMBOLS
 
 
 def step_instance(num_envs: int, num_cars: int, deg_mode: int, real_time: bool, log_data: bool, act_mode: int = ACT_F32, K: int = 1,

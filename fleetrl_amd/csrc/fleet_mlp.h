@@ -55,6 +55,15 @@ struct FleetMlpUser {
 // bytes; otherwise NULL, with "null <noun> handle" or "the handle is not a <noun> handle" in *why.
 FleetMlpHandle* mlp_borrow(void* owner, size_t record_bytes, const char* noun, std::string* why);
 
+// The normaliser's frozen statistics (when one is given) for a forward of h's `noun` ("policy") over obs_dim columns, its read opened
+// on h's stream (the caller ends it behind the launch: fleet_norm_end_read); *norm_obs: whether it normalises observations at all.
+// A normaliser of another shape or device is refused in h->error, `entry` in front.  Shared by fleet_policy.hip and fleet_sac.hip.
+struct MlpNormStats {
+  const double *mean, *sd;
+  double clip;
+};
+int mlp_bind_norm(FleetHandleBase* h, int obs_dim, const char* noun, const char* entry, fleet_norm_handle norm, MlpNormStats* out, bool* norm_obs);
+
 inline int mlp_round_up(int v, int m) { return (v + m - 1) / m * m; }
 
 // what *_create refuses about one head, before the device is touched; `who` opens the message ("head 0: "); "" when it passes

@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "fleet_norm.h"
+
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -90,7 +92,7 @@ int set_lds_limits(std::initializer_list<MlpKernelLds> kernels, const char* noun
 
 }  // namespace
 
-// FleetPolicy (fleet_policy.hip) and FleetQTarget (fleet_qtarget.hip) derive from FleetMlpHandle and from nothing else, and neither
+// FleetPolicy (fleet_policy.hip) and FleetQTarget (fleet_qtarget.h) derive from FleetMlpHandle and from nothing else, and neither
 // is polymorphic (mlp_image_is_first_base, asserted where each is defined): the image's handle is the first base, at the address
 // the opaque handle holds.  The families are told apart by the size of their records.
 FleetMlpHandle* mlp_borrow(void* owner, size_t record_bytes, const char* noun, std::string* why) {
@@ -102,6 +104,21 @@ FleetMlpHandle* mlp_borrow(void* owner, size_t record_bytes, const char* noun, s
   if (img->record_bytes == record_bytes) return img;
   *why = std::string("the handle is not a ") + noun + " handle";
   return nullptr;
+}
+
+int mlp_bind_norm(FleetHandleBase* h, int obs_dim, const char* noun, const char* entry, fleet_norm_handle norm, MlpNormStats* out, bool* norm_obs) {
+  *norm_obs = false;
+  if (!norm) return FLEET_OK;
+  FleetNormView v{};
+  FLEET_HANDLE_TRY(h, fleet_norm_begin_read(norm, h->stream, &v));
+  if (v.D != obs_dim || v.device != h->device) {
+    h->error = std::string(entry) + ": the normaliser has obs_dim " + std::to_string(v.D) + " on device " + std::to_string(v.device) +
+               ", the " + noun + " " + std::to_string(obs_dim) + " on device " + std::to_string(h->device);
+    return FLEET_ERR_INVALID;
+  }
+  out->mean = v.obs_mean, out->sd = v.obs_sd, out->clip = v.clip_obs;
+  *norm_obs = v.norm_obs != 0;
+  return FLEET_OK;
 }
 
 std::string mlp_validate_head(const FleetPolicyHead& H, const std::string& who) {

@@ -243,6 +243,8 @@ int fleet_offpolicy_create(fleet_replay_handle replay, fleet_qtarget_handle targ
   const QTargetDesc* desc = static_cast<const QTargetDesc*>(img->record);
   if (img == tgt) why = "the online and the target networks are one handle: the gradient handle must lie on a second image";
   else if (img->record_bytes != sizeof(QTargetDesc)) why = "the gradient handle does not lie on a fleet_qtarget image";
+  else if (qtarget_squashed(img) || qtarget_squashed(tgt))
+    why = "the networks' actor is a squashed Gaussian (fleet_sac_create): TD3's update does not train it";
   else if (img->device != tgt->device)
     why = "the online networks lie on device " + std::to_string(img->device) + ", the target networks on device " + std::to_string(tgt->device);
   else if (img->floats != tgt->floats || img->n_tensors != tgt->n_tensors || memcmp(img->record, tgt->record, sizeof(QTargetDesc)) != 0)

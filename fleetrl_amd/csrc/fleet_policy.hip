@@ -180,28 +180,6 @@ struct FleetPolicy : FleetMlpHandle {
 };
 static_assert(mlp_image_is_first_base<FleetPolicy>, "mlp_borrow (fleet_mlp.hip) reads a fleet_policy_handle as the image's handle");
 
-namespace {
-
-// The normaliser's frozen statistics (when one is given) into the forward's arguments, its read opened on the handle's stream
-// (the caller ends it behind the launch); *norm_obs: whether it normalises observations at all.  A normaliser of another shape or
-// device is refused.
-int bind_norm(FleetPolicy* h, const char* entry, fleet_norm_handle norm, ForwardArgs* a, bool* norm_obs) {
-  *norm_obs = false;
-  if (!norm) return FLEET_OK;
-  FleetNormView v{};
-  FLEET_HANDLE_TRY(h, fleet_norm_begin_read(norm, h->stream, &v));
-  if (v.D != h->p.obs_dim || v.device != h->device) {
-    h->error = std::string(entry) + ": the normaliser has obs_dim " + std::to_string(v.D) + " on device " + std::to_string(v.device) +
-               ", the policy " + std::to_string(h->p.obs_dim) + " on device " + std::to_string(h->device);
-    return FLEET_ERR_INVALID;
-  }
-  a->mean = v.obs_mean, a->sd = v.obs_sd, a->clip = v.clip_obs;
-  *norm_obs = v.norm_obs != 0;
-  return FLEET_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int fleet_policy_create(int device, const FleetPolicyParams* p, const float* host_weights, fleet_policy_handle* out) {
@@ -280,7 +258,9 @@ int fleet_policy_forward_dev(fleet_policy_handle h, const float* obs, int E, fle
   a.obs = obs, a.actions = actions, a.values = values, a.E = E;
   FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
   bool norm_obs;
-  if (const int rc = bind_norm(h, "fleet_policy_forward_dev", norm, &a, &norm_obs); rc != FLEET_OK) return rc;
+  MlpNormStats ns{};
+  if (const int rc = mlp_bind_norm(h, h->p.obs_dim, "policy", "fleet_policy_forward_dev", norm, &ns, &norm_obs); rc != FLEET_OK) return rc;
+  a.mean = ns.mean, a.sd = ns.sd, a.clip = ns.clip;
   const dim3 grid((unsigned)(((size_t)E + kPolicyRows - 1) / kPolicyRows), values ? 2 : 1), block(kPolicyThreads);
   if (norm_obs) hipLaunchKernelGGL(policy_forward<true>, grid, block, h->lds_bytes, h->stream, a);
   else hipLaunchKernelGGL(policy_forward<false>, grid, block, h->lds_bytes, h->stream, a);
@@ -336,7 +316,9 @@ int fleet_explore_act_dev(fleet_policy_handle h, const float* obs, int E, fleet_
   a.base = reinterpret_cast<const float*>(h->block);
   a.obs = obs, a.actions = nullptr, a.values = x.values, a.E = E;
   bool norm_obs;
-  if (const int rc = bind_norm(h, "fleet_explore_act_dev", norm, &a, &norm_obs); rc != FLEET_OK) return rc;
+  MlpNormStats ns{};
+  if (const int rc = mlp_bind_norm(h, h->p.obs_dim, "policy", "fleet_explore_act_dev", norm, &ns, &norm_obs); rc != FLEET_OK) return rc;
+  a.mean = ns.mean, a.sd = ns.sd, a.clip = ns.clip;
   const dim3 grid((unsigned)(((size_t)E + kPolicyRows - 1) / kPolicyRows), x.values ? 2 : 1), block(kPolicyThreads);
   if (norm_obs) hipLaunchKernelGGL(policy_forward_sample<true>, grid, block, h->sample_lds_bytes, h->stream, a, s);
   else hipLaunchKernelGGL(policy_forward_sample<false>, grid, block, h->sample_lds_bytes, h->stream, a, s);

@@ -138,16 +138,6 @@ std::string validate(const FleetQTargetParams* p) {
 const char* const kNetName[kQNets] = {"actor", "critic 0", "critic 1"};
 const MlpNames kTargetNames = {kNetName, "target networks", "target", "fleet_qtarget_create: "};
 
-}  // namespace
-
-struct FleetQTarget : FleetMlpHandle {
-  FleetQTargetParams p{};
-  QTargetDesc desc{};
-  size_t lds_bytes = 0;  // of one workgroup of qtarget_target
-};
-static_assert(mlp_image_is_first_base<FleetQTarget>, "mlp_borrow (fleet_mlp.hip) reads a fleet_qtarget_handle as the image's handle");
-
-namespace {
 
 // what fleet_qtarget_target_dev refuses, looked at without the handle; "" when the arguments pass
 std::string check_target_args(const float* next_obs, const float* rewards, const float* dones, int B, const FleetQTargetArgs* args) {
@@ -240,6 +230,10 @@ int fleet_qtarget_target_dev(fleet_qtarget_handle h, const float* next_obs, cons
                              const FleetQTargetArgs* args) {
   const std::string why = check_target_args(next_obs, rewards, dones, B, args);
   if (const int rc = handle_enter("fleet_qtarget_target_dev", why, h, g_qtarget_error); rc != FLEET_OK) return rc;
+  if (qtarget_squashed(h)) {  // (the actor's last layer is (mu, log_std): fleet_sac_target_dev is its target)
+    h->error = "fleet_qtarget_target_dev: the handle's actor is a squashed Gaussian (fleet_sac_create): use fleet_sac_target_dev";
+    return FLEET_ERR_INVALID;
+  }
   const FleetQTargetArgs& x = *args;
   TargetArgs t{};
   t.desc = reinterpret_cast<const QTargetDesc*>(h->block);

@@ -373,6 +373,10 @@ int fleet_td3_actor_grad_dev(fleet_td3_handle h, const FleetTd3ActorArgs* args, 
   std::string why = check_actor_args(args, grads, count);
   if (h && why.empty()) grad_check_sizes(&why, count, 2 * h->img->nets[0].n_layers, "W, b per layer of the actor", args->B, h->p.max_batch);
   if (const int rc = handle_enter("fleet_td3_actor_grad_dev", why, h, g_td3_error); rc != FLEET_OK) return rc;
+  if (qtarget_squashed(h->img)) {  // (td3_actor_rows takes act64 for the actor's last out64 and the last layer for the action)
+    h->error = "fleet_td3_actor_grad_dev: the networks' actor is a squashed Gaussian (fleet_sac_create): its gradient is not this entry's";
+    return FLEET_ERR_INVALID;
+  }
   RowsArgs t{};
   t.obs = args->obs, t.q = args->q, t.actions_out = args->actions_out, t.B = args->B;
   return launch_entry(h, td3_actor_rows, 1, t, kActorEntry, 0, 1, grads, args->stats);

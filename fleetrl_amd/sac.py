@@ -1,0 +1,195 @@
+"""`DeviceSACNetworks`: the networks of a SAC agent on the device (include/fleet_hip.h `fleet_sac_*`, fleetrl_amd/csrc/fleet_sac.hip).
+
+SB3's SAC actor -- `latent_pi`, then the two heads `mu` and `log_std` over the same input -- is stored as ONE chain whose last layer is
+`[2A, H]`: rows 0..A-1 `mu`, rows A..2A-1 `log_std`.  The handle is a `fleet_qtarget` handle, so everything a `DeviceTD3Target` does
+with its weights (`load_torch`, `polyak`, `export_torch`, `describe`) works tensor for tensor, `DeviceTD3Grad(nets, B).critic_grad`
+gives the critics' gradients and `DeviceAdam(nets, ..., nets="critic")` steps them.  Two launches are this module's own: `act`, the
+stochastic squashed-Gaussian action `tanh(mean + exp(log_std) * eps)` with its log-probability, and `target`, the entropy-regularised
+bootstrap target `r + (1 - d) * gamma * (min_c Q'_c(s', a') - alpha * log pi(a'|s'))` with `a'` drawn from the ONLINE actor and the
+critics of a second, TARGETS handle.  The actor and entropy-coefficient losses, and their backward passes, stay torch's.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import re
+
+import numpy as np
+
+from . import _capi
+from ._capi import FleetHipError
+from ._mlp import _arrays
+from .policy import _chain, _single, read_sb3_state_dict
+from .qtarget import DeviceTD3Target
+from .replay import _norm_handle
+
+__all__ = ["DeviceSACNetworks", "parse_sac_state_dict"]
+
+_KNOWN = re.compile(r"^actor\.latent_pi\.\d+\.(weight|bias)$|^actor\.(mu|log_std)\.(weight|bias)$|"
+                    r"^(critic|critic_target)\.qf[01]\.\d+\.(weight|bias)$")
+
+
+def parse_sac_state_dict(sd: dict, which: str = "online") -> dict:
+    """The networks of an SB3 SAC policy's state dict as the arguments of `DeviceSACNetworks`: {"actor_layers", "critics_layers"}.
+    The actor is `actor.latent_pi.<n>.*` followed by ONE layer, `actor.mu` and `actor.log_std` concatenated in that order along the
+    output axis; the critics are `critic.qf<k>.<n>.*` (which="online") or `critic_target.qf<k>.<n>.*` (which="target"; SAC has no
+    target actor, so the targets handle carries the online one, which nothing reads).  Any other key is refused by name."""
+    if which not in ("online", "target"):
+        raise ValueError(f"which must be 'online' or 'target', got {which!r}")
+    for k in sd:
+        if not _KNOWN.match(k):
+            raise ValueError(f"unsupported policy: state-dict key {k!r} is not part of a SAC MlpPolicy (actor.latent_pi.<n>, actor.mu, "
+                             "actor.log_std, critic.qf<k>.<n>, critic_target.qf<k>.<n>)")
+    (mw, mb), (lw, lb) = _single(sd, "actor.mu")[0], _single(sd, "actor.log_std")[0]
+    mw, mb, lw, lb = (np.asarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32) for t in (mw, mb, lw, lb))
+    if mw.shape != lw.shape or mb.shape != lb.shape:
+        raise ValueError(f"actor.mu {mw.shape} and actor.log_std {lw.shape} differ in shape")
+    actor = _chain(sd, "actor.latent_pi") + [(np.concatenate([mw, lw], 0), np.concatenate([mb, lb], 0))]
+    prefix = "critic" if which == "online" else "critic_target"
+    if not _chain(sd, f"{prefix}.qf0"):
+        raise ValueError(f"state dict has no {prefix}.qf0.<n>.weight")
+    critics = [c for c in (_chain(sd, f"{prefix}.qf0"), _chain(sd, f"{prefix}.qf1")) if c]
+    return {"actor_layers": actor, "critics_layers": critics}
+
+
+class DeviceSACNetworks(DeviceTD3Target):
+    """One handle `fleet_sac_create` made: a squashed-Gaussian actor over `obs_dim` columns whose last layer is `[2 * act_dim, H]` (mu
+    rows, then log_std rows) and one or two critics over `obs_dim + act_dim` columns.  actor_layers: [(W [out, in], b [out]), ...];
+    critics_layers: one such list per critic, the last width 1.  activation: "tanh" | "relu" after every layer but the last, of
+    every network (SB3's SAC default: "relu").  act_dim <= 256."""
+
+    def __init__(self, actor_layers, critics_layers, activation: str = "relu", device: int = 0):
+        self._set_transforms(activation, "none")
+        nets = [_arrays(actor_layers)] + [_arrays(c) for c in critics_layers]
+        if not nets[0] or len(nets) < 2 or len(nets) > 3 or not all(nets):
+            raise ValueError("the networks are an actor and one or two critics, each of at least one layer")
+        self.obs_dim = int(nets[0][0][0].shape[1]) if nets[0][0][0].ndim == 2 else 0
+        wide = int(nets[0][-1][0].shape[0])
+        self.act_dim = wide // 2  # (an odd width: refused by the library, with its reason)
+        self.n_critics = len(nets) - 1
+        p = _capi.FleetSacParams()
+        p.struct_bytes, p.obs_dim, p.n_critics = C.sizeof(_capi.FleetSacParams), self.obs_dim, self.n_critics
+        self._fill_head(p.actor, "actor", nets[0], self.obs_dim)
+        for c, net in enumerate(nets[1:]):
+            self._fill_head(p.critic[c], f"critic {c}", net, self.obs_dim + self.act_dim)
+        self._create(device, p, nets)
+
+    def _open(self, device: int, params, *more):
+        """fleet_sac_create: the one entry of the handle's life that is not fleet_qtarget_*."""
+        self.lib = _capi.load_library()
+        self.device = int(device)
+        h = C.c_void_p()
+        rc = self.lib.fleet_sac_create(self.device, C.byref(params), *more, C.byref(h))
+        if rc != _capi.OK:
+            raise FleetHipError(rc, self.lib.fleet_sac_last_error(None).decode())
+        self.h = h
+        self._stream = None
+
+    # ---- constructors from SB3's files ---------------------------------------------------------------------------------------
+    @classmethod
+    def from_state_dict(cls, sd, which: str = "online", activation: str = "relu", device: int = 0):
+        """From an SB3 SAC policy's state dict (`parse_sac_state_dict`).  The activation is not stored in a state dict: pass the one
+        the policy was trained with when it was not ReLU."""
+        return cls(**parse_sac_state_dict(dict(sd), which), activation=activation, device=device)
+
+    @classmethod
+    def from_sb3_zip(cls, path, which: str = "online", activation: str = "relu", device: int = 0):
+        """From the `policy.pth` of an archive `model.save()` wrote."""
+        return cls.from_state_dict(read_sb3_state_dict(path), which, activation, device)
+
+    # ---- the action ------------------------------------------------------------------------------------------------------------
+    def act_dev(self, obs_ptr: int, num_envs: int, norm, args: "_capi.FleetSacActArgs"):
+        """Raw device addresses in a FleetSacActArgs, on the handle's stream."""
+        args.struct_bytes = C.sizeof(_capi.FleetSacActArgs)
+        self._check(self.lib.fleet_sac_act_dev(self.h, obs_ptr, int(num_envs), _norm_handle(norm), C.byref(args)))
+
+    def act(self, obs, *, seed: int = 0, step: int = 0, deterministic: bool = False, env_id_offset: int = 0, normalizer=None, noise=None,
+            noise_given: bool = False, actions_out=None, gaussian_actions_out=None, log_prob_out=None, mean_out=None, log_std_out=None):
+        """SAC's action in one launch, on torch's current stream: obs f32 [E, obs_dim] -> actions f32 [E, act_dim], the squashed
+        action tanh(mean + exp(log_std) * eps) that both the env and the replay buffer get (SB3's `Actor.forward`), log_std clamped
+        to [-20, 2].  eps is Philox noise of (seed, env_id_offset + row, step, column) -- the bits `DevicePolicy.sample` draws under
+        the same key -- or `noise` f32 [E, act_dim] with noise_given; without it a given `noise` receives the draw.
+        log_prob_out f32 [E]: SB3's `SquashedDiagGaussianDistribution.log_prob`; gaussian_actions_out: the pre-squash action;
+        mean_out / log_std_out: the heads (log_std clamped).  deterministic: tanh(mean), no noise, no log-probability.  normalizer:
+        `obs` is RAW and goes through its statistics inside the launch.  Returns the actions."""
+        import torch
+
+        self.use_torch_stream()
+        f32, A = (torch.float32,), self.act_dim
+        E = int(obs.shape[0]) if obs.ndim == 2 else 0
+        obs = self._tensor(obs, (E, self.obs_dim), f32)
+        if actions_out is None:
+            actions_out = torch.empty((E, A), device=obs.device, dtype=torch.float32)
+        a = _capi.FleetSacActArgs()
+        a.noise_mode = _capi.EXPLORE_NOISE_GIVEN if noise_given else _capi.EXPLORE_NOISE_DRAW
+        a.deterministic, a.env_id_offset = int(bool(deterministic)), int(env_id_offset)
+        a.seed, a.step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+        if noise_given and noise is None:
+            raise ValueError("noise_given needs the noise tensor")
+        keep = [self._tensor(actions_out, (E, A), f32)]
+        a.actions = keep[0].data_ptr()
+        for name, t, shape in (("noise", noise, (E, A)), ("gaussian_actions", gaussian_actions_out, (E, A)), ("log_prob", log_prob_out, (E,)),
+                               ("mean", mean_out, (E, A)), ("log_std", log_std_out, (E, A))):
+            if t is not None:
+                keep.append(self._tensor(t, shape, f32))
+                setattr(a, name, keep[-1].data_ptr())
+        self.act_dev(obs.data_ptr(), E, normalizer, a)
+        return actions_out
+
+    # ---- the target ----------------------------------------------------------------------------------------------------------
+    def soft_target_dev(self, targets, next_obs_ptr: int, rewards_ptr: int, dones_ptr: int, batch: int, args: "_capi.FleetSacTargetArgs"):
+        """Raw device addresses in a FleetSacTargetArgs, on the handle's stream; `targets`: the DeviceSACNetworks of the targets.
+        (`target_dev` stays the inherited fleet_qtarget_target_dev, which refuses a squashed handle.)"""
+        args.struct_bytes = C.sizeof(_capi.FleetSacTargetArgs)
+        self._check(self.lib.fleet_sac_target_dev(self.h, getattr(targets, "h", None), next_obs_ptr, rewards_ptr, dones_ptr, int(batch),
+                                                  C.byref(args)))
+
+    def target(self, targets, next_obs, rewards, dones, *, gamma: float, ent_coef, seed: int, step: int, row_offset: int = 0, out=None,
+               next_actions_out=None, next_log_prob_out=None, q_out=None, noise=None, noise_given: bool = False):
+        """SAC's learning targets of a minibatch in one launch, called on the ONLINE networks: `targets` is the DeviceSACNetworks that
+        holds the target critics.  next_obs f32 [B, obs_dim] (normalised, as `DeviceReplayBuffer.sample` returns it), rewards f32 [B]
+        and dones f32 [B] (or [B, 1]) -> y f32 [B] (`out`, made when None),
+        y = rewards + ((1 - dones) * gamma) * (min_c Q'_c(next_obs, a') - alpha * log pi(a' | next_obs)), a' and its log-probability
+        what `act` gives on next_obs under (seed, row_offset + row, step).  ent_coef: alpha itself as a device tensor f32 [1], read
+        when the launch runs (a float also does, through a cached tensor: one that changes costs a host synchronisation).  Give the
+        target a seed of its own, not the acting seed.  next_actions_out f32 [B, act_dim], next_log_prob_out f32 [B] and q_out f32
+        [B, n_critics] receive a', its log-probability and the target critics' outputs."""
+        import torch
+
+        self.use_torch_stream()
+        if isinstance(targets, DeviceTD3Target):
+            targets.use_torch_stream()
+        f32, A = (torch.float32,), self.act_dim
+        B = int(next_obs.shape[0]) if next_obs.ndim == 2 else 0
+        next_obs = self._tensor(next_obs, (B, self.obs_dim), f32)
+        rewards, dones = self._tensor(rewards, (B,), f32), self._tensor(dones, (B,), f32)
+        if out is None:
+            out = torch.empty((B,), device=next_obs.device, dtype=torch.float32)
+        a = _capi.FleetSacTargetArgs()
+        a.noise_mode = _capi.EXPLORE_NOISE_GIVEN if noise_given else _capi.EXPLORE_NOISE_DRAW
+        a.seed, a.step, a.row_offset = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(row_offset)
+        a.gamma = float(gamma)
+        if isinstance(ent_coef, torch.Tensor):
+            alpha = self._tensor(ent_coef.detach(), (1,), f32)
+        else:
+            hit = self._constants.get("ent_coef")
+            if hit is None or hit[0] != float(ent_coef):
+                hit = self._constants["ent_coef"] = (float(ent_coef), torch.full((1,), float(ent_coef), device=next_obs.device, dtype=torch.float32))
+            alpha = hit[1]
+        a.ent_coef = alpha.data_ptr()
+        a.target_q = self._tensor(out, (B,), f32).data_ptr()
+        if noise_given and noise is None:
+            raise ValueError("noise_given needs the noise tensor")
+        keep = [alpha]
+        for name, t, shape in (("noise", noise, (B, A)), ("next_actions", next_actions_out, (B, A)), ("next_log_prob", next_log_prob_out, (B,)),
+                               ("q", q_out, (B, self.n_critics))):
+            if t is not None:
+                keep.append(self._tensor(t, shape, f32))
+                setattr(a, name, keep[-1].data_ptr())
+        self.soft_target_dev(targets, next_obs.data_ptr(), rewards.data_ptr(), dones.data_ptr(), B, a)
+        return out
+
+    def describe(self) -> dict:
+        """What fleet_qtarget_describe reports (the actor's last width is 2 * act_dim), and `squashed`: True."""
+        d = super().describe()
+        d["squashed"] = True
+        return d

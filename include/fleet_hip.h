@@ -2031,6 +2031,106 @@ typedef struct FleetPpoGradGatedArgs {
 } FleetPpoGradGatedArgs;
 FLEET_API int fleet_ppo_grad_gated_dev(fleet_ppo_handle h, const FleetPpoGradGatedArgs* args, float* const* grads, int count);
 
+/* ==== SAC on the device: squashed-Gaussian actor and soft Q targets (fleet_sac.hip; DESIGN.md "SAC on the device") ====================
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays.  The section stands behind the
+ * last of the "----" sections, whose order and count stay what they were, and every entry of it starts with fleet_sac_.)
+ * The forward side of stable-baselines3 2.3.2's SAC: the stochastic actor's action with its log-probability in ONE launch, and the
+ * entropy-regularised bootstrap target of a minibatch in ONE launch.  float32 throughout, no contraction except the fmaf written.
+ * Networks.  SB3's SAC actor is latent_pi (an MLP) followed by two linear heads over the same input, mu and log_std.  Here it is ONE
+ * FleetPolicyHead over D = obs_dim inputs whose last layer has width 2A: rows 0..A-1 are mu, rows A..2A-1 are log_std, the output
+ * transform is NONE.  One torch parameter pair [2A, H] / [2A] -- cat([mu.weight, log_std.weight]) -- is one layer of the weight image
+ * (Wt[in4][out64], zero padding, as the policy's).  2A <= FLEET_POLICY_MAX_WIDTH, so A <= 256.  Critic c is SB3's ContinuousCritic over
+ * D + A inputs (not D + 2A), last width 1, output NONE; D + A <= FLEET_POLICY_MAX_OBS_DIM.
+ * fleet_sac_create returns a fleet_qtarget_handle of the existing type, marked as a squashed actor's.  The entries that only walk nets
+ * or critics serve it unchanged: fleet_qtarget_destroy / _last_error / _set_stream / _load_host / _load_dev / _polyak_dev / _export_dev /
+ * _describe (FleetQTargetParams: the actor's last width reads 2A), fleet_td3_create with fleet_td3_critic_grad_dev (the critics' input is
+ * D + act_dim, and the scratch is laid out per net), fleet_adam_create_qtarget.  Three entries would run the actor forward as a TD3
+ * actor and REFUSE such a handle with FLEET_ERR_INVALID, their name and the reason in their last_error, nothing launched:
+ * fleet_qtarget_target_dev, fleet_td3_actor_grad_dev (its kernel takes act64 for the actor's last out64), fleet_offpolicy_create.
+ * The action, per row e of obs f32[E,D] (`norm` as for fleet_policy_forward_dev), exactly:
+ *   m[j], l[j]  = columns j and A + j of the actor's last layer: the policy section's chain (acc = 0; fmaf ascending k; + bias)
+ *   ls[j]       = l[j] < -20.0f ? -20.0f : (l[j] > 2.0f ? 2.0f : l[j])          (SB3's LOG_STD_MIN / LOG_STD_MAX)
+ *   sd[j]       = expf(ls[j]);   u[j] = fmaf(sd[j], eps[j], m[j]);   a[j] = tanhf(u[j])
+ *   t[j]        = fmaf(-0.5f * eps[j], eps[j], -ls[j]) - 0.9189385332f            (the Gaussian's log-density at u, written in eps)
+ *   c[j]        = logf((1.0f - a[j] * a[j]) + 1e-6f)                              (SB3's correction, epsilon 1e-6, on the STORED action)
+ *   log_prob    = S(t) - S(c)     S: the lane order of fleet_explore_act_dev (lane i of 64 adds j = i, i+64, ... ascending; xor butterfly 1..32)
+ *   deterministic: a[j] = tanhf(m[j]); no noise is read or written; log_prob / gaussian_actions / noise must be NULL
+ * eps is the existing draw: Philox4x32-10 under key (seed lo, seed hi) at counter (env_id_offset + e, j / 4, step lo, step hi) over the A
+ * action columns (not 2A), Box-Muller as there: under one (seed, step, env id) the bits fleet_explore_act_dev draws.  noise_mode
+ * FLEET_EXPLORE_NOISE_DRAW or _GIVEN as there; DRAW with a non-null `noise` records the draw.
+ * Deviation from SB3: torch's Normal.log_prob computes -(u - m)^2 / (2 sd^2) - ls - log(sqrt(2 pi)); t[j] is the same quantity with
+ * (u - m) / sd = eps put in.  It does not depend on expf's last bit, and it can be restated exactly from stored values (ls, eps).
+ * The correction is SB3's SquashedDiagGaussianDistribution.log_prob, log(1 - tanh(u)^2 + 1e-6), evaluated on the action that was stored.
+ * Every output of a row is a function of that row: not of E, of the row's place, of which optional outputs are asked for, of the stream.
+ * The target, per row b (next_obs f32[B,D] normalised, rewards f32[B], dones f32[B], as fleet_replay_sample_dev writes them):
+ *   a', lp = exactly the action above on next_obs[b], by the ONLINE handle's actor   (the same code path: the bits fleet_sac_act_dev
+ *            gives for that row, seed, step and offset)
+ *   q_c    = critic c of the TARGETS handle over concat(next_obs[b], a'): the learning targets' chain
+ *   qmin   = n_critics == 2 ? (q_1 < q_0 ? q_1 : q_0) : q_0
+ *   p = alpha * lp;  v = qmin - p;  t = (1.0f - dones[b]) * gamma;  y[b] = rewards[b] + t * v       (each rounded on its own: no fma)
+ * alpha = ent_coef[0], a device float read when the launch runs: the caller keeps exp(log_ent_coef) in a tensor.  One workgroup takes
+ * 16 rows through the online actor, then through the target critics: two image bases, no atomics, no ordering between workgroups.
+ * The targets handle keeps a copy of the actor that nothing reads; a Polyak update over all tensors stays correct.  As for the TD3
+ * targets, the target gets a SEED OF ITS OWN, different from the acting seed.
+ * Every *_dev call takes device pointers, only enqueues and runs on the handle's stream (fleet_qtarget_set_stream).  Out of scope: the
+ * actor and entropy-coefficient gradients, a one-call train(), a SAC collector, gSDE, a log_ent_coef form of alpha. */
+typedef struct FleetSacParams {
+  int32_t struct_bytes;       /* sizeof(FleetSacParams) */
+  int32_t obs_dim;            /* D >= 1 */
+  int32_t n_critics;          /* 1 or 2 */
+  int32_t reserved;           /* 0 */
+  FleetPolicyHead actor;      /* over D inputs; the last width is 2A (even), the output FLEET_POLICY_OUT_NONE */
+  FleetPolicyHead critic[2];  /* over D + A inputs; the last width must be 1, the output FLEET_POLICY_OUT_NONE */
+} FleetSacParams;
+typedef struct FleetSacActArgs {
+  int32_t struct_bytes;     /* sizeof(FleetSacActArgs) */
+  int32_t noise_mode;       /* FLEET_EXPLORE_NOISE_DRAW / _GIVEN */
+  int32_t deterministic;    /* 0 / 1 */
+  int32_t env_id_offset;    /* global id of row 0; >= 0 */
+  uint64_t seed;            /* Philox key */
+  uint64_t step;            /* Philox counter words 2, 3 */
+  float* noise;             /* device f32[E, A] or NULL: read (GIVEN), written when not NULL (DRAW) */
+  float* actions;           /* device f32[E, A]: the squashed action a, which both the env and the buffer get */
+  float* gaussian_actions;  /* device f32[E, A] or NULL: the pre-squash u */
+  float* log_prob;          /* device f32[E] or NULL */
+  float* mean;              /* device f32[E, A] or NULL: m */
+  float* log_std;           /* device f32[E, A] or NULL: the clamped ls */
+} FleetSacActArgs;
+typedef struct FleetSacTargetArgs {
+  int32_t struct_bytes;     /* sizeof(FleetSacTargetArgs) */
+  int32_t noise_mode;       /* FLEET_EXPLORE_NOISE_DRAW / _GIVEN */
+  uint64_t seed;            /* Philox key: not the acting seed */
+  uint64_t step;            /* Philox counter words 2, 3: the caller's gradient-step count */
+  int32_t row_offset;       /* global id of row 0 (a shard of a larger minibatch); >= 0 */
+  float gamma;              /* the discount */
+  const float* ent_coef;    /* device f32[1]: alpha itself, read when the launch runs */
+  float* noise;             /* device f32[B, A] or NULL: read (GIVEN), written when not NULL (DRAW) */
+  float* target_q;          /* device f32[B]: y */
+  float* next_actions;      /* device f32[B, A] or NULL: a' */
+  float* next_log_prob;     /* device f32[B] or NULL: lp */
+  float* q;                 /* device f32[B, n_critics] or NULL: q_c */
+} FleetSacTargetArgs;
+
+/* The parameters and the weights are validated BEFORE the device is touched: FLEET_ERR_INVALID (fleet_sac_last_error(NULL) says why,
+ * starting with the entry's name) for a wrong struct_bytes, obs_dim < 1, n_critics outside 1..2, a layer count outside 1..4, a width
+ * outside 1..512 (so 2A > 512), an odd last actor width, an actor output that is not NONE, D + A above 8192, a critic whose last width
+ * is not 1 or whose output is not NONE, an unknown activation, a null pointer, a weight that is not finite.
+ * host_weights: packed float32 -- the actor, then critic 0, then critic 1; for each layer W[out, in] (row-major) then b[out]. */
+int fleet_sac_create(int device, const FleetSacParams* p, const float* host_weights, fleet_qtarget_handle* out);
+/* h may be NULL: error of the last failed fleet_sac_* call without a handle; with a handle, what fleet_qtarget_last_error(h) returns */
+const char* fleet_sac_last_error(fleet_qtarget_handle h);
+/* One launch.  FLEET_ERR_INVALID (nothing is launched) for a null or wrongly sized FleetSacActArgs, an unknown noise_mode, E < 1, a null
+ * obs / actions, a deterministic outside 0..1, GIVEN with a null noise, a negative env_id_offset, a noise / log_prob / gaussian_actions
+ * with deterministic -- these are looked at before the handle is: with nets NULL the reason (or "null handle") goes to
+ * fleet_sac_last_error(NULL) -- and, with the handle, for one whose actor is not squashed and a normaliser of another width or device. */
+int fleet_sac_act_dev(fleet_qtarget_handle nets, const float* obs, int E, fleet_norm_handle norm, const FleetSacActArgs* a);
+/* One launch on the online handle's stream.  FLEET_ERR_INVALID (nothing is launched) for a null or wrongly sized FleetSacTargetArgs, an
+ * unknown noise_mode, B < 1, a null next_obs / rewards / dones / ent_coef / target_q, GIVEN with a null noise, a negative row_offset
+ * (before the handle, as above), and, in the online handle's last_error: a null `targets`, a handle of either that fleet_sac_create did
+ * not make, obs_dim, act_dim or n_critics that differ between the two, another device, handles that do not launch on one stream. */
+int fleet_sac_target_dev(fleet_qtarget_handle online, fleet_qtarget_handle targets, const float* next_obs, const float* rewards,
+                         const float* dones, int B, const FleetSacTargetArgs* a);
+
 #ifdef __cplusplus
 }
 #endif
