@@ -6,8 +6,9 @@ critics' gradients come from the existing `DeviceTD3Grad.critic_grad` launches, 
 targets.  What torch still does in a gradient step: the actor loss and the entropy-coefficient loss with their backward passes and
 optimiser steps, after which `load_torch` refreshes the online image.
 
-SB3's SAC critic loss is 0.5 * sum_c mse(q_c, y); the TD3 launches compute sum_c mse(q_c, y).  The loop below halves the gradients
-before the optimiser step and reports half of the launches' loss, so the update is SB3's.
+SB3's SAC critic loss is 0.5 * sum_c mse(q_c, y); the TD3 launches compute sum_c mse(q_c, y).  `fleetrl_amd.sac.critic_update` halves
+the gradients before the optimiser step and the loop reports half of the launches' loss, so the update is SB3's
+(tests/test_update_ref_gpu.py holds it to SB3's loop under torch autograd).
 
 Measured: with these 64-64 trunks at a batch of 256 the target launch takes 40 us against 361 us of the
 eager-torch restatement below (`--time`).
@@ -34,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import bench_config  # noqa: E402  (the reference's config dict with the benchmark's values)
 from fleetrl_amd import (DeviceAdam, DevicePolicy, DeviceReplayBuffer, DeviceSACNetworks, DeviceTD3Grad, FleetVecEnv,  # noqa: E402
                          FleetVecNormalize)
+from fleetrl_amd.sac import CRITIC_LOSS_SCALE, critic_update  # noqa: E402
 from fleetrl_amd.synth import synth_tables  # noqa: E402
 
 
@@ -124,10 +126,9 @@ def main():
             with torch.no_grad():
                 alpha.copy_(log_alpha.exp())
             # the critics: target (one launch), gradients (two launches), Adam on the image and the parameters (one launch)
-            y = nets.target(targets, b.next_observations, b.rewards, b.dones, gamma=gamma, ent_coef=alpha, seed=target_seed, step=updates)
-            grad.critic_grad(b, y, into=critic_params, stats_out=critic_stats)
-            torch._foreach_mul_([p.grad for p in critic_params], 0.5)  # SB3's 0.5 * (mse + mse): see the module's docstring
-            opt_c.step()
+            # (SB3's 0.5 * (mse + mse) is the helper's loss_scale: see the module's docstring)
+            critic_update(nets, targets, grad, opt_c, b, critic_params, gamma=gamma, ent_coef=alpha, seed=target_seed, step=updates,
+                          stats_out=critic_stats)
             # the actor (torch): alpha * log pi - min_c Q_c(s, pi(s)); the critics' parameters are the ones the device just stepped
             x = torch.cat([b.observations, pi], dim=1)
             a_loss = (alpha.detach() * log_pi - torch.min(q1(x), q2(x)).view(-1)).mean()
@@ -141,7 +142,7 @@ def main():
         if step % args.log_interval == 0 or step == args.steps:
             buf.check_errors()
             print(json.dumps({"step": step, "transitions": buf.size() * E, "gradient_steps": updates,
-                              "critic_loss": 0.5 * critic_stats[0].item(), "actor_loss": a_loss.item(), "ent_coef": alpha.item(),
+                              "critic_loss": CRITIC_LOSS_SCALE * critic_stats[0].item(), "actor_loss": a_loss.item(), "ent_coef": alpha.item(),
                               "mean_raw_reward": (reward_sum / step).item()}), flush=True)
 
     if args.time:

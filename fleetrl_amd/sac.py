@@ -22,10 +22,30 @@ from .policy import _chain, _single, read_sb3_state_dict
 from .qtarget import DeviceTD3Target
 from .replay import _norm_handle
 
-__all__ = ["DeviceSACNetworks", "parse_sac_state_dict"]
+__all__ = ["DeviceSACNetworks", "parse_sac_state_dict", "critic_update", "CRITIC_LOSS_SCALE"]
+
+# SB3's SAC critic loss is 0.5 * sum_c mse(q_c, y); the TD3 gradient launches form sum_c mse(q_c, y)
+CRITIC_LOSS_SCALE = 0.5
 
 _KNOWN = re.compile(r"^actor\.latent_pi\.\d+\.(weight|bias)$|^actor\.(mu|log_std)\.(weight|bias)$|"
                     r"^(critic|critic_target)\.qf[01]\.\d+\.(weight|bias)$")
+
+
+def critic_update(nets, targets, grad, adam, batch, critic_params, *, gamma: float, ent_coef, seed: int, step: int, stats_out=None,
+                  loss_scale: float = CRITIC_LOSS_SCALE):
+    """The critic half of one `SAC.train` gradient step, short of the Polyak update: `nets.target` (one launch), `grad.critic_grad` (a
+    `DeviceTD3Grad` on `nets`; two launches), the gradients times `loss_scale` -- the launches' loss is sum_c mse(q_c, y), SB3's is 0.5
+    times that --, and `adam.step()` (a `DeviceAdam` on `nets` with `nets="critic"`).  batch: what `DeviceReplayBuffer.sample` yields.
+    stats_out f32 [8] receives the launches' UNSCALED losses (`loss_scale * stats_out[0]` is SB3's `critic_loss`).  Returns the
+    target y f32 [B].  `targets.polyak(online_parameters, tau)` is the caller's, after whatever steps the actor."""
+    import torch
+
+    y = nets.target(targets, batch.next_observations, batch.rewards, batch.dones, gamma=gamma, ent_coef=ent_coef, seed=seed, step=step)
+    grad.critic_grad(batch, y, into=critic_params, stats_out=stats_out)
+    if loss_scale != 1.0:
+        torch._foreach_mul_([p.grad for p in critic_params], float(loss_scale))
+    adam.step()
+    return y
 
 
 def parse_sac_state_dict(sd: dict, which: str = "online") -> dict:

@@ -54,6 +54,16 @@ def networks(D, A, hidden, n_critics, seed):
     return net([D, *hidden, A]), [net([D + A, *hidden, 1]) for _ in range(n_critics)]
 
 
+def contents(E, R, D, A, seed):
+    """(the replay ring's six arrays as `Stack` fills them, float32 / uint8, and the generator behind them, for what follows)."""
+    rng = np.random.default_rng(seed + 1000)
+    out = {"observations": rng.standard_normal((R, E, D)).astype(F32), "next_observations": rng.standard_normal((R, E, D)).astype(F32),
+           "actions": rng.uniform(-1, 1, (R, E, A)).astype(F32), "rewards": rng.standard_normal((R, E)).astype(F32)}
+    out["dones"] = (rng.random((R, E)) < 0.3).astype(np.uint8)
+    out["timeouts"] = (out["dones"] * (rng.random((R, E)) < 0.5)).astype(np.uint8)
+    return out, rng
+
+
 class Stack:
     """Every handle of one TD3 / DDPG agent on random networks and a replay ring of R rows of E envs filled from `seed`; two Stacks
     from the same arguments start from the same bits."""
@@ -74,15 +84,9 @@ class Stack:
         self.opt_a = DeviceAdam(self.online, self.actor_params, nets="actor", lr=lr)
         self.opt_c = DeviceAdam(self.online, self.critic_params, nets="critic", lr=lr)
         self.buf = DeviceReplayBuffer(R * E, E, D, A, seed=seed + 77)
-        rng = np.random.default_rng(seed + 1000)
-        put = lambda t, a: t.copy_(torch.from_numpy(a).to(dev))  # noqa: E731
-        put(self.buf.observations, rng.standard_normal((R, E, D)).astype(F32))
-        put(self.buf.next_observations, rng.standard_normal((R, E, D)).astype(F32))
-        put(self.buf.actions, rng.uniform(-1, 1, (R, E, A)).astype(F32))
-        put(self.buf.rewards, rng.standard_normal((R, E)).astype(F32))
-        done = (rng.random((R, E)) < 0.3).astype(np.uint8)
-        put(self.buf.dones, done)
-        put(self.buf.timeouts, (done * (rng.random((R, E)) < 0.5)).astype(np.uint8))
+        arrays, rng = contents(E, R, D, A, seed)
+        for name, a in arrays.items():
+            getattr(self.buf, name).copy_(torch.from_numpy(a).to(dev))
         self.buf.set_position(pos, full, 0)
         self.env = None
         if with_norm:
