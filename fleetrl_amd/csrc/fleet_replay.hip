@@ -156,6 +156,20 @@ __global__ __launch_bounds__(kReplayThreads) void replay_sample(SampleArgs a) {
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 thread_local std::string g_replay_create_error;
 
+// replay_add walks the env rows, and copy_row / sample_row the words of a row, with an `int` that advances by a fixed stride: the
+// loop ends only if the last index plus one stride still fits the counter.  Create refuses what the widest grid cannot finish.
+constexpr int64_t kReplayLaneStride = kReplayThreads / kReplayWaves;  // the lanes of a wavefront
+constexpr int64_t kReplayMaxEnvStride = (int64_t)kReplayMaxBlocks * kReplayWaves;
+constexpr int64_t kReplayMaxEnvs = ((int64_t)1 << 31) - kReplayMaxEnvStride;
+constexpr int64_t kReplayMaxDim = ((int64_t)1 << 31) - kReplayLaneStride;
+static_assert(kReplayMaxEnvs > 0 && kReplayMaxDim > 0, "a stride that leaves no size to accept");
+const std::string kEnvsError = "num_envs must be <= " + std::to_string(kReplayMaxEnvs) + " (2^31 - " + std::to_string(kReplayMaxBlocks) +
+                               " * " + std::to_string(kReplayWaves) + ": a 32-bit env counter advances by up to that stride)";
+const std::string kDimWhy = std::to_string(kReplayMaxDim) + " (2^31 - " + std::to_string(kReplayLaneStride) +
+                            ": a 32-bit column counter advances by that stride)";
+const std::string kObsDimError = "obs_dim must be <= " + kDimWhy;
+const std::string kActDimError = "act_dim must be <= " + kDimWhy;
+
 uint64_t rows_of(const FleetReplayParams* p) {
   const uint64_t R = (uint64_t)p->buffer_size / (uint64_t)p->num_envs;
   return R < 1 ? 1 : R;  // SB3: max(buffer_size // n_envs, 1)
@@ -168,6 +182,9 @@ const char* validate(const FleetReplayParams* p) {
   if (p->buffer_size < 1) return "buffer_size must be >= 1";
   if (p->obs_dim < 1) return "obs_dim must be >= 1";
   if (p->act_dim < 1) return "act_dim must be >= 1";
+  if (p->num_envs > kReplayMaxEnvs) return kEnvsError.c_str();
+  if (p->obs_dim > kReplayMaxDim) return kObsDimError.c_str();
+  if (p->act_dim > kReplayMaxDim) return kActDimError.c_str();
   if (rows_of(p) * (uint64_t)p->num_envs >= ((uint64_t)1 << 31))
     return "rows * num_envs (rows = max(buffer_size / num_envs, 1)) must be < 2^31 (transition indices are int32)";
   return nullptr;

@@ -188,6 +188,17 @@ __global__ __launch_bounds__(kRolloutThreads) void rollout_gather(GatherArgs a) 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 thread_local std::string g_rollout_create_error;
 
+// copy_flat and gather_rows count their items in an `unsigned` that advances by the grid's stride: the loop ends only if the last
+// item's index plus one stride still fits the counter.  The host refuses, before any launch, a count the widest grid cannot finish.
+constexpr uint64_t kRolloutMaxStride = (uint64_t)kRolloutMaxBlocks * kRolloutThreads;
+constexpr uint64_t kRolloutMaxItems = ((uint64_t)1 << 32) - kRolloutMaxStride;
+static_assert(kRolloutMaxStride < ((uint64_t)1 << 31), "an env counter below 2^31 plus one stride fits 32 bits");
+const std::string kRolloutItemsWhy = std::to_string(kRolloutMaxItems) + " (2^32 - " + std::to_string(kRolloutMaxBlocks) + " * " +
+                                     std::to_string(kRolloutThreads) + ": a 32-bit item counter advances by up to that stride)";
+const std::string kRowItemsError = "num_envs * obs_dim and num_envs * act_dim must be <= " + kRolloutItemsWhy;
+const std::string kGatherItemsError =
+    "fleet_rollout_gather_dev: batch * obs_dim (act_dim) must be <= " + kRolloutItemsWhy + ": gather in pieces";
+
 const char* validate(const FleetRolloutParams* p) {
   if (!p) return "null FleetRolloutParams";
   if (p->struct_bytes != (int32_t)sizeof(FleetRolloutParams)) return "FleetRolloutParams.struct_bytes does not match this library";
@@ -196,8 +207,8 @@ const char* validate(const FleetRolloutParams* p) {
   if (p->obs_dim < 1) return "obs_dim must be >= 1";
   if (p->act_dim < 1) return "act_dim must be >= 1";
   if ((uint64_t)p->num_envs * (uint64_t)p->n_steps >= ((uint64_t)1 << 31)) return "num_envs * n_steps must be < 2^31 (flat indices are int32)";
-  if ((uint64_t)p->num_envs * (uint64_t)(p->obs_dim > p->act_dim ? p->obs_dim : p->act_dim) >= ((uint64_t)1 << 32))
-    return "num_envs * obs_dim and num_envs * act_dim must be < 2^32 (one time row is copied with 32-bit offsets)";
+  if ((uint64_t)p->num_envs * (uint64_t)(p->obs_dim > p->act_dim ? p->obs_dim : p->act_dim) > kRolloutMaxItems)
+    return kRowItemsError.c_str();
   if (!(p->gamma >= 0 && p->gamma <= 1)) return "gamma must be in [0, 1]";
   if (!(p->gae_lambda >= 0 && p->gae_lambda <= 1)) return "gae_lambda must be in [0, 1]";
   return nullptr;
@@ -377,8 +388,8 @@ int fleet_rollout_gather_dev(fleet_rollout_handle r, const int32_t* indices, int
     return FLEET_ERR_INVALID;
   }
   const size_t n_obs = (size_t)batch * r->D, n_act = (size_t)batch * r->A;
-  if ((out_obs && n_obs >= ((size_t)1 << 32)) || (out_actions && n_act >= ((size_t)1 << 32))) {
-    r->error = "fleet_rollout_gather_dev: batch * obs_dim (act_dim) must be < 2^32: gather in pieces";
+  if ((out_obs && n_obs > kRolloutMaxItems) || (out_actions && n_act > kRolloutMaxItems)) {
+    r->error = kGatherItemsError;
     return FLEET_ERR_INVALID;
   }
   if (batch == 0) return FLEET_OK;

@@ -717,8 +717,8 @@ typedef struct FleetRolloutParams {
   int32_t struct_bytes;  /* sizeof(FleetRolloutParams) */
   int32_t num_envs;      /* E >= 1 */
   int32_t n_steps;       /* K >= 1; E * K < 2^31 */
-  int32_t obs_dim;       /* D >= 1 */
-  int32_t act_dim;       /* A >= 1 */
+  int32_t obs_dim;       /* D >= 1; E * max(D, A) <= 2^32 - 2048 * 256 (a time row is copied under a 32-bit item counter that */
+  int32_t act_dim;       /* A >= 1;   advances by up to 2048 workgroups * 256 threads: a larger row would never finish) */
   int32_t reserved;      /* 0 */
   double gamma;          /* 0 <= gamma <= 1 */
   double gae_lambda;     /* 0 <= gae_lambda <= 1 */
@@ -764,8 +764,9 @@ typedef struct FleetRollout* fleet_rollout_handle;
 
 /* No device needed.  FLEET_ERR_INVALID (fleet_rollout_last_error(NULL) says why) for parameters fleet_rollout_create refuses. */
 int fleet_rollout_layout(const FleetRolloutParams* p, FleetRolloutLayout* out);
-/* The parameters are validated BEFORE the device is touched: FLEET_ERR_INVALID for E, K, D or A < 1, E * K >= 2^31, gamma or
- * gae_lambda outside [0, 1] (NaN included), a wrong struct_bytes, a null pointer.  Then: one allocation, zero-filled. */
+/* The parameters are validated BEFORE the device is touched: FLEET_ERR_INVALID for E, K, D or A < 1, E * K >= 2^31, a time
+ * row past the limit above (the message states it), gamma or gae_lambda outside [0, 1] (NaN included), a wrong struct_bytes, a null
+ * pointer.  Then: one allocation, zero-filled. */
 int fleet_rollout_create(int device, const FleetRolloutParams* p, fleet_rollout_handle* out);
 int fleet_rollout_destroy(fleet_rollout_handle r);
 const char* fleet_rollout_last_error(fleet_rollout_handle r);  /* r may be NULL: error of the last failed create / layout */
@@ -791,7 +792,9 @@ int fleet_rollout_finish_dev(fleet_rollout_handle r, const float* last_values, c
 /* One launch: out_x[b] = x[t, e] for indices[b] = e * K + t, b < batch; indices i32[batch] in device memory, the permutation is the
  * caller's.  Any output may be NULL (not wanted).  Rows of obs (and of actions) move as 16-byte words when D (A) is a multiple of
  * 4 and the output is 16-byte aligned, as single floats otherwise.  An index outside [0, K * E) writes nothing for its row and sets
- * the buffer's error word (fleet_rollout_check_errors). */
+ * the buffer's error word (fleet_rollout_check_errors).  FLEET_ERR_INVALID, before any launch, unless
+ * batch * D (batch * A) <= 2^32 - 2048 * 256 for the outputs asked for (the same 32-bit item counter; the message states the
+ * limit): gather in pieces. */
 int fleet_rollout_gather_dev(fleet_rollout_handle r, const int32_t* indices, int batch, float* out_obs, float* out_actions,
                              float* out_values, float* out_log_probs, float* out_advantages, float* out_returns);
 /* Waits for the stream, reads the error word back: FLEET_OK, or FLEET_ERR_STATE (a gather met an index out of range since the last
@@ -818,9 +821,9 @@ int fleet_rollout_check_errors(fleet_rollout_handle r);
  *           arithmetic, read from its device block when the launch RUNS, behind the normaliser's last enqueued launch */
 typedef struct FleetReplayParams {
   int32_t struct_bytes;  /* sizeof(FleetReplayParams) */
-  int32_t num_envs;      /* E >= 1 */
+  int32_t num_envs;      /* E >= 1; E <= 2^31 - 2048 * 4 (the env rows are walked under an int that advances by up to 2048 * 4) */
   int32_t buffer_size;   /* transitions, >= 1; R = max(buffer_size / E, 1), R * E < 2^31 */
-  int32_t obs_dim;       /* D >= 1 */
+  int32_t obs_dim;       /* D >= 1; D, A <= 2^31 - 64 (a row's words are walked under an int that advances by the 64 lanes) */
   int32_t act_dim;       /* A >= 1 */
   int32_t reserved;      /* 0 */
   uint64_t seed;         /* Philox key of the index draw */
@@ -856,8 +859,9 @@ typedef struct FleetReplay* fleet_replay_handle;
 
 /* No device needed.  FLEET_ERR_INVALID (fleet_replay_last_error(NULL) says why) for parameters fleet_replay_create refuses. */
 int fleet_replay_layout(const FleetReplayParams* p, FleetReplayLayout* out);
-/* The parameters are validated BEFORE the device is touched: FLEET_ERR_INVALID for E, buffer_size, D or A < 1, R * E >= 2^31, a
- * wrong struct_bytes, a null pointer.  Then: one allocation, zero-filled (a failure names its byte count). */
+/* The parameters are validated BEFORE the device is touched: FLEET_ERR_INVALID for E, buffer_size, D or A < 1, R * E >= 2^31, an
+ * E, D or A past the limits above (the message states them), a wrong struct_bytes, a null pointer.  Then: one allocation,
+ * zero-filled (a failure names its byte count). */
 int fleet_replay_create(int device, const FleetReplayParams* p, fleet_replay_handle* out);
 int fleet_replay_destroy(fleet_replay_handle r);
 const char* fleet_replay_last_error(fleet_replay_handle r);  /* r may be NULL: error of the last failed create / layout */
