@@ -7,7 +7,7 @@
     from fleetrl_amd import DevicePolicy, evaluate_policy
     from fleetrl_amd import DevicePinkNoise, DeviceOUNoise
     from fleetrl_amd import DeviceTD3Target
-    from fleetrl_amd import DeviceSACNetworks
+    from fleetrl_amd import DeviceSACNetworks, DeviceSACGrad
     from fleetrl_amd import DevicePPOGrad
     from fleetrl_amd import DeviceTD3Grad
     from fleetrl_amd import DeviceAdam
@@ -53,10 +53,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import qtarget
 
         return qtarget.DeviceTD3Target
-    if name == "DeviceSACNetworks":
+    if name in ("DeviceSACNetworks", "DeviceSACGrad", "SAC_ACTOR_STATS"):
         from . import sac
 
-        return sac.DeviceSACNetworks
+        return getattr(sac, name)
     if name == "DevicePPOGrad":
         from . import ppo
 

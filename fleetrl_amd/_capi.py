@@ -216,6 +216,15 @@ class FleetSacTargetArgs(C.Structure):
                 ("target_q", C.c_void_p), ("next_actions", C.c_void_p), ("next_log_prob", C.c_void_p), ("q", C.c_void_p)]
 
 
+# ---- SAC's actor and entropy-coefficient gradients (include/fleet_hip.h "SAC actor and entropy-coefficient gradients on the device") --
+class FleetSacActorArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("B", C.c_int32), ("noise_mode", C.c_int32), ("row_offset", C.c_int32),
+                ("seed", C.c_uint64), ("step", C.c_uint64), ("obs", C.c_void_p), ("ent_coef", C.c_void_p), ("noise", C.c_void_p),
+                ("log_ent_coef", C.c_void_p), ("log_ent_coef_grad", C.c_void_p), ("target_entropy", C.c_float), ("reserved", C.c_int32),
+                ("actions_out", C.c_void_p), ("log_prob_out", C.c_void_p), ("q_out", C.c_void_p), ("dheads_out", C.c_void_p),
+                ("stats", C.c_void_p)]
+
+
 # ---- PPO minibatch gradients (include/fleet_hip.h "PPO minibatch gradients on the device", fleet_ppo_*) ------------------------------
 class FleetPpoParams(C.Structure):
     _fields_ = [("struct_bytes", C.c_int32), ("max_batch", C.c_int32)]
@@ -712,6 +721,10 @@ def load_library():
     lib.fleet_sac_target_dev.argtypes = [vp, vp, f32p, f32p, f32p, C.c_int, C.POINTER(FleetSacTargetArgs)]
     for name in SAC_SYMBOLS:
         getattr(lib, name).restype = C.c_char_p if name == "fleet_sac_last_error" else C.c_int
+    # SAC's actor and entropy-coefficient gradients (fleet_td3.hip), on a fleet_td3 handle
+    lib.fleet_sac_actor_grad_dev.argtypes = [vp, C.POINTER(FleetSacActorArgs), C.POINTER(vp), C.c_int]
+    for name in SAC_GRAD_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
     # rollout collection (fleet_collect.hip)
     lib.fleet_collect_create.argtypes = [vp, vp, vp, C.POINTER(FleetCollectParams), C.POINTER(vp)]
     lib.fleet_collect_destroy.argtypes = [vp]
@@ -821,6 +834,10 @@ OFFPOLICY_SYMBOLS = ("fleet_offpolicy_create", "fleet_offpolicy_destroy", "fleet
                      "fleet_offpolicy_td3_dev", "fleet_offpolicy_polyak_dev")
 
 SAC_SYMBOLS = ("fleet_sac_create", "fleet_sac_last_error", "fleet_sac_act_dev", "fleet_sac_target_dev")
+
+# SAC's actor and entropy-coefficient gradients on the fleet_td3 handle: the header declares the entry `extern FLEET_API int`, behind the SAC
+# family's own (closed) entry list, so it stands in a list of its own here as well
+SAC_GRAD_SYMBOLS = ("fleet_sac_actor_grad_dev",)
 
 COLLECT_SYMBOLS = ("fleet_collect_create", "fleet_collect_destroy", "fleet_collect_last_error", "fleet_collect_describe",
                    "fleet_collect_reset_dev", "fleet_collect_ppo_dev", "fleet_collect_offpolicy_dev", "fleet_collect_episodes_dev",

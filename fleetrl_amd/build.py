@@ -12,7 +12,7 @@ SOURCES = ("fleet_kernels.hip", "fleet_capi.hip", "fleet_tables.hip", "fleet_hos
            "fleet_offpolicy.hip", "fleet_logsum.hip", "fleet_collect.hip", "fleet_eval.hip", "fleet_sac.hip")
 HEADERS = ("fleet_device.h", "fleet_batch.h", "fleet_direct.h", "fleet_norm.h", "fleet_lp.h", "fleet_state.h", "fleet_rollout.h", "fleet_replay.h",
            "fleet_handle.h", "fleet_mlp.h", "fleet_policy.h", "fleet_policy_dev.h", "fleet_philox.h", "fleet_noise.h", "fleet_qtarget.h",
-           "fleet_grad_dev.h", "fleet_adam.h", "fleet_train.h", "fleet_offpolicy.h", "fleet_logsum.h", "fleet_collect.h", "fleet_eval.h",
+           "fleet_grad_dev.h", "fleet_adam.h", "fleet_train.h", "fleet_offpolicy.h", "fleet_logsum.h", "fleet_collect.h", "fleet_eval.h", "fleet_sac_dev.h",
            # the parts of fleet_kernels.hip (one translation unit: these are compiled into the library AND into the code object)
            "fleet_stamps.h", "fleet_wave.h", "fleet_obs.h", "fleet_rainflow.h", "fleet_reset.h", "fleet_aux_kernels.h", "fleet_step_plan.h",
            os.path.join("..", "..", "include", "fleet_hip.h"))  # relative to csrc/

@@ -6,7 +6,12 @@ with its weights (`load_torch`, `polyak`, `export_torch`, `describe`) works tens
 gives the critics' gradients and `DeviceAdam(nets, ..., nets="critic")` steps them.  Two launches are this module's own: `act`, the
 stochastic squashed-Gaussian action `tanh(mean + exp(log_std) * eps)` with its log-probability, and `target`, the entropy-regularised
 bootstrap target `r + (1 - d) * gamma * (min_c Q'_c(s', a') - alpha * log pi(a'|s'))` with `a'` drawn from the ONLINE actor and the
-critics of a second, TARGETS handle.  The actor and entropy-coefficient losses, and their backward passes, stay torch's.
+critics of a second, TARGETS handle.
+
+`DeviceSACGrad` adds the backward side (include/fleet_hip.h `fleet_sac_actor_grad_dev`, fleetrl_amd/csrc/fleet_td3.hip): the actor loss
+`mean(alpha * log pi(a|s) - min_c Q_c(s, a))` with its gradient in the actor's parameters, and the entropy-coefficient loss with the
+gradient of `log_ent_coef`, in two launches.  `actor_update` and `gradient_step` compose SB3's whole `SAC.train` step from it,
+`critic_update`, `DeviceAdam` and `polyak`: torch's share of a gradient step is one `exp` of a one-element tensor.
 """
 from __future__ import annotations
 
@@ -21,8 +26,13 @@ from ._mlp import _arrays
 from .policy import _chain, _single, read_sb3_state_dict
 from .qtarget import DeviceTD3Target
 from .replay import _norm_handle
+from .td3 import DeviceTD3Grad
 
-__all__ = ["DeviceSACNetworks", "parse_sac_state_dict", "critic_update", "CRITIC_LOSS_SCALE"]
+__all__ = ["DeviceSACNetworks", "DeviceSACGrad", "parse_sac_state_dict", "critic_update", "actor_update", "gradient_step",
+           "fused_head_parameters", "CRITIC_LOSS_SCALE", "SAC_ACTOR_STATS"]
+
+# what `DeviceSACGrad.actor_grad` returns in stats[0..4] (ent_coef_loss: 0 when log_ent_coef is not given)
+SAC_ACTOR_STATS = ("actor_loss", "ent_coef_loss", "log_prob_mean", "qmin_mean", "ent_coef")
 
 # SB3's SAC critic loss is 0.5 * sum_c mse(q_c, y); the TD3 gradient launches form sum_c mse(q_c, y)
 CRITIC_LOSS_SCALE = 0.5
@@ -46,6 +56,70 @@ def critic_update(nets, targets, grad, adam, batch, critic_params, *, gamma: flo
         torch._foreach_mul_([p.grad for p in critic_params], float(loss_scale))
     adam.step()
     return y
+
+
+def actor_update(grad, adam, obs, actor_params, *, ent_coef, seed: int, step: int, log_ent_coef=None, ent_adam=None, target_entropy=None,
+                 stats_out=None, **outputs):
+    """The actor half of one `SAC.train` gradient step: `grad.actor_grad` (a `DeviceSACGrad`; two launches) and `adam.step()` (a
+    `DeviceAdam` on the networks with `nets="actor"`).  With `log_ent_coef` (a one-element leaf tensor on the device) the launches also
+    write its `.grad`, and `ent_adam` -- a `DeviceAdam(nets, [log_ent_coef], nets="none")` -- steps it.  The critics are the image's:
+    call this after `critic_update`, as SB3 does.  `outputs`: `actor_grad`'s optional tensors.  Returns the stats (`SAC_ACTOR_STATS`)."""
+    if (log_ent_coef is None) != (ent_adam is None):
+        raise ValueError("log_ent_coef and ent_adam are given together: a learned entropy coefficient has its own optimiser")
+    stats = grad.actor_grad(obs, ent_coef=ent_coef, seed=seed, step=step, into=actor_params, log_ent_coef=log_ent_coef,
+                            target_entropy=target_entropy, stats_out=stats_out, **outputs)
+    adam.step()
+    if ent_adam is not None:
+        ent_adam.step()
+    return stats
+
+
+def gradient_step(nets, targets, grad, actor_adam, critic_adam, batch, actor_params, critic_params, *, gamma: float, tau: float, seed: int,
+                  target_seed: int, step: int, ent_coef=None, log_ent_coef=None, ent_adam=None, target_entropy=None, alpha_out=None,
+                  critic_stats_out=None, actor_stats_out=None):
+    """One gradient step of SB3's `SAC.train`, in SB3's order of effects, with no autograd: (1) alpha = exp(log_ent_coef), read BEFORE
+    its optimiser step, into `alpha_out` f32 [1] (made when None) -- or the fixed `ent_coef`; (2) `critic_update` under `target_seed`;
+    (3) `actor_update` under `seed`, on the critics just stepped, which also steps `log_ent_coef`; (4) `targets.polyak` over the online
+    parameters.  Give exactly one of `ent_coef` (fixed: a device tensor f32 [1] or a float) and `log_ent_coef` with `ent_adam`
+    (learned).  Returns (critic stats, actor stats, alpha)."""
+    import torch
+
+    if (ent_coef is None) == (log_ent_coef is None):
+        raise ValueError("give exactly one of ent_coef (fixed) and log_ent_coef (learned)")
+    if log_ent_coef is not None:
+        alpha = torch.exp(log_ent_coef.detach(), out=alpha_out)
+    else:
+        alpha = ent_coef
+    cs = torch.empty(8, device=batch.observations.device, dtype=torch.float32) if critic_stats_out is None else critic_stats_out
+    critic_update(nets, targets, grad, critic_adam, batch, critic_params, gamma=gamma, ent_coef=alpha, seed=target_seed, step=step,
+                  stats_out=cs)
+    st = actor_update(grad, actor_adam, batch.observations, actor_params, ent_coef=alpha, seed=seed, step=step, log_ent_coef=log_ent_coef,
+                      ent_adam=ent_adam, target_entropy=target_entropy, stats_out=actor_stats_out)
+    targets.polyak(list(actor_params) + list(critic_params), tau)
+    return cs, st, alpha
+
+
+def fused_head_parameters(actor):
+    """The ONE `[2A, H]` / `[2A]` parameter pair of an SB3 SAC actor's two heads, made so that torch's own tensors follow it: one
+    concatenated leaf per kind is allocated (the one copy this costs), and `actor.mu.{weight,bias}` / `actor.log_std.{weight,bias}` are
+    re-pointed at its two halves -- `.data` AND `.grad` become views of the pair's storage and of the pair's `.grad`.  From then on a
+    gradient written into the pair is the `.grad` of torch's `mu` and `log_std`, and an optimiser step on either side moves both, with
+    no copy.  `actor`: anything with `mu` and `log_std` linear modules of one shape.  Returns (weight [2A, H], bias [2A]) leaves with
+    zeroed `.grad`.  An optimiser built over `actor.parameters()` BEFORE this call keeps working: the parameter objects stay."""
+    import torch
+
+    pair = []
+    for kind in ("weight", "bias"):
+        m, l = getattr(actor.mu, kind), getattr(actor.log_std, kind)
+        if m.shape != l.shape:
+            raise ValueError(f"actor.mu.{kind} {tuple(m.shape)} and actor.log_std.{kind} {tuple(l.shape)} differ in shape")
+        A = m.shape[0]
+        full = torch.cat([m.detach(), l.detach()], 0).contiguous().requires_grad_(True)
+        full.grad = torch.zeros_like(full)
+        m.data, l.data = full.data[:A], full.data[A:]
+        m.grad, l.grad = full.grad[:A], full.grad[A:]
+        pair.append(full)
+    return tuple(pair)
 
 
 def parse_sac_state_dict(sd: dict, which: str = "online") -> dict:
@@ -213,3 +287,69 @@ class DeviceSACNetworks(DeviceTD3Target):
         d = super().describe()
         d["squashed"] = True
         return d
+
+
+class DeviceSACGrad(DeviceTD3Grad):
+    """`DeviceTD3Grad` on a `DeviceSACNetworks` (the ONLINE networks) with SAC's actor entry.  `critic_grad` is inherited unchanged; the
+    inherited TD3 `actor_grad` is replaced by the squashed-Gaussian one (the library refuses the TD3 entry on such networks)."""
+
+    def __init__(self, nets, max_batch: int):
+        if not isinstance(nets, DeviceSACNetworks):
+            raise TypeError("DeviceSACGrad works on a DeviceSACNetworks; a TD3 actor's gradient is DeviceTD3Grad's")
+        super().__init__(nets, max_batch)
+
+    def sac_actor_grad_dev(self, args: "_capi.FleetSacActorArgs", grad_ptrs, count: int):
+        """Raw device addresses in a FleetSacActorArgs and a (c_void_p * count) array, on the networks handle's stream."""
+        args.struct_bytes = C.sizeof(_capi.FleetSacActorArgs)
+        self._check(self.lib.fleet_sac_actor_grad_dev(self.h, C.byref(args), grad_ptrs, int(count)))
+
+    def actor_grad(self, obs, *, ent_coef, seed: int, step: int, into, row_offset: int = 0, log_ent_coef=None, target_entropy=None, noise=None,
+                   noise_given: bool = False, actions_out=None, log_prob_out=None, q_out=None, dheads_out=None, stats_out=None):
+        """SAC's actor loss mean(alpha * log pi(a|obs) - min_c Q_c(obs, a)), a = the squashed sample `DeviceSACNetworks.act` draws under
+        (seed, row_offset + row, step), and its gradient in the ACTOR's parameters: two launches on torch's current stream, no host
+        synchronisation.  obs f32 [B, obs_dim]; ent_coef: alpha as a device tensor f32 [1], read when the launches run (a float also
+        does, through a cached tensor).  into: the actor's torch parameters, W, b per layer -- SB3's `latent_pi`, then the ONE
+        `[2A, H]` pair (`parse_sac_state_dict`; `fused_head_parameters` makes it from a torch actor); their `.grad` is overwritten, the
+        critics' is not touched.  log_ent_coef: a one-element device leaf tensor -- its `.grad` receives
+        -(mean(log pi) + target_entropy) (target_entropy: default -act_dim, SB3's "auto").  noise f32 [B, act_dim]: read with
+        noise_given, else it receives the draw.  actions_out [B, act_dim], log_prob_out [B], q_out [B, n_critics], dheads_out
+        [B, 2 * act_dim] (the last layer's delta: d mean, then d log_std).  Returns stats f32 [8]: `SAC_ACTOR_STATS`, then zeros."""
+        import torch
+
+        self.use_torch_stream()
+        f32, A = (torch.float32,), self.act_dim
+        B = int(obs.shape[0]) if obs.ndim == 2 else 0
+        a = _capi.FleetSacActorArgs()
+        a.B, a.row_offset = B, int(row_offset)
+        a.noise_mode = _capi.EXPLORE_NOISE_GIVEN if noise_given else _capi.EXPLORE_NOISE_DRAW
+        a.seed, a.step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+        a.target_entropy = -float(A) if target_entropy is None else float(target_entropy)
+        keep = [self._tensor(obs, (B, self.obs_dim), f32)]
+        a.obs = keep[0].data_ptr()
+        if isinstance(ent_coef, torch.Tensor):
+            alpha = self._tensor(ent_coef.detach(), (1,), f32)
+        else:
+            hit = self.nets._constants.get("ent_coef")
+            if hit is None or hit[0] != float(ent_coef):
+                hit = self.nets._constants["ent_coef"] = (float(ent_coef), torch.full((1,), float(ent_coef), device=keep[0].device, dtype=torch.float32))
+            alpha = hit[1]
+        keep.append(alpha)
+        a.ent_coef = alpha.data_ptr()
+        if stats_out is None:
+            stats_out = torch.empty(8, device=keep[0].device, dtype=torch.float32)
+        a.stats = self._tensor(stats_out, (8,), f32).data_ptr()
+        if noise_given and noise is None:
+            raise ValueError("noise_given needs the noise tensor")
+        if log_ent_coef is not None:
+            if log_ent_coef.grad is None:
+                log_ent_coef.grad = torch.zeros_like(log_ent_coef)
+            keep += [self._tensor(log_ent_coef.detach(), (1,), f32), self._tensor(log_ent_coef.grad, (1,), f32)]
+            a.log_ent_coef, a.log_ent_coef_grad = keep[-2].data_ptr(), keep[-1].data_ptr()
+        for name, t, shape in (("noise", noise, (B, A)), ("actions_out", actions_out, (B, A)), ("log_prob_out", log_prob_out, (B,)),
+                               ("q_out", q_out, (B, self.n_critics)), ("dheads_out", dheads_out, (B, 2 * A))):
+            if t is not None:
+                keep.append(self._tensor(t, shape, f32))
+                setattr(a, name, keep[-1].data_ptr())
+        arr = self._grad_pointers("actor", into, self._shapes["actor"], "the actor's")
+        self.sac_actor_grad_dev(a, arr, len(self._shapes["actor"]))
+        return stats_out

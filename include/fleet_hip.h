@@ -2076,8 +2076,9 @@ FLEET_API int fleet_ppo_grad_gated_dev(fleet_ppo_handle h, const FleetPpoGradGat
  * 16 rows through the online actor, then through the target critics: two image bases, no atomics, no ordering between workgroups.
  * The targets handle keeps a copy of the actor that nothing reads; a Polyak update over all tensors stays correct.  As for the TD3
  * targets, the target gets a SEED OF ITS OWN, different from the acting seed.
- * Every *_dev call takes device pointers, only enqueues and runs on the handle's stream (fleet_qtarget_set_stream).  Out of scope: the
- * actor and entropy-coefficient gradients, a one-call train(), a SAC collector, gSDE, a log_ent_coef form of alpha. */
+ * Every *_dev call takes device pointers, only enqueues and runs on the handle's stream (fleet_qtarget_set_stream).  The actor and
+ * entropy-coefficient gradients are the section below's.  Out of scope: a one-call train(), a SAC collector, gSDE, a log_ent_coef
+ * form of alpha. */
 typedef struct FleetSacParams {
   int32_t struct_bytes;       /* sizeof(FleetSacParams) */
   int32_t obs_dim;            /* D >= 1 */
@@ -2134,6 +2135,63 @@ int fleet_sac_act_dev(fleet_qtarget_handle nets, const float* obs, int E, fleet_
  * not make, obs_dim, act_dim or n_critics that differ between the two, another device, handles that do not launch on one stream. */
 int fleet_sac_target_dev(fleet_qtarget_handle online, fleet_qtarget_handle targets, const float* next_obs, const float* rewards,
                          const float* dones, int B, const FleetSacTargetArgs* a);
+
+/* ==== SAC actor and entropy-coefficient gradients on the device (fleet_td3.hip: sac_actor_rows, sac_weights; DESIGN.md "SAC's actor
+ * ==== and entropy-coefficient gradients on the device") ==============================================================================
+ * (an entry added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays.  It is declared
+ * `extern FLEET_API int`, behind the SAC section's own -- closed -- list of entries, and starts with fleet_sac_.)
+ * What stable-baselines3 2.3.2's SAC.train does with one minibatch for the actor and for a learned entropy coefficient, in TWO launches,
+ * on a fleet_td3 handle whose networks handle came from fleet_sac_create (the ONLINE networks, the critics AFTER their optimiser step):
+ *   actions_pi, log_prob = actor.action_log_prob(obs)
+ *   ent_coef_loss = -(log_ent_coef * (log_prob + target_entropy).detach()).mean()
+ *   actor_loss    = (ent_coef * log_prob - min_c critic_c(obs, actions_pi)).mean()              (gradient into the actor only)
+ * Forward, per row b: m, l, ls, eps, a and lp = log_prob exactly as the section above has them -- the same epilogue code: under one
+ * (seed, row_offset + b, step) the bits fleet_sac_act_dev gives for that row; q_c = critic c over concat(obs[b], a), the learning
+ * targets' chain; the selecting critic k = 1 when n_critics == 2 and NOT (q_0 <= q_1), else 0; qmin = q_k.
+ * Backward, float32, every operation rounded on its own (no contraction but the fmaf written); invB = 1.0f / (float)B, alpha =
+ * ent_coef[0] read when the launch runs, ab = alpha * invB:
+ *   critic c is walked back from dq = -invB in the rows with k == c and 0.0f in the others, as fleet_td3_actor_grad_dev walks critic 0,
+ *   to its first layer's delta d0 and into the action columns: da_c[j] = (acc = 0; acc = fmaf(Wt0[D + j][i], d0[i], acc), i ascending);
+ *   da[j] = da_0[j], with two critics da_0[j] + da_1[j]        (one addend is an exact zero in every row)
+ *   w     = 1.0f - a[j] * a[j];   g = (2.0f * a[j]) / (w + 1e-6f);   dLa = da[j] + ab * g;   du = dLa * w
+ *   dm[j] = du                                                       (the delta of column j of the actor's last layer)
+ *   dl[j] = (l[j] >= -20.0f && l[j] <= 2.0f) ? (du * (sdb * eps[j])) - ab : 0.0f      (the delta of column A + j; torch's clamp
+ *           backward, the bounds inclusive)   with sdb = (float)exp((double)ls[j]): the DOUBLE exponential rounded once, not the
+ *           forward's expf, so that the deltas can be restated from stored values (ls, eps, a) without the device's expf bits
+ *   then back through the actor's layers and into dW, db exactly as the TD3 section has it (d_prev, dW[j][k], db[j]).
+ * No critic gradient is produced (SB3 discards it there too).  The last layer's pair is the ONE [2A, H] / [2A] pair of the image.
+ * Statistics, stats f32[8], tiles and compensated sums as the TD3 section has them, term_b = alpha * lp - qmin (two roundings):
+ *   [0] actor_loss = total(term) * invB;  [2] = total(lp) * invB;  [3] = total(qmin) * invB;  [4] = alpha as read;  [5..7] 0
+ *   with log_ent_coef:  gl = -([2] + target_entropy);  log_ent_coef_grad[0] = gl;  [1] ent_coef_loss = log_ent_coef[0] * gl;  else [1] = 0
+ * Every result is a function of the inputs and B only, as for the TD3 entries; the gradient tensors, stats and log_ent_coef_grad are
+ * OVERWRITTEN.  Launches on the NETWORKS handle's stream; rows at and past B are neither read nor written. */
+typedef struct FleetSacActorArgs {
+  int32_t struct_bytes;        /* sizeof(FleetSacActorArgs) */
+  int32_t B;                   /* rows, 1..max_batch */
+  int32_t noise_mode;          /* FLEET_EXPLORE_NOISE_DRAW / _GIVEN */
+  int32_t row_offset;          /* global id of row 0; >= 0 */
+  uint64_t seed;               /* Philox key */
+  uint64_t step;               /* Philox counter words 2, 3 */
+  const float* obs;            /* device f32[B, D] (normalised, as the replay buffer samples them) */
+  const float* ent_coef;       /* device f32[1]: alpha itself, read when the launches run */
+  float* noise;                /* device f32[B, A] or NULL: read (GIVEN), written when not NULL (DRAW) */
+  const float* log_ent_coef;   /* device f32[1] or NULL: asks for ent_coef_loss and its gradient */
+  float* log_ent_coef_grad;    /* device f32[1]: given exactly when log_ent_coef is */
+  float target_entropy;        /* SB3's "auto": -(float)A */
+  int32_t reserved;            /* 0 */
+  float* actions_out;          /* device f32[B, A] or NULL: a */
+  float* log_prob_out;         /* device f32[B] or NULL: lp */
+  float* q_out;                /* device f32[B, n_critics] or NULL: q_c */
+  float* dheads_out;           /* device f32[B, 2A] or NULL: dm, then dl */
+  float* stats;                /* device f32[8] */
+} FleetSacActorArgs;
+/* Two launches, enqueued only.  grads: W, b per layer of the actor; count is checked as fleet_td3_actor_grad_dev checks it.
+ * FLEET_ERR_INVALID (nothing is launched; the message starts with the entry's name) for a null or wrongly sized FleetSacActorArgs, an
+ * unknown noise_mode, B < 1, a null obs / ent_coef / stats, GIVEN with a null noise, a negative row_offset, one of log_ent_coef and
+ * log_ent_coef_grad without the other, a reserved that is not 0, a null grads or a null pointer in it -- looked at before the handle:
+ * with h NULL the reason (or "null handle") goes to fleet_td3_last_error(NULL) -- and, with the handle, a wrong count, B > max_batch,
+ * and networks whose actor is not squashed (the message points to fleet_td3_actor_grad_dev). */
+extern FLEET_API int fleet_sac_actor_grad_dev(fleet_td3_handle h, const FleetSacActorArgs* a, float* const* grads, int count);
 
 #ifdef __cplusplus
 }
