@@ -404,6 +404,8 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   // the fetch cannot sink to its use.  Behind the leader's loads: the compiler takes a volatile asm for a store, and a uniform load
   // behind it is no longer a scalar one.
   if constexpr (kTailA) asm volatile("" ::"s"(d_arg.rf_row_stride), "s"(d_arg.stack_cap));
+  // (the same for rf_finish_win's stress_temp: the float32 rainflow twins only, as `kRfDeep` below)
+  if constexpr (DEAD && !A64 && DEG == FLEET_DEG_RAINFLOW) asm volatile("" ::"s"(d_arg.stress_temp));
   if (DEG == FLEET_DEG_RAINFLOW && MULTI) {
     rf_until = p_env[e].rf_until;
     if (G >= 64) rf_until = __builtin_amdgcn_readfirstlane(rf_until);

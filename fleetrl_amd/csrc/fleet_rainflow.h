@@ -248,6 +248,11 @@ __device__ __forceinline__ void rf_finish_own_b(const FleetDev& d, const EvIx& i
 // The live instances and the float64 twins keep rf_finish_own_b: with the deeper window they fall from five resident wavefronts per
 // SIMD to four (99 / 98 VGPRs), which the closed loop pays for at the large shapes (+2.7 % at 16384 x 50, +6.5 % at c5).
 // `b` gets a register of its own as in rf_finish_as<true>; the same care for the closed-cycle count (`k`).
+// stress_temp is read as the kernel argument (`d.stress_temp`), which the twin fetches with its entry's argument loads
+// (fleet_kernels.hip), not from the device-resident copy of the argument block as in rf_finish_as: that was a vector load of a launch
+// constant with a `vmcnt(0)` behind it in each inlined cycle_stress, a wait that also covers the push's stores -- and the copy's
+// pointer was one more late scalar fetch on every wavefront's path (EXPERIMENTS.md "Rainflow push in the twin: no load wait behind a
+// store", which also has the two re-orderings of this function's stores and of its `csum` update that were measured and not kept).
 __device__ __forceinline__ void rf_finish_win(const FleetDev& d, const EvIx& i, const RfReq& q, int& tail, RfTop& top, RfAccHead& acc_out,
                                                 uint32_t& err) {
   if (!q.push) return;
@@ -297,11 +302,11 @@ __device__ __forceinline__ void rf_finish_win(const FleetDev& d, const EvIx& i, 
     if (half2) stk[0] = b1;
     if (k > k_stress) {  // the last closure has the largest index: one test for both
       if (0 >= k_stress) {
-        dcsum = cycle_stress(fabs(a0 - b0), 0.5 * (a0 + b0), half ? 0.5 : 1.0, d.self->stress_temp);
+        dcsum = cycle_stress(fabs(a0 - b0), 0.5 * (a0 + b0), half ? 0.5 : 1.0, d.stress_temp);
         has_csum = true;
       }
       if (closes2) {
-        dcsum += cycle_stress(fabs(a1 - b1), 0.5 * (a1 + b1), half2 ? 0.5 : 1.0, d.self->stress_temp);
+        dcsum += cycle_stress(fabs(a1 - b1), 0.5 * (a1 + b1), half2 ? 0.5 : 1.0, d.stress_temp);
         has_csum = true;
       }
     }
@@ -309,7 +314,7 @@ __device__ __forceinline__ void rf_finish_win(const FleetDev& d, const EvIx& i, 
     if (full2 && (t >= 3) && !(fabs(p - b) < fabs(b - a))) {
       do {
         if (k >= k_stress) {
-          dcsum += cycle_stress(fabs(a - b), 0.5 * (a + b), (t == 3) ? 0.5 : 1.0, d.self->stress_temp);
+          dcsum += cycle_stress(fabs(a - b), 0.5 * (a + b), (t == 3) ? 0.5 : 1.0, d.stress_temp);
           has_csum = true;
         }
         mean_sum += 0.5 * (a + b);
