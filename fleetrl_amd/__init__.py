@@ -13,6 +13,7 @@
     from fleetrl_amd import DeviceAdam
     from fleetrl_amd import DevicePPOTrain
     from fleetrl_amd import DeviceTD3Train
+    from fleetrl_amd import DeviceSACTrain
     from fleetrl_amd import DevicePPOCollect, DeviceTD3Collect
     from fleetrl_amd import DeviceEvalCallback
     from fleetrl_amd import LogSummary, summarize_log, compare, evaluate_strategies
@@ -77,6 +78,10 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import offpolicy
 
         return offpolicy.DeviceTD3Train
+    if name in ("DeviceSACTrain", "SAC_TRAIN_STATS", "SAC_TRAIN_SB3_NAMES"):
+        from . import sac_train
+
+        return getattr(sac_train, name)
     if name in ("DevicePPOCollect", "DeviceTD3Collect"):
         from . import collect
 

@@ -317,6 +317,28 @@ class FleetOffpolicyInfo(C.Structure):
                 ("staging", C.c_void_p), ("slots", C.c_void_p)]
 
 
+# ---- SAC's whole update (include/fleet_hip.h "SAC's whole update on the device", fleet_sactrain_*) ----------------------------------------
+SACTRAIN_MAX_STEPS, SACTRAIN_SLOT_FLOATS, SACTRAIN_SCALE_CHUNK = 65536, 16, 1024
+
+
+class FleetSacTrainParams(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("max_steps", C.c_int32)]
+
+
+class FleetSacTrainArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("gradient_steps", C.c_int32), ("batch_size", C.c_int32), ("target_update_interval", C.c_int32),
+                ("gamma", C.c_float), ("target_entropy", C.c_float), ("tau", C.c_double), ("loss_scale", C.c_double), ("lr", C.c_double),
+                ("beta1", C.c_double * 3), ("beta2", C.c_double * 3), ("eps", C.c_double * 3), ("max_grad_norm", C.c_double * 3),
+                ("seed", C.c_uint64), ("target_seed", C.c_uint64), ("first_update", C.c_uint64), ("ent_coef", C.c_void_p),
+                ("log_ent_coef", C.c_void_p), ("log_ent_coef_grad", C.c_void_p), ("norm", C.c_void_p), ("stats", C.c_void_p)]
+
+
+class FleetSacTrainInfo(C.Structure):
+    _fields_ = [("obs_dim", C.c_int32), ("act_dim", C.c_int32), ("n_critics", C.c_int32), ("max_batch", C.c_int32), ("max_steps", C.c_int32),
+                ("n_actor_tensors", C.c_int32), ("n_critic_tensors", C.c_int32), ("learned_alpha", C.c_int32), ("scale_chunks", C.c_int32),
+                ("reserved", C.c_int32), ("staging_bytes", C.c_uint64), ("staging", C.c_void_p), ("alpha", C.c_void_p), ("slots", C.c_void_p)]
+
+
 # ---- rollout collection (include/fleet_hip.h "collect_rollouts on the device", fleet_collect_*) ----------------------------------------
 COLLECT_MAX_WINDOW, COLLECT_STATS = 4096, 16
 
@@ -725,6 +747,18 @@ def load_library():
     lib.fleet_sac_actor_grad_dev.argtypes = [vp, C.POINTER(FleetSacActorArgs), C.POINTER(vp), C.c_int]
     for name in SAC_GRAD_SYMBOLS:
         getattr(lib, name).restype = C.c_int
+    # SAC's whole update (fleet_sactrain.hip)
+    lib.fleet_sactrain_create.argtypes = [vp, vp, vp, vp, vp, vp, C.POINTER(FleetSacTrainParams), C.POINTER(vp)]
+    lib.fleet_sactrain_destroy.argtypes = [vp]
+    lib.fleet_sactrain_last_error.argtypes = [vp]
+    lib.fleet_sactrain_describe.argtypes = [vp, C.POINTER(FleetSacTrainInfo)]
+    lib.fleet_sactrain_alpha_dev.argtypes = [vp, vp, vp]
+    lib.fleet_sactrain_scale_dev.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_double]
+    lib.fleet_sactrain_polyak_dev.argtypes = [vp, C.c_double]
+    lib.fleet_sactrain_sac_dev.argtypes = [vp, C.POINTER(FleetSacTrainArgs), C.POINTER(vp), C.POINTER(vp), C.c_int, C.POINTER(vp),
+                                           C.POINTER(vp), C.c_int]
+    for name in SACTRAIN_SYMBOLS:
+        getattr(lib, name).restype = C.c_char_p if name == "fleet_sactrain_last_error" else C.c_int
     # rollout collection (fleet_collect.hip)
     lib.fleet_collect_create.argtypes = [vp, vp, vp, C.POINTER(FleetCollectParams), C.POINTER(vp)]
     lib.fleet_collect_destroy.argtypes = [vp]
@@ -838,6 +872,10 @@ SAC_SYMBOLS = ("fleet_sac_create", "fleet_sac_last_error", "fleet_sac_act_dev", 
 # SAC's actor and entropy-coefficient gradients on the fleet_td3 handle: the header declares the entry `extern FLEET_API int`, behind the SAC
 # family's own (closed) entry list, so it stands in a list of its own here as well
 SAC_GRAD_SYMBOLS = ("fleet_sac_actor_grad_dev",)
+
+# SAC's whole update: the header declares these `FLEET_API extern`, behind every closed entry list, so they stand in a list of their own
+SACTRAIN_SYMBOLS = ("fleet_sactrain_create", "fleet_sactrain_destroy", "fleet_sactrain_last_error", "fleet_sactrain_describe",
+                    "fleet_sactrain_alpha_dev", "fleet_sactrain_scale_dev", "fleet_sactrain_polyak_dev", "fleet_sactrain_sac_dev")
 
 COLLECT_SYMBOLS = ("fleet_collect_create", "fleet_collect_destroy", "fleet_collect_last_error", "fleet_collect_describe",
                    "fleet_collect_reset_dev", "fleet_collect_ppo_dev", "fleet_collect_offpolicy_dev", "fleet_collect_episodes_dev",

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ("fleet_kernels.hip", "fleet_capi.hip", "fleet_tables.hip", "fleet_hostpath.hip", "fleet_tape.hip", "fleet_rccl.hip", "fleet_direct.hip",
            "fleet_norm.hip", "fleet_lp.hip", "fleet_state.hip", "fleet_rollout.hip", "fleet_replay.hip", "fleet_policy.hip", "fleet_noise.hip",
            "fleet_qtarget.hip", "fleet_mlp.hip", "fleet_ppo.hip", "fleet_td3.hip", "fleet_adam.hip", "fleet_train.hip",
-           "fleet_offpolicy.hip", "fleet_logsum.hip", "fleet_collect.hip", "fleet_eval.hip", "fleet_sac.hip")
+           "fleet_offpolicy.hip", "fleet_logsum.hip", "fleet_collect.hip", "fleet_eval.hip", "fleet_sac.hip", "fleet_sactrain.hip")
 HEADERS = ("fleet_device.h", "fleet_batch.h", "fleet_direct.h", "fleet_norm.h", "fleet_lp.h", "fleet_state.h", "fleet_rollout.h", "fleet_replay.h",
            "fleet_handle.h", "fleet_mlp.h", "fleet_policy.h", "fleet_policy_dev.h", "fleet_philox.h", "fleet_noise.h", "fleet_qtarget.h",
            "fleet_grad_dev.h", "fleet_adam.h", "fleet_train.h", "fleet_offpolicy.h", "fleet_logsum.h", "fleet_collect.h", "fleet_eval.h", "fleet_sac_dev.h",

@@ -63,19 +63,6 @@ struct FinishArgs {
   uint32_t G, delay;
 };
 
-// the ordered sum's tree: every thread's `v` in, the total out to every thread
-__device__ inline double tree_total(double v, double* red) {
-  __syncthreads();  // (the previous total has been read)
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = kOffpolicyThreads / 2; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __global__ __launch_bounds__(kOffpolicyThreads) void offpolicy_finish(FinishArgs a) {
   __shared__ double red[kOffpolicyThreads];
   const uint32_t tid = threadIdx.x, G = a.G;
@@ -116,25 +103,6 @@ std::string check_params(const FleetOffpolicyParams* p) {
   return "";
 }
 
-std::string check_tau(double tau) {
-  if (!(tau >= 0.0 && tau <= 1.0)) return "tau must be in [0, 1], got " + std::to_string(tau);
-  return "";
-}
-
-// what fleet_adam_step_dev and the gradient entries refuse about one network's tensors, in their words behind `who`
-std::string check_tensors(const char* who, float* const* params, float* const* grads, int count) {
-  const std::string w = std::string(who) + ": ";
-  if (!params) return w + "null params";
-  if (!grads) return w + "null grads";
-  if (count < 1 || count > kMlpMaxTensors) return w + "count must be in 1.." + std::to_string(kMlpMaxTensors) + ", got " + std::to_string(count);
-  for (int i = 0; i < count; ++i) {
-    if (!params[i]) return w + "parameter tensor " + std::to_string(i) + " is null";
-    if (!grads[i]) return w + "gradient tensor " + std::to_string(i) + " is null";
-    if (params[i] == grads[i]) return w + "parameter tensor " + std::to_string(i) + " is its own gradient";
-  }
-  return "";
-}
-
 // what fleet_offpolicy_td3_dev refuses, looked at without the handle: its own checks, then fleet_qtarget_target_dev's,
 // fleet_qtarget_polyak_dev's and fleet_adam_step_dev's in their words; "" when the arguments pass
 std::string check_td3_args(const FleetOffpolicyArgs* x, float* const* actor_params, float* const* actor_grads, int n_actor,
@@ -149,7 +117,7 @@ std::string check_td3_args(const FleetOffpolicyArgs* x, float* const* actor_para
   if (!x->sigma) return "null sigma";
   if (!(x->act_lo <= x->act_hi)) return "the bounds need act_lo <= act_hi";
   if (!(x->noise_clip >= 0.0f)) return "noise_clip must be >= 0";
-  if (std::string why = check_tau(x->tau); !why.empty()) return why;
+  if (std::string why = offpolicy_check_tau(x->tau); !why.empty()) return why;
   if (!std::isfinite(x->lr) || x->lr < 0.0) return "lr must be finite and >= 0";
   for (int o = 0; o < 2; ++o) {
     const char* whose = o ? " (the critic optimiser's)" : " (the actor optimiser's)";
@@ -158,23 +126,14 @@ std::string check_td3_args(const FleetOffpolicyArgs* x, float* const* actor_para
     if (!(x->beta2[o] >= 0.0 && x->beta2[o] < 1.0)) return std::string("beta2 must be in [0, 1)") + whose;
     if (std::isnan(x->max_grad_norm[o])) return std::string("max_grad_norm is NaN") + whose;
   }
-  if (std::string why = check_tensors("actor", actor_params, actor_grads, n_actor); !why.empty()) return why;
-  return check_tensors("critics", critic_params, critic_grads, n_critic);
+  if (std::string why = offpolicy_check_tensors("actor", actor_params, actor_grads, n_actor); !why.empty()) return why;
+  return offpolicy_check_tensors("critics", critic_params, critic_grads, n_critic);
 }
-
-// The handles this family is created on keep their definitions in their own files; what it needs of them is what their scaffolds
-// share: a replay buffer's first base is FleetBufferBase<FleetReplayLayout> (fleet_handle.h), a gradient handle's and an optimiser's
-// is FleetMlpUser (fleet_mlp.h), and mlp_borrow relies on the image's handle being its family's first base.
-using ReplayBase = FleetBufferBase<FleetReplayLayout>;
-const ReplayBase* replay_base(fleet_replay_handle r) { return reinterpret_cast<const ReplayBase*>(r); }
-FleetMlpHandle* image_of(void* user) { return reinterpret_cast<FleetMlpUser*>(user)->img; }
 
 // floats of an image's record, rounded up as fleet_mlp.hip lays the first layer behind it
 size_t record_floats(const FleetMlpHandle* img) { return (size_t)mlp_round_up((int)img->record_bytes, 256) / 4; }
 
 }  // namespace
-
-enum { kStageObs, kStageAct, kStageNext, kStageDones, kStageRewards, kStageTargetQ, kStageArrays };
 
 struct FleetOffpolicy : FleetMlpUser {  // img: the ONLINE networks'; block: the staging arrays, then the slots
   fleet_replay_handle replay = nullptr;  // borrowed, as are the five below
@@ -189,14 +148,13 @@ struct FleetOffpolicy : FleetMlpUser {  // img: the ONLINE networks'; block: the
   float* slots() const { return reinterpret_cast<float*>(block + staging_bytes); }
 };
 
-namespace {
-
-// the one launch of the image-to-image update, on the targets' stream (the caller has seen that the online image launches there too)
-int launch_polyak(FleetOffpolicy* h, double tau) {
-  const size_t off = record_floats(h->tgt), n = h->tgt->floats - off;  // (create has seen that both images have these)
+// the one launch of the image-to-image update `tgt` <- `img`, on the targets' stream (the caller has seen that the online image launches
+// there too); h: the handle whose error a failure goes to.  fleet_sactrain.hip launches it on the two SAC images (fleet_offpolicy.h).
+int offpolicy_launch_polyak(FleetMlpUser* h, FleetMlpHandle* tgt, const FleetMlpHandle* img, double tau) {
+  const size_t off = record_floats(tgt), n = tgt->floats - off;  // (create has seen that both images have these)
   PolyakArgs a{};
-  a.t = reinterpret_cast<float*>(h->tgt->block) + off;
-  a.p = reinterpret_cast<const float*>(h->img->block) + off;
+  a.t = reinterpret_cast<float*>(tgt->block) + off;
+  a.p = reinterpret_cast<const float*>(img->block) + off;
   // 16-byte words where both streams reach a word's start together (hipMalloc'ed blocks and fleet_mlp.hip's layout: at once, head 0);
   // otherwise every float goes through the scalar head
   const uintptr_t mt = reinterpret_cast<uintptr_t>(a.t) & 15, mp = reinterpret_cast<uintptr_t>(a.p) & 15;
@@ -204,15 +162,13 @@ int launch_polyak(FleetOffpolicy* h, double tau) {
   if (head > n) head = n;
   a.head = (uint32_t)head, a.words = (uint32_t)((n - head) / 4), a.tail = (uint32_t)((n - head) % 4);
   a.tau = (float)tau, a.omt = (float)(1.0 - tau);
-  FLEET_HANDLE_TRY(h, hipSetDevice(h->tgt->device));
+  FLEET_HANDLE_TRY(h, hipSetDevice(tgt->device));
   const size_t most = a.words > a.head ? a.words : a.head;
   hipLaunchKernelGGL(offpolicy_polyak, dim3(grid_for(most, kOffpolicyThreads, kOffpolicyMaxBlocks)), dim3(kOffpolicyThreads), 0,
-                     h->tgt->stream, a);
+                     tgt->stream, a);
   FLEET_HANDLE_TRY(h, hipGetLastError());
   return FLEET_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -306,11 +262,11 @@ int fleet_offpolicy_describe(fleet_offpolicy_handle h, FleetOffpolicyInfo* out) 
 }
 
 int fleet_offpolicy_polyak_dev(fleet_offpolicy_handle h, double tau) {
-  std::string why = check_tau(tau);
+  std::string why = offpolicy_check_tau(tau);
   if (h && why.empty() && h->tgt->stream != h->img->stream)
     why = "the target networks launch on another stream than the online networks: fleet_qtarget_set_stream both to one first";
   if (const int rc = handle_enter("fleet_offpolicy_polyak_dev", why, h, g_offpolicy_error); rc != FLEET_OK) return rc;
-  return launch_polyak(h, tau);
+  return offpolicy_launch_polyak(h, h->tgt, h->img, tau);
 }
 
 int fleet_offpolicy_td3_dev(fleet_offpolicy_handle h, const FleetOffpolicyArgs* x, float* const* actor_params, float* const* actor_grads,
@@ -385,7 +341,7 @@ int fleet_offpolicy_td3_dev(fleet_offpolicy_handle h, const FleetOffpolicyArgs* 
       return failed(rc, fleet_td3_last_error(h->grad));
     if (const int rc = fleet_adam_step_dev(h->adam_actor, &s[0], actor_params, actor_grads, n_actor); rc != FLEET_OK)
       return failed(rc, fleet_adam_last_error(h->adam_actor));
-    if (const int rc = launch_polyak(h, x->tau); rc != FLEET_OK) return rc;
+    if (const int rc = offpolicy_launch_polyak(h, h->tgt, h->img, x->tau); rc != FLEET_OK) return rc;
   }
   FinishArgs f{};
   f.slots = h->slots(), f.out = x->stats, f.first = x->first_update, f.G = (uint32_t)G, f.delay = (uint32_t)x->policy_delay;

@@ -2193,6 +2193,126 @@ typedef struct FleetSacActorArgs {
  * and networks whose actor is not squashed (the message points to fleet_td3_actor_grad_dev). */
 extern FLEET_API int fleet_sac_actor_grad_dev(fleet_td3_handle h, const FleetSacActorArgs* a, float* const* grads, int count);
 
+/* ==== SAC's whole update on the device (fleet_sactrain.hip; DESIGN.md "SAC's whole update on the device") ===========================
+ * (entries added under FLEET_ABI_VERSION 11: nothing that existed before changes, so the number stays.  They are declared
+ * `FLEET_API extern`, behind the closed entry lists of the sections above, and every one starts with fleet_sactrain_.)
+ * stable-baselines3 2.3.2's SAC.train(gradient_steps, batch_size) as ONE enqueue-only call.  The handle BORROWS its handles, which must
+ * outlive it: a replay buffer, the TARGET critics' fleet_sac_create handle, and -- all on ONE second fleet_sac_create handle that holds
+ * the ONLINE networks -- a fleet_td3 gradient handle, a fleet_adam handle over the actor (span 0, 1, no extras), one over the critics
+ * (span 1, n_critics, no extras) and, for a learned entropy coefficient, one over no net with ONE extra of length 1 (log_ent_coef);
+ * NULL for a fixed alpha.  It owns one block, zeroed at create: the staging arrays of max_batch rows (the gradient handle's; the six
+ * of the TD3 section), one alpha cell, max_steps slots of f32[FLEET_SACTRAIN_SLOT_FLOATS] -- the critic launch's stats[8], then the
+ * actor launch's -- and the scale launch's chunk table.
+ * Gradient step g = 0 .. gradient_steps - 1 of a call, with u = first_update + g, through the families' own entries, as they are:
+ *   1. fleet_replay_sample_dev(replay, batch_size, norm, the staging arrays): the buffer's own call counter advances by gradient_steps
+ *   2. learned alpha only: the alpha launch, alpha = (float)exp((double)log_ent_coef[0]), into the alpha cell -- read BEFORE the
+ *      entropy coefficient's optimiser step of this gradient step, as SB3 reads it; a fixed alpha: the caller's ent_coef pointer as it is
+ *   3. fleet_sac_target_dev(online, targets) from the staged next_obs, rewards and dones into the staged target_q; DRAW (not recorded),
+ *      key (target_seed, row_offset 0, step = u)
+ *   4. fleet_td3_critic_grad_dev on the staged obs, actions and target_q; stats -> slot g, floats 0..7
+ *   5. the scale launch, grad[i] = grad[i] * (float)loss_scale over the critics' gradient tensors (SB3's critic loss is 0.5 * the
+ *      launches'); skipped when (float)loss_scale == 1
+ *   6. fleet_adam_step_dev(adam_critic, lr, beta1[1], beta2[1], eps[1], max_grad_norm[1])
+ *   7. fleet_sac_actor_grad_dev on the staged obs, on the critics just stepped; key (seed, row_offset 0, step = u); stats -> slot g,
+ *      floats 8..15; log_ent_coef and log_ent_coef_grad when learned
+ *   8. fleet_adam_step_dev(adam_actor, ... [0])
+ *   9. learned alpha only: fleet_adam_step_dev(adam_ent, ... [2]) on (log_ent_coef, log_ent_coef_grad)
+ *  10. iff g % target_update_interval == 0 -- the index INSIDE the call, not the update count: step 0 of every call updates the
+ *      targets -- the image-to-image Polyak update of the TD3 section on the two images (the same kernel)
+ * and one closing launch per call.  The result is bit-equal to the same entries called one by one.  Every argument is stateless.
+ * The alpha launch is the DOUBLE exponential rounded once, so that the value can be restated on the host; it is not torch.exp's bits.
+ * The scale launch: one workgroup per chunk of 1024 consecutive elements of ONE tensor, the tensors' pointers in the kernel arguments.
+ * The statistics block, stats f64[FLEET_TRAIN_STATS], written by the closing launch (one workgroup of 256 threads) with the ordered
+ * float64 sum S of "PPO's whole update on the device" over the call's slots, G = gradient_steps, c[g] / a[g] the critic / actor half:
+ *   [0] critic_loss = (double)(float)loss_scale * S((double)c[g][0]) / (double)G      [1] actor_loss = S(a[g][0]) / G
+ *   [2] ent_coef = S(a[g][4]) / G       [3] ent_coef_loss = S(a[g][1]) / G, NaN with a fixed alpha
+ *   [4] the LAST step's critic loss, (double)(float)loss_scale * (double)c[G-1][0]     [5] the last step's actor loss
+ *   [6] (double)(first_update + G) (train/n_updates)      [7] the call's target updates, (G - 1) / target_update_interval + 1
+ *   [8] S(a[g][2]) / G, the mean log_prob      [9] S(a[g][3]) / G, the mean qmin      [10..15] 0
+ * Every *_dev call takes device pointers, only enqueues and launches on the stream the borrowed handles launch on: the replay buffer,
+ * the target networks and the online networks must launch on ONE stream.  No atomics, no ordering between workgroups: launch
+ * boundaries only.  Calls are serialised by the caller.  Out of scope: a SAC collector, gSDE, learning-rate schedules inside a call. */
+#define FLEET_SACTRAIN_MAX_STEPS 65536
+#define FLEET_SACTRAIN_SLOT_FLOATS 16
+#define FLEET_SACTRAIN_SCALE_CHUNK 1024
+typedef struct FleetSacTrainParams {
+  int32_t struct_bytes;          /* sizeof(FleetSacTrainParams) */
+  int32_t max_steps;             /* 1..FLEET_SACTRAIN_MAX_STEPS: gradient steps one call may take */
+} FleetSacTrainParams;
+typedef struct FleetSacTrainArgs {
+  int32_t struct_bytes;          /* sizeof(FleetSacTrainArgs) */
+  int32_t gradient_steps;        /* 1..max_steps */
+  int32_t batch_size;            /* 1..max_batch */
+  int32_t target_update_interval; /* >= 1 */
+  float gamma;                   /* the discount, as fleet_sac_target_dev takes it */
+  float target_entropy;          /* as fleet_sac_actor_grad_dev takes it (SB3's "auto": -(float)A); read with a learned alpha only */
+  double tau;                    /* in [0, 1] */
+  double loss_scale;             /* finite; SB3: 0.5.  Used as (float)loss_scale */
+  double lr;                     /* finite, >= 0; all optimisers', constant within the call */
+  double beta1[3], beta2[3];     /* in [0, 1); [0] the actor optimiser's, [1] the critics', [2] the entropy coefficient's, here and below */
+  double eps[3];                 /* finite, >= 0 */
+  double max_grad_norm[3];       /* <= 0: no clipping (SB3's SAC) */
+  uint64_t seed;                 /* Philox key of the actor step's draw */
+  uint64_t target_seed;          /* Philox key of the target's draw: not `seed` */
+  uint64_t first_update;         /* gradient steps taken before this call */
+  const float* ent_coef;         /* device f32[1]: a FIXED alpha; exactly one of ent_coef and log_ent_coef */
+  float* log_ent_coef;           /* device f32[1]: the LEARNED coefficient's logarithm, stepped in place; given exactly when adam_ent was */
+  float* log_ent_coef_grad;      /* device f32[1]: given exactly when log_ent_coef is */
+  fleet_norm_handle norm;        /* or NULL: the minibatches are sampled raw */
+  double* stats;                 /* device f64[FLEET_TRAIN_STATS] */
+} FleetSacTrainArgs;
+typedef struct FleetSacTrainInfo {
+  int32_t obs_dim, act_dim, n_critics;   /* the networks' D, A and critics */
+  int32_t max_batch;             /* the gradient handle's: rows the staging arrays hold */
+  int32_t max_steps;             /* slots */
+  int32_t n_actor_tensors;       /* the counts the update takes: W, b per layer of the actor ... */
+  int32_t n_critic_tensors;      /* ... and of the critics, critic after critic */
+  int32_t learned_alpha;         /* 1 when created with an entropy-coefficient optimiser */
+  int32_t scale_chunks;          /* workgroups of the scale launch */
+  int32_t reserved;
+  uint64_t staging_bytes;        /* of the staging arrays */
+  void* staging;                 /* device: obs, actions, next_obs, dones, rewards, target_q as in FleetOffpolicyInfo */
+  void* alpha;                   /* device f32[1]: the alpha cell (the last step's alpha with a learned coefficient) */
+  void* slots;                   /* device f32[max_steps][FLEET_SACTRAIN_SLOT_FLOATS]: the last call's per-step stats */
+} FleetSacTrainInfo;
+typedef struct FleetSacTrain* fleet_sactrain_handle;
+
+/* FLEET_ERR_INVALID (fleet_sactrain_last_error(NULL) says why, starting with the entry's name) for a null or wrongly sized
+ * FleetSacTrainParams, max_steps out of range, a null output or handle (adam_ent alone may be NULL), networks that fleet_sac_create did
+ * not make (the message points to fleet_offpolicy_create), online and target networks that are one handle, whose records differ in any
+ * byte or that lie on different devices, an optimiser on another image than the gradient handle, an optimiser whose span is not the one
+ * stated above, a replay buffer on another device or whose D or A differs from the networks'.  FLEET_ERR_HIP with the byte count when
+ * the block cannot be allocated. */
+FLEET_API extern int fleet_sactrain_create(fleet_replay_handle replay, fleet_qtarget_handle targets, fleet_td3_handle grad,
+                                           fleet_adam_handle adam_actor, fleet_adam_handle adam_critic, fleet_adam_handle adam_ent,
+                                           const FleetSacTrainParams* p, fleet_sactrain_handle* out);
+FLEET_API extern int fleet_sactrain_destroy(fleet_sactrain_handle h);
+FLEET_API extern const char* fleet_sactrain_last_error(fleet_sactrain_handle h);  /* h may be NULL: the last failed call without a handle */
+FLEET_API extern int fleet_sactrain_describe(fleet_sactrain_handle h, FleetSacTrainInfo* out);
+/* The alpha launch on its own: out[0] = (float)exp((double)log_ent_coef[0]); out NULL: the handle's alpha cell.  FLEET_ERR_INVALID for
+ * a null log_ent_coef. */
+FLEET_API extern int fleet_sactrain_alpha_dev(fleet_sactrain_handle h, const float* log_ent_coef, float* out);
+/* The scale launch on its own: grads[t][i] = grads[t][i] * (float)s over the critics' gradient tensors (W, b per layer, critic after
+ * critic), also for s == 1.  FLEET_ERR_INVALID for an s that is not finite, a null grads or a null pointer in it, a wrong count. */
+FLEET_API extern int fleet_sactrain_scale_dev(fleet_sactrain_handle h, float* const* grads, int count, double s);
+/* The image-to-image Polyak update on its own, one launch: the targets' image <- the online image.  FLEET_ERR_INVALID for a tau outside
+ * [0, 1] or NaN, and when the two handles do not launch on one stream. */
+FLEET_API extern int fleet_sactrain_polyak_dev(fleet_sactrain_handle h, double tau);
+/* The update.  actor_params / actor_grads: host arrays of n_actor device pointers as fleet_adam_step_dev takes them (W, b per layer of
+ * the actor, the last pair the ONE [2A, H] / [2A] pair); critic_params / critic_grads: the critics', critic after critic.  The
+ * parameters are stepped in place (and the online image with them); the gradient tensors hold the last step's gradients (the critics'
+ * scaled).  Everything that can be refused is refused before the first launch: nothing is launched then, and the replay buffer's call
+ * counter and all three step counts stay.  FLEET_ERR_INVALID for a null or wrongly sized FleetSacTrainArgs, gradient_steps < 1,
+ * batch_size < 1, target_update_interval < 1, a null stats, both or neither of ent_coef and log_ent_coef, one of log_ent_coef and
+ * log_ent_coef_grad without the other, a loss_scale that is not finite, whatever the entries above refuse (in their words), and -- these
+ * need the handle -- gradient_steps above max_steps, batch_size above max_batch, wrong tensor counts, a log_ent_coef that is not given
+ * exactly when adam_ent was, a norm whose obs_dim is not D, a replay buffer, target networks and online networks that do not launch on
+ * one stream; FLEET_ERR_STATE for an empty buffer.  The arguments are looked at before the handle is: with h NULL the reason (or "null
+ * handle") goes to fleet_sactrain_last_error(NULL). */
+FLEET_API extern int fleet_sactrain_sac_dev(fleet_sactrain_handle h, const FleetSacTrainArgs* a, float* const* actor_params,
+                                            float* const* actor_grads, int n_actor, float* const* critic_params,
+                                            float* const* critic_grads, int n_critic);
+
 #ifdef __cplusplus
 }
 #endif
