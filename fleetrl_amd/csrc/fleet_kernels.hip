@@ -316,6 +316,11 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
   constexpr bool kTailA = kTail && DEG == FLEET_DEG_RAINFLOW && (FLEET_TWIN_TAIL & 1) != 0;
   constexpr bool kTailB = kTail && (FLEET_TWIN_TAIL & 2) != 0;
   constexpr bool kTailC = kTail && (FLEET_TWIN_TAIL & 4) != 0;
+  // The twin's lane body has no exec-mask region around it: every lane runs it, lanes g >= N on the env's last EV with their stores,
+  // their rainflow push and their sums switched off.  One path through the body for the wait-count pass: behind it nothing of the first
+  // burst is pending any more, and no `s_waitcnt vmcnt` stands between the body's stores and the env record's (EXPERIMENTS.md, "The
+  // twin's lane body on one path").  The same instances as `kTail`; the live instances keep the masked region.
+  constexpr bool kBody = kTail;
   typedef const __attribute__((address_space(4))) char* karg_ptr;
   auto late_args = [&]() -> const FleetDev& {
     if constexpr (!MULTI && !WIDE) {
@@ -572,7 +577,11 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       rr_n = *ev_at(d.seg, it);
     };
     if (kPipe) request_ev(g);
-    for (int c = g + kz; c < N; c += G) {
+    // (the twin: no exec-mask region around the body.  Every lane runs it, a surplus lane (g >= N) on the env's last EV, whose records
+    // the early loads handed it; `ev_ok` keeps it from storing, from the rainflow push and from the table read of `crosses`)
+    const bool lane_ok = kBody ? g < N : true;
+    const bool ev_ok = kBody ? (env_ok && lane_ok) : env_ok;
+    for (int c = kBody ? (g < N ? g : N - 1) : g + kz; kBody || c < N; c += G) {
       const EvIx i = {(size_t)e * N, (unsigned)c};
       // all loads of this EV are issued before anything is consumed
       const Hot hb = kEarly ? h_pre : (kPipe ? hb_n : *ev_at(d.hot, i));
@@ -630,7 +639,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       }
       // the schedule record of the row AFTER next, for the next launch: only when that row starts a new segment of the EV's
       // schedule (a departure, an arrival, ...).  Nothing in this step waits for it except the store at its very end.
-      const bool crosses = kEarly && (t1 + 1 >= SEG_END(rr.se));
+      const bool crosses = kEarly && (kBody ? lane_ok : true) && (t1 + 1 >= SEG_END(rr.se));
       SegRec nr = rr;
       const EvIx it2 = {(size_t)t2 * N, (unsigned)c};
       if (crosses) nr = *ev_at(d.seg, it2);
@@ -654,7 +663,7 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       // (the state-only twin with float32 actions: the deep request, for rf_finish_win's second closure)
       constexpr bool kRfDeep = kEarly && DEAD && !A64;
       constexpr bool kSplitRf = !MULTI;
-      if (kSplitRf && DEG == FLEET_DEG_RAINFLOW && env_ok && rf_live) rf_begin(d, i, old_deg, soc_deg, tail, sgn, rq, false, kRfDeep);
+      if (kSplitRf && DEG == FLEET_DEG_RAINFLOW && ev_ok && rf_live) rf_begin(d, i, old_deg, soc_deg, tail, sgn, rq, false, kRfDeep);
 
       FLEET_STAMP(3);
       // ---- observation of the advanced time row (fleet_environment.py:511-518, 645-652) ------------------------
@@ -677,10 +686,15 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
       FLEET_STAMP(4);
       // ---- SOC log + daily degradation (:655-673) -------------------------------------------------------------
       if (!kSplitRf && DEG == FLEET_DEG_RAINFLOW && env_ok && rf_live) rf_begin(d, i, old_deg, soc_deg, tail, sgn, rq, kRfEarly);
-      ev_finish<DEG, WIDE>(d, i, c, N, env_ok, deg_row, dt_step, rq, tail, sgn, soc, soc_deg, old_deg, hl, tb1.there, t090, inplane,
+      ev_finish<DEG, WIDE>(d, i, c, N, ev_ok, deg_row, dt_step, rq, tail, sgn, soc, soc_deg, old_deg, hl, tb1.there, t090, inplane,
                            crosses, nr, soh0, a, en, logs, lrow, hb, err, sei_sample, sei_soh, sei_tail, sei_top, sei_have_top, acc_c,
                            top_c, kRfCarry, kEarly, kRfDeep);
       if (!WIDE) break;  // N <= G: a single pass, and no loop for the compiler to hoist rare-path constants out of
+    }
+    if constexpr (kBody) {  // a surplus lane adds what it added when it skipped the body: nothing
+      rew = lane_ok ? rew : 0.0;
+      asum = lane_ok ? asum : 0.0;
+      penrec = lane_ok ? penrec : 0.0;
     }
     {  // ---- the rest of the step reads the argument block afresh (see `late_args`) ----
     const FleetDev& d = kTailB ? late_args_once() : late_args();
@@ -853,9 +867,9 @@ __global__ __launch_bounds__(kBlock, MULTI ? (WIDE ? kMultiWideWaves : kMultiWav
         penalty_record = 0.0;
         if constexpr (kTailC) {
           // (C) the new start row's flags for the head, read AND waited for here, in the rare branch, so that the common path does
-          // not join behind a pending load of the reset's.  (The drain in front of the env record's stores is still there: the
-          // compiler puts it back for the flags and the time row's leader terms of the FIRST burst, which are pending on the path
-          // around the lane loop's body -- EXPERIMENTS.md has the excerpt and what removing it cost.)
+          // not join behind a pending load of the reset's.  (The drain in front of the env record's stores that this alone left --
+          // for the flags and the time row's leader terms of the FIRST burst, pending on the path around the lane loop's body --
+          // went with that path: `kBody`.)
           head_after = d.tab_phys[r.t].flags_next;
           asm volatile("" : "+v"(head_after));
         }
