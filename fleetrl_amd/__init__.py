@@ -14,7 +14,7 @@
     from fleetrl_amd import DevicePPOTrain
     from fleetrl_amd import DeviceTD3Train
     from fleetrl_amd import DeviceSACTrain
-    from fleetrl_amd import DevicePPOCollect, DeviceTD3Collect
+    from fleetrl_amd import DevicePPOCollect, DeviceTD3Collect, DeviceSACCollect
     from fleetrl_amd import DeviceEvalCallback
     from fleetrl_amd import LogSummary, summarize_log, compare, evaluate_strategies
 """
@@ -82,7 +82,7 @@ def __getattr__(name):  # lazy: importing the package must not require the HIP l
         from . import sac_train
 
         return getattr(sac_train, name)
-    if name in ("DevicePPOCollect", "DeviceTD3Collect"):
+    if name in ("DevicePPOCollect", "DeviceTD3Collect", "DeviceSACCollect"):
         from . import collect
 
         return getattr(collect, name)

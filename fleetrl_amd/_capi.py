@@ -367,6 +367,18 @@ class FleetCollectInfo(C.Structure):
                 ("ring_return", C.c_void_p), ("ring_length", C.c_void_p), ("ring_count", C.c_void_p)]
 
 
+# ---- SAC's collector (include/fleet_hip_sac_loop.h, fleet_saccollect_*) -----------------------------------------------------------------
+class FleetSacUniformArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("env_id_offset", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("seed", C.c_uint64),
+                ("step", C.c_uint64), ("actions", C.c_void_p)]
+
+
+class FleetSacCollectArgs(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_steps", C.c_int32), ("env_id_offset", C.c_int32), ("reserved", C.c_int32),
+                ("learning_starts", C.c_uint64), ("replay", C.c_void_p), ("noise_lo", C.c_float), ("noise_hi", C.c_float),
+                ("seed", C.c_uint64), ("first_step", C.c_uint64), ("stats", C.c_void_p)]
+
+
 # ---- evaluation of the agent (include/fleet_hip.h "evaluation of the agent on the device", fleet_eval_*) -------------------------------
 EVAL_MAX_EPISODES, EVAL_STATS = 65536, 16
 
@@ -786,6 +798,15 @@ def load_library():
     lib.fleet_eval_episodes_read.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64)]
     for name in EVAL_SYMBOLS:
         getattr(lib, name).restype = C.c_char_p if name == "fleet_eval_last_error" else C.c_int
+    # SAC's collector and evaluation (include/fleet_hip_sac_loop.h; fleet_collect.hip, fleet_eval.hip), on the collect and eval handles
+    lib.fleet_saccollect_last_error.argtypes = [vp]
+    lib.fleet_saccollect_uniform_dev.argtypes = [vp, C.c_int, C.POINTER(FleetSacUniformArgs)]
+    lib.fleet_saccollect_create.argtypes = [vp, vp, vp, C.POINTER(FleetCollectParams), C.POINTER(vp)]
+    lib.fleet_saccollect_sac_dev.argtypes = [vp, C.POINTER(FleetSacCollectArgs)]
+    lib.fleet_saceval_create.argtypes = [vp, vp, vp, C.POINTER(FleetEvalParams), C.POINTER(vp)]
+    lib.fleet_saceval_best_load_dev.argtypes = [vp, vp]
+    for name in SACCOLLECT_SYMBOLS + SACEVAL_SYMBOLS:
+        getattr(lib, name).restype = C.c_char_p if name == "fleet_saccollect_last_error" else C.c_int
     for prefix, names in (("norm", NORM_SYMBOLS), ("rollout", ROLLOUT_SYMBOLS), ("replay", REPLAY_SYMBOLS), ("policy", POLICY_SYMBOLS),
                           ("noise", NOISE_SYMBOLS), ("qtarget", QTARGET_SYMBOLS), ("ppo", PPO_SYMBOLS),
                           ("td3", TD3_SYMBOLS), ("adam", ADAM_SYMBOLS), ("train", TRAIN_SYMBOLS), ("offpolicy", OFFPOLICY_SYMBOLS)):
@@ -884,6 +905,12 @@ COLLECT_SYMBOLS = ("fleet_collect_create", "fleet_collect_destroy", "fleet_colle
 EVAL_SYMBOLS = ("fleet_eval_create", "fleet_eval_destroy", "fleet_eval_last_error", "fleet_eval_describe", "fleet_eval_sync_norm_dev",
                 "fleet_eval_run_dev", "fleet_eval_episodes_dev", "fleet_eval_clear_dev", "fleet_eval_best_load_dev", "fleet_eval_best_export_dev",
                 "fleet_eval_episodes_read")
+
+# SAC's collector and evaluation: declared in a header of their own, include/fleet_hip_sac_loop.h (fleet_hip.h and its closed entry lists
+# stay as they are), so they stand in lists of their own, outside EXPORTED_SYMBOLS
+SACCOLLECT_SYMBOLS = ("fleet_saccollect_last_error", "fleet_saccollect_uniform_dev", "fleet_saccollect_create", "fleet_saccollect_sac_dev")
+
+SACEVAL_SYMBOLS = ("fleet_saceval_create", "fleet_saceval_best_load_dev")
 
 EXPORTED_SYMBOLS = (
     "fleet_obs_dim", "fleet_create", "fleet_destroy", "fleet_last_error", "fleet_set_stream", "fleet_get_stream", "fleet_use_own_stream",

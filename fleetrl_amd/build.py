@@ -15,7 +15,7 @@ HEADERS = ("fleet_device.h", "fleet_batch.h", "fleet_direct.h", "fleet_norm.h", 
            "fleet_grad_dev.h", "fleet_adam.h", "fleet_train.h", "fleet_offpolicy.h", "fleet_logsum.h", "fleet_collect.h", "fleet_eval.h", "fleet_sac_dev.h",
            # the parts of fleet_kernels.hip (one translation unit: these are compiled into the library AND into the code object)
            "fleet_stamps.h", "fleet_wave.h", "fleet_obs.h", "fleet_rainflow.h", "fleet_reset.h", "fleet_aux_kernels.h", "fleet_step_plan.h",
-           os.path.join("..", "..", "include", "fleet_hip.h"))  # relative to csrc/
+           os.path.join("..", "..", "include", "fleet_hip.h"), os.path.join("..", "..", "include", "fleet_hip_sac_loop.h"))  # relative to csrc/
 # -ffp-contract=off: no fused multiply-add contraction, so float64 results follow the reference's operation
 # order bit for bit on the SOC path.  No -ffast-math for the same reason.
 # -mllvm -disable-machine-licm: the machine-level loop-invariant code motion hoists every rare path's constant

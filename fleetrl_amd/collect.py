@@ -1,5 +1,5 @@
-"""`DevicePPOCollect` / `DeviceTD3Collect`: stable-baselines3's `collect_rollouts` as one enqueue-only call (include/fleet_hip.h
-`fleet_collect_*`, fleetrl_amd/csrc/fleet_collect.hip).
+"""`DevicePPOCollect` / `DeviceTD3Collect` / `DeviceSACCollect`: stable-baselines3's `collect_rollouts` as one enqueue-only call
+(include/fleet_hip.h `fleet_collect_*`, include/fleet_hip_sac_loop.h `fleet_saccollect_*`, fleetrl_amd/csrc/fleet_collect.hip).
 
 The other half of `learn()` beside `DevicePPOTrain.train` / `DeviceTD3Train.train`: per env step the exploration launch
 (`DevicePolicy.sample` / `explore` / `sample_uniform`), the env's step, the normaliser's step and the buffer's `add`, each the launch
@@ -8,7 +8,7 @@ to the loops of examples/ppo_device_train.py and examples/td3_pink_noise.py -- a
 `ep_info_buffer` on the device: the last `stats_window` finished episodes in the order `Monitor` reports them.  One block of statistics
 (`STATS`: what SB3 logs as `rollout/*`) is written at the end.  The observation a rollout ends on, its `episode_start` flags and the
 raw observation an off-policy loop keeps are the handle's: the next call starts from them.  Deterministic from (the handles' state, seed,
-first_step).  Out of scope: the time-limit bootstrap, gSDE, SAC, `train_freq` in episodes, callbacks.
+first_step).  Out of scope: the time-limit bootstrap, gSDE, `train_freq` in episodes, callbacks.
 """
 from __future__ import annotations
 
@@ -20,7 +20,7 @@ from . import _capi
 from ._capi import FleetHipError
 from ._handle import _DeviceHandle
 
-__all__ = ["DevicePPOCollect", "DeviceTD3Collect", "STATS", "SB3_NAMES"]
+__all__ = ["DevicePPOCollect", "DeviceTD3Collect", "DeviceSACCollect", "STATS", "SB3_NAMES"]
 
 # the statistics block f64[16]: the means over the ring (NaN while it is empty), the episodes that finished in the call, the episodes
 # appended so far, the env steps taken after the call; then zeros
@@ -30,9 +30,11 @@ SB3_NAMES = ("rollout/ep_rew_mean", "rollout/ep_len_mean", None, None, None)
 
 
 class _DeviceCollect(_DeviceHandle):
-    """One `fleet_collect_*` handle on `env` (a `FleetVecEnv`, or a `FleetVecNormalize` over one) and `policy` (a `DevicePolicy`), which
-    must outlive it.  `stats_window`: SB3's `stats_window_size`, the episodes `rollout/ep_*_mean` average over."""
+    """One `fleet_collect_*` handle on `env` (a `FleetVecEnv`, or a `FleetVecNormalize` over one) and `policy` (a `DevicePolicy`; for
+    `DeviceSACCollect` a `DeviceSACNetworks`), which must outlive it.  `stats_window`: SB3's `stats_window_size`, the episodes
+    `rollout/ep_*_mean` average over."""
     _prefix = "collect"
+    _create_entry = "fleet_collect_create"  # the create call of the family's handle: what the actor's kind decides
 
     def __init__(self, env, policy, stats_window: int = 100):
         self.env, self.policy = env, policy
@@ -45,7 +47,7 @@ class _DeviceCollect(_DeviceHandle):
         self.stats_window = int(stats_window)
         h = C.c_void_p()
         p = _capi.FleetCollectParams(C.sizeof(_capi.FleetCollectParams), self.stats_window)
-        rc = self.lib.fleet_collect_create(self.batch.h, None if self.norm is None else self.norm.h, policy.h, C.byref(p), C.byref(h))
+        rc = getattr(self.lib, self._create_entry)(self.batch.h, None if self.norm is None else self.norm.h, policy.h, C.byref(p), C.byref(h))
         if rc != _capi.OK:
             raise FleetHipError(rc, self.lib.fleet_collect_last_error(None).decode())
         self.h = h
@@ -203,6 +205,39 @@ class DeviceTD3Collect(_DeviceCollect):
         a.shift = None if shift is None else self._per_action("shift", shift).data_ptr()
         a.noise_lo, a.noise_hi = float(low), float(high)
         a.noise = None if noise is None else noise.h.value
+        a.seed, a.first_step = int(seed) & (2 ** 64 - 1), int(first_step) & (2 ** 64 - 1)
+        stats_out, a.stats = self._stats(stats_out)
+        self.collect_dev(a)
+        return stats_out
+
+
+class DeviceSACCollect(_DeviceCollect):
+    """`OffPolicyAlgorithm.collect_rollouts` on the device for SAC with `train_freq = (n_steps, "step")`: `collect` adds `n_steps` raw
+    transitions per env to a `DeviceReplayBuffer`, the actions drawn by `nets` (a `DeviceSACNetworks`, which stands where the others
+    have their policy: `set_stream` and `use_torch_stream` move it).  `DeviceSACTrain.train` takes the buffer from there."""
+    _create_entry = "fleet_saccollect_create"
+
+    def __init__(self, env, nets, stats_window: int = 100):
+        super().__init__(env, nets, stats_window)
+        self.nets = nets
+
+    def collect_dev(self, args: "_capi.FleetSacCollectArgs"):
+        """Raw device addresses in a FleetSacCollectArgs, on the stream the borrowed handles share."""
+        args.struct_bytes = C.sizeof(_capi.FleetSacCollectArgs)
+        self._check(self.lib.fleet_saccollect_sac_dev(self.h, C.byref(args)))
+
+    def collect(self, replay, n_steps: int, *, learning_starts: int, low: float = -1.0, high: float = 1.0, seed: int, first_step: int,
+                env_id_offset: int = 0, stats_out=None):
+        """`n_steps` env steps on torch's current stream, no host synchronisation.  Global step s = first_step + t draws uniform actions
+        in [low, high) while s < learning_starts (`DeviceSACNetworks.sample_uniform`) and the squashed-Gaussian sample
+        tanh(mean + exp(log_std) * eps) afterwards (`DeviceSACNetworks.act` on the carry observation), both keyed by (seed, s).  The
+        buffer gets the action the env got.  Returns the statistics f64 [16] on the device."""
+        self._lent = (replay,)
+        self.use_torch_stream()
+        a = _capi.FleetSacCollectArgs()
+        a.n_steps, a.env_id_offset, a.replay = int(n_steps), int(env_id_offset), replay.h.value
+        a.learning_starts = max(int(learning_starts), 0)
+        a.noise_lo, a.noise_hi = float(low), float(high)
         a.seed, a.first_step = int(seed) & (2 ** 64 - 1), int(first_step) & (2 ** 64 - 1)
         stats_out, a.stats = self._stats(stats_out)
         self.collect_dev(a)

@@ -2,7 +2,8 @@
 // device"; fleet_collect.h): per env step the exploration launch, the env step, the normaliser step and the buffer's add through
 // their own entries, as they are, on one stream, and the one thing of SB3's rollout log nothing else keeps on the device -- the ring
 // of the last W finished episodes.  The handle borrows an env, an optional normaliser and a policy and owns one block: the carry
-// buffers (two sides that ping-pong), the raw buffers, the step's small arrays and the ring.
+// buffers (two sides that ping-pong), the raw buffers, the step's small arrays and the ring.  The actor may also be the squashed-
+// Gaussian networks of fleet_sac_create (include/fleet_hip_sac_loop.h, fleet_saccollect_*): the off-policy loop with another action.
 //   collect_episodes  ONE workgroup of 1024 threads per env step: the step's finished envs in env order (ballot and popcount per
 //              wavefront, chunks of 1024 envs), the k-th of c to slot (count + k) % W iff c - k <= W; then count += c.  Behind one of
 //              two loaders: the env's records, or the caller's arrays.
@@ -14,11 +15,14 @@
 #include <cmath>
 #include <string>
 
+#include "../../include/fleet_hip_sac_loop.h"
 #include "fleet_batch.h"
 #include "fleet_collect.h"
 #include "fleet_handle.h"
 #include "fleet_mlp.h"
 #include "fleet_norm.h"
+#include "fleet_policy.h"
+#include "fleet_qtarget.h"
 
 namespace {
 
@@ -176,6 +180,29 @@ std::string check_offpolicy_args(const FleetCollectOffpolicyArgs* x) {
   return "";
 }
 
+// what fleet_saccollect_uniform_dev and fleet_saccollect_sac_dev refuse, looked at without their handles
+std::string check_uniform_args(int E, const FleetSacUniformArgs* x) {
+  if (!x) return "null FleetSacUniformArgs";
+  if (x->struct_bytes != (int32_t)sizeof(FleetSacUniformArgs)) return "FleetSacUniformArgs.struct_bytes does not match this library";
+  if (E < 1) return "E must be >= 1, got " + std::to_string(E);
+  if (!x->actions) return "null actions";
+  if (x->env_id_offset < 0) return "env_id_offset must be >= 0, got " + std::to_string(x->env_id_offset);
+  if (!(x->lo <= x->hi)) return "the bounds need lo <= hi";
+  return "";
+}
+
+std::string check_sac_args(const FleetSacCollectArgs* x) {
+  if (!x) return "null FleetSacCollectArgs";
+  if (x->struct_bytes != (int32_t)sizeof(FleetSacCollectArgs)) return "FleetSacCollectArgs.struct_bytes does not match this library";
+  if (x->n_steps < 1) return "n_steps must be >= 1, got " + std::to_string(x->n_steps);
+  if (x->reserved != 0) return "reserved must be 0";
+  if (x->env_id_offset < 0) return "env_id_offset must be >= 0, got " + std::to_string(x->env_id_offset);
+  if (!x->replay) return "null replay handle";
+  if (!(x->noise_lo <= x->noise_hi)) return "the bounds need noise_lo <= noise_hi";
+  if (!x->stats) return "null stats";
+  return "";
+}
+
 std::string check_episode_args(const uint8_t* done, const double* ep_return, const int32_t* ep_len, int E) {
   if (E < 1) return "E must be >= 1, got " + std::to_string(E);
   if (!done) return "null done";
@@ -205,8 +232,9 @@ enum { kObs0, kObs1, kRaw0, kRaw1, kTerm, kRawReward, kReward, kStart0, kStart1,
 struct FleetCollect {
   fleet_handle env = nullptr;  // borrowed, as are the two below
   fleet_norm_handle norm = nullptr;
-  fleet_policy_handle policy = nullptr;
-  FleetMlpHandle* pol = nullptr;  // the policy's image: its device and stream
+  fleet_policy_handle policy = nullptr;  // the actor is a policy's image (fleet_collect_create), or ...
+  fleet_qtarget_handle nets = nullptr;   // ... a squashed SAC image (fleet_saccollect_create): exactly one of the two
+  FleetMlpHandle* pol = nullptr;  // the actor's image: its device and stream
   std::string error;              // fleet_collect_last_error(handle)
   char* block = nullptr;          // owned
   int E = 0, D = 0, A = 0, W = 0, n_heads = 0, cur = 0, launches = 0;
@@ -226,10 +254,30 @@ namespace {
 std::string check_streams(const FleetCollect* h, const FleetHandleBase* more = nullptr, const char* noun = nullptr) {
   if (h->norm && base_of(h->norm)->stream != h->env->stream)
     return "the normaliser launches on another stream than the env: fleet_norm_set_stream it to the env's first";
-  if (h->pol->stream != h->env->stream) return "the policy launches on another stream than the env: fleet_policy_set_stream it to the env's first";
+  if (h->pol->stream != h->env->stream)
+    return h->nets ? "the networks launch on another stream than the env: fleet_qtarget_set_stream them to the env's first"
+                   : "the policy launches on another stream than the env: fleet_policy_set_stream it to the env's first";
   if (more && more->stream != h->env->stream)
     return std::string("the ") + noun + " launches on another stream than the env: set its stream to the env's first";
   return "";
+}
+
+// which run call serves the other kind of handle
+const char* const kServedBySac = "the handle borrows SAC networks (fleet_saccollect_create): fleet_saccollect_sac_dev runs it";
+const char* const kServedByPolicy = "the handle borrows a policy (fleet_collect_create): fleet_collect_ppo_dev and fleet_collect_offpolicy_dev run it";
+
+// what the off-policy run calls refuse about their replay buffer; "" when it fits and launches on the env's stream
+std::string check_replay(const FleetCollect* h, fleet_replay_handle replay) {
+  const ReplayBase* rb = reinterpret_cast<const ReplayBase*>(replay);
+  const FleetReplayLayout& L = rb->L;
+  const int E = (int)(L.row_bytes[FLEET_REPLAY_REWARDS] / 4);
+  const int D = (int)(L.row_bytes[FLEET_REPLAY_OBS] / L.row_bytes[FLEET_REPLAY_REWARDS]);
+  const int A = (int)(L.row_bytes[FLEET_REPLAY_ACTIONS] / L.row_bytes[FLEET_REPLAY_REWARDS]);
+  if (rb->device != h->env->device) return "the replay buffer lies on another device than the env";
+  if (E != h->E) return "the replay buffer's num_envs is " + std::to_string(E) + ", the env's " + std::to_string(h->E);
+  if (D != h->D) return "the replay buffer's obs_dim is " + std::to_string(D) + ", the env's " + std::to_string(h->D);
+  if (A != h->A) return "the replay buffer's act_dim is " + std::to_string(A) + ", the env's " + std::to_string(h->A);
+  return check_streams(h, rb, "replay buffer");
 }
 
 int launch_episodes(FleetCollect* h, const uint8_t* done) {
@@ -253,36 +301,77 @@ int launch_finish(FleetCollect* h, uint64_t steps_after, double* stats) {
   return FLEET_OK;
 }
 
-}  // namespace
+// The off-policy run calls' loop, once: per env step `action(s, cur, failed)` enqueues what writes the handle's env_actions from the
+// carry observation of side `cur` (and counts its launches beyond the one counted here), then the env's step, the normaliser's step,
+// the buffer's add and the episode launch; the sides swap; the closing launch ends the call.  failed(rc, said) puts "<entry>: <said>"
+// into the handle's error and returns rc.
+template <typename Action>
+int offpolicy_loop(FleetCollect* h, const char* entry, fleet_replay_handle replay, int n_steps, uint64_t first_step, double* stats,
+                   const Action& action) {
+  const auto failed = [&](int rc, const char* said) {
+    h->error = std::string(entry) + ": " + said;
+    return rc;
+  };
+  h->launches = 0;
+  FLEET_HANDLE_TRY(h, hipSetDevice(h->env->device));
+  float* act = h->arr<float>(kEnvAct);
+  float* term = h->arr<float>(kTerm);
+  double* raw_reward = h->arr<double>(kRawReward);
+  double* reward = h->arr<double>(kReward);
+  for (int t = 0; t < n_steps; ++t) {
+    const int cur = h->cur, nxt = cur ^ 1;
+    if (const int rc = action(first_step + (uint64_t)t, cur, failed); rc != FLEET_OK) return rc;
+    if (const int rc = fleet_step_dev(h->env, act, FLEET_ACT_F32, h->raw(nxt), raw_reward, h->start(nxt), term); rc != FLEET_OK)
+      return failed(rc, fleet_last_error(h->env));
+    h->launches += 2;
+    if (h->norm) {
+      if (const int rc = fleet_norm_step_dev(h->norm, h->raw(nxt), raw_reward, h->start(nxt), nullptr, h->obs(nxt), reward, nullptr); rc != FLEET_OK)
+        return failed(rc, fleet_norm_last_error(h->norm));
+      h->launches += 1;
+    }
+    if (const int rc = fleet_replay_add_dev(replay, h->raw(cur), h->raw(nxt), act, raw_reward, FLEET_ACT_F64, h->start(nxt), term, nullptr); rc != FLEET_OK)
+      return failed(rc, fleet_replay_last_error(replay));
+    h->launches += 1;
+    if (const int rc = launch_episodes(h, h->start(nxt)); rc != FLEET_OK) return rc;
+    h->cur = nxt;
+  }
+  return launch_finish(h, first_step + (uint64_t)n_steps, stats);
+}
 
-extern "C" {
-
-int fleet_collect_create(fleet_handle env, fleet_norm_handle norm, fleet_policy_handle policy, const FleetCollectParams* p,
-                         fleet_collect_handle* out) {
+// Both create entries: `actor` is a fleet_policy_handle, or with `sac` the fleet_qtarget_handle of fleet_sac_create; the refusals
+// name it "the policy" or "the networks".
+int create_on(const char* entry, fleet_handle env, fleet_norm_handle norm, void* actor, bool sac, const FleetCollectParams* p,
+              fleet_collect_handle* out) {
+  const char* const noun = sac ? "networks" : "policy";
   if (out) *out = nullptr;
   std::string why = check_params(p);
   if (!why.empty()) {
   } else if (!out) why = "null output handle";
   else if (!env) why = "null env handle";
-  else if (!policy) why = "null policy handle";
-  if (!why.empty()) return handle_refuse(g_collect_error, "fleet_collect_create", why, FLEET_ERR_INVALID);
-  FleetMlpHandle* pol = mlp_borrow(policy, sizeof(PolicyDesc), "policy", &why);
-  if (!pol) return handle_refuse(g_collect_error, "fleet_collect_create", why, FLEET_ERR_INVALID);
+  else if (!actor) why = std::string("null ") + noun + " handle";
+  if (!why.empty()) return handle_refuse(g_collect_error, entry, why, FLEET_ERR_INVALID);
+  FleetMlpHandle* pol = mlp_borrow(actor, sac ? sizeof(QTargetDesc) : sizeof(PolicyDesc), noun, &why);
+  if (!pol) return handle_refuse(g_collect_error, entry, why, FLEET_ERR_INVALID);
   const int E = env->d.E, D = env->d.obs_dim, A = env->d.N;
-  const PolicyHeadDesc& actor = pol->nets[0];
-  const int pd = actor.layer[0].in, pa = actor.layer[actor.n_layers - 1].out;
+  const PolicyHeadDesc& head = pol->nets[0];
+  const int pd = head.layer[0].in;
+  const int pa = sac ? static_cast<const QTargetDesc*>(pol->record)->act_dim : head.layer[head.n_layers - 1].out;
+  const std::string the = std::string("the ") + noun, whose = sac ? "the networks'" : "the policy's";
   if (!env->d.auto_reset) why = "the env needs auto_reset = 1: a rollout runs across episode ends";
+  else if (sac && !qtarget_squashed(pol)) why = "the networks' actor is not a squashed Gaussian: fleet_sac_create makes one";
   else if (pol->device != env->device)
-    why = "the policy lies on device " + std::to_string(pol->device) + ", the env on device " + std::to_string(env->device);
-  else if (pd != D) why = "the policy's obs_dim is " + std::to_string(pd) + ", the env's " + std::to_string(D);
-  else if (pa != A) why = "the policy's act_dim is " + std::to_string(pa) + ", the env's " + std::to_string(A);
-  else if (pol->n_nets > 1 && pol->nets[1].layer[pol->nets[1].n_layers - 1].out != 1)
+    why = the + (sac ? " lie" : " lies") + " on device " + std::to_string(pol->device) + ", the env on device " + std::to_string(env->device);
+  else if (pd != D) why = whose + " obs_dim is " + std::to_string(pd) + ", the env's " + std::to_string(D);
+  else if (pa != A) why = whose + " act_dim is " + std::to_string(pa) + ", the env's " + std::to_string(A);
+  else if (!sac && pol->n_nets > 1 && pol->nets[1].layer[pol->nets[1].n_layers - 1].out != 1)
     why = "the critic head's output width must be 1, got " + std::to_string(pol->nets[1].layer[pol->nets[1].n_layers - 1].out);
   else if (norm) (void)fleet_norm_check_fit(norm, E, D, env->device, &why);
-  if (!why.empty()) return handle_refuse(g_collect_error, "fleet_collect_create", why, FLEET_ERR_INVALID);
+  if (!why.empty()) return handle_refuse(g_collect_error, entry, why, FLEET_ERR_INVALID);
   FleetCollect* h = new FleetCollect();
-  h->env = env, h->norm = norm, h->policy = policy, h->pol = pol;
-  h->E = E, h->D = D, h->A = A, h->W = p->stats_window, h->n_heads = pol->n_nets;
+  h->env = env, h->norm = norm, h->pol = pol;
+  if (sac) h->nets = static_cast<fleet_qtarget_handle>(actor);
+  else h->policy = static_cast<fleet_policy_handle>(actor);
+  h->E = E, h->D = D, h->A = A, h->W = p->stats_window, h->n_heads = sac ? 0 : pol->n_nets;
   const uint64_t e = (uint64_t)E, od = e * D * 4, w = (uint64_t)h->W;
   const uint64_t bytes[kArrays] = {od, od, norm ? od : 0, norm ? od : 0, od, e * 8, e * 8, e, e, e * A * 4, e * A * 4, e * 4, w * 8, w * 4, 16};
   uint64_t off = 0;
@@ -298,9 +387,38 @@ int fleet_collect_create(fleet_handle env, fleet_norm_handle norm, fleet_policy_
   if (rc != FLEET_OK) {
     (void)hipGetLastError();
     fleet_collect_destroy(h);
-    return handle_refuse(g_collect_error, "fleet_collect_create", why, rc);
+    return handle_refuse(g_collect_error, entry, why, rc);
   }
   *out = h;
+  return FLEET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fleet_collect_create(fleet_handle env, fleet_norm_handle norm, fleet_policy_handle policy, const FleetCollectParams* p,
+                         fleet_collect_handle* out) {
+  return create_on("fleet_collect_create", env, norm, policy, false, p, out);
+}
+
+int fleet_saccollect_create(fleet_handle env, fleet_norm_handle norm, fleet_qtarget_handle nets, const FleetCollectParams* p,
+                            fleet_collect_handle* out) {
+  return create_on("fleet_saccollect_create", env, norm, nets, true, p, out);
+}
+
+const char* fleet_saccollect_last_error(fleet_collect_handle h) { return fleet_collect_last_error(h); }
+
+int fleet_saccollect_uniform_dev(fleet_qtarget_handle nets, int E, const FleetSacUniformArgs* x) {
+  const std::string why = check_uniform_args(E, x);
+  if (const int rc = handle_enter("fleet_saccollect_uniform_dev", why, nets, g_collect_error); rc != FLEET_OK) return rc;
+  if (nets->record_bytes != sizeof(QTargetDesc) || !qtarget_squashed(nets)) {
+    nets->error = "fleet_saccollect_uniform_dev: the handle's actor is not a squashed Gaussian: fleet_sac_create makes one";
+    return FLEET_ERR_INVALID;
+  }
+  FLEET_HANDLE_TRY(nets, hipSetDevice(nets->device));
+  const PolicyUniformArgs u{nullptr, x->actions, nullptr, x->seed, x->step, (uint32_t)x->env_id_offset, 0, x->lo, x->hi};
+  FLEET_HANDLE_TRY(nets, policy_launch_uniform(nets->stream, E, nets->desc.act_dim, u));
   return FLEET_OK;
 }
 
@@ -356,7 +474,8 @@ int fleet_collect_reset_dev(fleet_collect_handle h, int clear_episodes) {
 int fleet_collect_ppo_dev(fleet_collect_handle h, const FleetCollectPpoArgs* x) {
   std::string why = check_ppo_args(x);
   int K = 0;
-  if (h && why.empty()) {
+  if (h && why.empty() && h->nets) why = kServedBySac;
+  else if (h && why.empty()) {
     const RolloutBase* rb = reinterpret_cast<const RolloutBase*>(x->buffer);
     const FleetRolloutLayout& L = rb->L;
     const int E = (int)(L.row_bytes[FLEET_ROLLOUT_REWARDS] / 4);
@@ -425,18 +544,10 @@ int fleet_collect_ppo_dev(fleet_collect_handle h, const FleetCollectPpoArgs* x) 
 
 int fleet_collect_offpolicy_dev(fleet_collect_handle h, const FleetCollectOffpolicyArgs* x) {
   std::string why = check_offpolicy_args(x);
-  if (h && why.empty()) {
-    const ReplayBase* rb = reinterpret_cast<const ReplayBase*>(x->replay);
-    const FleetReplayLayout& L = rb->L;
-    const int E = (int)(L.row_bytes[FLEET_REPLAY_REWARDS] / 4);
-    const int D = (int)(L.row_bytes[FLEET_REPLAY_OBS] / L.row_bytes[FLEET_REPLAY_REWARDS]);
-    const int A = (int)(L.row_bytes[FLEET_REPLAY_ACTIONS] / L.row_bytes[FLEET_REPLAY_REWARDS]);
+  if (h && why.empty() && h->nets) why = kServedBySac;
+  else if (h && why.empty()) {
     FleetNoiseParams np{};
-    if (rb->device != h->env->device) why = "the replay buffer lies on another device than the env";
-    else if (E != h->E) why = "the replay buffer's num_envs is " + std::to_string(E) + ", the env's " + std::to_string(h->E);
-    else if (D != h->D) why = "the replay buffer's obs_dim is " + std::to_string(D) + ", the env's " + std::to_string(h->D);
-    else if (A != h->A) why = "the replay buffer's act_dim is " + std::to_string(A) + ", the env's " + std::to_string(h->A);
-    else why = check_streams(h, rb, "replay buffer");
+    why = check_replay(h, x->replay);
     if (why.empty() && x->noise) {
       if (fleet_noise_describe(x->noise, &np) != FLEET_OK) why = "the noise handle does not describe itself";
       else if (base_of(x->noise)->device != h->env->device) why = "the noise handle lies on another device than the env";
@@ -447,24 +558,13 @@ int fleet_collect_offpolicy_dev(fleet_collect_handle h, const FleetCollectOffpol
     }
   }
   if (const int rc = handle_enter("fleet_collect_offpolicy_dev", why, h, g_collect_error); rc != FLEET_OK) return rc;
-  const auto failed = [&](int rc, const char* said) {
-    h->error = std::string("fleet_collect_offpolicy_dev: ") + said;
-    return rc;
-  };
-  h->launches = 0;
-  FLEET_HANDLE_TRY(h, hipSetDevice(h->env->device));
   float* act = h->arr<float>(kEnvAct);
   float* eps = h->arr<float>(kEps);
-  float* term = h->arr<float>(kTerm);
-  double* raw_reward = h->arr<double>(kRawReward);
-  double* reward = h->arr<double>(kReward);
   FleetExploreArgs g{};
   g.struct_bytes = (int32_t)sizeof g;
   g.seed = x->seed, g.env_id_offset = x->env_id_offset, g.scale = x->sigma, g.shift = x->shift;
   g.noise_lo = x->noise_lo, g.noise_hi = x->noise_hi, g.actions = act, g.env_actions = act;
-  for (int t = 0; t < x->n_steps; ++t) {
-    const int cur = h->cur, nxt = cur ^ 1;
-    const uint64_t s = x->first_step + (uint64_t)t;
+  const auto action = [&](uint64_t s, int cur, const auto& failed) {
     g.step = s;
     if (s < x->learning_starts) {
       g.mode = FLEET_EXPLORE_UNIFORM, g.noise_mode = FLEET_EXPLORE_NOISE_DRAW, g.noise = nullptr;
@@ -476,21 +576,28 @@ int fleet_collect_offpolicy_dev(fleet_collect_handle h, const FleetCollectOffpol
       g.mode = FLEET_EXPLORE_ACTION_NOISE, g.noise_mode = FLEET_EXPLORE_NOISE_DRAW, g.noise = nullptr;
     }
     if (const int rc = fleet_explore_act_dev(h->policy, h->obs(cur), h->E, nullptr, &g); rc != FLEET_OK) return failed(rc, fleet_policy_last_error(h->policy));
-    if (const int rc = fleet_step_dev(h->env, act, FLEET_ACT_F32, h->raw(nxt), raw_reward, h->start(nxt), term); rc != FLEET_OK)
-      return failed(rc, fleet_last_error(h->env));
-    h->launches += 2;
-    if (h->norm) {
-      if (const int rc = fleet_norm_step_dev(h->norm, h->raw(nxt), raw_reward, h->start(nxt), nullptr, h->obs(nxt), reward, nullptr); rc != FLEET_OK)
-        return failed(rc, fleet_norm_last_error(h->norm));
-      h->launches += 1;
-    }
-    if (const int rc = fleet_replay_add_dev(x->replay, h->raw(cur), h->raw(nxt), act, raw_reward, FLEET_ACT_F64, h->start(nxt), term, nullptr); rc != FLEET_OK)
-      return failed(rc, fleet_replay_last_error(x->replay));
-    h->launches += 1;
-    if (const int rc = launch_episodes(h, h->start(nxt)); rc != FLEET_OK) return rc;
-    h->cur = nxt;
-  }
-  return launch_finish(h, x->first_step + (uint64_t)x->n_steps, x->stats);
+    return (int)FLEET_OK;
+  };
+  return offpolicy_loop(h, "fleet_collect_offpolicy_dev", x->replay, x->n_steps, x->first_step, x->stats, action);
+}
+
+int fleet_saccollect_sac_dev(fleet_collect_handle h, const FleetSacCollectArgs* x) {
+  std::string why = check_sac_args(x);
+  if (h && why.empty()) why = h->nets ? check_replay(h, x->replay) : std::string(kServedByPolicy);
+  if (const int rc = handle_enter("fleet_saccollect_sac_dev", why, h, g_collect_error); rc != FLEET_OK) return rc;
+  float* act = h->arr<float>(kEnvAct);
+  FleetSacUniformArgs u{};
+  u.struct_bytes = (int32_t)sizeof u;
+  u.env_id_offset = x->env_id_offset, u.lo = x->noise_lo, u.hi = x->noise_hi, u.seed = x->seed, u.actions = act;
+  FleetSacActArgs g{};
+  g.struct_bytes = (int32_t)sizeof g;
+  g.noise_mode = FLEET_EXPLORE_NOISE_DRAW, g.deterministic = 0, g.env_id_offset = x->env_id_offset, g.seed = x->seed, g.actions = act;
+  const auto action = [&](uint64_t s, int cur, const auto& failed) {
+    u.step = g.step = s;
+    const int rc = s < x->learning_starts ? fleet_saccollect_uniform_dev(h->nets, h->E, &u) : fleet_sac_act_dev(h->nets, h->obs(cur), h->E, nullptr, &g);
+    return rc != FLEET_OK ? failed(rc, fleet_sac_last_error(h->nets)) : (int)FLEET_OK;
+  };
+  return offpolicy_loop(h, "fleet_saccollect_sac_dev", x->replay, x->n_steps, x->first_step, x->stats, action);
 }
 
 int fleet_collect_episodes_dev(fleet_collect_handle h, const uint8_t* done, const double* ep_return, const int32_t* ep_len, int E) {

@@ -3,7 +3,8 @@
 // through their own entries, as they are, on one stream, and what nothing else keeps on the device -- evaluate_policy's episode
 // quotas and lists, their mean and std, SB3's "new best" test and the copy of the best weights.  The handle borrows an env, an
 // optional normaliser and a policy and owns one block: the step's buffers, the per-env bookkeeping, the lists, the scalars and the
-// snapshot.
+// snapshot.  The actor may also be the squashed-Gaussian networks of fleet_sac_create (include/fleet_hip_sac_loop.h, fleet_saceval_*):
+// the action is then fleet_sac_act_dev's deterministic one and the snapshot the whole image, critics included.
 //   eval_episodes  ONE workgroup of 1024 threads per env step: sums and lengths move on, the envs below their quota that finished
 //              take list slots in env order (ballot and popcount per wavefront, chunks of 1024 envs).  Behind one of two loaders:
 //              the env's records, or the caller's arrays.
@@ -17,11 +18,13 @@
 #include <limits>
 #include <string>
 
+#include "../../include/fleet_hip_sac_loop.h"
 #include "fleet_batch.h"
 #include "fleet_eval.h"
 #include "fleet_handle.h"
 #include "fleet_mlp.h"
 #include "fleet_norm.h"
+#include "fleet_qtarget.h"
 
 namespace {
 
@@ -226,8 +229,9 @@ enum { kObs, kRaw, kAct, kRawReward, kReward, kDone, kSums, kLengths, kCounts, k
 struct FleetEval {
   fleet_handle env = nullptr;  // borrowed, as are the two below
   fleet_norm_handle norm = nullptr;
-  fleet_policy_handle policy = nullptr;
-  FleetMlpHandle* pol = nullptr;  // the policy's image: its device and stream
+  fleet_policy_handle policy = nullptr;  // the actor is a policy's image (fleet_eval_create), or ...
+  fleet_qtarget_handle nets = nullptr;   // ... a squashed SAC image (fleet_saceval_create): exactly one of the two
+  FleetMlpHandle* pol = nullptr;  // the actor's image: its device and stream
   std::string error;              // fleet_eval_last_error(handle)
   char* block = nullptr;          // owned
   int E = 0, D = 0, A = 0, M = 0, launches = 0;
@@ -247,13 +251,23 @@ struct FleetEval {
 
 namespace {
 
-// env, normaliser and policy launch on one stream; `more`: another policy's image
+// what the refusals call the actor of either kind of handle, and the entry that moves it to another stream
+struct ActorWords {
+  const char *noun, *set_stream;
+};
+const ActorWords kPolicyWords = {"policy", "fleet_policy_set_stream"}, kSacWords = {"networks handle", "fleet_qtarget_set_stream"};
+
+// env, normaliser and actor launch on one stream; `more`: another image of the actor's kind
 std::string check_streams(const FleetEval* h, const FleetHandleBase* more = nullptr) {
   if (h->norm && base_of(h->norm)->stream != h->env->stream)
     return "the normaliser launches on another stream than the env: fleet_norm_set_stream it to the env's first";
-  if (h->pol->stream != h->env->stream) return "the policy launches on another stream than the env: fleet_policy_set_stream it to the env's first";
-  if (more && more->stream != h->env->stream)
-    return "the destination policy launches on another stream than the env: fleet_policy_set_stream it to the env's first";
+  if (h->pol->stream != h->env->stream)
+    return h->nets ? "the networks launch on another stream than the env: fleet_qtarget_set_stream them to the env's first"
+                   : "the policy launches on another stream than the env: fleet_policy_set_stream it to the env's first";
+  if (more && more->stream != h->env->stream) {
+    const ActorWords& w = h->nets ? kSacWords : kPolicyWords;
+    return std::string("the destination ") + w.noun + " launches on another stream than the env: " + w.set_stream + " it to the env's first";
+  }
   return "";
 }
 
@@ -292,34 +306,38 @@ bool same_layout(const FleetMlpHandle* a, const FleetMlpHandle* b) {
   return true;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fleet_eval_create(fleet_handle env, fleet_norm_handle norm, fleet_policy_handle policy, const FleetEvalParams* p, fleet_eval_handle* out) {
+// Both create entries: `actor` is a fleet_policy_handle, or with `sac` the fleet_qtarget_handle of fleet_sac_create; the refusals
+// name it "the policy" or "the networks".
+int create_on(const char* entry, fleet_handle env, fleet_norm_handle norm, void* actor, bool sac, const FleetEvalParams* p, fleet_eval_handle* out) {
+  const char* const noun = sac ? "networks" : "policy";
   if (out) *out = nullptr;
   std::string why = check_params(p);
   if (!why.empty()) {
   } else if (!out) why = "null output handle";
   else if (!env) why = "null env handle";
-  else if (!policy) why = "null policy handle";
-  if (!why.empty()) return handle_refuse(g_eval_error, "fleet_eval_create", why, FLEET_ERR_INVALID);
-  FleetMlpHandle* pol = mlp_borrow(policy, sizeof(PolicyDesc), "policy", &why);
-  if (!pol) return handle_refuse(g_eval_error, "fleet_eval_create", why, FLEET_ERR_INVALID);
+  else if (!actor) why = std::string("null ") + noun + " handle";
+  if (!why.empty()) return handle_refuse(g_eval_error, entry, why, FLEET_ERR_INVALID);
+  FleetMlpHandle* pol = mlp_borrow(actor, sac ? sizeof(QTargetDesc) : sizeof(PolicyDesc), noun, &why);
+  if (!pol) return handle_refuse(g_eval_error, entry, why, FLEET_ERR_INVALID);
   const int E = env->d.E, D = env->d.obs_dim, A = env->d.N;
-  const PolicyHeadDesc& actor = pol->nets[0];
-  const int pd = actor.layer[0].in, pa = actor.layer[actor.n_layers - 1].out;
+  const PolicyHeadDesc& head = pol->nets[0];
+  const int pd = head.layer[0].in;
+  const int pa = sac ? static_cast<const QTargetDesc*>(pol->record)->act_dim : head.layer[head.n_layers - 1].out;
   const size_t weights_at = (size_t)mlp_round_up((int)pol->record_bytes, 256) / 4;
+  const std::string the = std::string("the ") + noun, whose = sac ? "the networks'" : "the policy's";
   if (!env->d.auto_reset) why = "the env needs auto_reset = 1: an evaluation runs across episode ends";
+  else if (sac && !qtarget_squashed(pol)) why = "the networks' actor is not a squashed Gaussian: fleet_sac_create makes one";
   else if (pol->device != env->device)
-    why = "the policy lies on device " + std::to_string(pol->device) + ", the env on device " + std::to_string(env->device);
-  else if (pd != D) why = "the policy's obs_dim is " + std::to_string(pd) + ", the env's " + std::to_string(D);
-  else if (pa != A) why = "the policy's act_dim is " + std::to_string(pa) + ", the env's " + std::to_string(A);
-  else if (pol->floats < weights_at || (pol->floats - weights_at) % 4 != 0) why = "the policy image's weights are no multiple of four floats";
+    why = the + (sac ? " lie" : " lies") + " on device " + std::to_string(pol->device) + ", the env on device " + std::to_string(env->device);
+  else if (pd != D) why = whose + " obs_dim is " + std::to_string(pd) + ", the env's " + std::to_string(D);
+  else if (pa != A) why = whose + " act_dim is " + std::to_string(pa) + ", the env's " + std::to_string(A);
+  else if (pol->floats < weights_at || (pol->floats - weights_at) % 4 != 0) why = the + " image's weights are no multiple of four floats";
   else if (norm) (void)fleet_norm_check_fit(norm, E, D, env->device, &why);
-  if (!why.empty()) return handle_refuse(g_eval_error, "fleet_eval_create", why, FLEET_ERR_INVALID);
+  if (!why.empty()) return handle_refuse(g_eval_error, entry, why, FLEET_ERR_INVALID);
   FleetEval* h = new FleetEval();
-  h->env = env, h->norm = norm, h->policy = policy, h->pol = pol;
+  h->env = env, h->norm = norm, h->pol = pol;
+  if (sac) h->nets = static_cast<fleet_qtarget_handle>(actor);
+  else h->policy = static_cast<fleet_policy_handle>(actor);
   h->E = E, h->D = D, h->A = A, h->M = p->max_episodes, h->weights_at = weights_at;
   const uint64_t e = (uint64_t)E, od = e * D * 4, m = (uint64_t)h->M;
   const uint64_t bytes[kArrays] = {od, norm ? od : 0, e * A * 4, e * 8, e * 8, e, e * 8, e * 4, e * 4, m * 8, m * 4, 32, (uint64_t)pol->floats * 4};
@@ -339,10 +357,47 @@ int fleet_eval_create(fleet_handle env, fleet_norm_handle norm, fleet_policy_han
   if (rc != FLEET_OK) {
     (void)hipGetLastError();
     fleet_eval_destroy(h);
-    return handle_refuse(g_eval_error, "fleet_eval_create", why, rc);
+    return handle_refuse(g_eval_error, entry, why, rc);
   }
   *out = h;
   return FLEET_OK;
+}
+
+// fleet_eval_best_load_dev and fleet_saceval_best_load_dev: the snapshot into another image of the handle's kind, one launch
+int best_load(FleetEval* h, const char* entry, void* dst, bool sac) {
+  std::string why;
+  FleetMlpHandle* to = nullptr;
+  if (h && sac != (h->nets != nullptr)) {
+    why = sac ? "the handle evaluates a policy (fleet_eval_create): fleet_eval_best_load_dev loads its snapshot"
+              : "the handle evaluates SAC networks (fleet_saceval_create): fleet_saceval_best_load_dev loads its snapshot";
+  } else if (h) {
+    const ActorWords& w = sac ? kSacWords : kPolicyWords;
+    const std::string the = std::string("the destination ") + w.noun;
+    to = mlp_borrow(dst, sac ? sizeof(QTargetDesc) : sizeof(PolicyDesc), sac ? "networks" : "policy", &why);
+    if (to && sac && !qtarget_squashed(to)) why = the + "'s actor is not a squashed Gaussian: fleet_sac_create makes one";
+    else if (to && to->device != h->env->device) why = the + " lies on another device than the env";
+    else if (to && !same_layout(to, h->pol)) why = the + "'s layout differs from the evaluated " + (sac ? "networks'" : "policy's");
+    else if (to) why = check_streams(h, to);
+  }
+  if (const int rc = handle_enter(entry, why, h, g_eval_error); rc != FLEET_OK) return rc;
+  if (!h->ran) {
+    h->error = std::string(entry) + ": no evaluation has run on this handle: the snapshot is empty";
+    return FLEET_ERR_STATE;
+  }
+  FLEET_HANDLE_TRY(h, hipSetDevice(h->env->device));
+  return launch_copy(h, h->arr<float>(kSnapshot), reinterpret_cast<float*>(to->block), nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fleet_eval_create(fleet_handle env, fleet_norm_handle norm, fleet_policy_handle policy, const FleetEvalParams* p, fleet_eval_handle* out) {
+  return create_on("fleet_eval_create", env, norm, policy, false, p, out);
+}
+
+int fleet_saceval_create(fleet_handle env, fleet_norm_handle norm, fleet_qtarget_handle nets, const FleetEvalParams* p, fleet_eval_handle* out) {
+  return create_on("fleet_saceval_create", env, norm, nets, true, p, out);
 }
 
 int fleet_eval_destroy(fleet_eval_handle h) {
@@ -419,8 +474,15 @@ int fleet_eval_run_dev(fleet_eval_handle h, const FleetEvalArgs* x) {
   EpisodeArgs a = episode_args(h);
   a.done = done, a.reward = reward, a.env = h->env->d.env, a.cold = h->env->d.cold;
   a.E = h->E, a.n_eval = x->n_eval_episodes, a.round32 = h->norm == nullptr, a.source = x->reward_source;
+  FleetSacActArgs det{};  // a SAC handle's action: tanhf(mu), no noise, the observation already normalised
+  det.struct_bytes = (int32_t)sizeof det;
+  det.noise_mode = FLEET_EXPLORE_NOISE_DRAW, det.deterministic = 1, det.actions = act;
   for (int t = 0; t < x->n_steps; ++t) {
-    if (const int rc = fleet_policy_forward_dev(h->policy, obs, h->E, nullptr, act, nullptr); rc != FLEET_OK) return failed(rc, fleet_policy_last_error(h->policy));
+    if (h->nets) {
+      if (const int rc = fleet_sac_act_dev(h->nets, obs, h->E, nullptr, &det); rc != FLEET_OK) return failed(rc, fleet_sac_last_error(h->nets));
+    } else if (const int rc = fleet_policy_forward_dev(h->policy, obs, h->E, nullptr, act, nullptr); rc != FLEET_OK) {
+      return failed(rc, fleet_policy_last_error(h->policy));
+    }
     if (const int rc = fleet_step_dev(h->env, act, FLEET_ACT_F32, raw, raw_reward, done, nullptr); rc != FLEET_OK) return failed(rc, fleet_last_error(h->env));
     h->launches += 2;
     if (h->norm) {
@@ -464,23 +526,9 @@ int fleet_eval_clear_dev(fleet_eval_handle h) {
   return launch_clear(h);
 }
 
-int fleet_eval_best_load_dev(fleet_eval_handle h, fleet_policy_handle dst) {
-  std::string why;
-  FleetMlpHandle* to = nullptr;
-  if (h) {
-    to = mlp_borrow(dst, sizeof(PolicyDesc), "policy", &why);
-    if (to && to->device != h->env->device) why = "the destination policy lies on another device than the env";
-    else if (to && !same_layout(to, h->pol)) why = "the destination policy's layout differs from the evaluated policy's";
-    else if (to) why = check_streams(h, to);
-  }
-  if (const int rc = handle_enter("fleet_eval_best_load_dev", why, h, g_eval_error); rc != FLEET_OK) return rc;
-  if (!h->ran) {
-    h->error = "fleet_eval_best_load_dev: no evaluation has run on this handle: the snapshot is empty";
-    return FLEET_ERR_STATE;
-  }
-  FLEET_HANDLE_TRY(h, hipSetDevice(h->env->device));
-  return launch_copy(h, h->arr<float>(kSnapshot), reinterpret_cast<float*>(to->block), nullptr);
-}
+int fleet_eval_best_load_dev(fleet_eval_handle h, fleet_policy_handle dst) { return best_load(h, "fleet_eval_best_load_dev", dst, false); }
+
+int fleet_saceval_best_load_dev(fleet_eval_handle h, fleet_qtarget_handle dst) { return best_load(h, "fleet_saceval_best_load_dev", dst, true); }
 
 int fleet_eval_best_export_dev(fleet_eval_handle h, float* const* tensors, int count) {
   const std::string why = h ? check_streams(h) : "";

@@ -35,3 +35,17 @@ struct PolicyDesc {
   int32_t reserved;
   PolicyHeadDesc head[FLEET_POLICY_MAX_HEADS];
 };
+
+// The warm-up's uniform draw needs no network, so its ONE launch (explore_uniform, fleet_policy.hip) is open to whoever holds a stream:
+// fleet_explore_act_dev's UNIFORM mode on a policy, fleet_saccollect_uniform_dev (fleet_collect.hip) on SAC networks.  actions
+// f32[E, A] and, when given, env_actions f32[E, A] receive lo + (hi - lo) * u kept below hi; u is the column's word of the Philox block
+// of (seed, env0 + row, step), or noise[row][column] when `given`; without `given` a non-null noise receives u.  The caller has set
+// the device and checked the arguments.  Returns hipGetLastError() of the launch.
+struct PolicyUniformArgs {
+  float *noise, *actions, *env_actions;
+  uint64_t seed, step;
+  uint32_t env0;
+  int given;
+  float lo, hi;
+};
+hipError_t policy_launch_uniform(hipStream_t stream, int E, int A, const PolicyUniformArgs& u);

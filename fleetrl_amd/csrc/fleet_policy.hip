@@ -180,6 +180,16 @@ struct FleetPolicy : FleetMlpHandle {
 };
 static_assert(mlp_image_is_first_base<FleetPolicy>, "mlp_borrow (fleet_mlp.hip) reads a fleet_policy_handle as the image's handle");
 
+// the uniform draw's one launch site (fleet_policy.h)
+hipError_t policy_launch_uniform(hipStream_t stream, int E, int A, const PolicyUniformArgs& u) {
+  SampleArgs s{};
+  s.noise = u.noise, s.actions = u.actions, s.env_actions = u.env_actions;
+  s.seed = u.seed, s.step = u.step, s.env0 = u.env0;
+  s.mode = FLEET_EXPLORE_UNIFORM, s.given = u.given, s.lo = u.lo, s.hi = u.hi;
+  hipLaunchKernelGGL(explore_uniform, dim3(grid_for((size_t)E * ((A + 3) / 4), 256, 4096)), dim3(256), 0, stream, s, E, A);
+  return hipGetLastError();
+}
+
 extern "C" {
 
 int fleet_policy_create(int device, const FleetPolicyParams* p, const float* host_weights, fleet_policy_handle* out) {
@@ -307,8 +317,8 @@ int fleet_explore_act_dev(fleet_policy_handle h, const float* obs, int E, fleet_
   const int A = h->p.head[0].width[h->p.head[0].n_layers - 1];
   FLEET_HANDLE_TRY(h, hipSetDevice(h->device));
   if (uniform) {
-    hipLaunchKernelGGL(explore_uniform, dim3(grid_for((size_t)E * ((A + 3) / 4), 256, 4096)), dim3(256), 0, h->stream, s, E, A);
-    FLEET_HANDLE_TRY(h, hipGetLastError());
+    const PolicyUniformArgs u{s.noise, s.actions, s.env_actions, s.seed, s.step, s.env0, s.given, s.lo, s.hi};
+    FLEET_HANDLE_TRY(h, policy_launch_uniform(h->stream, E, A, u));
     return FLEET_OK;
   }
   ForwardArgs a{};

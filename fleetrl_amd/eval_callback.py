@@ -1,12 +1,13 @@
 """`DeviceEvalCallback`: stable-baselines3's `EvalCallback` as one enqueue-only call (include/fleet_hip.h `fleet_eval_*`,
-fleetrl_amd/csrc/fleet_eval.hip).
+include/fleet_hip_sac_loop.h `fleet_saceval_*`, fleetrl_amd/csrc/fleet_eval.hip).
 
 The third call of an SB3-style iteration beside `DevicePPOCollect.collect` and `DevicePPOTrain.train`: every `eval_freq` steps
 `evaluate(num_timesteps)` copies the training normaliser's statistics to the evaluation env's (`sync_envs_normalization`), runs
 `n_eval_episodes` deterministic episodes (`evaluate_policy`: the forward, the env's step and the normaliser's step, each the launch the
 pieces make on their own -- the episode lists are bit-equal to `sync_normalization` + `fleetrl_amd.evaluate_policy`), forms mean and std,
 and keeps the best weights, all on the device: the host does not wait, and does not learn whether the agent improved until it asks
-(`results()`).  Out of scope: stochastic evaluation, `real_time` envs, `callback_on_new_best`, success rates.
+(`results()`).  A SAC agent (`DeviceSACNetworks`) is evaluated with its deterministic action tanh(mean); its snapshot is the whole
+image, the actor and the critics.  Out of scope: stochastic evaluation, `real_time` envs, `callback_on_new_best`, success rates.
 """
 from __future__ import annotations
 
@@ -26,8 +27,8 @@ STATS = ("mean_reward", "std_reward", "mean_ep_length", "std_ep_length", "episod
 
 
 class DeviceEvalCallback(_DeviceHandle):
-    """One `fleet_eval_*` handle on `policy` (a `DevicePolicy`) and `eval_venv` (a `FleetVecEnv`, or a `FleetVecNormalize` over one), which
-    must outlive it.  monitor: the env counts as `Monitor`-wrapped (what `make_vec_env` gives SB3): an episode's reward is the env's own
+    """One `fleet_eval_*` handle on `policy` (a `DevicePolicy`, or a `DeviceSACNetworks`) and `eval_venv` (a `FleetVecEnv`, or a
+    `FleetVecNormalize` over one), which must outlive it.  monitor: the env counts as `Monitor`-wrapped (what `make_vec_env` gives SB3): an episode's reward is the env's own
     raw episode return; without it, the sum of what the env's step returns (the normalised rewards on a `FleetVecNormalize`).
     train_normalizer (a `FleetVecNormalize` or a `DeviceNormalizer`): its statistics go to the evaluation env's before every
     evaluation.  max_episodes: the episode lists' length (default `n_eval_episodes`)."""
@@ -53,7 +54,11 @@ class DeviceEvalCallback(_DeviceHandle):
         self.episode_steps = int(core.params.episode_steps)
         h = C.c_void_p()
         p = _capi.FleetEvalParams(C.sizeof(_capi.FleetEvalParams), self.max_episodes)
-        rc = self.lib.fleet_eval_create(self.batch.h, None if self.norm is None else self.norm.h, policy.h, C.byref(p), C.byref(h))
+        from .sac import DeviceSACNetworks
+
+        self._sac = isinstance(policy, DeviceSACNetworks)  # the create and the load entries are then fleet_saceval_*'s
+        create = self.lib.fleet_saceval_create if self._sac else self.lib.fleet_eval_create
+        rc = create(self.batch.h, None if self.norm is None else self.norm.h, policy.h, C.byref(p), C.byref(h))
         if rc != _capi.OK:
             raise FleetHipError(rc, self.lib.fleet_eval_last_error(None).decode())
         self.h = h
@@ -193,11 +198,13 @@ class DeviceEvalCallback(_DeviceHandle):
 
     # ---- the snapshot ------------------------------------------------------------------------------------------------------------
     def load_best_into(self, policy=None):
-        """The best weights so far into `policy` (default: the evaluated one), a `DevicePolicy` of the same layout; one launch."""
+        """The best weights so far into `policy` (default: the evaluated one), a `DevicePolicy` (for a SAC agent: a `DeviceSACNetworks`)
+        of the same layout; one launch."""
         policy = self.policy if policy is None else policy
         self.use_torch_stream()
         policy.use_torch_stream()
-        self._check(self.lib.fleet_eval_best_load_dev(self.h, policy.h))
+        load = self.lib.fleet_saceval_best_load_dev if self._sac else self.lib.fleet_eval_best_load_dev
+        self._check(load(self.h, policy.h))
 
     def best_parameters(self, like=None):
         """The best weights so far as torch tensors in torch's layout and order (W, b per layer, the actor's then the critic's): written

@@ -229,6 +229,30 @@ class DeviceSACNetworks(DeviceTD3Target):
         self.act_dev(obs.data_ptr(), E, normalizer, a)
         return actions_out
 
+    # ---- the warm-up's draw -----------------------------------------------------------------------------------------------------
+    def sample_uniform_dev(self, num_envs: int, args: "_capi.FleetSacUniformArgs"):
+        """Raw device addresses in a FleetSacUniformArgs (include/fleet_hip_sac_loop.h), on the handle's stream."""
+        args.struct_bytes = C.sizeof(_capi.FleetSacUniformArgs)
+        self._check(self.lib.fleet_saccollect_uniform_dev(self.h, int(num_envs), C.byref(args)))
+
+    def sample_uniform(self, num_envs: int, *, low: float = -1.0, high: float = 1.0, seed: int, step: int, env_id_offset: int = 0,
+                       actions_out=None):
+        """The warm-up's `action_space.sample()` (SB3: while num_timesteps < learning_starts) without a policy handle: uniform actions
+        f32 [num_envs, act_dim] in [low, high), one launch on torch's current stream, no network.  The kernel and the bits are
+        `DevicePolicy.sample_uniform`'s under the same (seed, step, env_id_offset + row)."""
+        import torch
+
+        self.use_torch_stream()
+        E = int(num_envs)
+        if actions_out is None:
+            actions_out = torch.empty((max(E, 0), self.act_dim), device=torch.device("cuda", self.device), dtype=torch.float32)
+        a = _capi.FleetSacUniformArgs()
+        a.env_id_offset, a.lo, a.hi = int(env_id_offset), float(low), float(high)
+        a.seed, a.step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+        a.actions = self._tensor(actions_out, (E, self.act_dim), (torch.float32,)).data_ptr()
+        self.sample_uniform_dev(E, a)
+        return actions_out
+
     # ---- the target ----------------------------------------------------------------------------------------------------------
     def soft_target_dev(self, targets, next_obs_ptr: int, rewards_ptr: int, dones_ptr: int, batch: int, args: "_capi.FleetSacTargetArgs"):
         """Raw device addresses in a FleetSacTargetArgs, on the handle's stream; `targets`: the DeviceSACNetworks of the targets.
